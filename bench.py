@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- suffix-array construction throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one complete SuffixArray::new-equivalent build (device-resident text in, device-resident SA out) of one
 synthetic text.  Default workload: the configuration the metric is quoted on, C3 = 256 MiB English-like corpus
@@ -10,28 +10,40 @@ scaling, no data-path collective; torch.distributed carri
 time only.  `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
 (torch.distributed.run, before this process touches a GPU); under an external torchrun it runs as one rank.
 
-Prints ONE JSON line on rank 0:
-  value / ms_per_step   device-resident builds, whole job (all ranks), timed as the contract says
+A plain run does only what the headline needs: the text is generated and loaded, one first-touch build (workspace, pool,
+pinned read-back buffer), W warm-up builds, K timed builds, the outputs if --dump-outputs asks, and the line.  Prints ONE
+JSON line on rank 0:
+  value / ms_per_step   device-resident builds, whole job (all ranks), max-over-ranks wall time of the K timed builds
+  ranks                 every rank's HIP device, PCI bus id and own ms per step (N > 1: the bus ids must be distinct unless
+                        SA_BENCH_SHARE_GPU=1 asks for a rehearsal on one GPU)
+  full                  whether the --full legs below ran (null fields otherwise)
+
+--dump-outputs DIR writes, after the timed builds, the suffix array the last timed build handed its caller: DIR/sa.npy
+(float64; every entry is exact) at the positions DIR/sa_index.npy (float64) -- the whole array when it has at most
+DUMP_ENTRIES = 3 Mi entries (48 MiB with its positions), else a fixed seeded sample of that many positions (the first and
+last 4 096 included), the same for the same arguments.  With N ranks every rank writes sa_rank<r>.npy /
+sa_index_rank<r>.npy, each with 1/N of the budget.
+
+--full adds everything else the benchmark measures or checks (with its own --no-* switches):
   roofline              the kernel class with the MOST device time in the timed region (HIP events on the launch stream around
                         every class that had >= 5 % of the device time of a profiled build just before it), roofline.kernels:
                         the same figures for every class with >= 10 %, roofline.whole_build: PMC bytes / device time
   kernels               per-kernel table from one extra build outside the timed region (every class)
   verified              sa_amd_check_integrity_device (reference src/sa.rs:72-84, linear time) on the last array of
-                        EVERY rank, outside the timed region -- always on
+                        EVERY rank, outside the timed region (+ --verify-cpu: the oracle's linear verifier)
   end_to_end            median of 5 sa_amd_saca_u8 calls on host buffers (what the reference's `SuffixArray::new`
                         hands over: src/sa.rs:23-27): H2D + build + D2H, all ranks concurrently
   configs               (N = 1) the other BASELINE.json configs behind the headline workload, same measurement each: C2 64 MiB uniform,
                         north_star's literal 256 MiB random-byte text, C4 1 GiB DNA, C5's 512 MiB per-GPU text -- device-resident
                         ms per build (1 warm-up + --config-steps timed), MB/s, verified, the class with the most device time
                         against the HBM roofline (HIP events inside the timed region), (5n + 4) / t, host-pointer calls
-  ranks                 every rank's HIP device, PCI bus id, own ms per step and own verification (N > 1: the bus ids must be
-                        distinct unless SA_BENCH_SHARE_GPU=1 asks for a rehearsal on one GPU)
   batch_c5              (N > 1) BASELINE config 5: one 512 MiB uniform text per rank, device-resident and end to end
   batch_api             (N = 1) BASELINE config 5 through its C-ABI form: ONE call of sa_amd_saca_batch with 8 texts of 512 MiB
                         over all visible devices, host pointers in and out (+ small_texts: 4 096 texts of 4 KiB through one
                         call of the same entry point, the reference's own size domain)
   cpu_baseline          CPU suffix sorter on a bounded sample, one pinned core (N = 1 only): libdivsufsort if a probe finds
                         one (kind "reference"), else the oracle's own SA-IS (kind "port"); the probe log is in the object
+  config.*              mean / max LCP and H0 of the text
 """
 from __future__ import annotations
 
@@ -85,7 +97,14 @@ def parse(argv=None):
     ap.add_argument("--no-configs", action="store_true")
     ap.add_argument("--config-steps", type=int, default=5, help="timed builds per extra config (after 1 warm-up)")
     ap.add_argument("--e2e-calls", type=int, default=5)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: profiled build, roofline, verification, end to end, configs, batch legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's suffix array (or a fixed seeded sample of it) as DIR/*.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---- rank launcher ---------------------------------------------------------------------------------
@@ -321,6 +340,12 @@ class HipBackend:
         import numpy as np
         return self.out.cpu().numpy().view(np.uint32)
 
+    def gather(self, idx):
+        """the entries of the last array at host positions `idx` (int64), gathered on the device (only those travel)"""
+        import numpy as np
+        pos = self.torch.from_numpy(idx).to(self.dev)
+        return self.out.index_select(0, pos).cpu().numpy().view(np.uint32)
+
     def build_host(self, text_h, out_h):
         self.sa.saca(text_h, out_h)
 
@@ -373,16 +398,48 @@ class HipBackend:
 
 
 def timed_steps(backend, barrier, steps, warmup, mask=0):
+    """`warmup` untimed then `steps` timed builds; mask None: no profiler at all (the plain run), else the classes with events"""
     for _ in range(warmup):
         backend.step()
-    backend.profile_begin(mask)
+    if mask is not None:
+        backend.profile_begin(mask)
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
         backend.step()
     barrier()
     dt = time.perf_counter() - t0
-    return dt, backend.profile_end()
+    return dt, (backend.profile_end() if mask is not None else None)
+
+
+DUMP_ENTRIES = 3 << 20         # entries written by --dump-outputs per job: values + positions, float64 each = 48 MiB
+DUMP_EDGE = 4096               # the first and last entries of the array are always in the sample
+DUMP_SEED = 20240917
+
+
+def dump_positions(n_entries, budget):
+    """positions of the array written by --dump-outputs: all of them when they fit in `budget` entries, else the first and
+    last DUMP_EDGE and a fixed seeded draw of the rest (sorted, distinct): the same for the same array length"""
+    import numpy as np
+    if n_entries <= budget:
+        return np.arange(n_entries, dtype=np.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    edge = min(DUMP_EDGE, budget // 4)
+    draw = rng.integers(0, n_entries, budget - 2 * edge, dtype=np.int64)
+    return np.unique(np.concatenate([np.arange(edge, dtype=np.int64), draw,
+                                     np.arange(n_entries - edge, n_entries, dtype=np.int64)]))
+
+
+def dump_outputs(backend, directory, n, rank, world):
+    """--dump-outputs: the suffix array the last timed build handed its caller (n + 1 entries, values < 2^31, exact in
+    float64) at dump_positions(), as <directory>/sa.npy beside the positions in sa_index.npy (N > 1: _rank<r> per rank)"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    idx = dump_positions(n + 1, DUMP_ENTRIES // world)
+    vals = backend.gather(idx) if hasattr(backend, "gather") else np.asarray(backend.download())[idx]
+    tag = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(directory, f"sa{tag}.npy"), vals.astype(np.float64))
+    np.save(os.path.join(directory, f"sa_index{tag}.npy"), idx.astype(np.float64))
 
 
 def end_to_end(backend, text_h, calls, barrier):
@@ -574,6 +631,43 @@ def batch_api_subprocess(args):
         return {"entry_point": "sa_amd_saca_batch", "verified": False, "ran_in": "child process", "error": f"{type(ex).__name__}: {ex}"[:300]}
 
 
+def headline(args, n, world, dt, stats, ranks, distinct):
+    """the line of a plain run: the headline figure and what it was measured on; the --full legs stay null (run() fills them)"""
+    per_step = dt / args.steps
+    return {
+        "metric": "input MB/s indexed (SA build)",
+        "value": round(world * n / 1e6 / per_step, 3),
+        "unit": "MB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(per_step * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "full": bool(args.full),
+        "config": {"workload": f"{args.workload}: {n} bytes per GPU, seed base + rank, one independent text per GPU",
+                   "n_bytes": n, "sigma": stats["sigma"], "bits_per_symbol": stats["bits_per_symbol"],
+                   "symbols_per_key": stats["symbols_per_key"], "refinement_rounds": stats["rounds"],
+                   "text_rounds": stats["text_rounds"], "radix_passes": stats["sort_passes"],
+                   "unresolved_after_initial_sort": stats["unresolved_after_initial"]},
+        "roofline": None,
+        "kernels": None,
+        "device_ms_per_step": None,
+        "verified": None,
+        "ranks": ranks,
+        "distinct_gpus": distinct if world > 1 else None,
+        "end_to_end": None,
+        "configs": None,
+        "batch_c5": None,
+        "batch_api": None,
+        "host": host_info(),
+        "cpu_baseline": None,
+    }
+
+
 def run(args, backend, rank, world, dist=None, share=False):
     """one rank of the benchmark; returns the result dict on rank 0 (None elsewhere).  `backend` is the HipBackend; the
     world-size-2 CPU test of tests/test_dist.py injects its own object with the same methods."""
@@ -606,20 +700,28 @@ def run(args, backend, rank, world, dist=None, share=False):
     text_h = corpus.workload(args.workload, rank=rank, n_override=args.n)
     n = int(text_h.size)
     backend.load(text_h)
-    names = backend.kernel_names()
-    # per-kernel table first: one untimed build with events around every launch.  It also says which classes matter: the
-    # timed region then carries events around every class with at least EVENT_SHARE of the device time (an event pair
-    # around each of the ~200 launches of a build would cost ~0.7 ms of host time per step)
-    dt_rank, prof, prof_all, device_ms = measure_resident(backend, barrier, args.steps, args.warmup, bcast_mask)
+    if args.full:
+        names = backend.kernel_names()
+        # per-kernel table first: one untimed build with events around every launch.  It also says which classes matter: the
+        # timed region then carries events around every class with at least EVENT_SHARE of the device time (an event pair
+        # around each of the ~200 launches of a build would cost ~0.7 ms of host time per step)
+        dt_rank, prof, prof_all, device_ms = measure_resident(backend, barrier, args.steps, args.warmup, bcast_mask)
+    else:
+        backend.step()                                        # (first touch of the workspace, pool, pinned read-back buffer)
+        dt_rank, _ = timed_steps(backend, barrier, args.steps, args.warmup, mask=None)
+    if args.dump_outputs:
+        dump_outputs(backend, args.dump_outputs, n, rank, world)
     dt = reduce(dt_rank, "MAX")
     stats = backend.stats_dict()
-    # correctness gate of every run, outside the timed region: every rank's last array
-    ok = bool(backend.verify())
-    if args.verify_cpu:
-        orc = load_oracle()
-        got = backend.download()
-        ok = ok and orc.oracle_verify_sa_mt(text_h.ctypes.data, n, got.ctypes.data, n + 1, 16) == 1
-    verified = reduce(1.0 if ok else 0.0, "MIN") == 1.0
+    ok = verified = None
+    if args.full:
+        # correctness gate of every --full run, outside the timed region: every rank's last array
+        ok = bool(backend.verify())
+        if args.verify_cpu:
+            orc = load_oracle()
+            got = backend.download()
+            ok = ok and orc.oracle_verify_sa_mt(text_h.ctypes.data, n, got.ctypes.data, n + 1, 16) == 1
+        verified = reduce(1.0 if ok else 0.0, "MIN") == 1.0
 
     # who ran where: every rank's device identity, its own time and its own check (the driver's N > 1 runs: N distinct GPUs)
     ident = dict(backend.identity()) if hasattr(backend, "identity") else {}
@@ -632,6 +734,9 @@ def run(args, backend, rank, world, dist=None, share=False):
     distinct = len(set(bus_ids)) == len(bus_ids) and None not in bus_ids
     if world > 1 and not distinct and os.environ.get("SA_BENCH_SHARE_GPU") != "1":
         raise SystemExit(f"bench.py: {world} ranks but their GPUs are not distinct ({bus_ids}); SA_BENCH_SHARE_GPU=1 allows a rehearsal")
+
+    if not args.full:
+        return headline(args, n, world, dt, stats, ranks, distinct) if rank == 0 else None
 
     e2e = None
     if not args.no_end_to_end and world == 1:
@@ -730,25 +835,9 @@ def run(args, backend, rank, world, dist=None, share=False):
                                "sum of the kernels' device time: the rate the whole build moves bytes at"}
     per_step = dt / args.steps
     job_gbs = (5 * n + 4) / per_step / 1e9
-    facts = corpus_facts(args.workload, n, text_h)
-    result = {
-        "metric": "input MB/s indexed (SA build)",
-        "value": round(world * n / 1e6 / per_step, 3),
-        "unit": "MB/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(per_step * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic",
-        "config": {"workload": f"{args.workload}: {n} bytes per GPU, seed base + rank, one independent text per GPU",
-                   "n_bytes": n, "sigma": stats["sigma"], "bits_per_symbol": stats["bits_per_symbol"],
-                   "symbols_per_key": stats["symbols_per_key"], "refinement_rounds": stats["rounds"],
-                   "text_rounds": stats["text_rounds"], "radix_passes": stats["sort_passes"],
-                   "unresolved_after_initial_sort": stats["unresolved_after_initial"], **facts},
+    result = headline(args, n, world, dt, stats, ranks, distinct)
+    result["config"].update(corpus_facts(args.workload, n, text_h))
+    result.update({
         "roofline": {"bound": "hbm", "kernel": dom["name"], "achieved": dom.get("achieved", 0.0), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": dom.get("frac", 0.0), "traffic": dom.get("traffic"),
                      "traffic_source": "profiles/traffic.json (builder-run PMC passes of this command, tools/profile_round.sh); "
@@ -766,14 +855,11 @@ def run(args, backend, rank, world, dist=None, share=False):
         "kernels": kernels,
         "device_ms_per_step": round(device_ms, 3),
         "verified": verified,
-        "ranks": ranks,
-        "distinct_gpus": distinct if world > 1 else None,
         "end_to_end": e2e,
         "configs": configs,
         "batch_c5": batch,
         "batch_api": batch_api,
-        "host": host_info(),
-    }
+    })
     if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
         try:
             result["cpu_baseline"] = cpu_baseline(text_h, min(args.cpu_sample, n))

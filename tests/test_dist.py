@@ -96,15 +96,14 @@ class OracleStandIn:
         return {"hip_device": r, "pci_bus_id": f"0000:{0x10 + r:02x}:00.0", "gpu": "stand-in", "pid": os.getpid()}
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world, port, q, argv=("--e2e-calls", "2", "--full")):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     import torch.distributed as dist
     import bench
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    args = bench.parse(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--workload", "c2_uniform_64m", "--n", "40000",
-                        "--e2e-calls", "2"])
+    args = bench.parse(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--workload", "c2_uniform_64m", "--n", "40000"] + list(argv))
     backend = OracleStandIn()
     res = bench.run(args, backend, rank, world, dist, share=True)
     q.put((rank, res, backend.builds))
@@ -146,12 +145,37 @@ def test_world_size_2_gloo_runs_bench_rank_logic():
     assert b0 == b1 and b0 >= 2 + 1 + 3                       # first touch + profiled build, warm-up, timed steps -- on every rank
 
 
+def test_world_size_2_plain_run_and_dump(tmp_path, oracle):
+    """the plain N > 1 line: every rank times its own builds, rank 0 prints the line, every rank dumps its own array"""
+    import torch.multiprocessing as mp
+    from suffix_array_amd import corpus
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, q, ("--dump-outputs", str(tmp_path)))) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = sorted((q.get(timeout=180) for _ in procs), key=lambda x: x[0])
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    (_, out0, b0), (_, out1, b1) = res
+    assert out1 is None and out0["full"] is False and out0["n_gpus"] == 2 and out0["verified"] is None
+    assert b0 == b1 == 1 + 1 + 3
+    assert out0["value"] == pytest.approx(2 * 40000 / 1e6 / (out0["ms_per_step"] / 1e3), rel=1e-3)
+    assert [r["rank"] for r in out0["ranks"]] == [0, 1] and out0["distinct_gpus"] is True
+    assert sorted(os.listdir(tmp_path)) == ["sa_index_rank0.npy", "sa_index_rank1.npy", "sa_rank0.npy", "sa_rank1.npy"]
+    for r in range(2):
+        exp = oracle.sais(corpus.workload("c2_uniform_64m", rank=r, n_override=40000)).astype(np.float64)
+        assert np.array_equal(np.load(tmp_path / f"sa_rank{r}.npy"), exp)
+
+
 def test_single_rank_path_with_stand_in():
     sys.path.insert(0, ROOT)
     import bench
     args = bench.parse(["--steps", "2", "--warmup", "0", "--workload", "c4_dna_1g", "--n", "30000", "--cpu-sample", "20000",
                         "--e2e-calls", "1", "--batch-texts", "3", "--small-batch-texts", "40", "--configs", "c2_uniform_64m,c5_uniform_512m",
-                        "--config-steps", "2"])
+                        "--config-steps", "2", "--full"])
     out = bench.run(args, OracleStandIn(), 0, 1)
     # the other BASELINE configs ride behind the headline workload, each verified and with its own dominant class
     cf = out["configs"]
@@ -191,7 +215,7 @@ def test_batch_api_child_process_failure_is_a_record_not_a_crash():
         def build_host(self, text_h, out_h):
             raise MemoryError("no staging")
     args = bench.parse(["--steps", "2", "--warmup", "0", "--workload", "c2_uniform_64m", "--n", "20000", "--cpu-sample", "10000", "--e2e-calls", "1",
-                        "--batch-texts", "2", "--small-batch-texts", "0", "--configs", "c5_uniform_512m", "--config-steps", "1"])
+                        "--batch-texts", "2", "--small-batch-texts", "0", "--configs", "c5_uniform_512m", "--config-steps", "1", "--full"])
     line = bench.run(args, Failing(), 0, 1)
     assert line["verified"] is True and line["value"] > 0                       # the headline stands
     assert "MemoryError" in line["end_to_end"]["error"] and "RuntimeError" in line["batch_api"]["error"]
@@ -227,3 +251,96 @@ def test_per_rank_texts_are_independent():
     a, b = corpus.workload("c5_uniform_512m", rank=0, n_override=5000), corpus.workload("c5_uniform_512m", rank=1, n_override=5000)
     assert a.size == b.size == 5000 and not np.array_equal(a, b)
     assert np.array_equal(a, corpus.workload("c5_uniform_512m", rank=0, n_override=5000))       # seeded: reproducible
+
+
+class CountingStandIn(OracleStandIn):
+    """the stand-in that also records whether the profiler or the checks were asked for"""
+
+    def __init__(self):
+        super().__init__()
+        self.calls = []
+
+    def profile_begin(self, mask):
+        self.calls.append("profile")
+        super().profile_begin(mask)
+
+    def verify(self):
+        self.calls.append("verify")
+        return super().verify()
+
+    def build_host(self, text_h, out_h):
+        self.calls.append("host")
+        super().build_host(text_h, out_h)
+
+
+def test_plain_run_does_only_the_headline():
+    """without --full: one first-touch build, --warmup untimed, --steps timed, the line -- no profiled build, no events, no
+    check, no end-to-end / config / batch / CPU legs; the headline keys mean what they do in a --full run"""
+    sys.path.insert(0, ROOT)
+    import bench
+    args = bench.parse(["--steps", "4", "--warmup", "2", "--workload", "c3_english_256m", "--n", "30000"])
+    assert args.full is False and args.dump_outputs is None
+    backend = CountingStandIn()
+    out = bench.run(args, backend, 0, 1)
+    assert backend.builds == 1 + 2 + 4 and backend.calls == []
+    assert out["full"] is False and out["steps"] == 4 and out["warmup"] == 2 and out["n_gpus"] == 1
+    assert out["metric"] == "input MB/s indexed (SA build)" and out["unit"] == "MB/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "u8" and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(30000 / 1e6 / (out["ms_per_step"] / 1e3), rel=1e-2)
+    for k in ("roofline", "kernels", "verified", "end_to_end", "configs", "batch_c5", "batch_api", "cpu_baseline"):
+        assert out[k] is None, k
+    assert out["config"]["n_bytes"] == 30000 and out["ranks"][0]["ms_per_step"] > 0
+    json.dumps(out)
+
+
+@pytest.mark.parametrize("steps", [1, 3])
+def test_steps_sets_the_number_of_timed_builds(steps):
+    sys.path.insert(0, ROOT)
+    import bench
+    args = bench.parse(["--steps", str(steps), "--warmup", "0", "--workload", "c2_uniform_64m", "--n", "5000"])
+    backend = OracleStandIn()
+    out = bench.run(args, backend, 0, 1)
+    assert backend.builds == 1 + steps and out["steps"] == steps
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_whole_array(tmp_path, oracle):
+    """--dump-outputs: the last timed build's suffix array, float64, at every position when it fits; the same every run"""
+    sys.path.insert(0, ROOT)
+    import bench
+    from suffix_array_amd import corpus
+    n = 20000
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        args = bench.parse(["--steps", "2", "--warmup", "1", "--workload", "c4_dna_1g", "--n", str(n), "--dump-outputs", str(d)])
+        bench.run(args, OracleStandIn(), 0, 1)
+        assert sorted(os.listdir(d)) == ["sa.npy", "sa_index.npy"]
+        dumps.append((np.load(d / "sa.npy"), np.load(d / "sa_index.npy")))
+    (v0, i0), (v1, i1) = dumps
+    assert v0.dtype == i0.dtype == np.float64 and v0.shape == i0.shape == (n + 1,)
+    assert np.array_equal(i0, np.arange(n + 1)) and np.array_equal(v0, v1) and np.array_equal(i0, i1)
+    assert np.array_equal(v0, oracle.sais(corpus.workload("c4_dna_1g", n_override=n)).astype(np.float64))
+
+
+def test_dump_outputs_sample_of_a_large_array(tmp_path, oracle, monkeypatch):
+    """an array longer than the budget: a fixed seeded sample of positions (sorted, distinct, both ends included), and at the
+    largest text the package accepts the files stay under 64 MB"""
+    sys.path.insert(0, ROOT)
+    import bench
+    from suffix_array_amd import corpus
+    monkeypatch.setattr(bench, "DUMP_ENTRIES", 3000)
+    n = 50000
+    args = bench.parse(["--steps", "1", "--warmup", "0", "--workload", "c2_uniform_64m", "--n", str(n), "--dump-outputs", str(tmp_path)])
+    bench.run(args, OracleStandIn(), 0, 1)
+    vals, idx = np.load(tmp_path / "sa.npy"), np.load(tmp_path / "sa_index.npy")
+    assert vals.dtype == idx.dtype == np.float64 and vals.shape == idx.shape and 2000 < idx.size <= 3000
+    assert idx[0] == 0 and idx[-1] == n and np.all(np.diff(idx) > 0)
+    exp = oracle.sais(corpus.workload("c2_uniform_64m", n_override=n))
+    assert np.array_equal(vals, exp[idx.astype(np.int64)].astype(np.float64))
+    assert np.array_equal(idx, bench.dump_positions(n + 1, 3000).astype(np.float64))
+    monkeypatch.undo()
+    big = bench.dump_positions(2**31, bench.DUMP_ENTRIES)
+    assert big.size <= bench.DUMP_ENTRIES and 2 * 8 * big.size + 256 <= 64e6
+    assert np.array_equal(big, bench.dump_positions(2**31, bench.DUMP_ENTRIES))

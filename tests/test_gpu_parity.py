@@ -1275,7 +1275,7 @@ def test_bench_two_ranks_share_one_gpu():
     env = dict(os.environ, SA_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                           "--workload", "c2_uniform_64m", "--n", str(8 << 20), "--e2e-calls", "2"],
+                           "--workload", "c2_uniform_64m", "--n", str(8 << 20), "--e2e-calls", "2", "--full"],
                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
@@ -1319,7 +1319,7 @@ def test_bench_three_ranks_share_one_gpu():
     env = dict(os.environ, SA_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1",
-                           "--workload", "c2_uniform_64m", "--n", str(4 << 20), "--e2e-calls", "1"],
+                           "--workload", "c2_uniform_64m", "--n", str(4 << 20), "--e2e-calls", "1", "--full"],
                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
@@ -1355,7 +1355,7 @@ def test_bench_single_rank_line_with_batch_api():
     env.pop("WORLD_SIZE", None)
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload",
                            "c3_english_256m", "--n", str(8 << 20), "--e2e-calls", "2", "--batch-texts", "4", "--cpu-sample", str(1 << 20),
-                           "--config-steps", "2"],
+                           "--config-steps", "2", "--full"],
                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-2000:]
     out = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][0])
@@ -1374,6 +1374,31 @@ def test_bench_single_rank_line_with_batch_api():
         assert c["roofline"]["kernel"] and 0 < c["roofline"]["frac"] < 1 and c["end_to_end"]["fresh_buffer"]["MB_per_s"] > 0, name
     assert cf["c4_dna_1g"]["sigma"] == 4 and cf["c2_uniform_64m"]["sigma"] == 256
     assert out["ranks"][0]["pci_bus_id"] and out["roofline"]["traffic_source"] is None      # (traffic.json is for the full-size text)
+
+
+def test_bench_plain_line_and_dump_outputs(oracle, tmp_path):
+    """`python bench.py` without --full: the headline only (no --full leg ran), and --dump-outputs writes the last timed build's
+    suffix array -- here a seeded sample of it (4 Mi + 1 entries > the budget), equal to the oracle's at every dumped position"""
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    n = 4 << 20
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload",
+                           "c3_english_256m", "--n", str(n), "--dump-outputs", str(tmp_path)],
+                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["full"] is False and out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(n / 1e6 / (out["ms_per_step"] / 1e3), rel=1e-2)
+    assert out["verified"] is None and out["roofline"] is None and out["cpu_baseline"] is None and out["configs"] is None
+    vals, idx = np.load(tmp_path / "sa.npy"), np.load(tmp_path / "sa_index.npy")
+    assert vals.dtype == idx.dtype == np.float64 and vals.shape == idx.shape and idx[0] == 0 and idx[-1] == n
+    assert (tmp_path / "sa.npy").stat().st_size + (tmp_path / "sa_index.npy").stat().st_size <= 64e6
+    exp = oracle.sais(corpus.english_corpus(n, 3))
+    assert np.array_equal(vals, exp[idx.astype(np.int64)].astype(np.float64))
 
 
 # ---- next rows (SURVEY.md 8f): bucket table and integrity check --------------------------------

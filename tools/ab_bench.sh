@@ -3,8 +3,8 @@
 O=$1; shift
 mkdir -p $O
 for w in "$@"; do
-  timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $w --no-cpu-baseline --no-end-to-end > $O/b_os_$w.json 2> $O/b_os_$w.err
-  SA_AMD_NO_ONESWEEP=1 timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $w --no-cpu-baseline --no-end-to-end > $O/b_old_$w.json 2> $O/b_old_$w.err
+  timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $w --no-cpu-baseline --no-end-to-end --full > $O/b_os_$w.json 2> $O/b_os_$w.err
+  SA_AMD_NO_ONESWEEP=1 timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $w --no-cpu-baseline --no-end-to-end --full > $O/b_old_$w.json 2> $O/b_old_$w.err
 done
 python - "$O" "$@" <<'PY'
 import json, sys

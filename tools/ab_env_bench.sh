@@ -4,7 +4,7 @@ mkdir -p $O
 for spec in "$@"; do
   tag=${spec%%=*}; envs=${spec#*=}
   ( for kv in $(echo "$envs" | tr ',' ' '); do [ "$kv" != "-" ] && export "$kv"; done
-    timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $W --no-cpu-baseline --no-end-to-end > $O/ab_${W}_$tag.json 2> $O/ab_${W}_$tag.err )
+    timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $W --no-cpu-baseline --no-end-to-end --full > $O/ab_${W}_$tag.json 2> $O/ab_${W}_$tag.err )
   python - "$O/ab_${W}_$tag.json" "$W" "$tag" <<'PY'
 import json, sys
 try:

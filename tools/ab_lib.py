@@ -5,7 +5,7 @@ import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 a, b, rest = sys.argv[1], sys.argv[2], sys.argv[3:]
 code = ("import sys, runpy; sys.path.insert(0, %r); import suffix_array_amd as sa; sa._LIB_NAME = sys.argv[1]; "
-        "sys.argv = ['bench.py', '--steps', '5', '--warmup', '1', '--no-cpu-baseline', '--no-end-to-end'] + sys.argv[2:]; "
+        "sys.argv = ['bench.py', '--steps', '5', '--warmup', '1', '--no-cpu-baseline', '--no-end-to-end', '--full'] + sys.argv[2:]; "
         "runpy.run_path(%r, run_name='__main__')") % (ROOT, os.path.join(ROOT, "bench.py"))
 for leg in (a, b, a, b):
     out = subprocess.run([sys.executable, "-c", code, leg] + rest, capture_output=True, text=True, cwd=ROOT)

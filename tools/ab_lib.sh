@@ -5,9 +5,9 @@ mkdir -p $O
 cp suffix_array_amd/libsuffix_array_amd.so /tmp/base_lib.so
 for w in "$@"; do
   cp /tmp/base_lib.so suffix_array_amd/libsuffix_array_amd.so
-  timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $w --no-cpu-baseline --no-end-to-end --no-batch-api > $O/b_base_$w.json 2> $O/b_base_$w.err
+  timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $w --no-cpu-baseline --no-end-to-end --no-batch-api --full > $O/b_base_$w.json 2> $O/b_base_$w.err
   cp $V suffix_array_amd/libsuffix_array_amd.so
-  timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $w --no-cpu-baseline --no-end-to-end --no-batch-api > $O/b_var_$w.json 2> $O/b_var_$w.err
+  timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $w --no-cpu-baseline --no-end-to-end --no-batch-api --full > $O/b_var_$w.json 2> $O/b_var_$w.err
 done
 cp /tmp/base_lib.so suffix_array_amd/libsuffix_array_amd.so
 python - "$O" "$@" <<'PY'

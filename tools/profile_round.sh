@@ -2,7 +2,7 @@
 # part 1: per WORKLOAD (every BASELINE config + north_star's literal 256 MiB random text): rocprofv3 --kernel-trace --stats of the bench
 #         command on that workload -> <tag>_<workload>_kernel_stats.csv, so that every roofline fraction of the bench line can be
 #         reproduced from profiles/; PMC passes (FETCH_SIZE / WRITE_SIZE, separate runs) on the headline workload -> traffic.json;
-#         the default `python bench.py` line (headline + configs + batch_api + cpu_baseline) and the two-rank rehearsal
+#         the `python bench.py --full` line (headline + configs + batch_api + cpu_baseline) and the two-rank rehearsal
 # part 2: timelines, adversarial families, host path (early download off / on, copy engine probes), small / mid-size latency, next-row timings, A/B knobs
 # everything lands in gpurun_out/<tag>/, to be copied into profiles/ by tools/copy_evidence.sh
 set -e
@@ -17,25 +17,25 @@ WORKLOADS="c3_english_256m c2_uniform_64m c2_uniform_256m c4_dna_1g c5_uniform_5
 if [ "$PART" = "all" ] || [ "$PART" = "1" ]; then
 cd /tmp
 for w in $WORKLOADS; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats_$w -o k -- python3 $R/bench.py --workload $w --steps 5 --warmup 1 --no-cpu-baseline --no-end-to-end --no-configs --no-batch-api > $O/prof_stats_$w.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats_$w -o k -- python3 $R/bench.py --workload $w --steps 5 --warmup 1 --no-cpu-baseline --no-end-to-end --no-configs --no-batch-api --full > $O/prof_stats_$w.log 2>&1
   cp $O/prof_stats_$w/k_kernel_stats.csv $O/${w}_kernel_stats.csv
   rm -rf $O/prof_stats_$w
   echo "kernel stats $w done"
 done
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc/pmc_FETCH_SIZE -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-end-to-end --no-configs --no-batch-api > $O/pmc_fetch.log 2>&1
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc/pmc_WRITE_SIZE -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-end-to-end --no-configs --no-batch-api > $O/pmc_write.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc/pmc_FETCH_SIZE -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-end-to-end --no-configs --no-batch-api --full > $O/pmc_fetch.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc/pmc_WRITE_SIZE -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-end-to-end --no-configs --no-batch-api --full > $O/pmc_write.log 2>&1
 cd $R
 # builds per PMC pass: first touch + profiled build + 1 warm-up + 2 timed = 5 (bench.py measure_resident()); the verification kernels run once
 python tools/pmc_traffic.py $O/pmc $O/traffic.json c3_english_256m 268435456 5
 cp $O/traffic.json profiles/traffic.json     # bench.py quotes the figures from there: measured first, on this code
 find $O/pmc -name "*.csv" -delete
 echo "pmc done"
-timeout -k 10 550 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 550 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "default bench done"
 for w in c3_iid_256m c4_dna_repeats_1g; do
-  timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $w --no-configs --no-batch-api --cpu-sample 67108864 > $O/bench_$w.json 2> $O/bench_$w.err
+  timeout -k 10 300 python bench.py --steps 5 --warmup 1 --workload $w --no-configs --no-batch-api --cpu-sample 67108864 --full > $O/bench_$w.json 2> $O/bench_$w.err
 done
-SA_BENCH_SHARE_GPU=1 timeout -k 10 400 python bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_2ranks_shared_gpu.json 2> $O/bench_2ranks_shared_gpu.err
+SA_BENCH_SHARE_GPU=1 timeout -k 10 400 python bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --full > $O/bench_2ranks_shared_gpu.json 2> $O/bench_2ranks_shared_gpu.err
 python - <<PY
 import json
 r = json.load(open("$O/bench_default.json"))
