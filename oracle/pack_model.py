@@ -70,3 +70,15 @@ def unpack(blob: bytes) -> np.ndarray:
                 if idx < length:
                     out[idx] = (stream >> (i * bits)) & ((1 << bits) - 1)
     return out
+
+
+def block_bytes(sa, b: int) -> bytes:
+    """the bytes of block b in pack(sa) (at offset 16 + b * bits * 16), without packing the rest of the array: a full block
+    is bits * 16 bytes, a partial last block is zero padded and right-trimmed of zero bytes"""
+    length = sa.size
+    bits = sa_bits(length)
+    chunk = np.zeros(128, dtype=np.uint32)
+    part = np.asarray(sa[128 * b:128 * b + 128], dtype=np.uint32)
+    chunk[:part.size] = part
+    buf = pack_block(chunk, bits).astype("<u4").tobytes()
+    return buf if part.size == 128 else buf.rstrip(b"\x00")

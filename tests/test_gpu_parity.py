@@ -1559,28 +1559,10 @@ def test_from_parts_uses_gpu_check(oracle):
 
 
 # ---- next row 8f-4: batched search (reference src/sa.rs:164-253) --------------------------------
-# naive checkers restated from the reference's own tests, src/tests.rs:104-132
-
-def _lcp(a, b):
-    k = 0
-    while k < len(a) and k < len(b) and a[k] == b[k]:
-        k += 1
-    return k
-
-
-def naive_contains(s, pat):
-    return any(pat == s[i:min(len(s), i + len(pat))] for i in range(0, max(len(s) - len(pat), 0) + 1))
-
-
-def naive_search_all(s, pat):
-    return [i for i in range(0, max(len(s) - len(pat), 0) + 1) if pat == s[i:min(len(s), i + len(pat))]]
-
-
-def naive_search_lcp(s, pat):
-    best = 0
-    for i in range(len(s) + 1):
-        best = max(best, _lcp(pat, s[i:]))
-    return pat[:best]
+# naive checkers restated from the reference's own tests (src/tests.rs:104-132) and the reference's search itself
+# (src/sa.rs:123-253) live in oracle/search_model.py, where the CPU suite checks them against each other
+from search_model import naive_contains, naive_search_all, naive_search_lcp  # noqa: E402
+import search_model  # noqa: E402
 
 
 def _bytes_with_pat(rng, n):
@@ -1676,6 +1658,130 @@ def test_batched_search_on_device_resident_index(oracle):
     ix.close()
 
 
+# Exact parity with the reference's search (oracle/search_model.py): every output of sa_amd_index_search -- contains, the slot
+# range of search_all, the start AND length of search_lcp -- equal to the model's, not only consistent with the text.  The
+# reference picks a particular start (src/sa.rs:231-252): Ok(i) gives start..s.len(), and between two neighbours of equal
+# lcp it takes sa[i], not sa[i - 1].
+
+def _tie(s, arr, p):
+    """the pattern's insertion point (no bucket) lies between two suffixes of EQUAL lcp with it, and no suffix equals it"""
+    i, _ = search_model.search_all(s, arr, p)
+    if not 0 < i < len(arr) or search_model.cmp_suffix(s, int(arr[i]), p) == 0:
+        return False
+    return search_model.lcp(p, s, int(arr[i - 1])) == search_model.lcp(p, s, int(arr[i]))
+
+
+def _exact_search_patterns(rng, s, arr):
+    n = len(s)
+    pats = [b"", b"\x00", b"\xff", b"\x00\xff", b"\xff\x00", b"\xff\xfe\xfd", b"e\x00", b"e\xff", b"q!", b"a\x01", b"\x00a",
+            s, s + b"\x00", s + b"a", s[:-1] + b"\x00", s[:-1] + b"\xff"]
+    for k in (1, 2, 3, n // 2, n - 1, n - 64, n - 65):             # equal to a suffix, and a suffix with one byte more
+        if 0 <= k < n:
+            pats += [s[k:], s[k:] + b"\x00", s[k:] + b"\xff"]
+    for ln in (63, 64, 65, 127, 128, 129, 4096, 4097, 6000):        # one, two and many 64-byte chunks of wave_compare
+        for _ in range(3):
+            i = int(rng.integers(0, max(1, n - ln + 1)))
+            p = s[i:i + ln]
+            pats.append(p)
+            if len(p) > 1:
+                pats.append(p[:-1] + bytes([(p[-1] + 1) & 255]))    # differs in the last byte only
+                m = len(p) // 2
+                pats.append(p[:m] + bytes([p[m] ^ 0x80]) + p[m + 1:])
+            pats.append(p + bytes([int(rng.integers(0, 256))]))
+    # ties: a prefix of the text followed by a byte between what follows its occurrences
+    for _ in range(40):
+        if n < 8:
+            break
+        i = int(rng.integers(0, n - 4)); ln = int(rng.integers(1, 6))
+        for c in (0x00, 0x21, 0x2f, 0x61, 0x6f, 0x7a, 0xff, int(rng.integers(0, 256))):
+            pats.append(s[i:i + ln] + bytes([c]))
+    for _ in range(100):
+        if n == 0:
+            break
+        i = int(rng.integers(0, n)); ln = int(rng.integers(1, 40))
+        p = s[i:i + ln]
+        if rng.random() < 0.4:
+            p = p[:-1] + bytes([int(rng.integers(0, 256))])
+        pats.append(p)
+    return pats
+
+
+def _search_texts_for_parity():
+    adv = adversarial_cases()
+    return {"english_200k": corpus.english(200_000, 12).tobytes(),
+            "english_corpus_repeats": corpus.english_corpus(600_000, 7, dup_fraction=0.4).tobytes(),
+            "a_run": adv["a_run"], "ab_period": adv["ab_period"], "fib": adv["fib"], "thue_morse": adv["thue_morse"],
+            "n0": b"", "n1": b"a", "n2": b"ab", "n2_ffs": b"\xff\xff"}
+
+
+def _assert_same_search(got, exp, pats, what):
+    for k in ("contains", "lo", "hi", "lcp_start", "lcp_len"):
+        bad = np.flatnonzero(np.asarray(got[k]) != np.asarray(exp[k]))
+        assert bad.size == 0, (what, k, bad.size, pats[int(bad[0])][:80], got[k][bad[0]], exp[k][bad[0]])
+
+
+@pytest.mark.parametrize("name", sorted(_search_texts_for_parity()))
+def test_search_equals_the_reference_exactly(oracle, name):
+    """all five outputs of the batched search equal oracle/search_model.py's restatement of src/sa.rs:123-253, on a fresh
+    DeviceIndex (no bucket table: the whole array), again after buckets() (get_bucket ranges, the empty-bucket branch of
+    search_lcp), and through the SuffixArray one-pattern wrappers without and with enable_buckets; patterns of 63-129 and
+    4096+ bytes (wave_compare over many chunks), longer than / equal to the text or a suffix, with 0x00 / 0xff, empty (c0, c1)
+    buckets, the empty pattern, and ties between the two neighbours of the insertion point"""
+    s = _search_texts_for_parity()[name]
+    text = np.frombuffer(s, dtype=np.uint8) if s else np.zeros(0, dtype=np.uint8)
+    arr = oracle.sais(s)
+    rng = np.random.default_rng(len(s) + 1)
+    pats = _exact_search_patterns(rng, s, arr)
+    if name == "english_200k":
+        assert sum(_tie(s, arr, p) for p in pats) >= 20           # the rule for equal lcp really is exercised
+    bkt = oracle.bucket_table(s)
+    assert any(len(p) > 1 and bkt[p[0] * 257 + p[1] + 1] == bkt[p[0] * 257 + p[1] + 2] for p in pats)   # an empty bucket
+    ix = sa.DeviceIndex(text)
+    assert np.array_equal(ix.suffix_array(), arr)
+    empty = ix.search([])
+    assert all(v.size == 0 for v in empty.values())                 # count = 0
+    _assert_same_search(ix.search(pats), search_model.search_many(s, arr, pats), pats, "no buckets")
+    assert np.array_equal(ix.buckets(), bkt)
+    _assert_same_search(ix.search(pats), search_model.search_many(s, arr, pats, bkt), pats, "buckets")
+    ix.close()
+    obj = sa.SuffixArray(s)
+    few = pats[:: max(1, len(pats) // 40)]
+    for table in (None, bkt):
+        if table is not None:
+            obj.enable_buckets()
+        for p in few:
+            c, lo, hi, st, ln = search_model.search(s, arr, p, table)
+            assert obj.contains(p) == c, p[:80]
+            assert np.array_equal(obj.search_all(p), arr[lo:hi]), p[:80]
+            assert obj.search_lcp(p) == range(st, st + ln), p[:80]
+
+
+def test_search_batch_of_many_thousand_blocks(oracle):
+    """one call with 100 003 patterns (25 001 workgroups of four waves): every slot of the output is the answer to ITS pattern
+    (2 000 distinct patterns in a shuffled order), with and without the bucket table"""
+    s = corpus.english(200_000, 13).tobytes()
+    text = np.frombuffer(s, dtype=np.uint8)
+    arr = oracle.sais(s)
+    rng = np.random.default_rng(17)
+    uniq = list(dict.fromkeys(_exact_search_patterns(rng, s, arr)))
+    while len(uniq) < 2000:
+        i = int(rng.integers(0, len(s) - 60)); p = s[i:i + int(rng.integers(1, 60))]
+        if rng.random() < 0.5:
+            p = p[:-1] + bytes([int(rng.integers(0, 256))])
+        if p not in uniq:
+            uniq.append(p)
+    which = rng.integers(0, len(uniq), 100_003)
+    pats = [uniq[int(k)] for k in which]
+    ix = sa.DeviceIndex(text, arr)
+    for table in (None, oracle.bucket_table(s)):
+        if table is not None:
+            ix.buckets()
+        exp = search_model.search_many(s, arr, uniq, table)
+        got = ix.search(pats)
+        _assert_same_search(got, {k: v[which] for k, v in exp.items()}, pats, "batch")
+    ix.close()
+
+
 # ---- next row 8f-3: packed format (reference src/packed_sa.rs; byte-level parity unpinned) ---------
 
 def test_pack_matches_model_and_round_trips(oracle):
@@ -1691,6 +1797,39 @@ def test_pack_matches_model_and_round_trips(oracle):
         sa.unpack(b"XXXX" + blob[4:])
     with pytest.raises(ValueError):
         sa.unpack(blob[:-3])
+
+
+@pytest.mark.parametrize("k", [17, 18, 19, 20, 21, 23, 25, 27, 28, 29])
+def test_pack_widths_17_to_30(k):
+    """lengths 2^k and 2^k + 1: bit widths k and k + 1 (src/packed_sa.rs:127-129), 17 .. 30 over the parameters.  Values
+    fill the whole width (every bit set somewhere; the packer does not look at what the values mean) for one length and are
+    a permutation for the other.  Byte equality with pack_model on the whole blob up to 2^20 entries, on the first, last
+    and ~2 000 random full blocks and the trimmed partial last block above; the header; the round trip"""
+    import pack_model
+    rng = np.random.default_rng(k)
+    for length in (1 << k, (1 << k) + 1):
+        bits = pack_model.sa_bits(length)
+        assert bits == (k if length == 1 << k else k + 1)
+        if length & 1:
+            arr = rng.integers(0, 1 << bits, length, dtype=np.uint32)
+            arr[-1] = (1 << bits) - 1
+        else:
+            arr = rng.permutation(length).astype(np.uint32) if k <= 24 else (np.arange(length, dtype=np.uint32) ^ np.uint32(0x5A5A5A5A & (length - 1)))
+        blob = sa.pack(arr)
+        blocks = (length + 127) // 128
+        assert blob[:4] == b"SA4x" and int.from_bytes(blob[4:8], "little") == length
+        assert int.from_bytes(blob[8:16], "little") == len(blob) - 16
+        assert len(blob) - 16 == (blocks - 1) * bits * 16 + len(pack_model.block_bytes(arr, blocks - 1))
+        if length <= (1 << 20) + 1:
+            assert blob == pack_model.pack(arr), length
+        else:
+            full = length // 128
+            for b in [0, full - 1] + rng.integers(0, full, 2000).tolist() + ([full] if length % 128 else []):
+                at = 16 + b * bits * 16
+                exp = pack_model.block_bytes(arr, b)
+                assert blob[at:at + len(exp)] == exp, (length, b)
+        assert np.array_equal(sa.unpack(blob), arr), length
+        del blob
 
 
 def test_pack_correctness_property_of_the_reference(oracle):
