@@ -92,9 +92,11 @@ class HelperPool {
     int want_ = 0;             // threads the pool should have
     bool have_cpus_ = false;
     cpu_set_t cpus_;
+    static inline thread_local HelperPool *owner_ = nullptr;      // on a helper thread: the pool it belongs to
 
     void worker()
     {
+        owner_ = this;
         if (have_cpus_) (void)sched_setaffinity(0, sizeof(cpus_), &cpus_);
         std::unique_lock<std::mutex> lk(mu_);
         for (;;) {
@@ -211,9 +213,11 @@ public:
         a.queued = false;
     }
     // runs fn once on a helper thread of this pool (its CPU affinity decides where first-touched pages land);
-    // on the calling thread when the pool has no helpers
+    // on the calling thread when the pool has no helpers, or when the caller IS one of them (an early puller that allocates
+    // its stage block: queueing the job and waiting for it would hang once every helper waits the same way)
     void run_on_helper(const std::function<void()> &fn)
     {
+        if (owner_ == this) { fn(); return; }
         bool have;
         {
             std::lock_guard<std::mutex> lk(mu_);

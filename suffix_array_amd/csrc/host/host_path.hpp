@@ -37,8 +37,7 @@ static double wall_ms()
 struct HostTiming { double acquire = 0, h2d = 0, build = 0, d2h = 0, release = 0, total = 0; int staged = 0; double early = 0, spill = 0; };      // early: fraction of the array that travelled before the build was done
 static thread_local HostTiming g_host_timing;
 
-// ---- device -> caller's pageable buffer through pinned staging + helper threads ----
-constexpr size_t STAGE_BYTES = (size_t)16 << 20;
+// ---- device -> caller's pageable buffer through pinned staging + helper threads (STAGE_BYTES: host/tuning.hpp) ----
 constexpr int STAGE_COUNT = 3;
 
 // Device -> pinned stage by the copy engine, or by a copy KERNEL that stores into the mapped block.  Measured
@@ -64,10 +63,9 @@ __global__ __launch_bounds__(256) void k_copy_to_host(const uint32_t *__restrict
     }
     if (blockIdx.x == 0 && threadIdx.x < (words & 3)) dst[n16 * 4 + threadIdx.x] = src[n16 * 4 + threadIdx.x];
 }
-static bool kernel_d2h() { return env_int("SA_AMD_NO_KERNEL_D2H", 0, 0, 1) == 0; }
 static int copy_to_stage(void *stage, const void *dsrc, size_t bytes, hipStream_t st, int blocks)
 {
-    if (kernel_d2h() && (bytes & 3) == 0 && (((uintptr_t)dsrc) & 3) == 0 && bytes >= 4) {
+    if ((bytes & 3) == 0 && (((uintptr_t)dsrc) & 3) == 0 && bytes >= 4) {
         hipLaunchKernelGGL(k_copy_to_host, dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t *)dsrc, (uint32_t *)stage, bytes / 4);
         return hip_status(hipGetLastError());
     }
@@ -79,7 +77,7 @@ constexpr int D2H_BLOCKS = 128;             // workgroups of a download's copy k
 // is cut into `copy_threads` page-aligned slices that the persistent helpers of the device's NUMA node (and the caller
 // itself) move into the caller's buffer, then the stage takes the chunk STAGE_COUNT further on.  The DMA of the
 // following chunks runs meanwhile.  No thread is created or joined per call (helpers.hpp).
-static int staged_download(void *dst_host, const void *dsrc, size_t bytes, hipStream_t st, int copy_threads, int device, int node)
+static int staged_download(void *dst_host, const void *dsrc, size_t bytes, hipStream_t st, const HostTuning &ht, int device, int node)
 {
     PinBlock stage[STAGE_COUNT];
     hipEvent_t ev[STAGE_COUNT] = { nullptr, nullptr, nullptr };
@@ -89,11 +87,11 @@ static int staged_download(void *dst_host, const void *dsrc, size_t bytes, hipSt
     for (int i = 0; i < STAGE_COUNT && rc == SA_AMD_OK; ++i) rc = hip_status(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
     const size_t nchunk = (bytes + STAGE_BYTES - 1) / STAGE_BYTES;
     auto len = [&](size_t c) { return c + 1 < nchunk ? STAGE_BYTES : bytes - c * STAGE_BYTES; };
-    const bool always = env_int("SA_AMD_KERNEL_D2H_ALWAYS", 0, 0, 1) != 0;
+    const bool always = ht.kernel_d2h_always;
     std::atomic<int> &state = g_engine_slow[(unsigned)device & 63u];
-    bool by_kernel = kernel_d2h() && (always || state.load(std::memory_order_relaxed) == 1);
+    bool by_kernel = ht.kernel_d2h && (always || state.load(std::memory_order_relaxed) == 1);
     // the timed chunk: the second (a whole one; a process's very first copy into a stage block takes milliseconds of set-up)
-    const bool timed = kernel_d2h() && !always && nchunk >= 3;
+    const bool timed = ht.kernel_d2h && !always && nchunk >= 3;
     const size_t timed_chunk = 1;
     if (timed && rc == SA_AMD_OK) rc = hip_status(hipEventCreate(&e0));
     if (timed && rc == SA_AMD_OK) rc = hip_status(hipEventCreate(&e1));
@@ -110,8 +108,8 @@ static int staged_download(void *dst_host, const void *dsrc, size_t bytes, hipSt
     };
     if (rc == SA_AMD_OK) {
         HelperPool &hp = helper_pool(node);
-        const int T = copy_threads < 1 ? 1 : copy_threads;
-        const bool trace = env_int("SA_AMD_VERBOSE", 0, 0, 9) >= 3;
+        const int T = ht.copy_threads < 1 ? 1 : ht.copy_threads;
+        const bool trace = ht.verbose >= 3;
         double t_wait = 0, t_copy = 0, t_mark = trace ? wall_ms() : 0;
         const bool started_by_kernel = by_kernel;
         for (size_t c = 0; c < nchunk && c < (size_t)STAGE_COUNT && rc == SA_AMD_OK; ++c) rc = issue(c);
@@ -188,7 +186,81 @@ struct PooledPin {
     PooledPin &operator=(const PooledPin &) = delete;
 };
 
-static int64_t lanes_min_n() { return env_int("SA_AMD_LANES_MIN_N", (int64_t)32 << 20, 0, (int64_t)1 << 40); }
+// ---- who writes the caller's array ----
+// After the upload, a byte of the caller's array is stored only by
+//  - the copy that delivers its final value: an early chunk (EarlyPull), the staged or plain download, or the early patch
+//    (download_array), or
+//  - the landing zone of the values sent behind the early chunks, inside the byte range download_array reserves for it at the end
+//    of the array: no early chunk reaches it, and the download overwrites it only after the patch job has been joined.
+// The page-mapping helpers (OutputPrefault) run beside all of them and never store a value they read: whole pages are mapped by
+// madvise(MADV_POPULATE_WRITE), which leaves the contents alone; the pages it does not cover (partial pages at the ends of a
+// piece, every page where the kernel refuses the call) get one atomic OR of 0 -- a locked read-modify-write (x86 `lock or`) that
+// a concurrent store of the download cannot be lost to, where a plain load and store back could write an old value over a final
+// one.  (The edge pages are touched rather than skipped so that a host without the madvise call still maps every page ahead.)
+
+// The caller's array is usually FRESH memory (`vec![0; n + 1]`, reference src/sa.rs:24: zero pages that are mapped on first
+// write): helper threads map its pages while the GPU builds, so the download later copies into mapped memory (C3, fresh buffer:
+// d2h 26-31 -> 20 ms).  SA_AMD_NO_PREFAULT=1: off.
+// In the order the download will fill the array, a staging chunk's worth (16 MiB) at a time, helper t taking the units
+// t, t + T, ...: when the build is done before the whole array is mapped (a 10 ms build of 512 MiB of random bytes against
+// 25-70 ms for the 2 GiB of its array) the helpers stop after the unit they are in and the download starts at once --
+// into the mapped front part at full speed, page-faulting the rest in as it goes, which costs less than waiting for it.
+// When the build ends first (random bytes: 4.6 ms of build against 20 ms of page mapping for a 1 GiB array), all but a few
+// helpers stop after the 2 MiB piece they are in -- the download needs them -- and the few go on mapping AHEAD of the
+// download, which would otherwise fault every page in from its copy threads (SA_AMD_PREFAULT_KEEP, default 3; 0: all stop).
+class OutputPrefault {
+    HelperPool &hp_;
+    std::atomic<bool> stop_{false};
+    std::atomic<size_t> next_{0};
+    HelperPool::Async job_;
+
+    // one byte per page (volatile: a compiler turns a plain idempotent atomic into a fence or a load, which maps nothing)
+    static void touch(uintptr_t from, uintptr_t to)
+    {
+        while (from < to) {
+            __atomic_fetch_or((volatile char *)from, (char)0, __ATOMIC_RELAXED);
+            from = (from + 4096) & ~(uintptr_t)4095;      // first byte of the next page
+        }
+    }
+
+public:
+    explicit OutputPrefault(HelperPool &hp) : hp_(hp) {}
+    ~OutputPrefault() { stop_.store(true); next_.store(~(size_t)0 >> 1); hp_.finish(job_); }      // (no unit is started any more)
+
+    void start(char *dst, size_t bytes, int threads, int keep)
+    {
+        const size_t units = (bytes + STAGE_BYTES - 1) / STAGE_BYTES;
+        hp_.start(job_, threads, [this, dst, bytes, units, keep](int t) {
+            // (2 MiB at a time inside a unit: the build waits for the piece a helper is in when it ends -- with whole 16 MiB
+            // units a 0.8 ms build of a 16 MiB text took 1.5 ms into a fresh buffer)
+            constexpr size_t PIECE = (size_t)2 << 20;
+            auto over = [&]() { return t >= keep && stop_.load(std::memory_order_relaxed); };
+            for (;;) {
+                if (over()) break;
+                const size_t u = next_.fetch_add(1, std::memory_order_relaxed);      // units in the order the download fills them
+                if (u >= units) break;
+                const size_t ub = u * STAGE_BYTES, ue = ub + STAGE_BYTES < bytes ? ub + STAGE_BYTES : bytes;
+                for (size_t b = ub; b < ue && !over(); b += PIECE) {
+                    const size_t e = b + PIECE < ue ? b + PIECE : ue;
+                    const uintptr_t a = (uintptr_t)(dst + b), end = (uintptr_t)(dst + e);
+                    // whole pages: one madvise call maps them writable without a trap per page (Linux >= 5.14; contents untouched)
+                    const uintptr_t pa = (a + 4095) & ~(uintptr_t)4095, pe = end & ~(uintptr_t)4095;
+                    if (pe > pa && madvise((void *)pa, pe - pa, SA_MADV_POPULATE_WRITE) == 0) {
+                        touch(a, pa < end ? pa : end);
+                        touch(pe > a ? pe : a, end);
+                    } else touch(a, end);
+                }
+            }
+        });
+    }
+    // the build is over (usually so is the mapping): no further unit is started -- wait (SA_AMD_PREFAULT_WAIT=1, A/B): every
+    // page is mapped before the download begins
+    void build_done(bool wait)
+    {
+        if (wait) hp_.finish(job_);
+        else stop_.store(true, std::memory_order_relaxed);
+    }
+};
 
 // ---- early download: the front of the array travels while the last refinement rounds run (EarlyDownload, host/pipeline.hpp) ----
 // From the moment the build says that only the slots of its tied list can still change until the build is done, a few helper
@@ -196,53 +268,130 @@ static int64_t lanes_min_n() { return env_int("SA_AMD_LANES_MIN_N", (int64_t)32 
 // their own) -> the caller's buffer (memcpy by the helper that asked for the chunk; one thread moves ~28 GB/s, four keep up with
 // the link).  (A plain hipMemcpy into the pageable buffer from one helper reaches the link rate too -- the runtime stages it
 // itself -- but the build ran 0.5 ms slower beside it, same box; with the pinned blocks the rounds keep their pace: 8.51 against
-// 8.65 ms for rounds 3-9 of C3 in the kernel traces with the copy off / on.)
+// 8.65 ms for rounds 3-9 of C3 in the kernel traces with the copy off / on.)  Each puller takes its staging block from the pool
+// itself, on its helper thread (run_on_helper runs inline there), so the blocks are first-touched on the GPU's node.
 // The entries that were still tied at that moment arrive with stale values: the build sends their final values behind
 // (compacted, with the bitmap that says which entries they are), the helpers patch them in while the rest of the array is
 // downloaded as before.  C3 (256 MiB): the copy starts ~9 ms before the build ends, 44 % of the array is there when it does.
+// SA_AMD_EARLY_DIV = d: the copy starts when at most n / d suffixes are still tied (0: never); the chunks it takes before the build
+// ends are bounded so that what has to be sent behind them fits into the part of the caller's array that is still free.
 constexpr int EARLY_PULLERS = 4;
-struct EarlyPull {
-    size_t chunk = STAGE_BYTES;              // bytes per copy (SA_AMD_EARLY_CHUNK_BYTES; a multiple of 4096, at most a staging block)
-    std::atomic<size_t> issued{0};          // chunks handed to the pullers (started or about to start)
-    std::atomic<bool> stop{false};
-    std::atomic<int> rc{SA_AMD_OK};
-    std::unique_ptr<std::atomic<uint8_t>[]> done;      // per chunk: it is in the caller's buffer
-    char *dst = nullptr;
-    const char *src = nullptr;
-    size_t bytes = 0, nchunk = 0, max_chunks = 0;
-    hipStream_t cst = nullptr;
-    hipEvent_t after = nullptr;
-    int device = -1, node = -1;
-    void run(int)                           // on EARLY_PULLERS helper threads
+class EarlyPull {
+    HelperPool &hp_;
+    int device_, node_;
+    hipStream_t cst_ = nullptr;             // the pullers' copy stream
+    size_t chunk_ = STAGE_BYTES;            // bytes per copy (a multiple of 4096, at most a staging block)
+    int64_t wait_chunks_ = 0;               // SA_AMD_EARLY_WAIT_CHUNKS
+    char *dst_ = nullptr;
+    const char *src_ = nullptr;
+    size_t bytes_ = 0, nchunk_ = 0, max_chunks_ = 0;
+    std::atomic<size_t> issued_{0};         // chunks handed to the pullers (started or about to start)
+    std::atomic<bool> stop_{false};
+    std::atomic<int> rc_{SA_AMD_OK};
+    std::unique_ptr<std::atomic<uint8_t>[]> done_;      // per chunk: it is in the caller's buffer
+    HelperPool::Async job_;
+
+    void run()                              // on EARLY_PULLERS helper threads
     {
-        if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); rc.store(SA_AMD_EHIP); return; }
+        if (hipSetDevice(device_) != hipSuccess) { (void)hipGetLastError(); rc_.store(SA_AMD_EHIP); return; }
         PinBlock stage;
         hipEvent_t ev = nullptr;
-        int r = pool().pinned(STAGE_BYTES, node, device, &stage);
+        int r = pool().pinned(STAGE_BYTES, node_, device_, &stage);
         if (r == SA_AMD_OK) r = hip_status(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         while (r == SA_AMD_OK) {
-            const size_t c = issued.fetch_add(1);
-            if (c >= max_chunks || stop.load()) break;      // (a chunk taken but not copied: the caller downloads it with the rest)
-            const size_t b = c * chunk, len = b + chunk < bytes ? chunk : bytes - b;
+            const size_t c = issued_.fetch_add(1);
+            if (c >= max_chunks_ || stop_.load()) break;    // (a chunk taken but not copied: the caller downloads it with the rest)
+            const size_t b = c * chunk_, len = b + chunk_ < bytes_ ? chunk_ : bytes_ - b;
             // (the copy engine here, whatever state it is in: copy kernels beside the last rounds of the build cost C3 more build time
             // than they saved -- build 60.9 against 50.7 ms on a stream like the build's, 55.6 with 32 workgroups on a stream of the
             // lowest priority, end to end 75.4 against 70.0 with the engine at 55 GB/s and 75.2 against 74.0 with it at 29.5)
-            r = hip_status(hipMemcpyAsync(stage.p, src + b, len, hipMemcpyDeviceToHost, cst));
-            if (r == SA_AMD_OK) r = hip_status(hipEventRecord(ev, cst));
+            r = hip_status(hipMemcpyAsync(stage.p, src_ + b, len, hipMemcpyDeviceToHost, cst_));
+            if (r == SA_AMD_OK) r = hip_status(hipEventRecord(ev, cst_));
             if (r == SA_AMD_OK) r = hip_status(hipEventSynchronize(ev));
             if (r != SA_AMD_OK) break;
-            memcpy(dst + b, stage.p, len);
-            done[c].store(1);
+            memcpy(dst_ + b, stage.p, len);
+            done_[c].store(1);
         }
-        if (r != SA_AMD_OK) { (void)hipGetLastError(); rc.store(r); }
+        if (r != SA_AMD_OK) { (void)hipGetLastError(); rc_.store(r); }
         if (ev) (void)hipEventDestroy(ev);
         pool().release_pinned(stage);
     }
-    size_t copied() const                   // chunks of the front that have arrived (call after the pullers have been joined)
+    void begin(hipEvent_t ev)               // EarlyDownload::start
+    {
+        // what is sent behind the early chunks -- tile offsets, bitmap, at most min(tied at the snapshot, entries taken) final
+        // values -- lands in the end of the caller's array: the most chunks K with K chunks + all that <= the array
+        size_t k = 0;
+        for (;;) {
+            const size_t b = (k + 1) * chunk_, e = b / 4;
+            const size_t holes = (size_t)early.m_snap < e ? (size_t)early.m_snap : e;
+            if (b + b / 32 + b / 2048 + holes * 4 + 16384 > bytes_) break;
+            ++k;
+        }
+        max_chunks_ = k;
+        if (hipStreamWaitEvent(cst_, ev, 0) != hipSuccess) { (void)hipGetLastError(); return; }      // (no copy before the marks and SA[0] are in place)
+        hp_.start(job_, EARLY_PULLERS, [this](int) { run(); });
+    }
+    int64_t halt()                          // EarlyDownload::stop: the entries [0, x) handed to the pullers
+    {
+        if (wait_chunks_ > 0) {
+            const size_t want = (size_t)wait_chunks_ < max_chunks_ ? (size_t)wait_chunks_ : max_chunks_;
+            const double t_give_up = wall_ms() + 2000.0;
+            for (;;) {
+                size_t have = 0;
+                while (have < want && done_[have].load()) ++have;
+                if (have >= want || rc_.load() != SA_AMD_OK || wall_ms() > t_give_up) break;
+                std::this_thread::yield();
+            }
+        }
+        stop_.store(true);
+        size_t k = issued_.load();
+        if (k > max_chunks_) k = max_chunks_;
+        const size_t b = k * chunk_;
+        return (int64_t)((b < bytes_ ? b : bytes_) / 4);
+    }
+
+public:
+    EarlyDownload early;                    // the build's hook, and what it sends behind the early chunks
+
+    EarlyPull(HelperPool &hp, int device, int node) : hp_(hp), device_(device), node_(node) {}
+    ~EarlyPull() { end(); }
+
+    // gives the build its hook when the array is large enough (off: entry of slot 0 in the array, 1 with the sentinel).  (The
+    // pullers are helper threads: a pool without helpers would run them only when the build is over.)
+    void arm(const HostTuning &ht, int32_t n, int off, uint32_t *dst, const uint32_t *src, size_t bytes)
+    {
+        chunk_ = ht.early_chunk;
+        if (ht.early_div <= 0 || bytes < ht.early_min || bytes < 4 * chunk_ || hp_.helpers() <= 0) return;
+        if (pool().stream(device_, &cst_) != SA_AMD_OK) { cst_ = nullptr; return; }
+        wait_chunks_ = ht.early_wait;
+        dst_ = (char *)dst; src_ = (const char *)src; bytes_ = bytes;
+        nchunk_ = (bytes + chunk_ - 1) / chunk_;
+        done_.reset(new std::atomic<uint8_t>[nchunk_]);
+        for (size_t c = 0; c < nchunk_; ++c) done_[c].store(0);
+        early.off = off;
+        early.threshold = (int64_t)n / ht.early_div;
+        early.start = [this](hipEvent_t ev) { begin(ev); };
+        early.stop = [this]() { return halt(); };
+    }
+    EarlyDownload *hook() { return early.start ? &early : nullptr; }
+    void stop() { stop_.store(true); }
+    int join()                              // the pullers are done; their first failure
+    {
+        stop_.store(true);
+        hp_.finish(job_);
+        return rc_.load();
+    }
+    size_t copied_bytes() const             // the front of the array that has arrived (after join)
     {
         size_t c = 0;
-        while (c < nchunk && c < max_chunks && done[c].load()) ++c;
-        return c;
+        while (c < nchunk_ && c < max_chunks_ && done_[c].load()) ++c;
+        return c * chunk_ < bytes_ ? c * chunk_ : bytes_;
+    }
+    void end()                              // join, and give back the event and the copy stream
+    {
+        join();
+        if (early.ev) { (void)hipEventDestroy(early.ev); early.ev = nullptr; }
+        if (cst_) { (void)hipStreamSynchronize(cst_); pool().release_stream(device_, cst_); cst_ = nullptr; }
     }
 };
 
@@ -271,6 +420,171 @@ static std::function<void(int)> early_patch_task(uint32_t *out, const uint32_t *
     };
 }
 
+struct HelperJob { HelperPool &hp; HelperPool::Async a; ~HelperJob() { hp.finish(a); } };      // joined on every path out of its scope
+
+// The array [src, src + bytes) into the caller's buffer, the early chunks and their patch included.  The values sent behind --
+// [tile offsets | bitmap | final values] -- land in the END of the caller's array (free until the rest of the download gets
+// there); the helpers patch the early part from them while the rest of the array travels.
+static int download_array(uint32_t *out, const uint32_t *src, size_t bytes, bool staged, hipStream_t st, const HostTuning &ht,
+                          int device, int node, EarlyPull &pull, HostTiming &tm)
+{
+    HelperPool &hp = helper_pool(node);
+    const EarlyDownload &early = pull.early;
+    int rc = SA_AMD_OK;
+    size_t have = 0;                                            // bytes of the array that are (or are about to be) in the caller's buffer
+    size_t zone_at = bytes;                                     // where the values sent behind have landed: free again once the patch is done
+    HelperJob patch{ hp, {} };                                  // (the patch tasks hold pointers into the caller's array)
+    if (early.started && early.covered > 0) {
+        const size_t covered = (size_t)early.covered, got = covered * 4 < bytes ? covered * 4 : bytes;
+        const size_t tiles_c = (covered + EARLY_TILE - 1) / EARLY_TILE;
+        const size_t off_b = align_up((tiles_c + 1) * 4, 256), bits_b = align_up(tiles_c * (EARLY_TILE / 8), 256), holes_b = (size_t)early.holes * 4;
+        const size_t aux = off_b + bits_b + holes_b;
+        if (got + aux + 8192 <= bytes) {
+            char *zone = (char *)out + ((bytes - aux) & ~(size_t)4095);
+            rc = hip_status(hipMemcpyAsync(zone, early.d_tile_off, (tiles_c + 1) * 4, hipMemcpyDeviceToHost, st));
+            if (rc == SA_AMD_OK) rc = hip_status(hipMemcpyAsync(zone + off_b, early.d_bits, tiles_c * (EARLY_TILE / 8), hipMemcpyDeviceToHost, st));
+            if (rc == SA_AMD_OK && holes_b) rc = hip_status(hipMemcpyAsync(zone + off_b + bits_b, early.d_holes, holes_b, hipMemcpyDeviceToHost, st));
+            if (rc == SA_AMD_OK) rc = hip_status(hipStreamSynchronize(st));
+            const int rp = pull.join();                         // (the chunk that was in flight when the build ended has arrived by now)
+            if (rc == SA_AMD_OK) rc = rp;
+            // chunks the puller took but did not copy (it saw the stop first) are downloaded with the rest
+            const size_t copied_b = pull.copied_bytes();
+            if (rc == SA_AMD_OK && copied_b > 0) {
+                const int pt = ht.copy_threads > 8 ? 8 : ht.copy_threads;
+                hp.start(patch.a, pt, early_patch_task(out, (const uint32_t *)zone, (const uint32_t *)(zone + off_b),
+                                                       (const uint32_t *)(zone + off_b + bits_b), copied_b / 4, pt));
+                have = copied_b;
+                zone_at = (size_t)(zone - (char *)out);
+                tm.early = (double)copied_b / (double)bytes;
+            }
+        }
+        // (else: the early chunks are simply downloaded again with everything else)
+    }
+    const int rp = pull.join();
+    if (rc == SA_AMD_OK) rc = rp;
+    auto fetch = [&](size_t from, size_t to) {
+        if (rc != SA_AMD_OK || from >= to) return;
+        if (staged) {
+            tm.staged = ht.copy_threads;
+            rc = staged_download((char *)out + from, (const char *)src + from, to - from, st, ht, device, node);
+        } else {
+            rc = hip_status(hipMemcpyAsync((char *)out + from, (const char *)src + from, to - from, hipMemcpyDeviceToHost, st));
+            if (rc == SA_AMD_OK) rc = hip_status(hipStreamSynchronize(st));      // (the turn ends when the copy has)
+        }
+    };
+    const size_t split = zone_at < bytes ? (zone_at > have ? zone_at & ~(STAGE_BYTES - 1) : have) : bytes;
+    fetch(have, split < have ? have : split);
+    hp.finish(patch.a);                                         // the landing zone is free from here on
+    fetch(split < have ? have : split, bytes);
+    return rc;
+}
+
+// Small texts: copy -> ONE launch -> copy.  The kernel reads the text from and writes the array to a pooled PINNED host
+// block over PCIe (zero-copy; hipHostMalloc memory is mapped into the device), so there is no device block, no
+// hipMemcpy and no read-back: 0.2 ms -> tens of microseconds for the sizes of the reference's own tests (src/tests.rs:14).
+static_assert(SM_MAX_N == 8192, "env_small_max (host/tuning.hpp) clamps SA_AMD_SMALL_MAX to SM_MAX_N");
+static int build_host_small(const uint8_t *T, uint32_t *SA_host, int32_t n, bool with_sentinel, int device, double t_begin)
+{
+    const size_t tb = align_up((size_t)n, 256), need = tb + ((size_t)n + 1) * 4;
+    PooledStream ps(device);
+    PooledPin pp;
+    int rc = pool().stream(device, &ps.st);
+    if (rc != SA_AMD_OK) return rc;
+    hipStream_t st = ps.st;
+    rc = pool().pinned(need < ((size_t)64 << 10) ? ((size_t)64 << 10) : need, -1, device, &pp.b);
+    if (rc != SA_AMD_OK) return rc;
+    PinBlock &pb = pp.b;
+    void *dbase = nullptr;
+    rc = hip_status(hipHostGetDevicePointer(&dbase, pb.p, 0));
+    if (rc == SA_AMD_OK) {
+        memcpy(pb.p, T, (size_t)n);
+        if (n <= SM_LITE_SINGLE_N)
+            hipLaunchKernelGGL((k_small_sa_lite), dim3(1), dim3(SM_LITE_THREADS), 0, st, (const uint8_t *)dbase, (uint32_t *)((char *)dbase + tb), (int)n,
+                               (uint32_t *)nullptr);
+        else
+            hipLaunchKernelGGL((k_small_sa), dim3(1), dim3(SM_THREADS), 0, st, (const uint8_t *)dbase, (uint32_t *)((char *)dbase + tb), (int)n,
+                               (uint32_t *)nullptr);
+        rc = hip_status(hipGetLastError());
+        const int rs = hip_status(hipStreamSynchronize(st));
+        if (rc == SA_AMD_OK) rc = rs;
+        if (rc == SA_AMD_OK) {
+            const uint32_t *src = (const uint32_t *)((const char *)pb.p + tb);
+            if (with_sentinel) memcpy(SA_host, src, ((size_t)n + 1) * 4); else memcpy(SA_host, src + 1, (size_t)n * 4);
+        }
+    }
+    { sa_amd_stats z; memset(&z, 0, sizeof(z)); g_last_stats = z; }
+    HostTiming tm;
+    tm.total = tm.build = wall_ms() - t_begin;
+    g_host_timing = tm;
+    return rc;
+}
+
+// The device memory of one build: text | array | workspace in a pooled device block, and on the reduced-memory route the
+// workspace slabs the block cannot hold in a pinned host block (spill); the build's stream.  All of it goes back to the pool
+// when the object dies -- the stream drained first --, also when something throws (the entry points catch at the ABI).
+struct BuildBlock {
+    int device;
+    hipStream_t st = nullptr;
+    DevBlock blk;
+    PinBlock spill;
+    void *dW2 = nullptr;                                        // device pointer of the spill
+    size_t tb = 0, sb = 0;                                      // bytes of the text / array part
+    size_t ws_dev = 0, ws_host = 0;                             // bytes of the workspace in the device block / in the spill
+    explicit BuildBlock(int d) : device(d) {}
+    BuildBlock(const BuildBlock &) = delete;
+    BuildBlock &operator=(const BuildBlock &) = delete;
+    ~BuildBlock()
+    {
+        if (st) (void)hipStreamSynchronize(st);
+        release();
+        if (spill.p) pool().release_pinned(spill);
+    }
+    uint8_t *text() const { return (uint8_t *)blk.p; }
+    uint32_t *sa() const { return (uint32_t *)((char *)blk.p + tb); }
+    void *work() const { return (char *)blk.p + tb + sb; }
+    void release()                                              // the device block and the stream (drained)
+    {
+        pool().release(blk);
+        blk = DevBlock();
+        if (st) pool().release_stream(device, st);
+        st = nullptr;
+    }
+};
+
+static int acquire_build_block(int32_t n, int node, const HostTuning &ht, BuildBlock &b)
+{
+    const size_t wb = (size_t)sa_amd_workspace_bytes(n);
+    b.tb = align_up((size_t)n, 256);
+    b.sb = align_up(((size_t)n + 1) * 4, 256);
+    b.ws_dev = wb;
+    hipStream_t st = nullptr;
+    int rc = pool().stream(b.device, &st);
+    if (rc != SA_AMD_OK) return rc;
+    b.st = st;
+    rc = pool().acquire(b.device, b.tb + b.sb + wb, &b.blk);
+    if (rc != SA_AMD_ENOMEM || !ht.reduced) return rc;
+    // The device cannot give text + array + the whole workspace (another tenant, or a text near MAX_LENGTH next to other
+    // blocks).  The reference's engine needs 257 KiB beside its output, so "out of memory" is not an answer a drop-in should
+    // give lightly: take what the device has, keep the text, the array and the most-used slabs there (carve() orders them by
+    // need) and put the slabs that do not fit into pinned host memory, which the kernels reach over PCIe -- slow (the lists
+    // and the third key buffer go first), correct.  SA_AMD_NO_REDUCED=1: SA_AMD_ENOMEM as before.
+    (void)hipGetLastError();
+    size_t free_b = 0, total_b = 0;
+    const size_t margin = (size_t)256 << 20;
+    const size_t floor_ws = carve(nullptr, n, ~(size_t)0, nullptr).bytes - (size_t)n * 32 - 64 * 8;      // everything but one value buffer, isa, the lists and the third key buffer
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b <= margin + b.tb + b.sb + floor_ws) { (void)hipGetLastError(); return rc; }
+    const size_t cap = ((free_b - margin) & ~(((size_t)2 << 20) - 1)) - b.tb - b.sb;
+    const Workspace dry = carve(nullptr, n, cap, nullptr);
+    rc = pool().acquire(b.device, b.tb + b.sb + align_up(dry.bytes, 256), &b.blk);
+    if (rc == SA_AMD_OK && dry.bytes2 > 0) {
+        rc = pool().pinned(dry.bytes2, node, b.device, &b.spill);
+        if (rc == SA_AMD_OK) rc = hip_status(hipHostGetDevicePointer(&b.dW2, b.spill.p, 0));
+        if (rc != SA_AMD_OK) { pool().release(b.blk); b.blk = DevBlock(); }
+    }
+    if (rc == SA_AMD_OK) { b.ws_dev = align_up(dry.bytes, 256); b.ws_host = dry.bytes2; }
+    return rc;
+}
+
 // host buffers in, host buffers out; with_sentinel writes SA[0] = n too (saca layout)
 static int build_host(const uint8_t *T, uint32_t *SA_host, int32_t n, bool with_sentinel, int device)
 {
@@ -283,302 +597,62 @@ static int build_host(const uint8_t *T, uint32_t *SA_host, int32_t n, bool with_
     if (guard.rc != SA_AMD_OK) return guard.rc;
     int cur = 0;
     HIP_TRY(hipGetDevice(&cur));
-    HostTiming tm;
+    const HostTuning ht = HostTuning::from_env();
     const int node = device_numa_node(cur);                       // staging buffers and copy helpers live next to the GPU's PCIe root
     const double t_begin = wall_ms();
-    const int small_max = (int)env_int("SA_AMD_SMALL_MAX", 8192, 0, SM_MAX_N);
-    if (n <= small_max) {
-        // Small texts: copy -> ONE launch -> copy.  The kernel reads the text from and writes the array to a pooled PINNED host
-        // block over PCIe (zero-copy; hipHostMalloc memory is mapped into the device), so there is no device block, no
-        // hipMemcpy and no read-back: 0.2 ms -> tens of microseconds for the sizes of the reference's own tests (src/tests.rs:14).
-        const size_t tb = align_up((size_t)n, 256), need = tb + ((size_t)n + 1) * 4;
-        PooledStream ps(cur);
-        PooledPin pp;
-        int rc = pool().stream(cur, &ps.st);
-        if (rc != SA_AMD_OK) return rc;
-        hipStream_t st = ps.st;
-        rc = pool().pinned(need < ((size_t)64 << 10) ? ((size_t)64 << 10) : need, -1, cur, &pp.b);
-        if (rc != SA_AMD_OK) return rc;
-        PinBlock &pb = pp.b;
-        void *dbase = nullptr;
-        rc = hip_status(hipHostGetDevicePointer(&dbase, pb.p, 0));
-        if (rc == SA_AMD_OK) {
-            memcpy(pb.p, T, (size_t)n);
-            if (n <= SM_LITE_SINGLE_N)
-                hipLaunchKernelGGL((k_small_sa_lite), dim3(1), dim3(SM_LITE_THREADS), 0, st, (const uint8_t *)dbase, (uint32_t *)((char *)dbase + tb), (int)n,
-                                   (uint32_t *)nullptr);
-            else
-                hipLaunchKernelGGL((k_small_sa), dim3(1), dim3(SM_THREADS), 0, st, (const uint8_t *)dbase, (uint32_t *)((char *)dbase + tb), (int)n,
-                                   (uint32_t *)nullptr);
-            rc = hip_status(hipGetLastError());
-            const int rs = hip_status(hipStreamSynchronize(st));
-            if (rc == SA_AMD_OK) rc = rs;
-            if (rc == SA_AMD_OK) {
-                const uint32_t *src = (const uint32_t *)((const char *)pb.p + tb);
-                if (with_sentinel) memcpy(SA_host, src, ((size_t)n + 1) * 4); else memcpy(SA_host, src + 1, (size_t)n * 4);
-            }
-        }
-        { sa_amd_stats z; memset(&z, 0, sizeof(z)); g_last_stats = z; }
-        tm.total = tm.build = wall_ms() - t_begin;
-        g_host_timing = tm;
-        return rc;
-    }
-    const size_t wb = (size_t)sa_amd_workspace_bytes(n);
-    const size_t tb = align_up((size_t)n, 256), sb = align_up(((size_t)n + 1) * 4, 256);
-    const size_t need = tb + sb + wb;
-    DevBlock blk;
-    PinBlock spill;                                              // reduced-memory route: the workspace slabs the device block cannot hold
-    struct SpillEnd { PinBlock &b_; ~SpillEnd() { if (b_.p) pool().release_pinned(b_); } } spill_end{ spill };
-    size_t ws_dev = wb, ws_host = 0;                             // bytes of the workspace in the device block / in pinned host memory
-    void *dW2 = nullptr;
-    hipStream_t st = nullptr;
-    int rc = pool().stream(cur, &st);
-    if (rc != SA_AMD_OK) return rc;
-    rc = pool().acquire(cur, need, &blk);
-    if (rc == SA_AMD_ENOMEM && env_int("SA_AMD_NO_REDUCED", 0, 0, 1) == 0) {
-        // The device cannot give text + array + the whole workspace (another tenant, or a text near MAX_LENGTH next to other
-        // blocks).  The reference's engine needs 257 KiB beside its output, so "out of memory" is not an answer a drop-in should
-        // give lightly: take what the device has, keep the text, the array and the most-used slabs there (carve() orders them by
-        // need) and put the slabs that do not fit into pinned host memory, which the kernels reach over PCIe -- slow (the lists
-        // and the third key buffer go first), correct.  SA_AMD_NO_REDUCED=1: SA_AMD_ENOMEM as before.
-        (void)hipGetLastError();
-        size_t free_b = 0, total_b = 0;
-        const size_t margin = (size_t)256 << 20;
-        const size_t floor_ws = carve(nullptr, n, ~(size_t)0, nullptr).bytes - (size_t)n * 32 - 64 * 8;      // everything but one value buffer, isa, the lists and the third key buffer
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > margin + tb + sb + floor_ws) {
-            const size_t cap = ((free_b - margin) & ~(((size_t)2 << 20) - 1)) - tb - sb;
-            const Workspace dry = carve(nullptr, n, cap, nullptr);
-            rc = pool().acquire(cur, tb + sb + align_up(dry.bytes, 256), &blk);
-            if (rc == SA_AMD_OK && dry.bytes2 > 0) {
-                rc = pool().pinned(dry.bytes2, node, cur, &spill);
-                if (rc == SA_AMD_OK) rc = hip_status(hipHostGetDevicePointer(&dW2, spill.p, 0));
-                if (rc != SA_AMD_OK) { pool().release(blk); blk = DevBlock(); }
-            }
-            if (rc == SA_AMD_OK) { ws_dev = align_up(dry.bytes, 256); ws_host = dry.bytes2; }
-        } else (void)hipGetLastError();
-    }
-    if (rc != SA_AMD_OK) { pool().release_stream(cur, st); return rc; }
-    double t0 = wall_ms();
-    tm.acquire = t0 - t_begin;
-    tm.spill = (double)ws_host;
-    uint8_t *dT = (uint8_t *)blk.p;
-    uint32_t *dSA = (uint32_t *)((char *)blk.p + tb);
-    void *dW = (char *)blk.p + tb + sb;
-    DeviceLanes &lanes = device_lanes(cur);
+    if (n <= ht.small_max) return build_host_small(T, SA_host, n, with_sentinel, cur, t_begin);
+
+    HostTiming tm;
+    const size_t out_bytes = ((size_t)n + (with_sentinel ? 1 : 0)) * 4;
+    const bool staged = ht.copy_threads > 0 && out_bytes >= ht.staged_min;
     // (texts below SA_AMD_LANES_MIN_N bytes take no turns: a mid-size build is bound by launches and read-backs, several of them
     // in flight on one device overlap -- 128 x 1 MiB of English through one batch call 195 -> 66 ms with four host threads)
-    const bool turns = env_int("SA_AMD_NO_LANES", 0, 0, 1) == 0 && n >= lanes_min_n();
-    // The caller's array is usually FRESH memory (`vec![0; n + 1]`, reference src/sa.rs:24: zero pages that are mapped on first
-    // write): the helpers touch its pages -- read a byte, write it back: the contents stay whatever they were -- while the GPU
-    // builds, so the download later copies into mapped memory (C3, fresh buffer: d2h 26-31 -> 20 ms).  SA_AMD_NO_PREFAULT=1: off.
-    const size_t out_bytes_all = ((size_t)n + (with_sentinel ? 1 : 0)) * 4;
-    const int copy_threads = (int)env_int("SA_AMD_COPY_THREADS", 12, 0, 32);      // 0: plain hipMemcpy into the caller's buffer
-    const size_t staged_min = (size_t)env_int("SA_AMD_STAGED_MIN_BYTES", (int64_t)64 << 20, 0, (int64_t)1 << 40);
-    const bool staged = copy_threads > 0 && out_bytes_all >= staged_min;
-    std::atomic<bool> prefault_stop(false);                     // (declared before the handle: the helpers read it until finish())
-    std::atomic<size_t> prefault_next(0);
-    HelperPool::Async prefault;
-    HelperPool &hp = helper_pool(node);
-    struct PrefaultEnd {                                         // (also when something below throws: the helpers hold a pointer to the handle)
-        HelperPool &pool_; HelperPool::Async &h_; std::atomic<size_t> &next_; std::atomic<bool> &stop_;
-        ~PrefaultEnd() { stop_.store(true); next_.store(~(size_t)0 >> 1); pool_.finish(h_); }      // (no unit is started any more)
-    } prefault_end{ hp, prefault, prefault_next, prefault_stop };
+    const bool turns = ht.lanes && n >= ht.lanes_min_n;
+    DeviceLanes &lanes = device_lanes(cur);
+    // Declared in this order, destroyed in the reverse one: on every path out the patch job (download_array) is joined first, then
+    // the early pullers, then the page-mapping helpers, and the device block goes back last.
+    BuildBlock blk(cur);
+    int rc = acquire_build_block(n, node, ht, blk);
+    if (rc != SA_AMD_OK) return rc;
+    double t0 = wall_ms();
+    tm.acquire = t0 - t_begin;
+    tm.spill = (double)blk.ws_host;
+    OutputPrefault prefault(helper_pool(node));
+    EarlyPull pull(helper_pool(node), cur, node);
     {
         LaneTurn turn(lanes.up, turns);
-        rc = hip_status(hipMemcpyAsync(dT, T, (size_t)n, hipMemcpyHostToDevice, st));
-        if (rc == SA_AMD_OK) rc = hip_status(hipStreamSynchronize(st));
+        rc = hip_status(hipMemcpyAsync(blk.text(), T, (size_t)n, hipMemcpyHostToDevice, blk.st));
+        if (rc == SA_AMD_OK) rc = hip_status(hipStreamSynchronize(blk.st));
     }
     double t1 = wall_ms();
     tm.h2d = t1 - t0;
     // (started behind the upload: the runtime's staging of the pageable text and the page touching would share the same cores)
-    if (staged && env_int("SA_AMD_NO_PREFAULT", 0, 0, 1) == 0) {
-        // In the order the download will fill the array, a staging chunk's worth (16 MiB) at a time, helper t taking the units
-        // t, t + T, ...: when the build is done before the whole array is mapped (a 10 ms build of 512 MiB of random bytes against
-        // 25-70 ms for the 2 GiB of its array) the helpers stop after the unit they are in and the download starts at once --
-        // into the mapped front part at full speed, page-faulting the rest in as it goes, which costs less than waiting for it.
-        // When the build ends first (random bytes: 4.6 ms of build against 20 ms of page mapping for a 1 GiB array), all but a few
-        // helpers stop after the 2 MiB piece they are in -- the download needs them -- and the few go on mapping AHEAD of the
-        // download, which would otherwise fault every page in from its copy threads (SA_AMD_PREFAULT_KEEP, default 3; 0: all stop).
-        char *dst = (char *)SA_host;
-        const size_t units = (out_bytes_all + STAGE_BYTES - 1) / STAGE_BYTES;
-        const int keep = (int)env_int("SA_AMD_PREFAULT_KEEP", 3, 0, 32);
-        std::atomic<bool> *stop = &prefault_stop;
-        std::atomic<size_t> *next = &prefault_next;
-        hp.start(prefault, copy_threads, [=](int t) {
-            auto touch = [](uintptr_t from, uintptr_t to) {
-                while (from < to) {
-                    volatile char *q = (volatile char *)from;
-                    const char c = *q;
-                    *q = c;
-                    from = (from + 4096) & ~(uintptr_t)4095;      // first byte of the next page
-                }
-            };
-            // (2 MiB at a time inside a unit: the build waits for the piece a helper is in when it ends -- with whole 16 MiB
-            // units a 0.8 ms build of a 16 MiB text took 1.5 ms into a fresh buffer)
-            constexpr size_t PIECE = (size_t)2 << 20;
-            auto over = [=]() { return t >= keep && stop->load(std::memory_order_relaxed); };
-            for (;;) {
-                if (over()) break;
-                const size_t u = next->fetch_add(1, std::memory_order_relaxed);      // units in the order the download fills them
-                if (u >= units) break;
-                const size_t ub = u * STAGE_BYTES, ue = ub + STAGE_BYTES < out_bytes_all ? ub + STAGE_BYTES : out_bytes_all;
-                for (size_t b = ub; b < ue && !over(); b += PIECE) {
-                    const size_t e = b + PIECE < ue ? b + PIECE : ue;
-                    const uintptr_t a = (uintptr_t)(dst + b), end = (uintptr_t)(dst + e);
-                    // whole pages: one madvise call maps them writable without a trap per page (Linux >= 5.14; contents untouched);
-                    // anything it refuses, and the partial pages at the ends, are touched byte by byte
-                    const uintptr_t pa = (a + 4095) & ~(uintptr_t)4095, pe = end & ~(uintptr_t)4095;
-                    if (pe > pa && madvise((void *)pa, pe - pa, SA_MADV_POPULATE_WRITE) == 0) {
-                        touch(a, pa < end ? pa : end);
-                        touch(pe > a ? pe : a, end);
-                    } else touch(a, end);
-                }
-            }
-        });
-    }
-    // early download (large arrays): see EarlyPull above.  SA_AMD_EARLY_DIV = d: the copy starts when at most n / d suffixes are
-    // still tied (0: never); the chunks it takes before the build ends are bounded so that what has to be sent behind them fits
-    // into the part of the caller's array that is still free.
-    const int64_t early_div = env_int("SA_AMD_EARLY_DIV", 4, 0, 1 << 20);
-    const size_t early_min = (size_t)env_int("SA_AMD_EARLY_MIN_BYTES", (int64_t)128 << 20, 0, (int64_t)1 << 40);
-    const uint32_t *dsrc = with_sentinel ? dSA : dSA + 1;
-    EarlyDownload early;
-    EarlyPull pull;
-    HelperPool::Async pull_job;
-    hipStream_t cst = nullptr;
-    pull.chunk = (size_t)env_int("SA_AMD_EARLY_CHUNK_BYTES", (int64_t)STAGE_BYTES, 65536, (int64_t)STAGE_BYTES) & ~(size_t)4095;
-    const int64_t early_wait = env_int("SA_AMD_EARLY_WAIT_CHUNKS", 0, 0, 1 << 20);     // tests: the build waits until so many chunks have been copied
-    // (the pullers are helper threads: a pool without helpers would run them only when the build is over)
+    if (staged && ht.prefault) prefault.start((char *)SA_host, out_bytes, ht.copy_threads, ht.prefault_keep);
+    const uint32_t *dsrc = with_sentinel ? blk.sa() : blk.sa() + 1;
     // (not on the reduced-memory route: the values sent behind would come out of a slab that may live in host memory)
-    const bool early_on = staged && early_div > 0 && out_bytes_all >= early_min && out_bytes_all >= 4 * pull.chunk && hp.helpers() > 0 && ws_host == 0;
-    if (early_on && rc == SA_AMD_OK && pool().stream(cur, &cst) == SA_AMD_OK) {
-        early.off = with_sentinel ? 1 : 0;
-        early.threshold = (int64_t)n / early_div;
-        pull.dst = (char *)SA_host; pull.src = (const char *)dsrc; pull.bytes = out_bytes_all;
-        pull.nchunk = (out_bytes_all + pull.chunk - 1) / pull.chunk;
-        pull.done.reset(new std::atomic<uint8_t>[pull.nchunk]);
-        for (size_t c = 0; c < pull.nchunk; ++c) pull.done[c].store(0);
-        pull.cst = cst; pull.device = cur; pull.node = node;
-        EarlyPull *pp = &pull;
-        HelperPool *hpp = &hp;
-        HelperPool::Async *pj = &pull_job;
-        EarlyDownload *ep = &early;
-        early.start = [pp, hpp, pj, ep](hipEvent_t ev) {
-            // what is sent behind the early chunks -- tile offsets, bitmap, at most min(tied at the snapshot, entries taken) final
-            // values -- lands in the end of the caller's array: the most chunks K with K chunks + all that <= the array
-            size_t k = 0;
-            for (;;) {
-                const size_t b = (k + 1) * pp->chunk, e = b / 4;
-                const size_t holes = (size_t)ep->m_snap < e ? (size_t)ep->m_snap : e;
-                if (b + b / 32 + b / 2048 + holes * 4 + 16384 > pp->bytes) break;
-                ++k;
-            }
-            pp->max_chunks = k;
-            pp->after = ev;
-            if (hipStreamWaitEvent(pp->cst, ev, 0) != hipSuccess) { (void)hipGetLastError(); return; }      // (no copy before the marks and SA[0] are in place)
-            hpp->start(*pj, EARLY_PULLERS, [pp](int t) { pp->run(t); });
-        };
-        early.stop = [pp, early_wait]() -> int64_t {
-            if (early_wait > 0) {
-                const size_t want = (size_t)early_wait < pp->max_chunks ? (size_t)early_wait : pp->max_chunks;
-                const double t_give_up = wall_ms() + 2000.0;
-                for (;;) {
-                    size_t have = 0;
-                    while (have < want && pp->done[have].load()) ++have;
-                    if (have >= want || pp->rc.load() != SA_AMD_OK || wall_ms() > t_give_up) break;
-                    std::this_thread::yield();
-                }
-            }
-            pp->stop.store(true);
-            size_t k = pp->issued.load();
-            if (k > pp->max_chunks) k = pp->max_chunks;
-            const size_t b = k * pp->chunk;
-            return (int64_t)((b < pp->bytes ? b : pp->bytes) / 4);
-        };
-    }
-    struct PullEnd {                                             // (the puller holds pointers to this frame: joined on every path)
-        HelperPool &pool_; HelperPool::Async &h_; EarlyPull &p_;
-        ~PullEnd() { p_.stop.store(true); pool_.finish(h_); }
-    } pull_end{ hp, pull_job, pull };
+    if (rc == SA_AMD_OK && staged && blk.ws_host == 0) pull.arm(ht, n, with_sentinel ? 1 : 0, SA_host, dsrc, out_bytes);
     if (rc == SA_AMD_OK) {
         LaneTurn turn(lanes.run, turns);
-        rc = build_device(dT, dSA, n, dW, (int64_t)ws_dev, st, nullptr, early.start ? &early : nullptr, dW2, (int64_t)ws_host);
+        rc = build_device(blk.text(), blk.sa(), n, blk.work(), (int64_t)blk.ws_dev, blk.st, nullptr, pull.hook(), blk.dW2, (int64_t)blk.ws_host);
     }
-    // (usually done by now; otherwise no further unit is started -- SA_AMD_PREFAULT_WAIT=1: every page is mapped first, A/B)
-    if (env_int("SA_AMD_PREFAULT_WAIT", 0, 0, 1) == 0) prefault_stop.store(true, std::memory_order_relaxed);
-    else hp.finish(prefault);                                    // (otherwise joined when the download is over: PrefaultEnd)
-    pull.stop.store(true);
+    prefault.build_done(ht.prefault_wait);
+    pull.stop();
     t0 = wall_ms();
     tm.build = t0 - t1;
-    HelperPool::Async patch_job;
-    struct PatchEnd {                                            // (the patch tasks hold pointers into the caller's array)
-        HelperPool &pool_; HelperPool::Async &h_;
-        ~PatchEnd() { pool_.finish(h_); }
-    } patch_end{ hp, patch_job };
     if (rc == SA_AMD_OK) {
         LaneTurn turn(lanes.down, turns);
-        const uint32_t *src = dsrc;
-        const size_t out_bytes = out_bytes_all;
-        size_t have = 0;                                        // bytes of the array that are (or are about to be) in the caller's buffer
-        size_t zone_at = out_bytes;                             // where the values sent behind have landed: free again once the patch is done
-        if (early.started && early.covered > 0) {
-            // the values sent behind: [tile offsets | bitmap | final values] land in the END of the caller's array (free until the
-            // rest of the download gets there); the helpers patch the front part from them while the rest of the array travels
-            const size_t covered = (size_t)early.covered, got = covered * 4 < out_bytes ? covered * 4 : out_bytes;
-            const size_t tiles_c = (covered + EARLY_TILE - 1) / EARLY_TILE;
-            const size_t off_b = align_up((tiles_c + 1) * 4, 256), bits_b = align_up(tiles_c * (EARLY_TILE / 8), 256), holes_b = (size_t)early.holes * 4;
-            const size_t aux = off_b + bits_b + holes_b;
-            if (got + aux + 8192 <= out_bytes) {
-                char *zone = (char *)SA_host + ((out_bytes - aux) & ~(size_t)4095);
-                rc = hip_status(hipMemcpyAsync(zone, early.d_tile_off, (tiles_c + 1) * 4, hipMemcpyDeviceToHost, st));
-                if (rc == SA_AMD_OK) rc = hip_status(hipMemcpyAsync(zone + off_b, early.d_bits, tiles_c * (EARLY_TILE / 8), hipMemcpyDeviceToHost, st));
-                if (rc == SA_AMD_OK && holes_b) rc = hip_status(hipMemcpyAsync(zone + off_b + bits_b, early.d_holes, holes_b, hipMemcpyDeviceToHost, st));
-                if (rc == SA_AMD_OK) rc = hip_status(hipStreamSynchronize(st));
-                hp.finish(pull_job);                             // (the chunk that was in flight when the build ended has arrived by now)
-                if (rc == SA_AMD_OK && pull.rc.load() != SA_AMD_OK) rc = pull.rc.load();
-                // chunks the puller took but did not copy (it saw the stop first) are downloaded with the rest
-                const size_t copied_b = pull.copied() * pull.chunk < out_bytes ? pull.copied() * pull.chunk : out_bytes;
-                if (rc == SA_AMD_OK && copied_b > 0) {
-                    const int pt = copy_threads > 8 ? 8 : copy_threads;
-                    hp.start(patch_job, pt, early_patch_task(SA_host, (const uint32_t *)zone, (const uint32_t *)(zone + off_b),
-                                                             (const uint32_t *)(zone + off_b + bits_b), copied_b / 4, pt));
-                    have = copied_b;
-                    zone_at = (size_t)(zone - (char *)SA_host);
-                    tm.early = (double)copied_b / (double)out_bytes;
-                }
-            }
-            // (else: the early chunks are simply downloaded again with everything else)
-        }
-        hp.finish(pull_job);
-        if (rc == SA_AMD_OK && pull.rc.load() != SA_AMD_OK) rc = pull.rc.load();
-        auto fetch = [&](size_t from, size_t to) {
-            if (rc != SA_AMD_OK || from >= to) return;
-            if (staged) {
-                tm.staged = copy_threads;
-                rc = staged_download((char *)SA_host + from, (const char *)src + from, to - from, st, copy_threads, cur, node);
-            } else {
-                rc = hip_status(hipMemcpyAsync((char *)SA_host + from, (const char *)src + from, to - from, hipMemcpyDeviceToHost, st));
-                if (rc == SA_AMD_OK) rc = hip_status(hipStreamSynchronize(st));      // (the turn ends when the copy has)
-            }
-        };
-        const size_t split = zone_at < out_bytes ? (zone_at > have ? zone_at & ~(STAGE_BYTES - 1) : have) : out_bytes;
-        fetch(have, split < have ? have : split);
-        hp.finish(patch_job);                                    // the landing zone is free from here on
-        fetch(split < have ? have : split, out_bytes);
+        rc = download_array(SA_host, dsrc, out_bytes, staged, blk.st, ht, cur, node, pull, tm);
     }
-    hp.finish(pull_job);
-    if (early.ev) { (void)hipEventDestroy(early.ev); early.ev = nullptr; }
-    if (cst) { (void)hipStreamSynchronize(cst); pool().release_stream(cur, cst); }
-    const int rs = hip_status(hipStreamSynchronize(st));       // also drains the stream after a failure
+    pull.end();
+    const int rs = hip_status(hipStreamSynchronize(blk.st));     // also drains the stream after a failure
     if (rc == SA_AMD_OK) rc = rs;
     t1 = wall_ms();
     tm.d2h = t1 - t0;
-    pool().release(blk);
-    pool().release_stream(cur, st);
+    blk.release();
     tm.release = wall_ms() - t1;
     tm.total = wall_ms() - t_begin;
     g_host_timing = tm;
-    if (env_int("SA_AMD_VERBOSE", 0, 0, 9) >= 2)
+    if (ht.verbose >= 2)
         fprintf(stderr, "suffix_array_amd: n=%d device %d numa node %d acquire %.2f h2d %.2f build %.2f d2h %.2f (staged %d, %.0f %% of the array sent before the build was done) release %.2f total %.2f ms%s\n", n,
                 cur, node, tm.acquire, tm.h2d, tm.build, tm.d2h, tm.staged, tm.early * 100.0, tm.release, tm.total,
                 tm.spill > 0 ? " -- REDUCED-MEMORY route: part of the workspace in pinned host memory" : "");
@@ -606,7 +680,7 @@ static int build_host_small_batch(const uint8_t *const *T, uint32_t *const *SA, 
     hipStream_t st = ps.st;
     int first = SA_AMD_OK;
     HelperPool &hp = helper_pool(device_numa_node(cur));
-    const int copy_slices = (int)env_int("SA_AMD_COPY_THREADS", 12, 0, 32) > 1 ? (int)env_int("SA_AMD_COPY_THREADS", 12, 0, 32) : 1;
+    const int copy_threads = HostTuning::from_env().copy_threads, copy_slices = copy_threads > 1 ? copy_threads : 1;
     size_t k0 = 0;
     while (k0 < count) {
         // the chunk [k0, k1): descriptors first, then the texts (16-byte slots), then the arrays (4 (n + 1) bytes each, 16-byte slots)

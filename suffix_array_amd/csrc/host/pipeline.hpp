@@ -774,7 +774,8 @@ struct PinnedWords {
 static thread_local PinnedWords g_pinned;
 static thread_local int g_readbacks = 0;        // blocking read-backs of the calling thread's current build (sa_amd_stats.readbacks)
 static thread_local bool g_posted_off = false;  // SA_AMD_NO_POSTED_READBACK (set per build from the tuning)
-static thread_local uint32_t g_post_seq = 0;
+// tags of posted read-backs: process-wide, so a block another thread used before cannot hold the tag this thread waits for
+static std::atomic<uint32_t> g_post_seq{0};
 
 // A read-back as a POSTED write: one tiny kernel stores the words into the (mapped) pinned block, every 64-byte line tagged with
 // a sequence number, and the host spins on the tags -- instead of a copy command plus hipStreamSynchronize, whose wake-up costs
@@ -794,10 +795,15 @@ __global__ __launch_bounds__(256) void k_post_words(const uint32_t *__restrict__
     for (int q = threadIdx.x; q < lines; q += 256) __hip_atomic_store(dst + q * POST_LINE, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// The thread's block is 8 KiB: the tagged lines of the posted path in the lower half (zeroed when the block is taken: a recycled
+// block holds old tags), the plain copy in the upper half (raw words, no tags).
 static int read_words(void *dst, const void *dsrc, size_t bytes, hipStream_t st)     // bytes <= 3840, a multiple of 4; synchronises the stream
 {
     ++g_readbacks;
-    if (!g_pinned.b.p && !g_pinned.failed && pool().pinned(4096, -1, -1, &g_pinned.b) != SA_AMD_OK) g_pinned.failed = true;
+    if (!g_pinned.b.p && !g_pinned.failed) {
+        if (pool().pinned(8192, -1, -1, &g_pinned.b) == SA_AMD_OK) memset(g_pinned.b.p, 0, 8192);
+        else g_pinned.failed = true;
+    }
     if (!g_pinned.b.p) {
         HIP_TRY(hipMemcpyAsync(dst, dsrc, bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -807,8 +813,8 @@ static int read_words(void *dst, const void *dsrc, size_t bytes, hipStream_t st)
     const int lines = (words + POST_LINE - 2) / (POST_LINE - 1);
     if (!g_posted_off && (bytes & 3) == 0 && words > 0 && (size_t)lines * POST_LINE * 4 <= 4096) {
         uint32_t *host = (uint32_t *)g_pinned.b.p;
-        if (++g_post_seq == 0) ++g_post_seq;
-        const uint32_t seq = g_post_seq;
+        uint32_t seq = g_post_seq.fetch_add(1, std::memory_order_relaxed) + 1;
+        if (seq == 0) seq = g_post_seq.fetch_add(1, std::memory_order_relaxed) + 1;      // (0 is what a fresh block holds)
         // (the pool's pinned blocks are portable and mapped: the host address is valid on every device)
         hipLaunchKernelGGL(k_post_words, dim3(1), dim3(256), 0, st, (const uint32_t *)dsrc, host, words, seq);
         if (hipGetLastError() == hipSuccess) {
@@ -837,9 +843,10 @@ static int read_words(void *dst, const void *dsrc, size_t bytes, hipStream_t st)
             }
         }
     }
-    HIP_TRY(hipMemcpyAsync(g_pinned.b.p, dsrc, bytes, hipMemcpyDeviceToHost, st));
+    char *copy = (char *)g_pinned.b.p + 4096;
+    HIP_TRY(hipMemcpyAsync(copy, dsrc, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    memcpy(dst, g_pinned.b.p, bytes);
+    memcpy(dst, copy, bytes);
     return SA_AMD_OK;
 }
 

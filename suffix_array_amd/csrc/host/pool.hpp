@@ -1,11 +1,11 @@
 // host/pool.hpp -- process-wide pool of device blocks, streams and pinned host blocks (mutex-protected).
 // One device block = text + SA + workspace of one build, so neither repeated calls of the host-pointer entry points
 // (the contract of `saca()`, reference src/saca.rs:9-15) nor the worker threads of sa_amd_saca_batch pay hipMalloc /
-// hipFree per call.  What the pool keeps PER DEVICE follows the work: at most twice the largest block any of the device's last
-// eight builds asked for (two workers of a batch alternate on two blocks), never more than SA_AMD_CACHE_MAX_BYTES (default
-// 128 GiB of a device's 288 GB: one 1 GiB text is a 58 GiB block) -- a process that indexed one 1 GiB text and goes on with
-// 64 MiB ones gives the 58 GiB back after eight of them instead of holding them for its lifetime -- and blocks that have not
-// been used for SA_AMD_CACHE_IDLE_MS (default 60 s: a block of 14 GiB costs half a second of hipMalloc to get back, and the copy engine reads a re-allocated block at half rate, host_path.hpp) are freed by the next call that touches the pool.
+// hipFree per call.  What the pool keeps PER DEVICE follows the work: at most twice the largest block any of the device's builds
+// of the last SA_AMD_CACHE_IDLE_MS asked for (two workers of a batch alternate on two blocks), never more than SA_AMD_CACHE_MAX_BYTES
+// (default 128 GiB of a device's 288 GB: one 1 GiB text is a 58 GiB block) -- a process that indexed one 1 GiB text and goes on
+// with 64 MiB ones gives the 58 GiB back once that much time has passed instead of holding them for its lifetime -- and blocks that
+// have not been used for SA_AMD_CACHE_IDLE_MS (default 60 s: a block of 14 GiB costs half a second of hipMalloc to get back, and the copy engine reads a re-allocated block at half rate, host_path.hpp) are freed by the next call that touches the pool.
 // sa_amd_release_cache() empties it.  Pinned blocks remember the NUMA node they were first touched on (helpers.hpp).
 #pragma once
 #include "helpers.hpp"

@@ -31,6 +31,10 @@ inline int64_t env_int(const char *name, int64_t def, int64_t lo, int64_t hi)
     return v < lo ? lo : (v > hi ? hi : (int64_t)v);
 }
 
+// SA_AMD_SMALL_MAX: texts of up to this many bytes are built by ONE launch of one workgroup (kernels/small.hpp, SM_MAX_N = 8192),
+// chosen by the host-pointer calls (HostTuning) and the device-resident one (Tuning) alike
+inline int env_small_max() { return (int)env_int("SA_AMD_SMALL_MAX", 8192, 0, 8192); }
+
 struct Tuning {
     int sort_variant = 0;            // SA_AMD_SORT_VARIANT: tile-scatter kernel shape, 64-bit keys (all shapes give the same order)
     int sort32_variant = 0;          // SA_AMD_SORT32_VARIANT: the same for the 32-bit first stage
@@ -145,7 +149,7 @@ struct Tuning {
         t.top32_partners_x100 = (int)env_int("SA_AMD_TOP32_PARTNERS_X100", 50, 0, 1000000);
         t.top32_collisions_x100 = (int)env_int("SA_AMD_TOP32_COLLISIONS_X100", 400, 0, 1000000);
         t.top32_probe_min_n = env_int("SA_AMD_TOP32_PROBE_MIN_N", (int64_t)1 << 21, 8192, (int64_t)1 << 40);
-        t.small_max = (int)env_int("SA_AMD_SMALL_MAX", 8192, 0, 8192);
+        t.small_max = env_small_max();
         t.no_onesweep = env_flag("SA_AMD_NO_ONESWEEP");
         t.onesweep_flags = (int)env_int("SA_AMD_ONESWEEP_FLAGS", 0, 0, 255);
         t.onesweep64_shape = (int)env_int("SA_AMD_ONESWEEP64_SHAPE", 0, 0, 1 << 20);
@@ -180,6 +184,50 @@ struct Tuning {
         t.timing_only_initial_sort = env_flag("SA_AMD_TIMING_ONLY_INITIAL_SORT");
 #endif
         return t;
+    }
+};
+
+constexpr size_t STAGE_BYTES = (size_t)16 << 20;      // pinned staging block of a download (host/host_path.hpp)
+
+// the knobs of the host-pointer entry points (host/host_path.hpp), read once per call: tests change them between calls
+struct HostTuning {
+    int small_max;                   // SA_AMD_SMALL_MAX (env_small_max)
+    int copy_threads;                // SA_AMD_COPY_THREADS: slices of a staged download, 0..32 (0: plain hipMemcpy into the caller's buffer)
+    size_t staged_min;               // SA_AMD_STAGED_MIN_BYTES: smallest array downloaded through the staging blocks
+    bool prefault;                   // SA_AMD_NO_PREFAULT=1: the helpers do not map the caller's fresh pages during the build
+    int prefault_keep;               // SA_AMD_PREFAULT_KEEP: helpers that go on mapping when the build ends first, 0..32
+    bool prefault_wait;              // SA_AMD_PREFAULT_WAIT=1: the download waits until every page is mapped (A/B)
+    int64_t early_div;               // SA_AMD_EARLY_DIV: the early download starts when at most n / d suffixes are tied (0: never)
+    size_t early_min;                // SA_AMD_EARLY_MIN_BYTES: smallest array downloaded early
+    size_t early_chunk;              // SA_AMD_EARLY_CHUNK_BYTES: bytes per early copy, whole pages, 64 KiB .. one staging block
+    int64_t early_wait;              // SA_AMD_EARLY_WAIT_CHUNKS (tests): the build waits until so many early chunks have been copied
+    bool reduced;                    // SA_AMD_NO_REDUCED=1: no reduced-memory route, SA_AMD_ENOMEM as before
+    bool lanes;                      // SA_AMD_NO_LANES=1: callers that share a device take no turns
+    int64_t lanes_min_n;             // SA_AMD_LANES_MIN_N: smallest text that takes turns
+    bool kernel_d2h;                 // SA_AMD_NO_KERNEL_D2H=1: downloads always by the copy engine
+    bool kernel_d2h_always;          // SA_AMD_KERNEL_D2H_ALWAYS=1: downloads always by the copy kernel
+    int verbose;                     // SA_AMD_VERBOSE: 2 one line per call, 3 the download's too
+
+    static HostTuning from_env()
+    {
+        HostTuning h;
+        h.small_max = env_small_max();
+        h.copy_threads = (int)env_int("SA_AMD_COPY_THREADS", 12, 0, 32);
+        h.staged_min = (size_t)env_int("SA_AMD_STAGED_MIN_BYTES", (int64_t)64 << 20, 0, (int64_t)1 << 40);
+        h.prefault = env_int("SA_AMD_NO_PREFAULT", 0, 0, 1) == 0;
+        h.prefault_keep = (int)env_int("SA_AMD_PREFAULT_KEEP", 3, 0, 32);
+        h.prefault_wait = env_int("SA_AMD_PREFAULT_WAIT", 0, 0, 1) != 0;
+        h.early_div = env_int("SA_AMD_EARLY_DIV", 4, 0, 1 << 20);
+        h.early_min = (size_t)env_int("SA_AMD_EARLY_MIN_BYTES", (int64_t)128 << 20, 0, (int64_t)1 << 40);
+        h.early_chunk = (size_t)env_int("SA_AMD_EARLY_CHUNK_BYTES", (int64_t)STAGE_BYTES, 65536, (int64_t)STAGE_BYTES) & ~(size_t)4095;
+        h.early_wait = env_int("SA_AMD_EARLY_WAIT_CHUNKS", 0, 0, 1 << 20);
+        h.reduced = env_int("SA_AMD_NO_REDUCED", 0, 0, 1) == 0;
+        h.lanes = env_int("SA_AMD_NO_LANES", 0, 0, 1) == 0;
+        h.lanes_min_n = env_int("SA_AMD_LANES_MIN_N", (int64_t)32 << 20, 0, (int64_t)1 << 40);
+        h.kernel_d2h = env_int("SA_AMD_NO_KERNEL_D2H", 0, 0, 1) == 0;
+        h.kernel_d2h_always = env_int("SA_AMD_KERNEL_D2H_ALWAYS", 0, 0, 1) != 0;
+        h.verbose = (int)env_int("SA_AMD_VERBOSE", 0, 0, 9);
+        return h;
     }
 };
 

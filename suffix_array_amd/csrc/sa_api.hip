@@ -46,11 +46,11 @@ SA_EXPORT int32_t sa_amd_saca_batch(const uint8_t *const *T, uint32_t *const *SA
     std::vector<std::vector<int>> per_dev((size_t)ndev), small_dev((size_t)ndev);
     // texts of up to SA_AMD_SMALL_MAX bytes (the one-workgroup kernel's) are built together, one launch per device and chunk
     // (host/host_path.hpp, build_host_small_batch) -- unless a device has a single one, which takes the single-call path
-    const int small_max = (int)sa::env_int("SA_AMD_SMALL_MAX", 8192, 0, sa::SM_MAX_N);
+    const sa::HostTuning ht = sa::HostTuning::from_env();
     for (int i = 0; i < count; ++i) {
         const int d = device ? device[i] : i % ndev;
         if (d < 0 || d >= ndev) { st[(size_t)i] = SA_AMD_EINVAL; continue; }
-        if (n[i] > 0 && n[i] <= small_max && T[i] && SA[i]) small_dev[(size_t)d].push_back(i);
+        if (n[i] > 0 && n[i] <= ht.small_max && T[i] && SA[i]) small_dev[(size_t)d].push_back(i);
         else per_dev[(size_t)d].push_back(i);
     }
     for (int d = 0; d < ndev; ++d)
@@ -64,7 +64,7 @@ SA_EXPORT int32_t sa_amd_saca_batch(const uint8_t *const *T, uint32_t *const *SA
     // when they are all below 8 MiB -- those builds leave most of the GPU idle and take no turns, host/host_path.hpp; measured,
     // one GPU: 128 x 1 MiB of English 196 ms with two threads and turns, 67 with eight, 58 with twelve; 16 x 16 MiB 75 / 65 / 71)
     const int per_env = (int)sa::env_int("SA_AMD_BATCH_THREADS", 0, 0, 16);
-    const int64_t lanes_min = sa::lanes_min_n();
+    const int64_t lanes_min = ht.lanes_min_n;
     std::vector<int> per_of((size_t)ndev, 2);
     for (int d = 0; d < ndev; ++d) {
         int64_t largest = 0;

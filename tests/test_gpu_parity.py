@@ -401,6 +401,38 @@ def test_early_download_patches_the_slots_that_were_still_tied(oracle, monkeypat
         assert sa.last_stats()["rounds"] >= 1
 
 
+def test_early_pullers_on_a_pool_of_few_helpers_do_not_hang(oracle, tmp_path):
+    """the early pullers run on the helper pool of the GPU's NUMA node and take their staging blocks from the pinned pool; on a
+    cold pool that allocation runs on a helper of the same pool (host/helpers.hpp, run_on_helper).  With no more helpers than
+    pullers, every helper used to wait for a job that only a helper could run.  A fresh process (a cold pool) with one helper
+    thread per device of the node and the early download forced as in the test above must finish, and bit-exact."""
+    import re
+    import subprocess
+    import sys
+    t = corpus.english_corpus(3_000_001, 3)
+    out_path = tmp_path / "sa.u32"
+    env = dict(os.environ, SA_AMD_HELPER_THREADS="1", SA_AMD_STAGED_MIN_BYTES="0", SA_AMD_EARLY_MIN_BYTES="0",
+               SA_AMD_EARLY_CHUNK_BYTES="65536", SA_AMD_EARLY_DIV="1", SA_AMD_EARLY_WAIT_CHUNKS="8", SA_AMD_VERBOSE="3")
+    code = ("import json, sys; sys.path.insert(0, %r); import numpy as np; import suffix_array_amd as sa; from suffix_array_amd import corpus; "
+            "t = corpus.english_corpus(3_000_001, 3); out = np.full(t.size + 1, 0xDEADBEEF, dtype=np.uint32); sa.saca(t, out); "
+            "out.tofile(sys.argv[1]); print(json.dumps(sa.last_host_timing()))") % ROOT
+    try:
+        proc = subprocess.run([sys.executable, "-c", code, str(out_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                              text=True, timeout=240)
+    except subprocess.TimeoutExpired:
+        pytest.fail("the build did not finish within 240 s on a pool of few helpers (early pullers waiting on their own pool)")
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    assert np.array_equal(np.fromfile(out_path, dtype=np.uint32), oracle.sais(t))
+    assert json.loads(proc.stdout.strip().splitlines()[-1])["early_fraction"] > 0, proc.stdout
+    node = re.search(r"numa node (-?\d+)", proc.stderr)
+    helpers = re.search(r"(\d+) helpers\)", proc.stderr)
+    assert node and helpers, proc.stderr[-2000:]
+    if int(node.group(1)) < 0:
+        pytest.skip("the device has no NUMA node here: staging blocks are allocated by the caller, the hang cannot occur")
+    if int(helpers.group(1)) > 4:
+        pytest.skip(f"the node's pool has {helpers.group(1)} helpers, more than the four early pullers: the hang cannot occur")
+
+
 def _hip():
     hip = ctypes.CDLL("libamdhip64.so")
     hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
