@@ -193,6 +193,41 @@ int64_t sa_amd_pack_bound(int64_t length);
 int32_t sa_amd_pack(const uint32_t *SA, int64_t length, uint8_t *out, int64_t capacity, int64_t *out_len);
 int32_t sa_amd_unpack(const uint8_t *bytes, int64_t nbytes, uint32_t *SA, int64_t capacity, int64_t *length);
 
+/*
+ * LCP array (an extension: the reference lists it as a TODO, "construct enhanced suffix array"), aligned with the layout
+ * of sa_amd_saca_u8: n + 1 entries, LCP[0] = 0, LCP[i] = length of the longest common prefix of the suffixes at SA[i-1]
+ * and SA[i] (1 <= i <= n; LCP[1] = 0, the empty suffix), each at most n - 1.  Built on the device from the text and the
+ * array by the permuted LCP (irreducible values compared directly, the rest by one max-scan): the bytes compared are at
+ * most about 2 n log2 n whatever the LCP values.
+ * SA must be the suffix array of T -- not proved here (sa_amd_check_integrity does that); an entry > n returns
+ * SA_AMD_ERANGE (range pass before anything reads through the entries), SA[0] != n returns SA_AMD_EINVAL.
+ */
+/* bytes of device scratch sa_amd_lcp_device needs: at most sa_amd_check_integrity_work_bytes(n), about 20 (n + 1) */
+int64_t sa_amd_lcp_work_bytes(int32_t n);
+/* device pointers: dT n bytes (any byte address, read as sa_amd_saca_device reads it), dSA and dLCP n + 1 entries, dWork
+ * sa_amd_lcp_work_bytes(n) bytes 256-byte aligned (else SA_AMD_EINVAL); stream a hipStream_t (NULL = default stream).
+ * Blocks until done. */
+int32_t sa_amd_lcp_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, uint32_t *dLCP,
+                          void *dWork, int64_t work_bytes, void *stream);
+/* host pointers: T (n bytes) and SA (n + 1 entries) go up, LCP (n + 1 entries) comes back */
+int32_t sa_amd_lcp(const uint8_t *T, int32_t n, const uint32_t *SA, uint32_t *LCP);
+/* sa_amd_saca_u8 and the LCP array in one device round trip: the array is built on the device and never uploaded */
+int32_t sa_amd_saca_u8_lcp(const uint8_t *T, uint32_t *SA, int32_t n, uint32_t *LCP);
+/* from the index's resident text and suffix array (n + 1 entries) */
+int32_t sa_amd_index_lcp(const sa_amd_index *ix, uint32_t *LCP);
+
+typedef struct sa_amd_lcp_stats {   /* of the calling thread's most recent LCP build */
+    int64_t irreducible;            /* positions whose value was computed directly */
+    int64_t compared_bytes;         /* text bytes loaded for comparison (both suffixes), short and long paths together */
+    int64_t long_pairs;             /* pairs that went to the long-compare path (equal over the compare cap) */
+    int32_t readbacks, reserved;    /* blocking device -> host read-backs of counters */
+} sa_amd_lcp_stats;
+void sa_amd_last_lcp_stats(sa_amd_lcp_stats *out);
+/* route switch of the calling thread's later LCP builds (never changes a result): bytes one lane compares before a pair goes to
+ * the long-compare path, clamped to 0 .. 1 048 576 (0: every irreducible pair takes it); a negative value restores the default
+ * (64).  Returns the previous value. */
+int32_t sa_amd_lcp_set_compare_cap(int32_t bytes);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

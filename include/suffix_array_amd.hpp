@@ -5,6 +5,7 @@
 //   SuffixArray::new_/set/len/is_empty/into_parts/from_parts/unchecked_from_parts
 //                                           reference src/sa.rs:23-70, check_integrity src/sa.rs:72-84
 //   SuffixArray::enable_buckets / buckets   reference src/sa.rs:89-119 (the table, built on the GPU from the text alone)
+//   SuffixArray::lcp_array                  EXTENSION: the LCP array (the reference's README TODO "enhanced suffix array")
 // Rust panics (assert!, engine failure) are std::logic_error / std::runtime_error here.
 #pragma once
 #include "suffix_array_amd.h"
@@ -76,6 +77,17 @@ public:
         bkt_ = std::move(b);
     }
     const std::vector<std::uint32_t> &buckets() const { return bkt_; }     // empty: not enabled (the reference's bkt: None)
+    // EXTENSION (not in the reference): the LCP array aligned with sa(), n + 1 entries, lcp[0] = 0, lcp[i] = longest common
+    // prefix of the suffixes at sa[i-1] and sa[i]; computed on the GPU (sa_amd_lcp)
+    std::vector<std::uint32_t> lcp_array() const
+    {
+        if (n_ + 1 != sa_.size()) throw std::logic_error("assertion failed: s.len() + 1 == sa.len()");
+        std::vector<std::uint32_t> l(n_ + 1);
+        const std::int32_t rc = sa_amd_lcp(s_, static_cast<std::int32_t>(n_), sa_.data(), l.data());
+        if (rc == SA_AMD_ERANGE) throw std::out_of_range("suffix offset out of range");
+        if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
+        return l;
+    }
 
 private:
     SuffixArray(const std::uint8_t *s, std::size_t n, std::vector<std::uint32_t> sa) : s_(s), n_(n), sa_(std::move(sa)) {}

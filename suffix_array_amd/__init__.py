@@ -20,7 +20,9 @@ from typing import Optional
 import numpy as np
 
 __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag_lib", "library_path", "Stats", "last_host_timing",
-           "saca_batch", "workspace_bytes", "device_pci_bus_id", "saca_device_ptr", "bucket_table", "check_integrity", "last_stats", "DeviceIndex", "pack", "unpack"]
+           "saca_batch", "workspace_bytes", "device_pci_bus_id", "saca_device_ptr", "bucket_table", "check_integrity", "last_stats", "DeviceIndex", "pack", "unpack",
+           "lcp", "saca_lcp", "last_lcp_stats", "lcp_work_bytes", "lcp_device_ptr", "LcpStats",
+           "lcp_set_compare_cap"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
@@ -49,6 +51,15 @@ class Stats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class LcpStats(ctypes.Structure):
+    """sa_amd_lcp_stats of include/suffix_array_amd.h"""
+    _fields_ = [("irreducible", ctypes.c_int64), ("compared_bytes", ctypes.c_int64), ("long_pairs", ctypes.c_int64),
+                ("readbacks", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 def library_path() -> str:
@@ -122,6 +133,20 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_check_integrity_device.restype = ctypes.c_int32
         L.sa_amd_check_integrity_work_bytes.argtypes = [ctypes.c_int32]
         L.sa_amd_check_integrity_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_lcp_work_bytes.argtypes = [ctypes.c_int32]
+        L.sa_amd_lcp_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_lcp_device.argtypes = [c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_lcp_device.restype = ctypes.c_int32
+        L.sa_amd_lcp.argtypes = [c_vp, ctypes.c_int32, c_vp, c_vp]
+        L.sa_amd_lcp.restype = ctypes.c_int32
+        L.sa_amd_saca_u8_lcp.argtypes = [c_vp, c_vp, ctypes.c_int32, c_vp]
+        L.sa_amd_saca_u8_lcp.restype = ctypes.c_int32
+        L.sa_amd_index_lcp.argtypes = [c_vp, c_vp]
+        L.sa_amd_index_lcp.restype = ctypes.c_int32
+        L.sa_amd_last_lcp_stats.argtypes = [c_vp]
+        L.sa_amd_last_lcp_stats.restype = None
+        L.sa_amd_lcp_set_compare_cap.argtypes = [ctypes.c_int32]
+        L.sa_amd_lcp_set_compare_cap.restype = ctypes.c_int32
         _lib = L
     return _lib
 
@@ -310,6 +335,57 @@ def unpack(blob: bytes) -> np.ndarray:
     return out[:got.value]
 
 
+def _lcp_rc(rc: int) -> None:
+    if rc == -6:
+        raise IndexError("suffix offset out of range")
+    _check(rc)
+
+
+def lcp(s, sa: np.ndarray) -> np.ndarray:
+    """LCP array of the text and its suffix array (an extension the reference lacks: its README's TODO "construct enhanced
+    suffix array"), computed on the GPU: uint32, ``len(s) + 1`` entries aligned with ``sa`` (``sa[0] == len(s)``);
+    ``lcp[0] == 0`` and ``lcp[i]`` is the longest common prefix of the suffixes at ``sa[i-1]`` and ``sa[i]``.  ``sa`` must
+    be the suffix array of ``s`` (not proved here; ``check_integrity`` does that): IndexError for an entry > len(s)."""
+    t = _as_u8(s)
+    a = np.ascontiguousarray(sa, dtype=np.uint32)
+    assert a.size == t.size + 1
+    out = np.empty(t.size + 1, dtype=np.uint32)
+    _lcp_rc(lib().sa_amd_lcp(t.ctypes.data, t.size, a.ctypes.data, out.ctypes.data))
+    return out
+
+
+def saca_lcp(s):
+    """-> (sa, lcp): the suffix array (layout of ``saca``) and its LCP array in one device round trip"""
+    t = _as_u8(s)
+    assert t.size <= MAX_LENGTH
+    a = np.empty(t.size + 1, dtype=np.uint32)
+    out = np.empty(t.size + 1, dtype=np.uint32)
+    _check(lib().sa_amd_saca_u8_lcp(t.ctypes.data, a.ctypes.data, t.size, out.ctypes.data))
+    return a, out
+
+
+def last_lcp_stats() -> dict:
+    """irreducible / compared_bytes / long_pairs / readbacks of this thread's most recent LCP build"""
+    st = LcpStats()
+    lib().sa_amd_last_lcp_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def lcp_set_compare_cap(nbytes: int) -> int:
+    """route switch for this thread's later LCP builds (never changes a result): bytes one lane compares before a pair goes to
+    the long-compare path, clamped to 0 .. 2**20; negative restores the default (64).  Returns the previous value."""
+    return int(lib().sa_amd_lcp_set_compare_cap(int(nbytes)))
+
+
+def lcp_work_bytes(n: int) -> int:
+    return int(lib().sa_amd_lcp_work_bytes(n))
+
+
+def lcp_device_ptr(text_ptr: int, sa_ptr: int, n: int, lcp_ptr: int, work_ptr: int, work_bytes: int, stream: int = 0) -> None:
+    """Device-resident LCP build (raw device pointers, e.g. torch ``tensor.data_ptr()``); blocks until done."""
+    _lcp_rc(lib().sa_amd_lcp_device(text_ptr, sa_ptr, n, lcp_ptr, work_ptr, work_bytes, stream))
+
+
 class DeviceIndex:
     """Text + suffix array resident in HBM (sa_amd_index of include/suffix_array_amd.h): batched
     `contains` / `search_all` / `search_lcp` (reference src/sa.rs:164-253), bucket table, integrity check.
@@ -347,6 +423,12 @@ class DeviceIndex:
         if rc < 0 and rc != -6:
             _check(rc)
         return rc == 1
+
+    def lcp(self) -> np.ndarray:
+        """LCP array of the resident text and suffix array (see ``lcp``)"""
+        out = np.empty(self._s.size + 1, dtype=np.uint32)
+        _lcp_rc(lib().sa_amd_index_lcp(self._h, out.ctypes.data))
+        return out
 
     def search(self, patterns):
         """-> dict of arrays over the patterns: contains (bool), lo/hi (search_all == sa[lo:hi]),
@@ -504,6 +586,12 @@ class SuffixArray:
     def search_lcp(self, pat) -> range:
         r = self._index().search([pat])
         return range(int(r["lcp_start"][0]), int(r["lcp_start"][0]) + int(r["lcp_len"][0]))
+
+    def lcp_array(self) -> np.ndarray:
+        """EXTENSION (the reference lacks it: its README's TODO "construct enhanced suffix array"): the LCP array aligned
+        with the suffix array, ``lcp[0] == 0``, ``lcp[i]`` = longest common prefix of the suffixes at ``sa[i-1]`` and
+        ``sa[i]``; computed on the GPU from the text and the array"""
+        return lcp(self._s, self._sa)
 
     def __array__(self, dtype=None):                   # From<SuffixArray> for Vec<u32>, src/sa.rs:364-368
         return self._sa if dtype is None else self._sa.astype(dtype)

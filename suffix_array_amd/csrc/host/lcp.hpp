@@ -1,0 +1,192 @@
+// host/lcp.hpp -- LCP array from a device-resident text and suffix array (kernels/lcp.hpp): work-block
+// layout, the device entry point's sequence and the host-pointer routes.
+#pragma once
+#include "pipeline.hpp"
+#include "host_path.hpp"
+#include "../kernels/lcp.hpp"
+
+namespace sa {
+
+static thread_local sa_amd_lcp_stats g_last_lcp_stats;
+static thread_local int32_t g_lcp_cap = -1;         // sa_amd_lcp_set_compare_cap of the calling thread (-1: LCP_CAP_DEFAULT)
+
+// layout of the work block: error + control words | Φ / v / PLCP | four n-entry buffers (binned scatter's pairs, then the long
+// lists and their mismatch words) | sort spine | single-pass granules | tile maxima.  Never more than the streaming integrity
+// check's block (the rank array there is Φ here; the tile maxima are smaller than its first-byte bitmap).
+struct LcpLayout { size_t ctl, phi, alt, alt_elems, spine, status, tiles, bytes; };
+static LcpLayout lcp_layout(int32_t n)
+{
+    LcpLayout L;
+    const size_t N1 = (size_t)n + 1;
+    size_t off = 0;
+    auto take = [&](size_t b) { const size_t o = off; off = align_up(off + b, 256); return o; };
+    L.ctl = take(256);                     // bytes 0..15: the sort scratch's error words; 32: range flags; 64..: LCP_C_* (uint64)
+    L.phi = take(N1 * 4);
+    L.alt_elems = (N1 + 67) & ~(size_t)3;
+    L.alt = take(4 * L.alt_elems * 4);
+    L.spine = take(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4);
+    L.status = take(((size_t)ceil_div((int64_t)N1, OS_MIN_TILE) + 1) * RADIX * 8);
+    L.tiles = take(((size_t)ceil_div((int64_t)N1, LCP_TILE) + 1) * 4);
+    L.bytes = off;
+    return L;
+}
+
+constexpr int LCP_CTL_OFF = 64;            // byte offset of the control words in the ctl slab
+constexpr int LCP_FLAGS_WORD = 8;          // uint32 index of the range pass's flags in the ctl slab
+constexpr int LCP_MAX_ROUNDS = 64;         // doubling windows from 16 bytes cover 2^31 in fewer than 32
+
+// dT, dSA (n + 1 entries, SA[0] = n), dLCP (n + 1 entries): device memory on the current device; dWork: lcp_layout(n).bytes,
+// 256-byte aligned.  Blocks until the array is complete.
+static int lcp_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, uint32_t *dLCP, void *dWork, int64_t work_bytes, hipStream_t st)
+{
+    const int64_t n = n32;
+    sa_amd_lcp_stats stats;
+    memset(&stats, 0, sizeof(stats));
+    g_last_lcp_stats = stats;
+    const LcpLayout L = lcp_layout(n32);
+    if (work_bytes < (int64_t)L.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
+    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
+    g_posted_off = tn.no_posted_readback;
+    const int rb0 = g_readbacks;
+    char *base = (char *)dWork;
+    uint32_t *err = (uint32_t *)(base + L.ctl);
+    unsigned long long *ctl = (unsigned long long *)(base + L.ctl + LCP_CTL_OFF);
+    HIP_TRY(hipMemsetAsync(err, 0, 256, st));
+
+    // ---- range pass before anything reads through the entries ----
+    int64_t blocks = ceil_div(n + 1, 256);
+    if (blocks > 16384) blocks = 16384;
+    PROF(KC_LCP_PHI, n + 1, st, hipLaunchKernelGGL(k_ci_range, dim3((unsigned)blocks), dim3(256), 0, st, dSA, n, err + LCP_FLAGS_WORD));
+    {
+        uint32_t f = 0;
+        const int rcw = read_words(&f, err + LCP_FLAGS_WORD, 4, st); if (rcw) return rcw;
+        if (f & 1u) return SA_AMD_ERANGE;
+        if (f & 2u) return SA_AMD_EINVAL;             // SA[0] != n (or n in another slot)
+    }
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(dLCP, 0, 4, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        stats.readbacks = g_readbacks - rb0;
+        g_last_lcp_stats = stats;
+        return SA_AMD_OK;
+    }
+
+    // ---- Φ[SA[i]] = SA[i-1] ----
+    uint32_t *phi = (uint32_t *)(base + L.phi);
+    uint32_t *alt = (uint32_t *)(base + L.alt);
+    const size_t ae = L.alt_elems;
+    if (binned(n, n, tn)) {
+        // the binned scatter of the ISA writes, keyed by SA[i] with the value SA[i-1]: the sort passes move the pairs, so they
+        // are copies (the caller's array is read-only)
+        Workspace w;
+        memset(&w, 0, sizeof(w));
+        w.isa = phi;
+        w.spine = (uint32_t *)(base + L.spine);
+        w.digit_tot = w.spine + (size_t)RADIX * SORT_MAX_WG;
+        w.os_status = (unsigned long long *)(base + L.status);
+        w.os_err = err;
+        w.ss.spine = w.spine; w.ss.digit_tot = w.digit_tot; w.ss.status = w.os_status; w.ss.err = w.os_err;
+        HIP_TRY(hipMemcpyAsync(alt, dSA + 1, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(alt + ae, dSA, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        sa_amd_stats local;
+        memset(&local, 0, sizeof(local));
+        const int rcs = scatter_binned(alt, alt + ae, alt + 2 * ae, alt + 3 * ae, n, n, w, st, &local, tn);
+        if (rcs) return rcs;
+    } else {
+        int64_t pb = ceil_div(n, 256);
+        if (pb > 16384) pb = 16384;
+        PROF(KC_LCP_PHI, n, st, hipLaunchKernelGGL(k_lcp_phi, dim3((unsigned)pb), dim3(256), 0, st, dSA, n, phi));
+    }
+
+    // ---- irreducible values up to the cap; the rest to the long list ----
+    const int64_t tiles = ceil_div(n, LCP_TILE);
+    const int64_t cap = g_lcp_cap < 0 ? LCP_CAP_DEFAULT : g_lcp_cap;
+    uint32_t *tile_max = (uint32_t *)(base + L.tiles);
+    uint32_t *list = alt, *res = alt + ae, *list2 = alt + 2 * ae, *res2 = alt + 3 * ae;
+    PROF(KC_LCP_IRRED, n, st, hipLaunchKernelGGL(k_lcp_irreducible, dim3((unsigned)tiles), dim3(LCP_THREADS), 0, st, dT, n, phi, cap,
+                                                 list, res, tile_max, ctl));
+    uint32_t head[(LCP_CTL_OFF + LCP_C_WORDS * 8) / 4];
+    { const int rcw = read_words(head, err, sizeof(head), st); if (rcw) return rcw; }
+    if (head[0]) return SA_AMD_EINTERNAL;           // a look-back of the binned scatter's sort gave up (never seen; never a silent wrong Φ)
+    unsigned long long cw[LCP_C_WORDS];
+    memcpy(cw, (const char *)head + LCP_CTL_OFF, sizeof(cw));
+    int64_t cnt = (int64_t)cw[LCP_C_LONG];
+    stats.irreducible = (int64_t)cw[LCP_C_IRRED];
+    stats.compared_bytes = (int64_t)cw[LCP_C_BYTES];
+    stats.long_pairs = cnt;
+
+    // ---- long compares: windows that double, every pair of the list spread over the whole GPU ----
+    int64_t lo = cap, win = cap > LCP_PIECE ? cap : LCP_PIECE;
+    for (int round = 0; cnt > 0; ++round) {
+        if (round >= LCP_MAX_ROUNDS) return SA_AMD_EINTERNAL;
+        HIP_TRY(hipMemsetAsync(&ctl[LCP_C_NEXT], 0, 8, st));
+        const int64_t units = cnt * ceil_div(win, LCP_PIECE);
+        int64_t gb = ceil_div(units, LCP_THREADS);
+        if (gb > 65536) gb = 65536;
+        PROF(KC_LCP_LONG, units * LCP_PIECE, st, hipLaunchKernelGGL(k_lcp_long, dim3((unsigned)gb), dim3(LCP_THREADS), 0, st, dT, n,
+                                                                    (const uint32_t *)phi, (const uint32_t *)list, cnt, lo, win, res, ctl));
+        int64_t sb = ceil_div(cnt, LCP_THREADS);
+        if (sb > 16384) sb = 16384;
+        PROF(KC_LCP_LONG, cnt, st, hipLaunchKernelGGL(k_lcp_settle, dim3((unsigned)sb), dim3(LCP_THREADS), 0, st, n, phi,
+                                                      (const uint32_t *)list, (const uint32_t *)res, cnt, lo + win, list2, res2, tile_max, ctl));
+        { const int rcw = read_words(cw, ctl, sizeof(cw), st); if (rcw) return rcw; }
+        cnt = (int64_t)cw[LCP_C_NEXT];
+        stats.compared_bytes = (int64_t)cw[LCP_C_BYTES];
+        std::swap(list, list2);
+        std::swap(res, res2);
+        lo += win;
+        win *= 2;
+    }
+
+    // ---- PLCP[j] = max(v[0..j]) - j, then LCP[i] = PLCP[SA[i]] ----
+    PROF(KC_LCP_SCAN, tiles, st, hipLaunchKernelGGL(k_lcp_scan_spine, dim3(1), dim3(LCP_SPINE_THREADS), 0, st, tile_max, tiles));
+    PROF(KC_LCP_SCAN, n, st, hipLaunchKernelGGL(k_lcp_scan, dim3((unsigned)tiles), dim3(LCP_THREADS), 0, st, phi, n, (const uint32_t *)tile_max));
+    int64_t gb = ceil_div(n + 1, 256 * 4);
+    if (gb > 65536) gb = 65536;
+    PROF(KC_LCP_GATHER, n + 1, st, hipLaunchKernelGGL(k_lcp_gather, dim3((unsigned)gb), dim3(256), 0, st, dSA, n, (const uint32_t *)phi, dLCP));
+    HIP_TRY(hipStreamSynchronize(st));
+    g_prof.resolve();
+    stats.readbacks = g_readbacks - rb0;
+    g_last_lcp_stats = stats;
+    return SA_AMD_OK;
+}
+
+// host buffers: the text and the suffix array go up (with_build: the array is built on the device instead and comes back
+// together with the LCP array), the LCP array comes back.  Device block and stream from the process-wide pool.
+static int lcp_host(const uint8_t *T, int32_t n, uint32_t *SA, uint32_t *LCP, bool with_build)
+{
+    if (n < 0 || !SA || !LCP || (n > 0 && !T)) return SA_AMD_EINVAL;
+    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    DeviceGuard guard(pick_device());
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    int cur = 0;
+    HIP_TRY(hipGetDevice(&cur));
+    const size_t N1 = (size_t)n + 1;
+    const size_t tb = align_up((size_t)n + 16, 256), ab = align_up(N1 * 4, 256);
+    size_t wb = lcp_layout(n).bytes;
+    if (with_build) { const size_t bb = (size_t)carve(nullptr, n).bytes; wb = bb > wb ? bb : wb; }
+    DevBlock blk;
+    hipStream_t st = nullptr;
+    int32_t rc = pool().stream(cur, &st);
+    if (rc != SA_AMD_OK) return rc;
+    rc = pool().acquire(cur, wb + tb + 2 * ab, &blk);
+    if (rc != SA_AMD_OK) { pool().release_stream(cur, st); return rc; }
+    void *dW = blk.p;                                               // (first: the block's start is 256-byte aligned)
+    uint8_t *dT = (uint8_t *)blk.p + wb;
+    uint32_t *dSA = (uint32_t *)((char *)dT + tb), *dL = (uint32_t *)((char *)dSA + ab);
+    if (n > 0) rc = hip_status(hipMemcpyAsync(dT, T, (size_t)n, hipMemcpyHostToDevice, st));
+    if (rc == SA_AMD_OK) {
+        if (with_build) rc = build_device(dT, dSA, n, dW, (int64_t)wb, st, nullptr);
+        else rc = hip_status(hipMemcpyAsync(dSA, SA, N1 * 4, hipMemcpyHostToDevice, st));
+    }
+    if (rc == SA_AMD_OK) rc = lcp_device(dT, dSA, n, dL, dW, (int64_t)wb, st);
+    if (rc == SA_AMD_OK && with_build) rc = hip_status(hipMemcpyAsync(SA, dSA, N1 * 4, hipMemcpyDeviceToHost, st));
+    if (rc == SA_AMD_OK) rc = hip_status(hipMemcpyAsync(LCP, dL, N1 * 4, hipMemcpyDeviceToHost, st));
+    const int32_t rs = hip_status(hipStreamSynchronize(st));       // (also drains the stream after a failure)
+    if (rc == SA_AMD_OK) rc = rs;
+    pool().release(blk);
+    pool().release_stream(cur, st);
+    return rc;
+}
+
+}  // namespace sa

@@ -14,6 +14,7 @@
 #include "host/tuning.hpp"
 #include "host/pipeline.hpp"
 #include "host/host_path.hpp"
+#include "host/lcp.hpp"
 
 extern "C" {
 
@@ -472,6 +473,69 @@ SA_EXPORT int32_t sa_amd_index_search(const sa_amd_index *ix, const uint8_t *pat
     if (lcp_len) HIP_TRY(hipMemcpy(lcp_len, R + 3 * C, C * 4, hipMemcpyDeviceToHost));
     return SA_AMD_OK;
     SA_ABI_GUARD_END(0)
+}
+
+// ---- LCP array (host/lcp.hpp, kernels/lcp.hpp) ----
+
+SA_EXPORT int64_t sa_amd_lcp_work_bytes(int32_t n)
+{
+    if (n < 0) return -1;
+    return (int64_t)sa::lcp_layout(n).bytes;
+}
+
+SA_EXPORT int32_t sa_amd_lcp_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, uint32_t *dLCP, void *dWork,
+                                    int64_t work_bytes, void *stream)
+{
+    if (n < 0 || !dSA || !dLCP || !dWork || (n > 0 && !dT)) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    return sa::lcp_device(dT, dSA, n, dLCP, dWork, work_bytes, (hipStream_t)stream);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_lcp(const uint8_t *T, int32_t n, const uint32_t *SA, uint32_t *LCP)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::lcp_host(T, n, (uint32_t *)SA, LCP, false);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_saca_u8_lcp(const uint8_t *T, uint32_t *SA, int32_t n, uint32_t *LCP)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::lcp_host(T, n, SA, LCP, true);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_lcp(const sa_amd_index *ix, uint32_t *LCP)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !LCP) return SA_AMD_EINVAL;
+    sa::DeviceGuard guard(ix->device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess) return SA_AMD_EHIP;
+    const size_t wb = sa::lcp_layout(ix->n).bytes, lb = ((size_t)ix->n + 1) * 4;
+    sa::DevBlock blk;
+    int32_t rc = sa::pool().acquire(cur, wb + lb, &blk);
+    if (rc) return rc;
+    uint32_t *dL = (uint32_t *)((char *)blk.p + wb);
+    rc = sa::lcp_device(ix->dT, ix->dSA, ix->n, dL, blk.p, (int64_t)wb, nullptr);
+    if (rc == SA_AMD_OK) rc = sa::hip_status(hipMemcpy(LCP, dL, lb, hipMemcpyDeviceToHost));
+    sa::pool().release(blk);
+    return rc;
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_lcp_set_compare_cap(int32_t bytes)
+{
+    const int32_t prev = sa::g_lcp_cap < 0 ? sa::LCP_CAP_DEFAULT : sa::g_lcp_cap;
+    sa::g_lcp_cap = bytes < 0 ? -1 : (bytes > sa::LCP_CAP_MAX ? sa::LCP_CAP_MAX : bytes);
+    return prev;
+}
+
+SA_EXPORT void sa_amd_last_lcp_stats(sa_amd_lcp_stats *out)
+{
+    if (out) *out = sa::g_last_lcp_stats;
 }
 
 // ---- packed format (reference src/packed_sa.rs); byte layout: u32 magic "SA4x" LE, u32 length, u64 data length
