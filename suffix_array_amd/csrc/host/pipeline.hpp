@@ -252,7 +252,8 @@ static int sort_pairs_onesweep(KeyT *keys_in, uint32_t *vals_in, KeyT *keys_alt,
                                int *skipped, const Tuning &tn, bool iota, bool may_skip, bool first_counted,
                                const uint8_t *text = nullptr, int64_t text_n = 0,      // != nullptr (32-bit keys only): the FIRST pass reads its keys from the text (k_onesweep<..., TEXT_KEYS>)
                                int text_bits = 8,                                      //   8: the text itself (all 256 byte values), 2: the bit-packed text of a four-symbol alphabet
-                               int val_extra = 0)                                      //   the first pass puts that many key bits below the 32 into the top bits of the values (OnesweepPass::val_extra)
+                               int val_extra = 0,                                      //   the first pass puts that many key bits below the 32 into the top bits of the values (OnesweepPass::val_extra)
+                               KeyT *keys_out2 = nullptr)                              // != nullptr: keys_in is read-only -- the second pass writes its keys here, not into keys_in
 {
     constexpr int TILE = THREADS * ITEMS;
     constexpr int R = 1 << RBITS;
@@ -346,7 +347,7 @@ static int sort_pairs_onesweep(KeyT *keys_in, uint32_t *vals_in, KeyT *keys_alt,
         PROF(K64 ? KC_ONESWEEP : KC_ONESWEEP32, count, st,
              hipLaunchKernelGGL((k_onesweep<THREADS, ITEMS, KeyT, SEQ, WG_PER_CU, RBITS>), dim3(grid), dim3(THREADS), 0, st, (const KeyT *)kin,
                                 (const uint32_t *)((iota && *passes == 0) ? nullptr : vin), kout, vdst, P));
-        KeyT *tk = kin; kin = kout; kout = tk;
+        KeyT *tk = kin; kin = kout; kout = (keys_out2 && *passes == 0) ? keys_out2 : tk;
         uint32_t *free_v = vin;                   // the values just consumed become the next scratch target
         vin = vdst;
         vout = free_v;
@@ -480,9 +481,11 @@ static int sort_pairs32(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_alt
                         const Tuning &tn, bool iota = false, bool first_counted = false,
                         int rbits = RADIX_BITS,       // 9: nine-bit digits (single-pass engine only, first digit counted by the producer)
                         const uint8_t *text = nullptr, int64_t text_n = 0, int text_bits = 8,      // the first pass reads its keys from this text (single-pass engine, default tile, counted)
-                        int val_extra = 0)
+                        int val_extra = 0,
+                        uint32_t *keys_out2 = nullptr)      // != nullptr: keys_in is read-only, the second pass writes its keys here (sort_pairs_onesweep)
 {
     res->keys = keys_in; res->vals = vals_in; res->passes = 0;
+    if (keys_out2 && (rbits != RADIX_BITS || text)) return SA_AMD_EINTERNAL;
     if (count <= 1 || end_bit <= begin_bit) return SA_AMD_OK;
     if (rbits != RADIX_BITS && (rbits != 9 || !onesweep_on(ss, tn) || !first_counted)) return SA_AMD_EINTERNAL;
     if (text && (!onesweep_on(ss, tn) || !first_counted || tn.onesweep32_shape != 0)) return SA_AMD_EINTERNAL;
@@ -495,7 +498,8 @@ static int sort_pairs32(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_alt
             return sort_pairs_onesweep<uint32_t, 1024, 12, false, RADIX_BITS>(keys_in, vals_in, keys_alt, vals_alt, count, begin_bit, end_bit, ss, final_vals, st,
                                                                               &res->keys, &res->vals, &res->passes, &skipped, tn, iota, false, first_counted, text, text_n, text_bits, val_extra);
 #define OS_CALL32(T, I, S) sort_pairs_onesweep<uint32_t, T, I, S>(keys_in, vals_in, keys_alt, vals_alt, count, begin_bit, end_bit, ss, final_vals, st, \
-                                                                 &res->keys, &res->vals, &res->passes, &skipped, tn, iota, false, first_counted)
+                                                                 &res->keys, &res->vals, &res->passes, &skipped, tn, iota, false, first_counted, \
+                                                                 nullptr, 0, 8, 0, keys_out2)
         switch (tn.onesweep32_shape) {
         case 1: return OS_CALL32(512, 16, true);
         case 2: return OS_CALL32(512, 12, false);
@@ -536,7 +540,7 @@ static int sort_pairs32(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_alt
                                                          (const uint32_t *)((iota && res->passes == 0) ? nullptr : vin), kout,
                                                          vdst, spine, (const uint32_t *)digit_tot, count, shift, dmask,
                                                          tiles_per_wg, G));
-        uint32_t *tk = kin; kin = kout; kout = tk;
+        uint32_t *tk = kin; kin = kout; kout = (keys_out2 && res->passes == 0) ? keys_out2 : tk;
         uint32_t *free_v = vin;
         vin = vdst;
         vout = free_v;
@@ -864,7 +868,8 @@ static bool binned(int64_t n, int64_t count, const Tuning &tn)
 // windows of the ISA are assembled in LDS and stored in address order (k_scatter_windows); smaller ones: one pass on the top
 // 8 bits and a plain scatter inside 2^(nb-8)-entry windows.  SA_AMD_SCATTER_LEVELS = 1 / 2 forces either.
 // iota: the value of pair i is i and pk is READ-ONLY (the suffix array itself): the passes then go pk -> (altk, altv) ->
-// (altk2, altv2) and never write into pk.
+// (altk2, altv2) and never write into pk.  Without iota, altk2 != nullptr: pk is read-only likewise (the keys of the rank set-up
+// are the suffix array), the second pass writes its keys to altk2 and its values back into pv.
 static int scatter_binned(uint32_t *pk, uint32_t *pv, uint32_t *altk, uint32_t *altv, int64_t count, int64_t n,
                           const Workspace &w, hipStream_t st, sa_amd_stats *local, const Tuning &tn, bool iota = false,
                           uint32_t *altk2 = nullptr, uint32_t *altv2 = nullptr)
@@ -890,7 +895,7 @@ static int scatter_binned(uint32_t *pk, uint32_t *pv, uint32_t *altk, uint32_t *
                 local->sort_passes += pr.passes; local->sorted_elements += (int64_t)pr.passes * count;
             }
         } else {
-            rc = sort_pairs32(pk, pv, altk, altv, count, wlog, nb, w.ss, nullptr, st, &pr, tn);
+            rc = sort_pairs32(pk, pv, altk, altv, count, wlog, nb, w.ss, nullptr, st, &pr, tn, false, false, RADIX_BITS, nullptr, 0, 8, 0, altk2);
             if (rc) return rc;
             local->sort_passes += pr.passes; local->sorted_elements += (int64_t)pr.passes * count;
         }
@@ -1928,15 +1933,30 @@ struct DeviceBuild {
                 PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan_next), dim3(1), dim3(SPINE_THREADS), 0, st, w.tnext, tiles, (uint32_t *)nullptr));
             if (binned(n, n, tn)) {
                 uint64_t *pk = (sr.keys == w.keysA) ? w.keysB : w.keysA;
+                // the pairs are (SA[i], rank of slot i): k_rr_apply writes only the ranks and the binning reads its keys from the suffix
+                // array itself, dSA[0 .. n] with the sentinel n in front (skipped by the scatter, as in the inverse permutation of the
+                // text-round route) -- 4n bytes less written than a copy of SA.  The 64-bit buffers serve as two halves of n + 1 32-bit
+                // entries each: ranks at pk[H + 1 ..], pass 1 -> sr.keys (dead once k_rr_apply has read it), pass 2 -> pk.
+                // (Tuning::setup_key_copy, diagnostic library: k_rr_apply copies SA into the pairs' keys, as before)
+                const bool from_sa = !tn.setup_key_copy && (((uintptr_t)dSA) & 15) == 0;
+                const size_t H = ((size_t)n + 1 + 3) & ~(size_t)3;
+                uint32_t *pk32 = (uint32_t *)pk, *sk32 = (uint32_t *)sr.keys;
+                uint64_t *pk_out = from_sa ? (uint64_t *)nullptr : pk;
+                uint32_t *pv_out = from_sa ? pk32 + H + 1 : w.U1;
                 if (isa_tail_ranks)
                     PROF(KC_RR_APPLY, n, st, hipLaunchKernelGGL((k_rr_apply<true, false, 2, uint64_t, true>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
                                                                 sr.keys, (const uint32_t *)SA, (const uint32_t *)nullptr, n, w.tcnt, w.thead,
-                                                                SA, w.isa, Ucur, Gcur, Vcur, (uint32_t)n, (uint32_t *)nullptr, 0, pk, w.U1, (const uint32_t *)w.total, 0, (const uint32_t *)w.tnext, 0, (uint32_t *)nullptr));
+                                                                SA, w.isa, Ucur, Gcur, Vcur, (uint32_t)n, (uint32_t *)nullptr, 0, pk_out, pv_out, (const uint32_t *)w.total, 0, (const uint32_t *)w.tnext, 0, (uint32_t *)nullptr));
                 else
                 PROF(KC_RR_APPLY, n, st, hipLaunchKernelGGL((k_rr_apply<true, false, 2>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
                                                             sr.keys, (const uint32_t *)SA, (const uint32_t *)nullptr, n, w.tcnt, w.thead,
-                                                            SA, w.isa, Ucur, Gcur, Vcur, (uint32_t)n, (uint32_t *)nullptr, 0, pk, w.U1, (const uint32_t *)w.total, 0, (const uint32_t *)nullptr, 0, (uint32_t *)nullptr));
-                rc = scatter_binned((uint32_t *)pk, w.U1, (uint32_t *)sr.keys, w.G1, n, n, w, st, &local, tn);
+                                                            SA, w.isa, Ucur, Gcur, Vcur, (uint32_t)n, (uint32_t *)nullptr, 0, pk_out, pv_out, (const uint32_t *)w.total, 0, (const uint32_t *)nullptr, 0, (uint32_t *)nullptr));
+                if (from_sa) {
+                    hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, st, dSA, (uint32_t)n);
+                    LAUNCH_CHECK(st);
+                    rc = scatter_binned(dSA, pk32 + H, sk32, sk32 + H, n + 1, n, w, st, &local, tn, false, pk32);
+                } else
+                    rc = scatter_binned((uint32_t *)pk, w.U1, (uint32_t *)sr.keys, w.G1, n, n, w, st, &local, tn);
                 if (rc) return rc;
             } else if (isa_tail_ranks) {
                 PROF(KC_RR_APPLY, n, st, hipLaunchKernelGGL((k_rr_apply<true, false, 0, uint64_t, true>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
@@ -2060,6 +2080,9 @@ struct DeviceBuild {
         // read-backs (RoundCtl): a round whose predecessor had nothing for the global sort defers that question and blocks ONCE
         bool all_small = false;                           // ... and listed no group for k_group_sort_big: no group is larger than GS_CAP any more
         bool counters_clear = false;                      // the previous round's k_rr_scan_round zeroed the big-group counters
+        // dense rounds write a slot of SA once, in the round its suffix leaves the tied list (k_rr_apply sa_final); the loop runs
+        // until the list is empty, so every slot gets its final value.  Sparse rounds look suffixes up in SA (sparse_key2): every round
+        const int sa_final = (!sparse && !tn.sa_every_round) ? 1 : 0;
         while (m > 0) {
             if (local.rounds >= 48) return SA_AMD_EINTERNAL;
             if ((rc = early_maybe_start())) return rc;     // (every slot outside the tied list is final from here on)
@@ -2117,7 +2140,7 @@ struct DeviceBuild {
                     PROF(KC_RR_APPLY, m, st, hipLaunchKernelGGL((k_rr_apply<false, true, 2>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
                                                                 keysS, valsS, Ucur, m, w.tcnt, w.thead, SA, w.isa, Unext, Gnext, Vnext,
                                                                 (uint32_t)n, (uint32_t *)nullptr, key2_bits, pk, Gcur, (const uint32_t *)w.total, 0,
-                                                                (const uint32_t *)w.tnext, parent_tail ? 1 : 0, w.chg));
+                                                                (const uint32_t *)w.tnext, parent_tail ? 1 : 0, w.chg, (const uint32_t *)nullptr, sa_final));
                     // (only the ranks that change became pairs; their number is in the counters -- read together with the round's
                     // other results: the one read-back of this round)
                     { const int rcw = read_words(words, w.total, sizeof(words), st); if (rcw) return rcw; }
@@ -2133,7 +2156,7 @@ struct DeviceBuild {
                                                                 keysS, valsS, Ucur, m, w.tcnt, w.thead, SA, w.isa, Unext, Gnext, Vnext,
                                                                 (uint32_t)n, (uint32_t *)nullptr, key2_bits, (uint64_t *)nullptr,
                                                                 (uint32_t *)nullptr, (const uint32_t *)w.total, 0,
-                                                                (const uint32_t *)w.tnext, parent_tail ? 1 : 0, w.chg, gate));
+                                                                (const uint32_t *)w.tnext, parent_tail ? 1 : 0, w.chg, gate, sa_final));
                 }
                 // w.total (64 words) and the changed-rank counters behind it (w.chg) in one read-back
                 { const int rcw = read_words(words, w.total, sparse ? (size_t)RC_WORDS * 4 : sizeof(words), st); if (rcw) return rcw; }

@@ -8,6 +8,7 @@
 #pragma once
 #include <cstdlib>
 #include <cstdint>
+#include <atomic>
 
 namespace sa {
 
@@ -35,6 +36,11 @@ inline int64_t env_int(const char *name, int64_t def, int64_t lo, int64_t hi)
 // chosen by the host-pointer calls (HostTuning) and the device-resident one (Tuning) alike
 inline int env_small_max() { return (int)env_int("SA_AMD_SMALL_MAX", 8192, 0, 8192); }
 
+#ifdef SA_AMD_DIAG
+// the old forms of the re-rank writes (Tuning::sa_every_round / setup_key_copy), set by sa_amd_debug_rerank_routes
+inline std::atomic<int> g_rerank_routes{0};
+#endif
+
 struct Tuning {
     int sort_variant = 0;            // SA_AMD_SORT_VARIANT: tile-scatter kernel shape, 64-bit keys (all shapes give the same order)
     int sort32_variant = 0;          // SA_AMD_SORT32_VARIANT: the same for the 32-bit first stage
@@ -56,6 +62,9 @@ struct Tuning {
     int64_t run_skip_min = (int64_t)1 << 25;   // SA_AMD_RUN_SKIP_MIN: smallest refinement sort that looks for such passes
     int64_t dense_rekey_min = (int64_t)1 << 22;   // SA_AMD_DENSE_REKEY_MIN: smallest whole-list global sort that is re-keyed by group index
     bool no_first_tail = false;      // SA_AMD_NO_FIRST_TAIL: the dense route's first ranks are head ranks (the first doubling round then rewrites every rank)
+    // the re-rank writes of round 4 (diag library only, sa_amd_debug_rerank_routes: A/B and route tests; the product library has no switch)
+    bool sa_every_round = false;     // bit 0: the dense rounds write SA for every listed element each round, not only when it leaves the list
+    bool setup_key_copy = false;     // bit 1: the binned rank set-up copies SA into a pair-key array instead of binning straight from SA
     bool no_repeat_probe = false;    // SA_AMD_NO_REPEAT_PROBE: never start rank doubling right after the initial sort
     int64_t binned_min = (int64_t)1 << 26;   // SA_AMD_BINNED_MIN: fewest (suffix, rank) pairs a round bins before scattering
     int chase = 7;                   // SA_AMD_CHASE: rank look-ups per member and dense doubling round (1 = plain doubling), 1..15
@@ -182,6 +191,11 @@ struct Tuning {
         t.sample_log = (int)env_int("SA_AMD_SAMPLE_LOG", 0, 0, 24);
         if (t.sample_log != 0 && t.sample_log < 16) t.sample_log = 16;
         t.timing_only_initial_sort = env_flag("SA_AMD_TIMING_ONLY_INITIAL_SORT");
+        {
+            const int r = g_rerank_routes.load(std::memory_order_relaxed);
+            t.sa_every_round = (r & 1) != 0;
+            t.setup_key_copy = (r & 2) != 0;
+        }
 #endif
         return t;
     }

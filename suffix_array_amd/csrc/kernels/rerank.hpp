@@ -13,8 +13,8 @@ namespace sa {
 //                head slot (+1) inside the tile; dense rounds: also the tile's first group start
 //   k_rr_scan  : exclusive sum / exclusive max over the tiles (one workgroup)
 //   k_rr_scan_next : dense rounds: for every tile the first group start behind it (one workgroup)
-//   k_rr_apply : SA[U[j]] = V[j]; ISA[V[j]] = rank; compact (slot, group head, suffix) of the
-//                elements that are still tied
+//   k_rr_apply : SA[U[j]] = V[j] (dense rounds: only for the elements that leave the list); ISA[V[j]] = rank;
+//                compact (slot, group head, suffix) of the elements that are still tied
 // Algorithmic traffic per element: 12 B read twice (keys + vals [+ 4 B slot]), 4 B SA write,
 // 4 B ISA scatter, 12 B per surviving element.
 // ------------------------------------------------------------------------------------------
@@ -280,7 +280,8 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_apply(
     uint32_t n_text, uint32_t *__restrict__ has_isa, int g_shift, uint64_t *__restrict__ pair_k,
     uint32_t *__restrict__ pair_v, const uint32_t *__restrict__ tile_total, int key_shift,
     const uint32_t *__restrict__ tile_next, int parent_tail, uint32_t *__restrict__ changed_cnt,
-    const uint32_t *__restrict__ gate = nullptr)      // != nullptr: the launch does nothing when *gate != 0
+    const uint32_t *__restrict__ gate = nullptr,      // != nullptr: the launch does nothing when *gate != 0
+    int sa_final = 0)                                 // 1: SA[slot] = suffix only for the elements that leave the tied list (see below)
 {
     constexpr bool SPARSE = ISA_MODE == 1;
     if (gate && *gate) return;
@@ -403,7 +404,10 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_apply(
             if (COUNT_CHANGED && !PAIRS) n_changed += (uint32_t)__popcll(__ballot(i < m && changed));
         }
         if (i < m) {
-            if (WRITE_SA && slot[r] < n_text) SA[slot[r]] = v[r];
+            // sa_final (dense doubling rounds): an element that stays tied is listed again with its suffix (Vo) and its slot is
+            // written in the round it leaves -- nothing reads SA inside the tied list before then (early download: see
+            // DeviceBuild::early_maybe_start) and the rounds only end when the list is empty
+            if (WRITE_SA && slot[r] < n_text && !(sa_final && ((g.tied[r] >> l) & 1ull))) SA[slot[r]] = v[r];
             if (PAIRS) {
                 if (changed) {
                     const uint32_t o = pair_off + (uint32_t)__popcll(cmask[r] & lt_mask);
@@ -411,7 +415,7 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_apply(
                     pair_v[o] = rank;
                 }
             } else if (ISA_MODE == 2) {
-                ((uint32_t *)pair_k)[i] = v[r];
+                if (pair_k) ((uint32_t *)pair_k)[i] = v[r];      // nullptr (FIRST): the keys are V itself, the suffix array, and are read from there
                 pair_v[i] = rank;
             } else if (ISA_MODE != 3 && ISA_MODE != 4 && v[r] < n_text) {
                 if (changed) {

@@ -15,6 +15,10 @@ extern "C" {
 int32_t sa_amd_debug_phase_cycles(uint64_t *out, int32_t count);
 /* k_group_sort: switch its per-phase stamps on / off (entries 8..13 of the same array) */
 int32_t sa_amd_debug_group_sort_stamps(int32_t on);
+/* the old forms of the dense route's re-rank writes, for A/B and the route tests (process-wide; returns the previous flags):
+ * bit 0: dense rounds write SA for every listed suffix each round (not only in the round it leaves the list),
+ * bit 1: the binned rank set-up copies SA into its pair keys (instead of binning straight from the suffix array) */
+int32_t sa_amd_debug_rerank_routes(int32_t flags);
 int32_t sa_amd_debug_sort_variant_count(void);
 const char *sa_amd_debug_sort_variant_name(int32_t index);
 /* stable LSD radix sort of (u64 key, u32 value) pairs on bits [begin_bit, end_bit); host buffers */

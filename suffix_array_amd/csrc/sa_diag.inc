@@ -19,6 +19,11 @@ SA_EXPORT int32_t sa_amd_debug_group_sort_stamps(int32_t on)
     return hipMemcpyToSymbol(HIP_SYMBOL(sa::g_gs_stamp_on), &v, sizeof(v)) == hipSuccess ? SA_AMD_OK : SA_AMD_EHIP;
 }
 
+SA_EXPORT int32_t sa_amd_debug_rerank_routes(int32_t flags)
+{
+    return sa::g_rerank_routes.exchange(flags & 3);
+}
+
 SA_EXPORT int32_t sa_amd_debug_sort_variant_count(void) { return sa::N_SORT_VARIANTS; }
 SA_EXPORT const char *sa_amd_debug_sort_variant_name(int32_t i)
 {
