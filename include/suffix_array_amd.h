@@ -216,6 +216,28 @@ int32_t sa_amd_saca_u8_lcp(const uint8_t *T, uint32_t *SA, int32_t n, uint32_t *
 /* from the index's resident text and suffix array (n + 1 entries) */
 int32_t sa_amd_index_lcp(const sa_amd_index *ix, uint32_t *LCP);
 
+/*
+ * Enhanced suffix array (an extension: the reference's README TODO "speed up searching by LCP array"), opt-in per index.
+ * sa_amd_index_enable_lcp builds the LCP array of the resident text and array (as sa_amd_index_lcp, on the device), turns it
+ * into the LCP table of a fixed search tree -- one uint64 per slot, 8 (n + 1) bytes kept in the index -- and drops the LCP
+ * array.  A no-op when the index has the table; errors as sa_amd_index_lcp (SA_AMD_ERANGE, SA_AMD_EINVAL), SA_AMD_ENOMEM when
+ * the table does not fit.  Later sa_amd_index_search calls take the LCP route: Manber-Myers search, at most
+ * 2 plen + 128 log2 P text bytes compared per pattern (P the smallest power of two >= n + 2) instead of O(plen log n), with
+ * answers identical to the plain route's, bucket table or not.  When the resident array is not the
+ * suffix array of the text the answers are unspecified, but nothing is read outside the text, the patterns or the tables.
+ */
+int32_t sa_amd_index_enable_lcp(sa_amd_index *ix);
+
+typedef struct sa_amd_search_stats {   /* of the calling thread's most recent sa_amd_index_search */
+    int64_t patterns;                  /* patterns of that call */
+    int64_t compared_bytes;            /* text bytes compared, every 64-byte chunk a wave loaded counted whole (LCP route) */
+    int64_t steps;                     /* tree steps, 2 log2 P per pattern (LCP route) */
+    int64_t table_steps;               /* steps decided from the table, without loading SA or the text (LCP route) */
+    int32_t route;                     /* 0: plain binary search (the three counters above read -1), 1: LCP route */
+    int32_t reserved;
+} sa_amd_search_stats;
+void sa_amd_last_search_stats(sa_amd_search_stats *out);
+
 typedef struct sa_amd_lcp_stats {   /* of the calling thread's most recent LCP build */
     int64_t irreducible;            /* positions whose value was computed directly */
     int64_t compared_bytes;         /* text bytes loaded for comparison (both suffixes), short and long paths together */

@@ -22,7 +22,7 @@ import numpy as np
 __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag_lib", "library_path", "Stats", "last_host_timing",
            "saca_batch", "workspace_bytes", "device_pci_bus_id", "saca_device_ptr", "bucket_table", "check_integrity", "last_stats", "DeviceIndex", "pack", "unpack",
            "lcp", "saca_lcp", "last_lcp_stats", "lcp_work_bytes", "lcp_device_ptr", "LcpStats",
-           "lcp_set_compare_cap"]
+           "lcp_set_compare_cap", "last_search_stats", "SearchStats"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
@@ -60,6 +60,15 @@ class LcpStats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class SearchStats(ctypes.Structure):
+    """sa_amd_search_stats of include/suffix_array_amd.h"""
+    _fields_ = [("patterns", ctypes.c_int64), ("compared_bytes", ctypes.c_int64), ("steps", ctypes.c_int64),
+                ("table_steps", ctypes.c_int64), ("route", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
 def library_path() -> str:
@@ -147,6 +156,10 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_last_lcp_stats.restype = None
         L.sa_amd_lcp_set_compare_cap.argtypes = [ctypes.c_int32]
         L.sa_amd_lcp_set_compare_cap.restype = ctypes.c_int32
+        L.sa_amd_index_enable_lcp.argtypes = [c_vp]
+        L.sa_amd_index_enable_lcp.restype = ctypes.c_int32
+        L.sa_amd_last_search_stats.argtypes = [c_vp]
+        L.sa_amd_last_search_stats.restype = None
         _lib = L
     return _lib
 
@@ -377,6 +390,14 @@ def lcp_set_compare_cap(nbytes: int) -> int:
     return int(lib().sa_amd_lcp_set_compare_cap(int(nbytes)))
 
 
+def last_search_stats() -> dict:
+    """sa_amd_search_stats of this thread's most recent DeviceIndex.search: route 1 (LCP route, enable_lcp) with the compared
+    bytes, tree steps and steps decided from the table; route 0 (plain binary search) with those counters at -1"""
+    st = SearchStats()
+    lib().sa_amd_last_search_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
 def lcp_work_bytes(n: int) -> int:
     return int(lib().sa_amd_lcp_work_bytes(n))
 
@@ -429,6 +450,11 @@ class DeviceIndex:
         out = np.empty(self._s.size + 1, dtype=np.uint32)
         _lcp_rc(lib().sa_amd_index_lcp(self._h, out.ctypes.data))
         return out
+
+    def enable_lcp(self) -> None:
+        """EXTENSION (the reference's README TODO "speed up searching by LCP array"): build and keep the LCP table of the
+        search tree (8 (n + 1) bytes); later searches take the LCP route with the same answers.  A no-op when it exists."""
+        _lcp_rc(lib().sa_amd_index_enable_lcp(self._h))
 
     def search(self, patterns):
         """-> dict of arrays over the patterns: contains (bool), lo/hi (search_all == sa[lo:hi]),
@@ -490,6 +516,7 @@ class SuffixArray:
         self._sa = np.zeros(self._s.size + 1, dtype=np.uint32)     # vec![0; s.len() + 1]
         saca(self._s, self._sa)
         self._bkt = None
+        self._esa = False
         self._ix = None
 
     @classmethod
@@ -535,6 +562,7 @@ class SuffixArray:
         obj._s = _as_u8(s)
         obj._sa = np.ascontiguousarray(sa, dtype=np.uint32)
         obj._bkt = None
+        obj._esa = False
         obj._ix = None
         return obj
 
@@ -574,6 +602,8 @@ class SuffixArray:
             self._ix = DeviceIndex(self._s, self._sa)
             if self._bkt is not None:
                 self._ix.buckets()
+            if getattr(self, "_esa", False):
+                self._ix.enable_lcp()
         return self._ix
 
     def contains(self, pat) -> bool:
@@ -592,6 +622,13 @@ class SuffixArray:
         with the suffix array, ``lcp[0] == 0``, ``lcp[i]`` = longest common prefix of the suffixes at ``sa[i-1]`` and
         ``sa[i]``; computed on the GPU from the text and the array"""
         return lcp(self._s, self._sa)
+
+    def enable_lcp(self) -> None:
+        """EXTENSION (the reference's README TODO "speed up searching by LCP array"): contains / search_all / search_lcp
+        from now on search over the LCP table of the device-resident index (DeviceIndex.enable_lcp), with the same answers;
+        remembered like the bucket table, so the index that set() drops is rebuilt with it"""
+        self._esa = True
+        self._index().enable_lcp()
 
     def __array__(self, dtype=None):                   # From<SuffixArray> for Vec<u32>, src/sa.rs:364-368
         return self._sa if dtype is None else self._sa.astype(dtype)

@@ -15,6 +15,7 @@
 #include "host/pipeline.hpp"
 #include "host/host_path.hpp"
 #include "host/lcp.hpp"
+#include "host/esa.hpp"
 
 extern "C" {
 
@@ -347,6 +348,7 @@ struct sa_amd_index {
     uint8_t *dT;
     uint32_t *dSA;
     uint32_t *dBkt;       // bucket table once sa_amd_index_buckets has built it (narrows the searches, src/sa.rs:123-161)
+    uint64_t *dPair;      // LCP table of the search tree once sa_amd_index_enable_lcp has built it (kernels/esa.hpp)
 };
 
 SA_EXPORT int32_t sa_amd_index_create(const uint8_t *T, int32_t n, const uint32_t *SA, sa_amd_index **out)
@@ -373,7 +375,7 @@ SA_EXPORT int32_t sa_amd_index_create(const uint8_t *T, int32_t n, const uint32_
     }
     sa_amd_index *ix = new (std::nothrow) sa_amd_index();
     if (!ix) return SA_AMD_ENOMEM;
-    ix->n = n; ix->device = 0; ix->dBkt = nullptr;
+    ix->n = n; ix->device = 0; ix->dBkt = nullptr; ix->dPair = nullptr;
     (void)hipGetDevice(&ix->device);
     ix->dT = dT.as<uint8_t>(); ix->dSA = dSA.as<uint32_t>();
     dT.p = nullptr; dSA.p = nullptr;                             // ownership moves to the index
@@ -388,6 +390,7 @@ SA_EXPORT void sa_amd_index_destroy(sa_amd_index *ix)      // (frees and deletes
     if (ix->dT) (void)hipFree(ix->dT);
     if (ix->dSA) (void)hipFree(ix->dSA);
     if (ix->dBkt) (void)hipFree(ix->dBkt);
+    if (ix->dPair) (void)hipFree(ix->dPair);
     delete ix;
 }
 
@@ -444,7 +447,14 @@ SA_EXPORT int32_t sa_amd_index_search(const sa_amd_index *ix, const uint8_t *pat
     SA_ABI_GUARD_BEGIN
     using namespace sa;
     if (!ix || count < 0 || (count > 0 && !pat_off)) return SA_AMD_EINVAL;
-    if (count == 0) return SA_AMD_OK;
+    if (count == 0) {
+        sa_amd_search_stats z;
+        memset(&z, 0, sizeof(z));
+        z.route = ix->dPair ? 1 : 0;
+        if (!ix->dPair) z.compared_bytes = z.steps = z.table_steps = -1;
+        g_last_search_stats = z;
+        return SA_AMD_OK;
+    }
     const int64_t total = pat_off[count];
     if (total < 0 || (total > 0 && !pat_data)) return SA_AMD_EINVAL;
     for (int32_t i = 0; i < count; ++i) if (pat_off[i + 1] < pat_off[i] || pat_off[i] < 0) return SA_AMD_EINVAL;
@@ -461,11 +471,33 @@ SA_EXPORT int32_t sa_amd_index_search(const sa_amd_index *ix, const uint8_t *pat
     HIP_TRY(hipMemcpy(dO.p, pat_off, (C + 1) * 8, hipMemcpyHostToDevice));
     uint32_t *R = dR.as<uint32_t>();
     const int64_t threads = (int64_t)count * WAVE;
-    hipLaunchKernelGGL(k_search_batch, dim3((unsigned)ceil_div(threads, SEARCH_THREADS)), dim3(SEARCH_THREADS), 0, nullptr,
-                       (const uint8_t *)ix->dT, (const uint32_t *)ix->dSA, (int64_t)ix->n, dP.as<const uint8_t>(),
-                       dO.as<const int64_t>(), count, dC.as<uint8_t>(), R, R + C, R + 2 * C, R + 3 * C, (const uint32_t *)ix->dBkt);
+    const dim3 grid((unsigned)ceil_div(threads, SEARCH_THREADS));
+    sa_amd_search_stats stats;
+    memset(&stats, 0, sizeof(stats));
+    stats.patterns = count;
+    stats.compared_bytes = stats.steps = stats.table_steps = -1;
+    DevBuf dS;
+    if (ix->dPair) {                                             // LCP route (kernels/esa.hpp)
+        if ((rc = dS.alloc(3 * 8))) return rc;
+        HIP_TRY(hipMemset(dS.p, 0, 3 * 8));
+        hipLaunchKernelGGL(k_esa_search, grid, dim3(SEARCH_THREADS), 0, nullptr, (const uint8_t *)ix->dT,
+                           (const uint32_t *)ix->dSA, (int64_t)ix->n, (const uint64_t *)ix->dPair, esa_log_p(ix->n),
+                           dP.as<const uint8_t>(), dO.as<const int64_t>(), count, dC.as<uint8_t>(), R, R + C, R + 2 * C, R + 3 * C,
+                           (const uint32_t *)ix->dBkt, dS.as<unsigned long long>());
+    } else {
+        hipLaunchKernelGGL(k_search_batch, grid, dim3(SEARCH_THREADS), 0, nullptr,
+                           (const uint8_t *)ix->dT, (const uint32_t *)ix->dSA, (int64_t)ix->n, dP.as<const uint8_t>(),
+                           dO.as<const int64_t>(), count, dC.as<uint8_t>(), R, R + C, R + 2 * C, R + 3 * C, (const uint32_t *)ix->dBkt);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
+    if (ix->dPair) {
+        int64_t cw[3];
+        HIP_TRY(hipMemcpy(cw, dS.p, sizeof(cw), hipMemcpyDeviceToHost));
+        stats.compared_bytes = cw[0]; stats.steps = cw[1]; stats.table_steps = cw[2];
+        stats.route = 1;
+    }
+    g_last_search_stats = stats;
     if (contains) HIP_TRY(hipMemcpy(contains, dC.p, C, hipMemcpyDeviceToHost));
     if (range_lo) HIP_TRY(hipMemcpy(range_lo, R, C * 4, hipMemcpyDeviceToHost));
     if (range_hi) HIP_TRY(hipMemcpy(range_hi, R + C, C * 4, hipMemcpyDeviceToHost));
@@ -524,6 +556,38 @@ SA_EXPORT int32_t sa_amd_index_lcp(const sa_amd_index *ix, uint32_t *LCP)
     sa::pool().release(blk);
     return rc;
     SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_enable_lcp(sa_amd_index *ix)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix) return SA_AMD_EINVAL;
+    if (ix->dPair) return SA_AMD_OK;
+    sa::DeviceGuard guard(ix->device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess) return SA_AMD_EHIP;
+    uint64_t *dPair = nullptr;
+    if (hipMalloc((void **)&dPair, ((size_t)ix->n + 1) * 8) != hipSuccess) { (void)hipGetLastError(); return SA_AMD_ENOMEM; }
+    // LCP array and its work block from the pool, as sa_amd_index_lcp; the tile minima of the table build behind them
+    const size_t wb = sa::lcp_layout(ix->n).bytes, lb = sa::align_up(((size_t)ix->n + 1) * 4, 256);
+    sa::DevBlock blk;
+    int32_t rc = sa::pool().acquire(cur, wb + lb + sa::esa_mins_elems(ix->n) * 4, &blk);
+    if (rc) { (void)hipFree(dPair); return rc; }
+    uint32_t *dL = (uint32_t *)((char *)blk.p + wb);
+    rc = sa::lcp_device(ix->dT, ix->dSA, ix->n, dL, blk.p, (int64_t)wb, nullptr);
+    if (rc == SA_AMD_OK) rc = sa::esa_build(dL, ix->n, dPair, (uint32_t *)((char *)dL + lb), nullptr);
+    if (rc == SA_AMD_OK) rc = sa::hip_status(hipDeviceSynchronize());
+    sa::pool().release(blk);
+    if (rc != SA_AMD_OK) { (void)hipFree(dPair); return rc; }
+    ix->dPair = dPair;                                           // kept: later searches take the LCP route
+    return SA_AMD_OK;
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_search_stats(sa_amd_search_stats *out)
+{
+    if (out) *out = sa::g_last_search_stats;
 }
 
 SA_EXPORT int32_t sa_amd_lcp_set_compare_cap(int32_t bytes)
