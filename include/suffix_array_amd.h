@@ -150,6 +150,9 @@ int32_t sa_amd_bucket_table_device(const uint8_t *dT, const uint32_t *dSA, int32
  * (random-store inverse permutation); with sa_amd_check_integrity_work_bytes(n) bytes, 256-byte
  * aligned, and a 16-byte aligned dSA the check runs at streaming cost (binned inverse permutation,
  * one random rank line per slot: 25 -> ~10 ms at 256 MiB).
+ * Empty text (n == 0): SA = {0} gives 1 and any other single entry SA_AMD_ERANGE.  The reference returns
+ * true there without reading the entry (its pair loop never runs); an index built on such an array
+ * would read past the text, so the check rejects it like any other entry beyond n.
  */
 int64_t sa_amd_check_integrity_work_bytes(int32_t n);
 int32_t sa_amd_check_integrity(const uint8_t *T, int32_t n, const uint32_t *SA, int64_t sa_len);

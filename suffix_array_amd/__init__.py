@@ -484,17 +484,28 @@ def saca_device_ptr(text_ptr: int, sa_ptr: int, n: int, work_ptr: int, work_byte
 
 def _check_integrity(s: np.ndarray, sa: np.ndarray) -> bool:
     """reference src/sa.rs:72-84, in its linear-time equivalent form:
-    a length check, then every adjacent pair must be strictly increasing as byte slices."""
+    a length check, then every adjacent pair must be strictly increasing as byte slices.
+    IndexError for an entry > n, also for the empty text (as the GPU check: see sa_amd_check_integrity)."""
     n = s.size
     if n + 1 != sa.size:                              # src/sa.rs:73-75
         return False
-    if n == 0:
-        return int(sa[0]) == 0                        # sa[0] > n would panic in the reference
     if sa.max() > n:
         raise IndexError("suffix offset out of range (the reference panics here, src/sa.rs:77-78)")
     if n <= 64:                                       # literal form for tiny inputs
-        b = s.tobytes()
-        return all(b[int(sa[i - 1]):] < b[int(sa[i]):] for i in range(1, n + 1))
+        return _check_integrity_literal(s, sa)
+    return _check_integrity_linear(s, sa)
+
+
+def _check_integrity_literal(s: np.ndarray, sa: np.ndarray) -> bool:
+    """the pairwise slice comparison of src/sa.rs:76-82 (entries already known to be <= n)"""
+    b = s.tobytes()
+    return all(b[int(sa[i - 1]):] < b[int(sa[i]):] for i in range(1, s.size + 1))
+
+
+def _check_integrity_linear(s: np.ndarray, sa: np.ndarray) -> bool:
+    """the same answer in linear time: sa[0] = n, a permutation, first bytes then ranks of the next suffixes increasing
+    (entries already known to be <= n)"""
+    n = s.size
     if int(sa[0]) != n:
         return False
     rank = np.full(n + 1, -1, dtype=np.int64)

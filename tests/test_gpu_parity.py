@@ -812,16 +812,17 @@ def test_concurrent_callers(oracle):
         assert np.array_equal(o, oracle.sais(t_))
 
 
-def test_max_length_text():
+def test_max_length_text(oracle):
     """n = MAX_LENGTH = i32::MAX (reference src/saca.rs:6,10): index arithmetic at the top of the range.
-    Checked with the HIP integrity check (reference src/sa.rs:72-84) and direct comparisons of
-    sampled neighbours."""
+    Checked with the HIP integrity check (reference src/sa.rs:72-84), the oracle's linear-time verifier and direct
+    comparisons of sampled neighbours."""
     n = sa.MAX_LENGTH
     text = corpus.uniform(n, 77)
     arr = np.empty(n + 1, dtype=np.uint32)
     sa.saca(text, arr)
     assert arr[0] == n
     assert sa.check_integrity(text, arr) is True
+    assert oracle.verify_mt(text, arr) == 1
     rng = np.random.default_rng(1)
     for i in rng.integers(1, n, 2000):
         a, b = int(arr[i]), int(arr[i + 1])

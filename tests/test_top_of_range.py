@@ -263,6 +263,21 @@ def test_integrity_check_at_the_top(big):
             i = int(i)
             with _mutated(arr, [i, i + 1], [arr[i + 1], arr[i]]):
                 assert forms(arr) == (0, 0, 0), i
+        # the slots where the streaming check takes separate paths: first-byte boundaries (skipped by the slot-order pass,
+        # proved by k_ci_first_bytes), the first lane of a wave and of a workgroup (no shuffle: SA[i - 1] fetched) above
+        # 2^30, and suffix n - 1 (its next suffix is the empty one)
+        counts = np.bincount(text, minlength=256)
+        starts = 1 + np.cumsum(counts) - counts
+        slots = [int(s) - 1 for c, s in enumerate(starts) if counts[c] and s > 1]
+        lane0 = ((1 << 30) + 64) & ~63
+        last0 = (n - 2) & ~63
+        slots += [lane0, lane0 + 1, last0, last0 + 1, (1 << 30) + 2048]
+        r = int(np.flatnonzero(arr == n - 1)[0])
+        slots += [r - 1, r]
+        for i in slots:
+            assert 0 <= i < n, i
+            with _mutated(arr, [i, i + 1], [arr[i + 1], arr[i]]):
+                assert forms(arr) == (0, 0, 0), i
         j = int(rng.integers(1 << 30, n))
         with _mutated(arr, [j], [arr[j + 1]]):                             # a value twice, another one missing
             assert forms(arr) == (0, 0, 0)
