@@ -253,6 +253,69 @@ void sa_amd_last_lcp_stats(sa_amd_lcp_stats *out);
  * (64).  Returns the previous value. */
 int32_t sa_amd_lcp_set_compare_cap(int32_t bytes);
 
+/*
+ * Burrows-Wheeler transform and its inverse (an extension of this crate's path; the group `divbwt` / `inverse_bw_transform`
+ * of the C engine the reference binds).  libdivsufsort's sources are not part of this project, so the layout below is this
+ * library's own contract, restated from the published description of divbwt and pinned by the tests.
+ * With SA in the layout of sa_amd_saca_u8 (n + 1 entries, SA[0] = n):
+ *   primary = the slot i with SA[i] == 0: 1 <= primary <= n for n > 0, and 0 for the empty text;
+ *   B has n bytes: B[k] = T[SA[k] - 1] for k < primary and B[k] = T[SA[k + 1] - 1] for k >= primary.  So B[0] = T[n - 1], and
+ *   the row of the whole text (where a sentinel would stand) is left out.  "banana" -> "annbaa", primary 4.
+ * The inverse takes (B, n, primary) and returns T, for every byte string (zeros included).
+ * Argument errors of the forward calls, as for the LCP array: a range pass runs before anything is read through the entries;
+ * an entry > n is SA_AMD_ERANGE; SA[0] != n, or not exactly one entry equal to 0, is SA_AMD_EINVAL.  The array is not otherwise
+ * proved to be the suffix array (sa_amd_check_integrity does that): with a wrong permutation the bytes of B are unspecified,
+ * but nothing is read outside the text or written outside B.
+ */
+/* bytes of device scratch sa_amd_bwt_device needs (256, whatever n) */
+int64_t sa_amd_bwt_work_bytes(int32_t n);
+/* device pointers: dT n bytes (any byte address, read byte by byte), dSA n + 1 entries, dBWT n bytes (any byte address; may not
+ * alias dT), dWork sa_amd_bwt_work_bytes(n) bytes 256-byte aligned (else SA_AMD_EINVAL), primary_out a HOST pointer; stream a
+ * hipStream_t (NULL = default stream).  Blocks until done. */
+int32_t sa_amd_bwt_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, uint8_t *dBWT, int32_t *primary_out,
+                          void *dWork, int64_t work_bytes, void *stream);
+/* host pointers.  SA == NULL: the array is built on the device, used there and never downloaded (divbwt(T, U, NULL, n)): n bytes
+ * go up and n come back.  SA != NULL (n + 1 entries): the caller's array goes up instead of being rebuilt. */
+int32_t sa_amd_bwt(const uint8_t *T, int32_t n, const uint32_t *SA, uint8_t *BWT, int32_t *primary_out);
+/* from the index's resident text and suffix array */
+int32_t sa_amd_index_bwt(const sa_amd_index *ix, uint8_t *BWT, int32_t *primary_out);
+
+/*
+ * Inverse: one stable 8-bit sort of the indices of B gives the row permutation psi; rows whose hash is 0 mod S (and `primary`)
+ * are splitters; one lane per splitter walks psi to the next splitter, the sublists are ranked from primary's by pointer
+ * jumping, and a second walk writes the text.  primary outside 1 .. n (0 for n = 0) is SA_AMD_EINVAL; a
+ * pair (B, primary) that is not the transform of any text (the walk from primary closes before it has visited n + 1 rows) is
+ * SA_AMD_EINVAL too: the call still terminates and has then written nothing to T_out.
+ */
+/* bytes of device scratch sa_amd_unbwt_device needs: about 16.5 (n + 1) */
+int64_t sa_amd_unbwt_work_bytes(int32_t n);
+/* device pointers: dBWT and dT_out n bytes each (any byte address), dWork sa_amd_unbwt_work_bytes(n) bytes 256-byte aligned (else
+ * SA_AMD_EINVAL); stream a hipStream_t (NULL = default stream).  Blocks until done. */
+int32_t sa_amd_unbwt_device(const uint8_t *dBWT, int32_t n, int32_t primary, uint8_t *dT_out, void *dWork,
+                            int64_t work_bytes, void *stream);
+/* host pointers: BWT (n bytes) goes up, T_out (n bytes) comes back */
+int32_t sa_amd_unbwt(const uint8_t *BWT, int32_t n, int32_t primary, uint8_t *T_out);
+
+typedef struct sa_amd_unbwt_stats {  /* of the calling thread's most recent inverse transform */
+    int64_t walkers;                 /* splitters = lanes of a walk launch (the last attempt's) */
+    int64_t steps;                   /* psi steps taken by all walkers, both walking phases and every attempt: 2 (n + 1) without a restart */
+    int64_t longest_walk;            /* rows of the longest sublist (summed over resumed launches) */
+    int32_t splitter_spacing;        /* S in use at the end */
+    int32_t walk_launches;           /* launches of the first walking phase, every attempt */
+    int32_t restarts;                /* attempts thrown away: lanes were still walking at the launch limit (S / 8, another hash seed) */
+    int32_t readbacks;               /* blocking device -> host read-backs of counters */
+} sa_amd_unbwt_stats;
+void sa_amd_last_unbwt_stats(sa_amd_unbwt_stats *out);
+/* route switch of the calling thread's later inverse transforms (never changes a result; there so that the resume and restart
+ * paths can be exercised on small inputs).  cap_steps: psi steps one lane takes per walk launch before it saves its place and
+ * goes on in the next launch, clamped to 1 .. 16 777 216 (default 4096).  max_launches: walk launches after which an attempt
+ * whose lanes are still walking is restarted with denser splitters (default: as many as 64 S steps take; never at S = 4, the
+ * densest set).  A negative argument restores that default. */
+void sa_amd_unbwt_set_walk_limits(int32_t cap_steps, int32_t max_launches);
+/* the same kind of switch for the splitter spacing S of the first attempt: rounded down to a power of two in 4 .. 65 536 (default
+ * 256, measured in DESIGN.md section 12); a negative value restores the default.  Returns the previous value. */
+int32_t sa_amd_unbwt_set_splitter_spacing(int32_t spacing);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

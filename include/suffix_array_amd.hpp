@@ -6,6 +6,8 @@
 //                                           reference src/sa.rs:23-70, check_integrity src/sa.rs:72-84
 //   SuffixArray::enable_buckets / buckets   reference src/sa.rs:89-119 (the table, built on the GPU from the text alone)
 //   SuffixArray::lcp_array                  EXTENSION: the LCP array (the reference's README TODO "enhanced suffix array")
+//   SuffixArray::bwt, bwt(), unbwt()        EXTENSION: the Burrows-Wheeler transform and its inverse (divbwt /
+//                                           inverse_bw_transform of the C engine the reference binds)
 // Rust panics (assert!, engine failure) are std::logic_error / std::runtime_error here.
 #pragma once
 #include "suffix_array_amd.h"
@@ -29,6 +31,31 @@ inline void saca(const std::uint8_t *s, std::size_t n, std::uint32_t *sa, std::s
     if (n + 1 != sa_len) throw std::logic_error("assertion failed: s.len() + 1 == sa.len()");   // :11
     const std::int32_t rc = sa_amd_saca_u8(s, sa, static_cast<std::int32_t>(n));                 // :13-14
     if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
+}
+
+// EXTENSION: the Burrows-Wheeler transform of s (layout in suffix_array_amd.h): n bytes and the primary index.  sa == nullptr:
+// the suffix array is built on the device and never downloaded (sa_amd_bwt)
+inline std::pair<std::vector<std::uint8_t>, std::int32_t> bwt(const std::uint8_t *s, std::size_t n, const std::uint32_t *sa = nullptr)
+{
+    if (n > MAX_LENGTH) throw std::logic_error("assertion failed: s.len() <= MAX_LENGTH");
+    std::vector<std::uint8_t> b(n);
+    std::int32_t primary = 0;
+    const std::int32_t rc = sa_amd_bwt(s, static_cast<std::int32_t>(n), sa, b.data(), &primary);
+    if (rc == SA_AMD_ERANGE) throw std::out_of_range("suffix offset out of range");
+    if (rc == SA_AMD_EINVAL) throw std::invalid_argument("not a suffix array of this layout");
+    if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
+    return { std::move(b), primary };
+}
+
+// EXTENSION: the text whose transform is (b, primary); std::invalid_argument when the pair is not a transform (sa_amd_unbwt)
+inline std::vector<std::uint8_t> unbwt(const std::uint8_t *b, std::size_t n, std::int32_t primary)
+{
+    if (n > MAX_LENGTH) throw std::logic_error("assertion failed: b.len() <= MAX_LENGTH");
+    std::vector<std::uint8_t> t(n);
+    const std::int32_t rc = sa_amd_unbwt(b, static_cast<std::int32_t>(n), primary, t.data());
+    if (rc == SA_AMD_EINVAL) throw std::invalid_argument("not a Burrows-Wheeler transform");
+    if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
+    return t;
 }
 
 class SuffixArray {
@@ -87,6 +114,12 @@ public:
         if (rc == SA_AMD_ERANGE) throw std::out_of_range("suffix offset out of range");
         if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
         return l;
+    }
+    // EXTENSION (not in the reference): the Burrows-Wheeler transform from the text and this array (sa_amd_bwt)
+    std::pair<std::vector<std::uint8_t>, std::int32_t> bwt() const
+    {
+        if (n_ + 1 != sa_.size()) throw std::logic_error("assertion failed: s.len() + 1 == sa.len()");
+        return suffix_array::bwt(s_, n_, sa_.data());
     }
 
 private:

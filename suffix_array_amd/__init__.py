@@ -22,7 +22,9 @@ import numpy as np
 __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag_lib", "library_path", "Stats", "last_host_timing",
            "saca_batch", "workspace_bytes", "device_pci_bus_id", "saca_device_ptr", "bucket_table", "check_integrity", "last_stats", "DeviceIndex", "pack", "unpack",
            "lcp", "saca_lcp", "last_lcp_stats", "lcp_work_bytes", "lcp_device_ptr", "LcpStats",
-           "lcp_set_compare_cap", "last_search_stats", "SearchStats"]
+           "lcp_set_compare_cap", "last_search_stats", "SearchStats",
+           "bwt", "unbwt", "bwt_device_ptr", "unbwt_device_ptr", "bwt_work_bytes", "unbwt_work_bytes", "last_unbwt_stats",
+           "unbwt_set_walk_limits", "unbwt_set_splitter_spacing", "UnbwtStats"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
@@ -69,6 +71,16 @@ class SearchStats(ctypes.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+class UnbwtStats(ctypes.Structure):
+    """sa_amd_unbwt_stats of include/suffix_array_amd.h"""
+    _fields_ = [("walkers", ctypes.c_int64), ("steps", ctypes.c_int64), ("longest_walk", ctypes.c_int64),
+                ("splitter_spacing", ctypes.c_int32), ("walk_launches", ctypes.c_int32), ("restarts", ctypes.c_int32),
+                ("readbacks", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 def library_path() -> str:
@@ -160,6 +172,26 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_index_enable_lcp.restype = ctypes.c_int32
         L.sa_amd_last_search_stats.argtypes = [c_vp]
         L.sa_amd_last_search_stats.restype = None
+        L.sa_amd_bwt_work_bytes.argtypes = [ctypes.c_int32]
+        L.sa_amd_bwt_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_bwt_device.argtypes = [c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_bwt_device.restype = ctypes.c_int32
+        L.sa_amd_bwt.argtypes = [c_vp, ctypes.c_int32, c_vp, c_vp, c_vp]
+        L.sa_amd_bwt.restype = ctypes.c_int32
+        L.sa_amd_index_bwt.argtypes = [c_vp, c_vp, c_vp]
+        L.sa_amd_index_bwt.restype = ctypes.c_int32
+        L.sa_amd_unbwt_work_bytes.argtypes = [ctypes.c_int32]
+        L.sa_amd_unbwt_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_unbwt_device.argtypes = [c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_unbwt_device.restype = ctypes.c_int32
+        L.sa_amd_unbwt.argtypes = [c_vp, ctypes.c_int32, ctypes.c_int32, c_vp]
+        L.sa_amd_unbwt.restype = ctypes.c_int32
+        L.sa_amd_last_unbwt_stats.argtypes = [c_vp]
+        L.sa_amd_last_unbwt_stats.restype = None
+        L.sa_amd_unbwt_set_walk_limits.argtypes = [ctypes.c_int32, ctypes.c_int32]
+        L.sa_amd_unbwt_set_walk_limits.restype = None
+        L.sa_amd_unbwt_set_splitter_spacing.argtypes = [ctypes.c_int32]
+        L.sa_amd_unbwt_set_splitter_spacing.restype = ctypes.c_int32
         _lib = L
     return _lib
 
@@ -407,6 +439,85 @@ def lcp_device_ptr(text_ptr: int, sa_ptr: int, n: int, lcp_ptr: int, work_ptr: i
     _lcp_rc(lib().sa_amd_lcp_device(text_ptr, sa_ptr, n, lcp_ptr, work_ptr, work_bytes, stream))
 
 
+def _bwt_rc(rc: int) -> None:
+    if rc == -6:
+        raise IndexError("suffix offset out of range")
+    if rc == -1:
+        raise ValueError("invalid argument: not a suffix array of this layout / not a Burrows-Wheeler transform")
+    _check(rc)
+
+
+def bwt(s, sa: Optional[np.ndarray] = None):
+    """-> (b, primary): the Burrows-Wheeler transform of ``s`` on the GPU (the layout of libdivsufsort's ``divbwt`` as
+    restated in include/suffix_array_amd.h).  With ``sa`` in the layout of ``saca`` (``sa[0] == len(s)``), ``primary`` is the
+    slot with ``sa[primary] == 0`` and ``b`` (uint8, ``len(s)`` bytes) is ``s[sa[k] - 1]`` for ``k < primary`` and
+    ``s[sa[k + 1] - 1]`` from there on.  ``sa=None``: the array is built on the device and never downloaded.
+    IndexError for an entry > len(s); ValueError when ``sa[0] != len(s)`` or not exactly one entry is 0."""
+    t = _as_u8(s)
+    assert t.size <= MAX_LENGTH
+    a = None
+    if sa is not None:
+        a = np.ascontiguousarray(sa, dtype=np.uint32)
+        assert a.size == t.size + 1
+    out = np.empty(t.size, dtype=np.uint8)
+    primary = ctypes.c_int32(0)
+    _bwt_rc(lib().sa_amd_bwt(t.ctypes.data, t.size, None if a is None else a.ctypes.data, out.ctypes.data, ctypes.byref(primary)))
+    return out, int(primary.value)
+
+
+def unbwt(b, primary: int) -> np.ndarray:
+    """the text whose transform is ``(b, primary)`` (see ``bwt``), on the GPU; ValueError when ``primary`` is outside
+    1 .. len(b) (0 for the empty string) or the pair is not the transform of any text"""
+    t = _as_u8(b)
+    assert t.size <= MAX_LENGTH
+    if not -2**31 <= int(primary) < 2**31:
+        raise ValueError("primary index out of range")
+    out = np.empty(t.size, dtype=np.uint8)
+    _bwt_rc(lib().sa_amd_unbwt(t.ctypes.data, t.size, int(primary), out.ctypes.data))
+    return out
+
+
+def last_unbwt_stats() -> dict:
+    """walkers / steps / longest_walk / splitter_spacing / walk_launches / restarts / readbacks of this thread's most recent
+    inverse transform"""
+    st = UnbwtStats()
+    lib().sa_amd_last_unbwt_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def unbwt_set_walk_limits(cap_steps: int = -1, max_launches: int = -1) -> None:
+    """route switch for this thread's later inverse transforms (never changes a result): steps one lane walks per launch, and
+    walk launches after which an attempt restarts with denser splitters; a negative value restores that default"""
+    lib().sa_amd_unbwt_set_walk_limits(int(cap_steps), int(max_launches))
+
+
+def unbwt_set_splitter_spacing(spacing: int = -1) -> int:
+    """route switch for this thread's later inverse transforms (never changes a result): the splitter spacing S of the first
+    attempt, rounded down to a power of two in 4 .. 65536; negative restores the default (256).  Returns the previous value."""
+    return int(lib().sa_amd_unbwt_set_splitter_spacing(int(spacing)))
+
+
+def bwt_work_bytes(n: int) -> int:
+    return int(lib().sa_amd_bwt_work_bytes(n))
+
+
+def unbwt_work_bytes(n: int) -> int:
+    return int(lib().sa_amd_unbwt_work_bytes(n))
+
+
+def bwt_device_ptr(text_ptr: int, sa_ptr: int, n: int, bwt_ptr: int, work_ptr: int, work_bytes: int, stream: int = 0) -> int:
+    """Device-resident forward transform (raw device pointers, e.g. torch ``tensor.data_ptr()``); blocks until done and
+    returns the primary index."""
+    primary = ctypes.c_int32(0)
+    _bwt_rc(lib().sa_amd_bwt_device(text_ptr, sa_ptr, n, bwt_ptr, ctypes.byref(primary), work_ptr, work_bytes, stream))
+    return int(primary.value)
+
+
+def unbwt_device_ptr(bwt_ptr: int, n: int, primary: int, text_ptr: int, work_ptr: int, work_bytes: int, stream: int = 0) -> None:
+    """Device-resident inverse transform (raw device pointers); blocks until done."""
+    _bwt_rc(lib().sa_amd_unbwt_device(bwt_ptr, n, int(primary), text_ptr, work_ptr, work_bytes, stream))
+
+
 class DeviceIndex:
     """Text + suffix array resident in HBM (sa_amd_index of include/suffix_array_amd.h): batched
     `contains` / `search_all` / `search_lcp` (reference src/sa.rs:164-253), bucket table, integrity check.
@@ -450,6 +561,13 @@ class DeviceIndex:
         out = np.empty(self._s.size + 1, dtype=np.uint32)
         _lcp_rc(lib().sa_amd_index_lcp(self._h, out.ctypes.data))
         return out
+
+    def bwt(self):
+        """-> (b, primary): the Burrows-Wheeler transform from the resident text and suffix array (see ``bwt``)"""
+        out = np.empty(self._s.size, dtype=np.uint8)
+        primary = ctypes.c_int32(0)
+        _bwt_rc(lib().sa_amd_index_bwt(self._h, out.ctypes.data, ctypes.byref(primary)))
+        return out, int(primary.value)
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): build and keep the LCP table of the
@@ -633,6 +751,11 @@ class SuffixArray:
         with the suffix array, ``lcp[0] == 0``, ``lcp[i]`` = longest common prefix of the suffixes at ``sa[i-1]`` and
         ``sa[i]``; computed on the GPU from the text and the array"""
         return lcp(self._s, self._sa)
+
+    def bwt(self):
+        """EXTENSION (the reference lacks it; ``divbwt`` of the C engine it binds): -> (b, primary), the Burrows-Wheeler
+        transform from the text and the array, computed on the GPU (see ``bwt``)"""
+        return bwt(self._s, self._sa)
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): contains / search_all / search_lcp

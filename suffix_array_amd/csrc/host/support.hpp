@@ -100,6 +100,7 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 enum KClass { KC_BYTE_HIST = 0, KC_BUILD_KEYS, KC_UPSWEEP, KC_SPINE, KC_DOWNSWEEP, KC_RR_COUNT, KC_RR_SCAN, KC_RR_APPLY,
               KC_GATHER, KC_SCATTER, KC_LOCAL, KC_MISC, KC_UPSWEEP32, KC_DOWNSWEEP32, KC_ONESWEEP, KC_ONESWEEP32, KC_FINISH, KC_BUCKET,
               KC_LCP_PHI, KC_LCP_IRRED, KC_LCP_LONG, KC_LCP_SCAN, KC_LCP_GATHER,
+              KC_BWT_GATHER, KC_UNBWT_WALK, KC_UNBWT_RANK, KC_UNBWT_WRITE,
 #ifdef SA_AMD_DIAG
               KC_SS_COUNT, KC_SS_SCATTER, KC_SS_BUCKET,
 #endif
@@ -114,7 +115,9 @@ static const char *const kclass_names[KC_COUNT] = { "k_byte_hist", "k_build_keys
                                                     "k_bucket_sort",                   // the low 16 bits of the 32-bit first stage, bucket by bucket in LDS (kernels/bucket_sort.hpp)
                                                     "k_lcp_phi", "k_lcp_irreducible",  // LCP array (kernels/lcp.hpp): range pass + plain Φ scatter, irreducible values up to the cap,
                                                     "k_lcp_long", "k_lcp_scan",        // long compares + settle, max-scan (spine + tiles),
-                                                    "k_lcp_gather"                     // LCP[i] = PLCP[SA[i]]
+                                                    "k_lcp_gather",                    // LCP[i] = PLCP[SA[i]]
+                                                    "k_bwt_gather", "k_unbwt_walk",    // Burrows-Wheeler transform (kernels/bwt.hpp): range pass + gather; inverse: splitters + walks,
+                                                    "k_unbwt_rank", "k_unbwt_write"    // pointer jumping over the sublists, second walk that writes the text
 #ifdef SA_AMD_DIAG
                                                     , "k_ss_count", "k_ss_scatter",    // diagnostic library: sample sort of the 64-bit stage (kernels/sample_sort.hpp), the two distribution
                                                     "k_ss_bucket_sort"                 // levels and every bucket ordered in LDS

@@ -15,6 +15,14 @@ namespace sa {
 constexpr int64_t SPARSE_DIV_DEFAULT = 64;  // sparse refinement when at most n / 64 suffixes are tied after the initial sort
 constexpr int GROUP_CAP_MAX = 1024;         // == GS_CAP (kernels/refine.hpp), checked there
 
+// inverse Burrows-Wheeler transform (host/bwt.hpp)
+constexpr int UNBWT_SPACING_DEFAULT = 256;  // S: one row in S is a splitter (a power of two; sa_amd_unbwt_set_splitter_spacing); DESIGN.md section 12 has the measured table
+constexpr int UNBWT_SPACING_MAX = 65536;
+constexpr int UNBWT_SPACING_MIN = 4;        // the densest set a restart goes to (the walker tables hold (n + 68) / 2.5 walkers); no launch limit there
+constexpr int UNBWT_CAP_DEFAULT = 4096;     // steps of one lane per walk launch (sa_amd_unbwt_set_walk_limits): a few ms of dependent misses at most
+constexpr int UNBWT_CAP_MAX = 1 << 24;
+constexpr int UNBWT_RESTART_WALKS = 64;     // lanes still walking after 64 S steps (twice the bound the tests hold the hash to): denser splitters, other seed
+
 inline bool env_flag(const char *name)
 {
     const char *e = getenv(name);

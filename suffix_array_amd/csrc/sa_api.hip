@@ -16,6 +16,7 @@
 #include "host/host_path.hpp"
 #include "host/lcp.hpp"
 #include "host/esa.hpp"
+#include "host/bwt.hpp"
 
 extern "C" {
 
@@ -600,6 +601,93 @@ SA_EXPORT int32_t sa_amd_lcp_set_compare_cap(int32_t bytes)
 SA_EXPORT void sa_amd_last_lcp_stats(sa_amd_lcp_stats *out)
 {
     if (out) *out = sa::g_last_lcp_stats;
+}
+
+// ---- Burrows-Wheeler transform and its inverse (host/bwt.hpp, kernels/bwt.hpp) ----
+
+SA_EXPORT int64_t sa_amd_bwt_work_bytes(int32_t n)
+{
+    if (n < 0) return -1;
+    return (int64_t)sa::BWT_WORK_BYTES;
+}
+
+SA_EXPORT int32_t sa_amd_bwt_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, uint8_t *dBWT, int32_t *primary_out,
+                                    void *dWork, int64_t work_bytes, void *stream)
+{
+    if (n < 0 || !dSA || !primary_out || !dWork || (n > 0 && (!dT || !dBWT))) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    return sa::bwt_device(dT, dSA, n, dBWT, primary_out, dWork, work_bytes, (hipStream_t)stream);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_bwt(const uint8_t *T, int32_t n, const uint32_t *SA, uint8_t *BWT, int32_t *primary_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::bwt_host(T, n, SA, BWT, primary_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_bwt(const sa_amd_index *ix, uint8_t *BWT, int32_t *primary_out)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !primary_out || (ix->n > 0 && !BWT)) return SA_AMD_EINVAL;
+    sa::DeviceGuard guard(ix->device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess) return SA_AMD_EHIP;
+    const size_t wb = sa::BWT_WORK_BYTES;
+    sa::DevBlock blk;
+    int32_t rc = sa::pool().acquire(cur, wb + (size_t)ix->n + 16, &blk);
+    if (rc) return rc;
+    uint8_t *dB = (uint8_t *)blk.p + wb;
+    rc = sa::bwt_device(ix->dT, ix->dSA, ix->n, dB, primary_out, blk.p, (int64_t)wb, nullptr);
+    if (rc == SA_AMD_OK && ix->n > 0) rc = sa::hip_status(hipMemcpy(BWT, dB, (size_t)ix->n, hipMemcpyDeviceToHost));
+    sa::pool().release(blk);
+    return rc;
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int64_t sa_amd_unbwt_work_bytes(int32_t n)
+{
+    if (n < 0) return -1;
+    return (int64_t)sa::unbwt_layout(n).bytes;
+}
+
+SA_EXPORT int32_t sa_amd_unbwt_device(const uint8_t *dBWT, int32_t n, int32_t primary, uint8_t *dT_out, void *dWork,
+                                      int64_t work_bytes, void *stream)
+{
+    if (n < 0 || (n > 0 && (!dBWT || !dT_out || !dWork))) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    return sa::unbwt_device(dBWT, n, primary, dT_out, dWork, work_bytes, (hipStream_t)stream);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_unbwt(const uint8_t *BWT, int32_t n, int32_t primary, uint8_t *T_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::unbwt_host(BWT, n, primary, T_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_unbwt_stats(sa_amd_unbwt_stats *out)
+{
+    if (out) *out = sa::g_last_unbwt_stats;
+}
+
+SA_EXPORT void sa_amd_unbwt_set_walk_limits(int32_t cap_steps, int32_t max_launches)
+{
+    sa::g_unbwt_cap = cap_steps < 0 ? -1 : (cap_steps < 1 ? 1 : (cap_steps > sa::UNBWT_CAP_MAX ? sa::UNBWT_CAP_MAX : cap_steps));
+    sa::g_unbwt_launches = max_launches < 0 ? -1 : (max_launches < 1 ? 1 : max_launches);
+}
+
+SA_EXPORT int32_t sa_amd_unbwt_set_splitter_spacing(int32_t spacing)
+{
+    const int32_t prev = sa::g_unbwt_spacing < 0 ? sa::UNBWT_SPACING_DEFAULT : sa::g_unbwt_spacing;
+    if (spacing < 0) { sa::g_unbwt_spacing = -1; return prev; }
+    int32_t s = sa::UNBWT_SPACING_MIN;                       // rounded down to a power of two inside the range
+    while (s * 2 <= spacing && s < sa::UNBWT_SPACING_MAX) s *= 2;
+    sa::g_unbwt_spacing = s;
+    return prev;
 }
 
 // ---- packed format (reference src/packed_sa.rs); byte layout: u32 magic "SA4x" LE, u32 length, u64 data length
