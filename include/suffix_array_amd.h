@@ -316,6 +316,66 @@ void sa_amd_unbwt_set_walk_limits(int32_t cap_steps, int32_t max_launches);
  * 256, measured in DESIGN.md section 12); a negative value restores the default.  Returns the previous value. */
 int32_t sa_amd_unbwt_set_splitter_spacing(int32_t spacing);
 
+/*
+ * Repeat finding (an extension): the longest-repeat array and the byte ranges that are copies, from the text and its suffix
+ * array, on the device.  T has n bytes; SA and LCP are in the layout of sa_amd_saca_u8 / sa_amd_lcp
+ * (n + 1 entries each); read LCP[n + 1] as 0.
+ *   LR (n entries, text order): LR[p] = length of the longest substring starting at p that also starts at some other position
+ *     q != p.  Equivalently LR[SA[i]] = max(LCP[i], LCP[i + 1]) for 1 <= i <= n.  p + LR[p] <= n, and LR[p] >= LR[p - 1] - 1:
+ *     p + LR[p] never decreases.  "banana": LR = {0, 3, 2, 3, 2, 1}.
+ *   Spans, mode SA_AMD_REPEATS_ALL, min_len = k >= 1: the union of [p, p + LR[p]) over all p with LR[p] >= k, as maximal
+ *     intervals [start, end), ascending, disjoint and not adjacent: every byte inside some occurrence of a substring of length
+ *     >= k that occurs at least twice, first occurrences included.  "banana", k = 2: {[1, 6)}.
+ *   Spans, mode SA_AMD_REPEATS_KEEP_FIRST: p is flagged iff the window T[p .. p + k) equals an earlier window T[q .. q + k),
+ *     q < p; the spans are the union of [p, p + k) over the flagged p, in the same form.  Equivalently: of every maximal slot
+ *     run [a, b] with LCP[a + 1 .. b] >= k all members but the one with the smallest SA value are flagged.  The first copy of
+ *     every repeated window survives: what a deduplicator removes.  "banana", k = 2: {[3, 6)}.
+ *   A span has at least k bytes and spans are not adjacent: there are at most (n + 1) / (k + 1) of them
+ *     (sa_amd_repeat_spans_bound).
+ * Spans come as pairs of uint32 (start, end).  `capacity` pairs fit the output: more spans than that is no error -- the first
+ * `capacity` are written, *count_out is the number of all of them and the statistics cover all of them.
+ * Errors, as for the LCP array: an entry > n is SA_AMD_ERANGE, SA[0] != n is SA_AMD_EINVAL (range pass before anything is read
+ * through the entries); min_len < 1, an unknown mode, a negative capacity or a misaligned or short work block is
+ * SA_AMD_EINVAL with nothing written.  n = 0: no spans, an empty LR, all-zero statistics (longest_pos -1); n = 1: LR = {0}.
+ * The array is not otherwise proved to be the suffix array: with a wrong permutation the answers are unspecified, but nothing
+ * is read outside T or the tables and nothing is written outside the outputs.
+ */
+#define SA_AMD_REPEATS_ALL        0
+#define SA_AMD_REPEATS_KEEP_FIRST 1
+/* bytes of device scratch the two device calls need: sa_amd_lcp_work_bytes(n) plus one n-entry buffer, about 24.5 (n + 1) */
+int64_t sa_amd_repeats_work_bytes(int32_t n);
+/* (n + 1) / (min_len + 1); -1 when n < 0 or min_len < 1 */
+int64_t sa_amd_repeat_spans_bound(int32_t n, int32_t min_len);
+/* device pointers: dT n bytes (any byte address), dSA n + 1 entries, dLR n entries, dWork sa_amd_repeats_work_bytes(n) bytes
+ * 256-byte aligned; stream a hipStream_t (NULL = default stream).  Blocks until done. */
+int32_t sa_amd_repeat_lengths_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, uint32_t *dLR, void *dWork,
+                                     int64_t work_bytes, void *stream);
+/* dSpans: 2 * capacity entries of device memory (may be NULL when capacity is 0); count_out a HOST pointer */
+int32_t sa_amd_repeat_spans_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, int32_t min_len, int32_t mode,
+                                   uint32_t *dSpans, int64_t capacity, int64_t *count_out, void *dWork, int64_t work_bytes,
+                                   void *stream);
+/* host pointers.  SA == NULL: the array is built on the device, used there and never downloaded: n bytes go up, 4 n bytes (LR)
+ * or 8 bytes per span come back.  SA != NULL (n + 1 entries): the caller's array goes up instead of being rebuilt. */
+int32_t sa_amd_repeat_lengths(const uint8_t *T, int32_t n, const uint32_t *SA, uint32_t *LR);
+int32_t sa_amd_repeat_spans(const uint8_t *T, int32_t n, const uint32_t *SA, int32_t min_len, int32_t mode, uint32_t *spans,
+                            int64_t capacity, int64_t *count_out);
+/* from the index's resident text and suffix array */
+int32_t sa_amd_index_repeat_lengths(const sa_amd_index *ix, uint32_t *LR);
+int32_t sa_amd_index_repeat_spans(const sa_amd_index *ix, int32_t min_len, int32_t mode, uint32_t *spans, int64_t capacity,
+                                  int64_t *count_out);
+
+typedef struct sa_amd_repeat_stats { /* of the calling thread's most recent repeat call (sa_amd_last_lcp_stats is filled too) */
+    int64_t longest;                 /* max LCP = max LR */
+    int64_t longest_pos;             /* the smallest p with LR[p] == longest; -1 when longest is 0 */
+    int64_t lcp_sum;                 /* sum of the LCP array */
+    int64_t distinct_substrings;     /* n (n + 1) / 2 - lcp_sum: the number of distinct non-empty substrings of T */
+    int64_t spans;                   /* all spans, written or not (0 after a call that only made LR, as the next two) */
+    int64_t covered_bytes;           /* bytes inside the spans */
+    int64_t flagged;                 /* positions with LR >= min_len (ALL) or flagged as later copies (KEEP_FIRST) */
+    int32_t readbacks, reserved;     /* blocking device -> host read-backs of counters */
+} sa_amd_repeat_stats;
+void sa_amd_last_repeat_stats(sa_amd_repeat_stats *out);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

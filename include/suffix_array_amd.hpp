@@ -8,6 +8,8 @@
 //   SuffixArray::lcp_array                  EXTENSION: the LCP array (the reference's README TODO "enhanced suffix array")
 //   SuffixArray::bwt, bwt(), unbwt()        EXTENSION: the Burrows-Wheeler transform and its inverse (divbwt /
 //                                           inverse_bw_transform of the C engine the reference binds)
+//   SuffixArray::repeat_lengths / repeat_spans, repeat_lengths(), repeat_spans()
+//                                           EXTENSION: the longest-repeat array and the byte ranges that are copies
 // Rust panics (assert!, engine failure) are std::logic_error / std::runtime_error here.
 #pragma once
 #include "suffix_array_amd.h"
@@ -45,6 +47,40 @@ inline std::pair<std::vector<std::uint8_t>, std::int32_t> bwt(const std::uint8_t
     if (rc == SA_AMD_EINVAL) throw std::invalid_argument("not a suffix array of this layout");
     if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
     return { std::move(b), primary };
+}
+
+// EXTENSION: the longest-repeat array of s (suffix_array_amd.h): n entries in text order.  sa == nullptr: the suffix array is
+// built on the device and never downloaded (sa_amd_repeat_lengths)
+inline std::vector<std::uint32_t> repeat_lengths(const std::uint8_t *s, std::size_t n, const std::uint32_t *sa = nullptr)
+{
+    if (n > MAX_LENGTH) throw std::logic_error("assertion failed: s.len() <= MAX_LENGTH");
+    std::vector<std::uint32_t> lr(n);
+    const std::int32_t rc = sa_amd_repeat_lengths(s, static_cast<std::int32_t>(n), sa, lr.data());
+    if (rc == SA_AMD_ERANGE) throw std::out_of_range("suffix offset out of range");
+    if (rc == SA_AMD_EINVAL) throw std::invalid_argument("not a suffix array of this layout");
+    if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
+    return lr;
+}
+
+// EXTENSION: the byte ranges of s that are copies, as [start, end) pairs, ascending, disjoint and not adjacent: every occurrence of
+// a substring of at least min_len bytes that occurs twice, or (keep_first) every window of min_len bytes that equals an earlier
+// one (sa_amd_repeat_spans).  Only the spans come back from the device.
+inline std::vector<std::pair<std::uint32_t, std::uint32_t>> repeat_spans(const std::uint8_t *s, std::size_t n, std::int32_t min_len,
+                                                                         bool keep_first = false, const std::uint32_t *sa = nullptr)
+{
+    if (n > MAX_LENGTH) throw std::logic_error("assertion failed: s.len() <= MAX_LENGTH");
+    if (min_len < 1) throw std::invalid_argument("min_len must be at least 1");
+    const std::int64_t cap = sa_amd_repeat_spans_bound(static_cast<std::int32_t>(n), min_len);
+    std::vector<std::uint32_t> flat(static_cast<std::size_t>(cap) * 2);
+    std::int64_t count = 0;
+    const std::int32_t rc = sa_amd_repeat_spans(s, static_cast<std::int32_t>(n), sa, min_len,
+                                                keep_first ? SA_AMD_REPEATS_KEEP_FIRST : SA_AMD_REPEATS_ALL, flat.data(), cap, &count);
+    if (rc == SA_AMD_ERANGE) throw std::out_of_range("suffix offset out of range");
+    if (rc == SA_AMD_EINVAL) throw std::invalid_argument("not a suffix array of this layout");
+    if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
+    std::vector<std::pair<std::uint32_t, std::uint32_t>> out(static_cast<std::size_t>(count < cap ? count : cap));
+    for (std::size_t i = 0; i < out.size(); ++i) out[i] = { flat[2 * i], flat[2 * i + 1] };
+    return out;
 }
 
 // EXTENSION: the text whose transform is (b, primary); std::invalid_argument when the pair is not a transform (sa_amd_unbwt)
@@ -120,6 +156,17 @@ public:
     {
         if (n_ + 1 != sa_.size()) throw std::logic_error("assertion failed: s.len() + 1 == sa.len()");
         return suffix_array::bwt(s_, n_, sa_.data());
+    }
+    // EXTENSION (not in the reference): the longest-repeat array and the duplicate spans from the text and this array
+    std::vector<std::uint32_t> repeat_lengths() const
+    {
+        if (n_ + 1 != sa_.size()) throw std::logic_error("assertion failed: s.len() + 1 == sa.len()");
+        return suffix_array::repeat_lengths(s_, n_, sa_.data());
+    }
+    std::vector<std::pair<std::uint32_t, std::uint32_t>> repeat_spans(std::int32_t min_len, bool keep_first = false) const
+    {
+        if (n_ + 1 != sa_.size()) throw std::logic_error("assertion failed: s.len() + 1 == sa.len()");
+        return suffix_array::repeat_spans(s_, n_, min_len, keep_first, sa_.data());
     }
 
 private:

@@ -24,7 +24,9 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "lcp", "saca_lcp", "last_lcp_stats", "lcp_work_bytes", "lcp_device_ptr", "LcpStats",
            "lcp_set_compare_cap", "last_search_stats", "SearchStats",
            "bwt", "unbwt", "bwt_device_ptr", "unbwt_device_ptr", "bwt_work_bytes", "unbwt_work_bytes", "last_unbwt_stats",
-           "unbwt_set_walk_limits", "unbwt_set_splitter_spacing", "UnbwtStats"]
+           "unbwt_set_walk_limits", "unbwt_set_splitter_spacing", "UnbwtStats",
+           "repeat_lengths", "repeat_spans", "last_repeat_stats", "repeats_work_bytes", "repeat_spans_bound",
+           "repeat_lengths_device_ptr", "repeat_spans_device_ptr", "RepeatStats", "REPEATS_ALL", "REPEATS_KEEP_FIRST"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
@@ -81,6 +83,21 @@ class UnbwtStats(ctypes.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RepeatStats(ctypes.Structure):
+    """sa_amd_repeat_stats of include/suffix_array_amd.h"""
+    _fields_ = [("longest", ctypes.c_int64), ("longest_pos", ctypes.c_int64), ("lcp_sum", ctypes.c_int64),
+                ("distinct_substrings", ctypes.c_int64), ("spans", ctypes.c_int64), ("covered_bytes", ctypes.c_int64),
+                ("flagged", ctypes.c_int64), ("readbacks", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+#: span modes of ``repeat_spans_device_ptr`` (SA_AMD_REPEATS_* of include/suffix_array_amd.h)
+REPEATS_ALL = 0
+REPEATS_KEEP_FIRST = 1
 
 
 def library_path() -> str:
@@ -192,6 +209,25 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_unbwt_set_walk_limits.restype = None
         L.sa_amd_unbwt_set_splitter_spacing.argtypes = [ctypes.c_int32]
         L.sa_amd_unbwt_set_splitter_spacing.restype = ctypes.c_int32
+        L.sa_amd_repeats_work_bytes.argtypes = [ctypes.c_int32]
+        L.sa_amd_repeats_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_repeat_spans_bound.argtypes = [ctypes.c_int32, ctypes.c_int32]
+        L.sa_amd_repeat_spans_bound.restype = ctypes.c_int64
+        L.sa_amd_repeat_lengths_device.argtypes = [c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_repeat_lengths_device.restype = ctypes.c_int32
+        L.sa_amd_repeat_spans_device.argtypes = [c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int64,
+                                                 c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_repeat_spans_device.restype = ctypes.c_int32
+        L.sa_amd_repeat_lengths.argtypes = [c_vp, ctypes.c_int32, c_vp, c_vp]
+        L.sa_amd_repeat_lengths.restype = ctypes.c_int32
+        L.sa_amd_repeat_spans.argtypes = [c_vp, ctypes.c_int32, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_repeat_spans.restype = ctypes.c_int32
+        L.sa_amd_index_repeat_lengths.argtypes = [c_vp, c_vp]
+        L.sa_amd_index_repeat_lengths.restype = ctypes.c_int32
+        L.sa_amd_index_repeat_spans.argtypes = [c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_repeat_spans.restype = ctypes.c_int32
+        L.sa_amd_last_repeat_stats.argtypes = [c_vp]
+        L.sa_amd_last_repeat_stats.restype = None
         _lib = L
     return _lib
 
@@ -518,6 +554,83 @@ def unbwt_device_ptr(bwt_ptr: int, n: int, primary: int, text_ptr: int, work_ptr
     _bwt_rc(lib().sa_amd_unbwt_device(bwt_ptr, n, int(primary), text_ptr, work_ptr, work_bytes, stream))
 
 
+def _repeat_min_len(min_len) -> int:
+    k = int(min_len)
+    if k < 1:
+        raise ValueError("min_len must be at least 1")
+    return min(k, 2**31 - 1)            # (no repeat is longer than MAX_LENGTH - 1: a larger threshold gives the same, empty, answer)
+
+
+def repeat_spans_bound(n: int, min_len: int) -> int:
+    """no text of ``n`` bytes has more spans of threshold ``min_len`` than this: ``(n + 1) // (min_len + 1)``"""
+    return int(lib().sa_amd_repeat_spans_bound(int(n), _repeat_min_len(min_len)))
+
+
+def repeat_lengths(s, sa: Optional[np.ndarray] = None) -> np.ndarray:
+    """Longest-repeat array of ``s`` on the GPU: uint32, ``len(s)`` entries in text order; ``lr[p]`` is the length of the
+    longest substring starting at ``p`` that also starts at some other position.  With the LCP array of ``lcp``,
+    ``lr[sa[i]] == max(lcp[i], lcp[i + 1])``.  ``sa=None``: the array is built on the device and never downloaded; else it
+    must be the suffix array of ``s`` in the layout of ``saca`` (IndexError for an entry > len(s), ValueError when
+    ``sa[0] != len(s)``)."""
+    t = _as_u8(s)
+    assert t.size <= MAX_LENGTH
+    a = None
+    if sa is not None:
+        a = np.ascontiguousarray(sa, dtype=np.uint32)
+        assert a.size == t.size + 1
+    out = np.empty(t.size, dtype=np.uint32)
+    _bwt_rc(lib().sa_amd_repeat_lengths(t.ctypes.data, t.size, None if a is None else a.ctypes.data, out.ctypes.data))
+    return out
+
+
+def repeat_spans(s, min_len: int, keep_first: bool = False, sa: Optional[np.ndarray] = None) -> np.ndarray:
+    """Byte ranges of ``s`` that are copies, on the GPU: a ``(count, 2)`` uint32 array of ``[start, end)`` rows, ascending,
+    disjoint and not adjacent.  ``keep_first=False``: every byte inside some occurrence of a substring of at least
+    ``min_len`` bytes that occurs at least twice (first occurrences included).  ``keep_first=True``: the union of the windows
+    ``s[p : p + min_len]`` that equal a window starting earlier -- the first copy of everything survives, which is what a
+    deduplicator removes.  ``sa`` as for ``repeat_lengths``; only the spans come back from the device."""
+    t = _as_u8(s)
+    assert t.size <= MAX_LENGTH
+    k = _repeat_min_len(min_len)
+    a = None
+    if sa is not None:
+        a = np.ascontiguousarray(sa, dtype=np.uint32)
+        assert a.size == t.size + 1
+    cap = (t.size + 1) // (k + 1)
+    out = np.empty((cap, 2), dtype=np.uint32)
+    count = ctypes.c_int64(0)
+    _bwt_rc(lib().sa_amd_repeat_spans(t.ctypes.data, t.size, None if a is None else a.ctypes.data, k,
+                                      REPEATS_KEEP_FIRST if keep_first else REPEATS_ALL, out.ctypes.data, cap, ctypes.byref(count)))
+    return out[:min(int(count.value), cap)].copy()
+
+
+def last_repeat_stats() -> dict:
+    """longest / longest_pos / lcp_sum / distinct_substrings / spans / covered_bytes / flagged / readbacks of this thread's
+    most recent repeat call (the span fields read 0 after ``repeat_lengths``)"""
+    st = RepeatStats()
+    lib().sa_amd_last_repeat_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def repeats_work_bytes(n: int) -> int:
+    return int(lib().sa_amd_repeats_work_bytes(n))
+
+
+def repeat_lengths_device_ptr(text_ptr: int, sa_ptr: int, n: int, lr_ptr: int, work_ptr: int, work_bytes: int, stream: int = 0) -> None:
+    """Device-resident longest-repeat array (raw device pointers, e.g. torch ``tensor.data_ptr()``); blocks until done."""
+    _bwt_rc(lib().sa_amd_repeat_lengths_device(text_ptr, sa_ptr, n, lr_ptr, work_ptr, work_bytes, stream))
+
+
+def repeat_spans_device_ptr(text_ptr: int, sa_ptr: int, n: int, min_len: int, mode: int, spans_ptr: int, capacity: int,
+                            work_ptr: int, work_bytes: int, stream: int = 0) -> int:
+    """Device-resident spans (raw device pointers; ``spans_ptr``: ``2 * capacity`` uint32); blocks until done and returns the
+    number of all spans, of which the first ``capacity`` have been written."""
+    count = ctypes.c_int64(0)
+    _bwt_rc(lib().sa_amd_repeat_spans_device(text_ptr, sa_ptr, n, int(min_len), int(mode), spans_ptr, int(capacity),
+                                             ctypes.byref(count), work_ptr, work_bytes, stream))
+    return int(count.value)
+
+
 class DeviceIndex:
     """Text + suffix array resident in HBM (sa_amd_index of include/suffix_array_amd.h): batched
     `contains` / `search_all` / `search_lcp` (reference src/sa.rs:164-253), bucket table, integrity check.
@@ -568,6 +681,22 @@ class DeviceIndex:
         primary = ctypes.c_int32(0)
         _bwt_rc(lib().sa_amd_index_bwt(self._h, out.ctypes.data, ctypes.byref(primary)))
         return out, int(primary.value)
+
+    def repeat_lengths(self) -> np.ndarray:
+        """longest-repeat array from the resident text and suffix array (see ``repeat_lengths``)"""
+        out = np.empty(self._s.size, dtype=np.uint32)
+        _bwt_rc(lib().sa_amd_index_repeat_lengths(self._h, out.ctypes.data))
+        return out
+
+    def repeat_spans(self, min_len: int, keep_first: bool = False) -> np.ndarray:
+        """duplicate spans from the resident text and suffix array (see ``repeat_spans``)"""
+        k = _repeat_min_len(min_len)
+        cap = (self._s.size + 1) // (k + 1)
+        out = np.empty((cap, 2), dtype=np.uint32)
+        count = ctypes.c_int64(0)
+        _bwt_rc(lib().sa_amd_index_repeat_spans(self._h, k, REPEATS_KEEP_FIRST if keep_first else REPEATS_ALL, out.ctypes.data, cap,
+                                                ctypes.byref(count)))
+        return out[:min(int(count.value), cap)].copy()
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): build and keep the LCP table of the
@@ -756,6 +885,14 @@ class SuffixArray:
         """EXTENSION (the reference lacks it; ``divbwt`` of the C engine it binds): -> (b, primary), the Burrows-Wheeler
         transform from the text and the array, computed on the GPU (see ``bwt``)"""
         return bwt(self._s, self._sa)
+
+    def repeat_lengths(self) -> np.ndarray:
+        """EXTENSION (the reference lacks it): the longest-repeat array of the text, on the GPU (see ``repeat_lengths``)"""
+        return repeat_lengths(self._s, self._sa)
+
+    def repeat_spans(self, min_len: int, keep_first: bool = False) -> np.ndarray:
+        """EXTENSION (the reference lacks it): the byte ranges that are copies, on the GPU (see ``repeat_spans``)"""
+        return repeat_spans(self._s, min_len, keep_first, self._sa)
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): contains / search_all / search_lcp

@@ -35,19 +35,14 @@ constexpr int LCP_CTL_OFF = 64;            // byte offset of the control words i
 constexpr int LCP_FLAGS_WORD = 8;          // uint32 index of the range pass's flags in the ctl slab
 constexpr int LCP_MAX_ROUNDS = 64;         // doubling windows from 16 bytes cover 2^31 in fewer than 32
 
-// dT, dSA (n + 1 entries, SA[0] = n), dLCP (n + 1 entries): device memory on the current device; dWork: lcp_layout(n).bytes,
-// 256-byte aligned.  Blocks until the array is complete.
-static int lcp_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, uint32_t *dLCP, void *dWork, int64_t work_bytes, hipStream_t st)
+// The stages both the LCP array and the repeat finder (host/repeats.hpp) start with: the range pass, Φ, the irreducible values,
+// the long compares and the max-scan.  Afterwards PLCP stands in text order in the Φ buffer (n entries), the four n-entry
+// buffers are free and the control slab holds the LCP_C_* words; nothing has been synchronised since the last read-back.
+// n == 0: returns behind the range pass.  dWork: lcp_layout(n).bytes (L), 256-byte aligned; stats: irreducible, compared_bytes
+// and long_pairs are filled in.
+static int lcp_front(const uint8_t *dT, const uint32_t *dSA, int64_t n, void *dWork, const LcpLayout &L, hipStream_t st, const Tuning &tn,
+                     sa_amd_lcp_stats &stats)
 {
-    const int64_t n = n32;
-    sa_amd_lcp_stats stats;
-    memset(&stats, 0, sizeof(stats));
-    g_last_lcp_stats = stats;
-    const LcpLayout L = lcp_layout(n32);
-    if (work_bytes < (int64_t)L.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
-    g_posted_off = tn.no_posted_readback;
-    const int rb0 = g_readbacks;
     char *base = (char *)dWork;
     uint32_t *err = (uint32_t *)(base + L.ctl);
     unsigned long long *ctl = (unsigned long long *)(base + L.ctl + LCP_CTL_OFF);
@@ -63,13 +58,7 @@ static int lcp_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, uint3
         if (f & 1u) return SA_AMD_ERANGE;
         if (f & 2u) return SA_AMD_EINVAL;             // SA[0] != n (or n in another slot)
     }
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(dLCP, 0, 4, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        stats.readbacks = g_readbacks - rb0;
-        g_last_lcp_stats = stats;
-        return SA_AMD_OK;
-    }
+    if (n == 0) return SA_AMD_OK;
 
     // ---- Φ[SA[i]] = SA[i-1] ----
     uint32_t *phi = (uint32_t *)(base + L.phi);
@@ -138,12 +127,39 @@ static int lcp_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, uint3
         win *= 2;
     }
 
-    // ---- PLCP[j] = max(v[0..j]) - j, then LCP[i] = PLCP[SA[i]] ----
+    // ---- PLCP[j] = max(v[0..j]) - j ----
     PROF(KC_LCP_SCAN, tiles, st, hipLaunchKernelGGL(k_lcp_scan_spine, dim3(1), dim3(LCP_SPINE_THREADS), 0, st, tile_max, tiles));
     PROF(KC_LCP_SCAN, n, st, hipLaunchKernelGGL(k_lcp_scan, dim3((unsigned)tiles), dim3(LCP_THREADS), 0, st, phi, n, (const uint32_t *)tile_max));
+    return SA_AMD_OK;
+}
+
+// dT, dSA (n + 1 entries, SA[0] = n), dLCP (n + 1 entries): device memory on the current device; dWork: lcp_layout(n).bytes,
+// 256-byte aligned.  Blocks until the array is complete.
+static int lcp_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, uint32_t *dLCP, void *dWork, int64_t work_bytes, hipStream_t st)
+{
+    const int64_t n = n32;
+    sa_amd_lcp_stats stats;
+    memset(&stats, 0, sizeof(stats));
+    g_last_lcp_stats = stats;
+    const LcpLayout L = lcp_layout(n32);
+    if (work_bytes < (int64_t)L.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
+    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
+    g_posted_off = tn.no_posted_readback;
+    const int rb0 = g_readbacks;
+    { const int rcf = lcp_front(dT, dSA, n, dWork, L, st, tn, stats); if (rcf) return rcf; }
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(dLCP, 0, 4, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        stats.readbacks = g_readbacks - rb0;
+        g_last_lcp_stats = stats;
+        return SA_AMD_OK;
+    }
+
+    // ---- LCP[i] = PLCP[SA[i]] ----
+    const uint32_t *plcp = (const uint32_t *)((char *)dWork + L.phi);
     int64_t gb = ceil_div(n + 1, 256 * 4);
     if (gb > 65536) gb = 65536;
-    PROF(KC_LCP_GATHER, n + 1, st, hipLaunchKernelGGL(k_lcp_gather, dim3((unsigned)gb), dim3(256), 0, st, dSA, n, (const uint32_t *)phi, dLCP));
+    PROF(KC_LCP_GATHER, n + 1, st, hipLaunchKernelGGL(k_lcp_gather, dim3((unsigned)gb), dim3(256), 0, st, dSA, n, plcp, dLCP));
     HIP_TRY(hipStreamSynchronize(st));
     g_prof.resolve();
     stats.readbacks = g_readbacks - rb0;

@@ -104,6 +104,7 @@ enum KClass { KC_BYTE_HIST = 0, KC_BUILD_KEYS, KC_UPSWEEP, KC_SPINE, KC_DOWNSWEE
 #ifdef SA_AMD_DIAG
               KC_SS_COUNT, KC_SS_SCATTER, KC_SS_BUCKET,
 #endif
+              KC_REP_LR, KC_REP_SPANS,         // (behind every earlier class of either library: no index moves)
               KC_COUNT };
 static_assert(KC_COUNT <= 32, "bench.py reads 32 kernel classes");
 static const char *const kclass_names[KC_COUNT] = { "k_byte_hist", "k_build_keys", "k_radix_upsweep", "k_spine_rows",
@@ -122,6 +123,7 @@ static const char *const kclass_names[KC_COUNT] = { "k_byte_hist", "k_build_keys
                                                     , "k_ss_count", "k_ss_scatter",    // diagnostic library: sample sort of the 64-bit stage (kernels/sample_sort.hpp), the two distribution
                                                     "k_ss_bucket_sort"                 // levels and every bucket ordered in LDS
 #endif
+                                                    , "k_rep_lr", "k_rep_spans"        // repeat finder (kernels/repeats.hpp): slot pass + KEEP_FIRST flags, the span passes
                                                     };
 struct Profiler {
     bool on = false;

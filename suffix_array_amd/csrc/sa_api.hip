@@ -17,6 +17,7 @@
 #include "host/lcp.hpp"
 #include "host/esa.hpp"
 #include "host/bwt.hpp"
+#include "host/repeats.hpp"
 
 extern "C" {
 
@@ -667,6 +668,106 @@ SA_EXPORT int32_t sa_amd_unbwt(const uint8_t *BWT, int32_t n, int32_t primary, u
     SA_ABI_GUARD_BEGIN
     return sa::unbwt_host(BWT, n, primary, T_out);
     SA_ABI_GUARD_END(0)
+}
+
+// ---- repeat finding (host/repeats.hpp, kernels/repeats.hpp) ----
+
+SA_EXPORT int64_t sa_amd_repeats_work_bytes(int32_t n)
+{
+    if (n < 0) return -1;
+    return (int64_t)sa::rep_layout(n).bytes;
+}
+
+SA_EXPORT int64_t sa_amd_repeat_spans_bound(int32_t n, int32_t min_len)
+{
+    if (n < 0 || min_len < 1) return -1;
+    return sa::repeat_spans_bound(n, min_len);
+}
+
+SA_EXPORT int32_t sa_amd_repeat_lengths_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, uint32_t *dLR, void *dWork,
+                                               int64_t work_bytes, void *stream)
+{
+    if (n < 0 || !dSA || !dWork || (n > 0 && (!dT || !dLR))) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    return sa::repeats_device(dT, dSA, n, false, dLR, 1, 0, nullptr, 0, nullptr, dWork, work_bytes, (hipStream_t)stream);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_repeat_spans_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, int32_t min_len, int32_t mode,
+                                             uint32_t *dSpans, int64_t capacity, int64_t *count_out, void *dWork,
+                                             int64_t work_bytes, void *stream)
+{
+    if (n < 0 || !dSA || !dWork || !count_out || (n > 0 && !dT) || (capacity > 0 && !dSpans)) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    return sa::repeats_device(dT, dSA, n, true, nullptr, min_len, mode, dSpans, capacity, count_out, dWork, work_bytes, (hipStream_t)stream);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_repeat_lengths(const uint8_t *T, int32_t n, const uint32_t *SA, uint32_t *LR)
+{
+    if (n > 0 && !LR) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    return sa::repeats_host(T, n, SA, false, LR, 1, 0, nullptr, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_repeat_spans(const uint8_t *T, int32_t n, const uint32_t *SA, int32_t min_len, int32_t mode, uint32_t *spans,
+                                      int64_t capacity, int64_t *count_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::repeats_host(T, n, SA, true, nullptr, min_len, mode, spans, capacity, count_out);
+    SA_ABI_GUARD_END(0)
+}
+
+// the index's resident text and array: the work block, and the output behind it, from the pool
+static int32_t index_repeats(const sa_amd_index *ix, bool spans, uint32_t *LR, int32_t min_len, int32_t mode, uint32_t *out_spans,
+                             int64_t capacity, int64_t *count_out)
+{
+    if (!ix) return SA_AMD_EINVAL;
+    if (spans ? (min_len < 1 || (mode != SA_AMD_REPEATS_ALL && mode != SA_AMD_REPEATS_KEEP_FIRST) || capacity < 0 || !count_out ||
+                 (capacity > 0 && !out_spans))
+              : (ix->n > 0 && !LR)) return SA_AMD_EINVAL;
+    sa::DeviceGuard guard(ix->device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess) return SA_AMD_EHIP;
+    int64_t cap = 0;
+    if (spans) { cap = sa::repeat_spans_bound(ix->n, min_len); cap = capacity < cap ? capacity : cap; }
+    const size_t wb = sa::rep_layout(ix->n).bytes, ob = spans ? (size_t)cap * 8 + 8 : ((size_t)ix->n + 1) * 4;
+    sa::DevBlock blk;
+    int32_t rc = sa::pool().acquire(cur, wb + ob, &blk);
+    if (rc) return rc;
+    uint32_t *dOut = (uint32_t *)((char *)blk.p + wb);
+    int64_t count = 0;
+    rc = sa::repeats_device(ix->dT, ix->dSA, ix->n, spans, dOut, min_len, mode, dOut, cap, &count, blk.p, (int64_t)wb, nullptr);
+    if (rc == SA_AMD_OK && !spans && ix->n > 0) rc = sa::hip_status(hipMemcpy(LR, dOut, (size_t)ix->n * 4, hipMemcpyDeviceToHost));
+    if (rc == SA_AMD_OK && spans) {
+        const int64_t wr = count < cap ? count : cap;
+        if (wr > 0) rc = sa::hip_status(hipMemcpy(out_spans, dOut, (size_t)wr * 8, hipMemcpyDeviceToHost));
+        if (rc == SA_AMD_OK) *count_out = count;
+    }
+    sa::pool().release(blk);
+    return rc;
+}
+
+SA_EXPORT int32_t sa_amd_index_repeat_lengths(const sa_amd_index *ix, uint32_t *LR)
+{
+    SA_ABI_GUARD_BEGIN
+    return index_repeats(ix, false, LR, 1, 0, nullptr, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_repeat_spans(const sa_amd_index *ix, int32_t min_len, int32_t mode, uint32_t *spans, int64_t capacity,
+                                            int64_t *count_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return index_repeats(ix, true, nullptr, min_len, mode, spans, capacity, count_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_repeat_stats(sa_amd_repeat_stats *out)
+{
+    if (out) *out = sa::g_last_repeat_stats;
 }
 
 SA_EXPORT void sa_amd_last_unbwt_stats(sa_amd_unbwt_stats *out)
