@@ -14,6 +14,11 @@ extern "C" {
     // include/suffix_array_amd.h: the LCP array (an extension; uncompiled like the rest of this file)
     fn sa_amd_lcp(t: *const u8, n: i32, sa: *const u32, lcp: *mut u32) -> i32;
     fn sa_amd_saca_u8_lcp(t: *const u8, sa: *mut u32, n: i32, lcp: *mut u32) -> i32;
+    // include/suffix_array_amd.h: Lempel-Ziv factorisation (an extension; `sa` may be null: the array is then built on the device)
+    #[allow(dead_code)]
+    fn sa_amd_lpf(t: *const u8, n: i32, sa: *const u32, lpf: *mut u32, src: *mut u32) -> i32;
+    #[allow(dead_code)]
+    fn sa_amd_lz77(t: *const u8, n: i32, sa: *const u32, phrases: *mut u32, capacity: i64, count_out: *mut i64) -> i32;
     // include/suffix_array_amd.h: repeat finding (an extension; `sa` may be null: the array is then built on the device)
     fn sa_amd_repeat_spans_bound(n: i32, min_len: i32) -> i64;
     fn sa_amd_repeat_lengths(t: *const u8, n: i32, sa: *const u32, lr: *mut u32) -> i32;

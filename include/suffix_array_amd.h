@@ -376,6 +376,64 @@ typedef struct sa_amd_repeat_stats { /* of the calling thread's most recent repe
 } sa_amd_repeat_stats;
 void sa_amd_last_repeat_stats(sa_amd_repeat_stats *out);
 
+/*
+ * Lempel-Ziv factorisation (an extension): the longest-previous-factor array with a source for every position, and the greedy
+ * LZ77 parse that follows from it, from the text and its suffix array, on the device.  T has n bytes;
+ * SA is in the layout of sa_amd_saca_u8 (n + 1 entries, SA[0] = n); "slot" means an index into SA[1 .. n].
+ *   For position p with slot i (SA[i] = p): P(p) = SA[j] for the nearest slot j < i with SA[j] < p, N(p) = SA[k] for the nearest
+ *     slot k > i with SA[k] < p (n where there is none); lp(p) = lcp(T[p..], T[P(p)..]) (0 when P(p) = n), ln(p) likewise.
+ *   LPF (n entries, text order): LPF[p] = max(lp(p), ln(p)) = the length of the longest prefix of T[p..] that also starts at
+ *     some q < p (the copy may overlap p).  LPF[p] >= LPF[p - 1] - 1.
+ *   SRC (n entries): P(p) if lp(p) >= ln(p) and LPF[p] > 0; N(p) if ln(p) > lp(p); SA_AMD_LZ_LITERAL if LPF[p] = 0.
+ *     "banana": LPF = {0, 0, 0, 3, 2, 1}, SRC = {LIT, LIT, LIT, 1, 2, 3} (position 5 has no smaller left neighbour; the right one is 3).
+ *   Parse: phrase starts s_0 = 0, s_{k+1} = s_k + max(1, LPF[s_k]) until n is reached; phrase k is the pair of uint32
+ *     (SRC[s_k], max(1, LPF[s_k])), a literal (SA_AMD_LZ_LITERAL, 1): the byte T[s_k] itself.  The lengths sum to n; there are
+ *     at most n phrases and none for n = 0.  "banana": {(LIT, 1), (LIT, 1), (LIT, 1), (1, 3)}.
+ * `capacity` pairs fit the output: more phrases than that is no error -- the first `capacity` are written, *count_out is the
+ * number of all of them and the statistics cover all of them.
+ * Errors, as for the LCP array: an entry > n is SA_AMD_ERANGE, SA[0] != n is SA_AMD_EINVAL (range pass before anything is read
+ * through the entries); a negative capacity or a misaligned or short work block is SA_AMD_EINVAL with nothing written.
+ * The array is not otherwise proved to be the suffix array: with a wrong permutation the answers are unspecified, but nothing
+ * is read outside T or the tables, nothing is written outside the outputs and every walk terminates.
+ */
+#define SA_AMD_LZ_LITERAL 0xffffffffu
+/* bytes of device scratch the two device calls need: sa_amd_lcp_work_bytes(n) plus three n-entry buffers, about 32 (n + 1) */
+int64_t sa_amd_lz_work_bytes(int32_t n);
+/* device pointers: dT n bytes (any byte address), dSA n + 1 entries, dLPF and dSRC n entries each (either may be NULL), dWork
+ * sa_amd_lz_work_bytes(n) bytes 256-byte aligned; stream a hipStream_t (NULL = default stream).  Blocks until done. */
+int32_t sa_amd_lpf_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, uint32_t *dLPF, uint32_t *dSRC, void *dWork,
+                          int64_t work_bytes, void *stream);
+/* dPhrases: 2 * capacity entries of device memory (may be NULL when capacity is 0); count_out a HOST pointer */
+int32_t sa_amd_lz77_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, uint32_t *dPhrases, int64_t capacity,
+                           int64_t *count_out, void *dWork, int64_t work_bytes, void *stream);
+/* host pointers.  SA == NULL: the array is built on the device, used there and never downloaded: n bytes go up, 4 n bytes per
+ * array (LPF, SRC; either may be NULL) or 8 bytes per phrase come back.  SA != NULL (n + 1 entries): the caller's array goes up. */
+int32_t sa_amd_lpf(const uint8_t *T, int32_t n, const uint32_t *SA, uint32_t *LPF, uint32_t *SRC);
+int32_t sa_amd_lz77(const uint8_t *T, int32_t n, const uint32_t *SA, uint32_t *phrases, int64_t capacity, int64_t *count_out);
+/* from the index's resident text and suffix array */
+int32_t sa_amd_index_lpf(const sa_amd_index *ix, uint32_t *LPF, uint32_t *SRC);
+int32_t sa_amd_index_lz77(const sa_amd_index *ix, uint32_t *phrases, int64_t capacity, int64_t *count_out);
+
+typedef struct sa_amd_lz_stats {     /* of the calling thread's most recent LPF / LZ77 call (sa_amd_last_lcp_stats is filled too:
+                                        irreducible positions and compared bytes of both value passes together) */
+    int64_t phrases;                 /* all phrases, written or not (0 after a call that only made LPF / SRC, as the next three) */
+    int64_t literals;                /* phrases that are a literal byte */
+    int64_t longest;                 /* length of the longest phrase */
+    int64_t longest_pos;             /* where the first phrase of that length starts; -1 when there is no phrase */
+    int64_t unresolved;              /* slots whose nearest smaller value, on either side, was not inside their tile of 1024 slots */
+    int64_t hierarchy_steps;         /* words of the block minima (and of SA) those slots loaded, all of them together */
+    int64_t hierarchy_max;           /* the most one side of one slot loaded: at most 31 (K - 1) + 32 K, K the number of levels */
+    int64_t walkers;                 /* splitters = lanes of a walk launch (the last attempt's) */
+    int64_t walk_steps;              /* steps of all walkers, both walking phases and every attempt */
+    int32_t walk_launches;           /* launches of the first walking phase, every attempt */
+    int32_t restarts;                /* attempts thrown away: lanes were still walking at the launch limit (S / 8, another hash seed) */
+    int32_t splitter_spacing;        /* S in use at the end (0 after a call that only made LPF / SRC) */
+    int32_t readbacks;               /* blocking device -> host read-backs of counters */
+} sa_amd_lz_stats;
+void sa_amd_last_lz_stats(sa_amd_lz_stats *out);
+/* The parse's walk takes its route switches from sa_amd_unbwt_set_walk_limits and sa_amd_unbwt_set_splitter_spacing (the code
+ * is shared); they never change a result. */
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

@@ -26,7 +26,8 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "bwt", "unbwt", "bwt_device_ptr", "unbwt_device_ptr", "bwt_work_bytes", "unbwt_work_bytes", "last_unbwt_stats",
            "unbwt_set_walk_limits", "unbwt_set_splitter_spacing", "UnbwtStats",
            "repeat_lengths", "repeat_spans", "last_repeat_stats", "repeats_work_bytes", "repeat_spans_bound",
-           "repeat_lengths_device_ptr", "repeat_spans_device_ptr", "RepeatStats", "REPEATS_ALL", "REPEATS_KEEP_FIRST"]
+           "repeat_lengths_device_ptr", "repeat_spans_device_ptr", "RepeatStats", "REPEATS_ALL", "REPEATS_KEEP_FIRST",
+           "lpf", "lz77", "lz77_decode", "lz77_literals", "last_lz_stats", "lz_work_bytes", "lpf_device_ptr", "lz77_device_ptr", "LzStats", "LZ_LITERAL"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
@@ -94,6 +95,20 @@ class RepeatStats(ctypes.Structure):
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
+
+class LzStats(ctypes.Structure):
+    """sa_amd_lz_stats of include/suffix_array_amd.h"""
+    _fields_ = [("phrases", ctypes.c_int64), ("literals", ctypes.c_int64), ("longest", ctypes.c_int64), ("longest_pos", ctypes.c_int64),
+                ("unresolved", ctypes.c_int64), ("hierarchy_steps", ctypes.c_int64), ("hierarchy_max", ctypes.c_int64),
+                ("walkers", ctypes.c_int64), ("walk_steps", ctypes.c_int64), ("walk_launches", ctypes.c_int32),
+                ("restarts", ctypes.c_int32), ("splitter_spacing", ctypes.c_int32), ("readbacks", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+#: the source of a literal phrase, and of a position without an earlier copy (SA_AMD_LZ_LITERAL of include/suffix_array_amd.h)
+LZ_LITERAL = 0xFFFFFFFF
 
 #: span modes of ``repeat_spans_device_ptr`` (SA_AMD_REPEATS_* of include/suffix_array_amd.h)
 REPEATS_ALL = 0
@@ -228,6 +243,22 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_index_repeat_spans.restype = ctypes.c_int32
         L.sa_amd_last_repeat_stats.argtypes = [c_vp]
         L.sa_amd_last_repeat_stats.restype = None
+        L.sa_amd_lz_work_bytes.argtypes = [ctypes.c_int32]
+        L.sa_amd_lz_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_lpf_device.argtypes = [c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_lpf_device.restype = ctypes.c_int32
+        L.sa_amd_lz77_device.argtypes = [c_vp, c_vp, ctypes.c_int32, c_vp, ctypes.c_int64, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_lz77_device.restype = ctypes.c_int32
+        L.sa_amd_lpf.argtypes = [c_vp, ctypes.c_int32, c_vp, c_vp, c_vp]
+        L.sa_amd_lpf.restype = ctypes.c_int32
+        L.sa_amd_lz77.argtypes = [c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_lz77.restype = ctypes.c_int32
+        L.sa_amd_index_lpf.argtypes = [c_vp, c_vp, c_vp]
+        L.sa_amd_index_lpf.restype = ctypes.c_int32
+        L.sa_amd_index_lz77.argtypes = [c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_lz77.restype = ctypes.c_int32
+        L.sa_amd_last_lz_stats.argtypes = [c_vp]
+        L.sa_amd_last_lz_stats.restype = None
         _lib = L
     return _lib
 
@@ -253,6 +284,8 @@ def diag_lib() -> ctypes.CDLL:
         L.sa_amd_test_sample_sort64.restype = ctypes.c_int32
         L.sa_amd_test_bucket_sort32.argtypes = [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, c_vp]
         L.sa_amd_test_bucket_sort32.restype = ctypes.c_int32
+        L.sa_amd_test_lz_nsv.argtypes = [c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]
+        L.sa_amd_test_lz_nsv.restype = ctypes.c_int32
         L.sa_amd_test_build_keys.argtypes = [c_vp, ctypes.c_int32, c_vp, c_vp, c_vp]
         L.sa_amd_test_build_keys.restype = ctypes.c_int32
         L.sa_amd_debug_phase_cycles.argtypes = [c_vp, ctypes.c_int32]
@@ -631,6 +664,100 @@ def repeat_spans_device_ptr(text_ptr: int, sa_ptr: int, n: int, min_len: int, mo
     return int(count.value)
 
 
+def _sa_arg(t, sa):
+    if sa is None:
+        return None
+    a = np.ascontiguousarray(sa, dtype=np.uint32)
+    assert a.size == t.size + 1
+    return a
+
+
+def lpf(s, sa: Optional[np.ndarray] = None):
+    """Longest-previous-factor array of ``s`` on the GPU, with a source for every position: ``(LPF, SRC)``, two uint32 arrays of
+    ``len(s)`` entries in text order.  ``LPF[p]`` is the length of the longest prefix of ``s[p:]`` that also starts at some
+    ``q < p`` (the copy may overlap ``p``); ``SRC[p]`` is such a ``q`` -- of the two suffix-array neighbours with a smaller
+    position the one with the longer match, the left one on a tie -- or ``LZ_LITERAL`` where ``LPF[p] == 0``.  ``sa`` as for
+    ``repeat_lengths``."""
+    t = _as_u8(s)
+    assert t.size <= MAX_LENGTH
+    a = _sa_arg(t, sa)
+    out = np.empty((2, t.size), dtype=np.uint32)
+    _bwt_rc(lib().sa_amd_lpf(t.ctypes.data, t.size, None if a is None else a.ctypes.data, out[0].ctypes.data, out[1].ctypes.data))
+    return out[0], out[1]
+
+
+def lz77(s, sa: Optional[np.ndarray] = None) -> np.ndarray:
+    """Greedy LZ77 parse of ``s`` on the GPU: a ``(z, 2)`` uint32 array of ``(source, length)`` rows.  Phrase starts are
+    ``s_0 = 0``, ``s_{k+1} = s_k + max(1, LPF[s_k])``; row ``k`` is ``(SRC[s_k], max(1, LPF[s_k]))``, a literal byte
+    ``(LZ_LITERAL, 1)``.  The lengths sum to ``len(s)``; ``lz77_decode`` takes them together with the literal bytes
+    (``lz77_literals``).  Only the phrases come back from the device."""
+    t = _as_u8(s)
+    assert t.size <= MAX_LENGTH
+    a = _sa_arg(t, sa)
+    cap = min(t.size, max(1 << 16, t.size // 8))        # (a second call when there are more phrases than that)
+    while True:
+        out = np.empty((cap, 2), dtype=np.uint32)
+        count = ctypes.c_int64(0)
+        _bwt_rc(lib().sa_amd_lz77(t.ctypes.data, t.size, None if a is None else a.ctypes.data, out.ctypes.data, cap, ctypes.byref(count)))
+        if count.value <= cap:
+            return out[:int(count.value)].copy()
+        cap = int(count.value)
+
+
+def lz77_literals(s, phrases) -> bytes:
+    """the bytes of the literal phrases of ``phrases`` (a parse of ``s``), in phrase order: what a parse needs besides its
+    ``(source, length)`` rows to be decoded"""
+    t = _as_u8(s)
+    ph = np.asarray(phrases, dtype=np.int64).reshape(-1, 2)
+    starts = np.cumsum(ph[:, 1]) - ph[:, 1]
+    return t[starts[ph[:, 0] == LZ_LITERAL]].tobytes()
+
+
+def lz77_decode(phrases, literals) -> bytes:
+    """Host helper, not a GPU path: the text of a parse.  ``phrases`` as ``lz77`` returns them, ``literals`` the bytes of the
+    literal phrases in order (``lz77_literals``): a ``(LZ_LITERAL, 1)`` row does not carry its byte.  Copies go byte by byte,
+    because a source may overlap its own phrase."""
+    lit = bytes(_as_u8(literals))
+    out = bytearray()
+    k = 0
+    for src, ln in np.asarray(phrases, dtype=np.int64).reshape(-1, 2).tolist():
+        if src == LZ_LITERAL:
+            out.append(lit[k])
+            k += 1
+        else:
+            for j in range(ln):
+                out.append(out[src + j])
+    return bytes(out)
+
+
+def last_lz_stats() -> dict:
+    """phrases / literals / longest / longest_pos / unresolved / hierarchy_steps / hierarchy_max / walkers / walk_steps /
+    walk_launches / restarts / splitter_spacing / readbacks of this thread's most recent ``lpf`` / ``lz77`` call (the phrase and
+    walk fields read 0 after ``lpf``); ``last_lcp_stats`` holds the compares of both value passes together"""
+    st = LzStats()
+    lib().sa_amd_last_lz_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def lz_work_bytes(n: int) -> int:
+    return int(lib().sa_amd_lz_work_bytes(n))
+
+
+def lpf_device_ptr(text_ptr: int, sa_ptr: int, n: int, lpf_ptr: int, src_ptr: int, work_ptr: int, work_bytes: int, stream: int = 0) -> None:
+    """Device-resident LPF and SRC (raw device pointers, either output may be 0); blocks until done."""
+    _bwt_rc(lib().sa_amd_lpf_device(text_ptr, sa_ptr, n, lpf_ptr or None, src_ptr or None, work_ptr, work_bytes, stream))
+
+
+def lz77_device_ptr(text_ptr: int, sa_ptr: int, n: int, phrases_ptr: int, capacity: int, work_ptr: int, work_bytes: int,
+                    stream: int = 0) -> int:
+    """Device-resident parse (raw device pointers; ``phrases_ptr``: ``2 * capacity`` uint32); blocks until done and returns the
+    number of all phrases, of which the first ``capacity`` have been written."""
+    count = ctypes.c_int64(0)
+    _bwt_rc(lib().sa_amd_lz77_device(text_ptr, sa_ptr, n, phrases_ptr or None, int(capacity), ctypes.byref(count), work_ptr, work_bytes,
+                                     stream))
+    return int(count.value)
+
+
 class DeviceIndex:
     """Text + suffix array resident in HBM (sa_amd_index of include/suffix_array_amd.h): batched
     `contains` / `search_all` / `search_lcp` (reference src/sa.rs:164-253), bucket table, integrity check.
@@ -697,6 +824,23 @@ class DeviceIndex:
         _bwt_rc(lib().sa_amd_index_repeat_spans(self._h, k, REPEATS_KEEP_FIRST if keep_first else REPEATS_ALL, out.ctypes.data, cap,
                                                 ctypes.byref(count)))
         return out[:min(int(count.value), cap)].copy()
+
+    def lpf(self):
+        """``(LPF, SRC)`` from the resident text and suffix array (see ``lpf``)"""
+        out = np.empty((2, self._s.size), dtype=np.uint32)
+        _bwt_rc(lib().sa_amd_index_lpf(self._h, out[0].ctypes.data, out[1].ctypes.data))
+        return out[0], out[1]
+
+    def lz77(self) -> np.ndarray:
+        """the LZ77 parse from the resident text and suffix array (see ``lz77``)"""
+        cap = min(self._s.size, max(1 << 16, self._s.size // 8))
+        while True:
+            out = np.empty((cap, 2), dtype=np.uint32)
+            count = ctypes.c_int64(0)
+            _bwt_rc(lib().sa_amd_index_lz77(self._h, out.ctypes.data, cap, ctypes.byref(count)))
+            if count.value <= cap:
+                return out[:int(count.value)].copy()
+            cap = int(count.value)
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): build and keep the LCP table of the
@@ -893,6 +1037,14 @@ class SuffixArray:
     def repeat_spans(self, min_len: int, keep_first: bool = False) -> np.ndarray:
         """EXTENSION (the reference lacks it): the byte ranges that are copies, on the GPU (see ``repeat_spans``)"""
         return repeat_spans(self._s, min_len, keep_first, self._sa)
+
+    def lpf(self):
+        """EXTENSION (the reference lacks it): the longest-previous-factor array and its sources, on the GPU (see ``lpf``)"""
+        return lpf(self._s, self._sa)
+
+    def lz77(self) -> np.ndarray:
+        """EXTENSION (the reference lacks it): the greedy LZ77 parse of the text, on the GPU (see ``lz77``)"""
+        return lz77(self._s, self._sa)
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): contains / search_all / search_lcp

@@ -35,32 +35,27 @@ constexpr int LCP_CTL_OFF = 64;            // byte offset of the control words i
 constexpr int LCP_FLAGS_WORD = 8;          // uint32 index of the range pass's flags in the ctl slab
 constexpr int LCP_MAX_ROUNDS = 64;         // doubling windows from 16 bytes cover 2^31 in fewer than 32
 
-// The stages both the LCP array and the repeat finder (host/repeats.hpp) start with: the range pass, Φ, the irreducible values,
-// the long compares and the max-scan.  Afterwards PLCP stands in text order in the Φ buffer (n entries), the four n-entry
-// buffers are free and the control slab holds the LCP_C_* words; nothing has been synchronised since the last read-back.
-// n == 0: returns behind the range pass.  dWork: lcp_layout(n).bytes (L), 256-byte aligned; stats: irreducible, compared_bytes
-// and long_pairs are filled in.
-static int lcp_front(const uint8_t *dT, const uint32_t *dSA, int64_t n, void *dWork, const LcpLayout &L, hipStream_t st, const Tuning &tn,
-                     sa_amd_lcp_stats &stats)
+// The range pass every entry point starts with, before anything reads through the entries: the control slab is cleared, an
+// entry > n is SA_AMD_ERANGE, SA[0] != n (or n in another slot) SA_AMD_EINVAL.
+static int lcp_range(const uint32_t *dSA, int64_t n, void *dWork, const LcpLayout &L, hipStream_t st)
 {
-    char *base = (char *)dWork;
-    uint32_t *err = (uint32_t *)(base + L.ctl);
-    unsigned long long *ctl = (unsigned long long *)(base + L.ctl + LCP_CTL_OFF);
+    uint32_t *err = (uint32_t *)((char *)dWork + L.ctl);
     HIP_TRY(hipMemsetAsync(err, 0, 256, st));
-
-    // ---- range pass before anything reads through the entries ----
     int64_t blocks = ceil_div(n + 1, 256);
     if (blocks > 16384) blocks = 16384;
     PROF(KC_LCP_PHI, n + 1, st, hipLaunchKernelGGL(k_ci_range, dim3((unsigned)blocks), dim3(256), 0, st, dSA, n, err + LCP_FLAGS_WORD));
-    {
-        uint32_t f = 0;
-        const int rcw = read_words(&f, err + LCP_FLAGS_WORD, 4, st); if (rcw) return rcw;
-        if (f & 1u) return SA_AMD_ERANGE;
-        if (f & 2u) return SA_AMD_EINVAL;             // SA[0] != n (or n in another slot)
-    }
-    if (n == 0) return SA_AMD_OK;
+    uint32_t f = 0;
+    const int rcw = read_words(&f, err + LCP_FLAGS_WORD, 4, st); if (rcw) return rcw;
+    if (f & 1u) return SA_AMD_ERANGE;
+    if (f & 2u) return SA_AMD_EINVAL;                 // SA[0] != n (or n in another slot)
+    return SA_AMD_OK;
+}
 
-    // ---- Φ[SA[i]] = SA[i-1] ----
+// Partner-array stage of the LCP array: Φ[SA[i]] = SA[i-1] into the Φ buffer (n > 0, behind lcp_range).
+static int lcp_partner_phi(const uint32_t *dSA, int64_t n, void *dWork, const LcpLayout &L, hipStream_t st, const Tuning &tn)
+{
+    char *base = (char *)dWork;
+    uint32_t *err = (uint32_t *)(base + L.ctl);
     uint32_t *phi = (uint32_t *)(base + L.phi);
     uint32_t *alt = (uint32_t *)(base + L.alt);
     const size_t ae = L.alt_elems;
@@ -86,6 +81,24 @@ static int lcp_front(const uint8_t *dT, const uint32_t *dSA, int64_t n, void *dW
         if (pb > 16384) pb = 16384;
         PROF(KC_LCP_PHI, n, st, hipLaunchKernelGGL(k_lcp_phi, dim3((unsigned)pb), dim3(256), 0, st, dSA, n, phi));
     }
+
+    return SA_AMD_OK;
+}
+
+// Value stage: phi (n entries, 16-byte aligned) holds ANY partner array in text order, every entry <= n or clamped to n (n: no
+// partner, value 0).  Position j is compared directly unless j > 0, phi[j] is neither 0 nor n and T[j-1] == T[phi[j]-1]; for
+// the partner arrays this is used with (Φ of the LCP array; the nearest smaller suffix-array neighbours of host/lz.hpp) such a
+// position's value is its predecessor's minus one and j + value never decreases, so the max-scan fills it in.  Afterwards
+// phi[j] = lcp(T[j..], T[partner[j]..]), the four n-entry buffers are free and the control slab holds the LCP_C_* words; nothing
+// has been synchronised since the last read-back.  stats: irreducible, compared_bytes and long_pairs are SET from the
+// control words (the caller clears LCP_C_* between two runs over one work block and sums).
+static int lcp_values(const uint8_t *dT, int64_t n, uint32_t *phi, void *dWork, const LcpLayout &L, hipStream_t st, sa_amd_lcp_stats &stats)
+{
+    char *base = (char *)dWork;
+    uint32_t *err = (uint32_t *)(base + L.ctl);
+    unsigned long long *ctl = (unsigned long long *)(base + L.ctl + LCP_CTL_OFF);
+    uint32_t *alt = (uint32_t *)(base + L.alt);
+    const size_t ae = L.alt_elems;
 
     // ---- irreducible values up to the cap; the rest to the long list ----
     const int64_t tiles = ceil_div(n, LCP_TILE);
@@ -131,6 +144,20 @@ static int lcp_front(const uint8_t *dT, const uint32_t *dSA, int64_t n, void *dW
     PROF(KC_LCP_SCAN, tiles, st, hipLaunchKernelGGL(k_lcp_scan_spine, dim3(1), dim3(LCP_SPINE_THREADS), 0, st, tile_max, tiles));
     PROF(KC_LCP_SCAN, n, st, hipLaunchKernelGGL(k_lcp_scan, dim3((unsigned)tiles), dim3(LCP_THREADS), 0, st, phi, n, (const uint32_t *)tile_max));
     return SA_AMD_OK;
+}
+
+// The stages both the LCP array and the repeat finder (host/repeats.hpp) start with: the range pass, Φ, and the value stage over
+// it.  Afterwards PLCP stands in text order in the Φ buffer (n entries), the four n-entry buffers are free and the control slab
+// holds the LCP_C_* words; nothing has been synchronised since the last read-back.
+// n == 0: returns behind the range pass.  dWork: lcp_layout(n).bytes (L), 256-byte aligned; stats: irreducible, compared_bytes
+// and long_pairs are filled in.
+static int lcp_front(const uint8_t *dT, const uint32_t *dSA, int64_t n, void *dWork, const LcpLayout &L, hipStream_t st, const Tuning &tn,
+                     sa_amd_lcp_stats &stats)
+{
+    { const int rcr = lcp_range(dSA, n, dWork, L, st); if (rcr) return rcr; }
+    if (n == 0) return SA_AMD_OK;
+    { const int rcp = lcp_partner_phi(dSA, n, dWork, L, st, tn); if (rcp) return rcp; }
+    return lcp_values(dT, n, (uint32_t *)((char *)dWork + L.phi), dWork, L, st, stats);
 }
 
 // dT, dSA (n + 1 entries, SA[0] = n), dLCP (n + 1 entries): device memory on the current device; dWork: lcp_layout(n).bytes,

@@ -18,6 +18,7 @@
 #include "host/esa.hpp"
 #include "host/bwt.hpp"
 #include "host/repeats.hpp"
+#include "host/lz.hpp"
 
 extern "C" {
 
@@ -768,6 +769,96 @@ SA_EXPORT int32_t sa_amd_index_repeat_spans(const sa_amd_index *ix, int32_t min_
 SA_EXPORT void sa_amd_last_repeat_stats(sa_amd_repeat_stats *out)
 {
     if (out) *out = sa::g_last_repeat_stats;
+}
+
+// ---- Lempel-Ziv factorisation (host/lz.hpp, kernels/lz.hpp) ----
+
+SA_EXPORT int64_t sa_amd_lz_work_bytes(int32_t n)
+{
+    if (n < 0) return -1;
+    return (int64_t)sa::lz_layout(n).bytes;
+}
+
+SA_EXPORT int32_t sa_amd_lpf_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, uint32_t *dLPF, uint32_t *dSRC, void *dWork,
+                                    int64_t work_bytes, void *stream)
+{
+    if (n < 0 || !dSA || !dWork || (n > 0 && !dT)) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    return sa::lz_device(dT, dSA, n, false, dLPF, dSRC, nullptr, 0, nullptr, dWork, work_bytes, (hipStream_t)stream);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_lz77_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, uint32_t *dPhrases, int64_t capacity,
+                                     int64_t *count_out, void *dWork, int64_t work_bytes, void *stream)
+{
+    if (n < 0 || !dSA || !dWork || !count_out || (n > 0 && !dT) || (capacity > 0 && !dPhrases)) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    return sa::lz_device(dT, dSA, n, true, nullptr, nullptr, dPhrases, capacity, count_out, dWork, work_bytes, (hipStream_t)stream);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_lpf(const uint8_t *T, int32_t n, const uint32_t *SA, uint32_t *LPF, uint32_t *SRC)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::lz_host(T, n, SA, false, LPF, SRC, nullptr, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_lz77(const uint8_t *T, int32_t n, const uint32_t *SA, uint32_t *phrases, int64_t capacity, int64_t *count_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::lz_host(T, n, SA, true, nullptr, nullptr, phrases, capacity, count_out);
+    SA_ABI_GUARD_END(0)
+}
+
+// the index's resident text and array: the work block, and the outputs behind it, from the pool
+static int32_t index_lz(const sa_amd_index *ix, bool parse, uint32_t *LPF, uint32_t *SRC, uint32_t *phrases, int64_t capacity, int64_t *count_out)
+{
+    if (!ix) return SA_AMD_EINVAL;
+    if (parse && (capacity < 0 || !count_out || (capacity > 0 && !phrases))) return SA_AMD_EINVAL;
+    sa::DeviceGuard guard(ix->device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess) return SA_AMD_EHIP;
+    const int64_t cap = parse ? (capacity < ix->n ? capacity : ix->n) : 0;
+    const size_t ab = sa::align_up(((size_t)ix->n + 1) * 4, 256);
+    const size_t wb = sa::lz_layout(ix->n).bytes, ob = parse ? (size_t)cap * 8 + 8 : 2 * ab;
+    sa::DevBlock blk;
+    int32_t rc = sa::pool().acquire(cur, wb + ob, &blk);
+    if (rc) return rc;
+    uint32_t *dOut = (uint32_t *)((char *)blk.p + wb), *dOut2 = (uint32_t *)((char *)dOut + ab);
+    int64_t count = 0;
+    rc = sa::lz_device(ix->dT, ix->dSA, ix->n, parse, LPF ? dOut : nullptr, SRC ? dOut2 : nullptr, dOut, cap, &count, blk.p, (int64_t)wb, nullptr);
+    if (rc == SA_AMD_OK && !parse && ix->n > 0) {
+        if (LPF) rc = sa::hip_status(hipMemcpy(LPF, dOut, (size_t)ix->n * 4, hipMemcpyDeviceToHost));
+        if (rc == SA_AMD_OK && SRC) rc = sa::hip_status(hipMemcpy(SRC, dOut2, (size_t)ix->n * 4, hipMemcpyDeviceToHost));
+    }
+    if (rc == SA_AMD_OK && parse) {
+        const int64_t wr = count < cap ? count : cap;
+        if (wr > 0) rc = sa::hip_status(hipMemcpy(phrases, dOut, (size_t)wr * 8, hipMemcpyDeviceToHost));
+        if (rc == SA_AMD_OK) *count_out = count;
+    }
+    sa::pool().release(blk);
+    return rc;
+}
+
+SA_EXPORT int32_t sa_amd_index_lpf(const sa_amd_index *ix, uint32_t *LPF, uint32_t *SRC)
+{
+    SA_ABI_GUARD_BEGIN
+    return index_lz(ix, false, LPF, SRC, nullptr, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_lz77(const sa_amd_index *ix, uint32_t *phrases, int64_t capacity, int64_t *count_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return index_lz(ix, true, nullptr, nullptr, phrases, capacity, count_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_lz_stats(sa_amd_lz_stats *out)
+{
+    if (out) *out = sa::g_last_lz_stats;
 }
 
 SA_EXPORT void sa_amd_last_unbwt_stats(sa_amd_unbwt_stats *out)

@@ -28,6 +28,8 @@ int32_t sa_amd_test_sort_pairs(uint64_t *keys, uint32_t *vals, int64_t count, in
 int32_t sa_amd_test_sample_sort64(uint64_t *keys, uint32_t *vals, int64_t count, int32_t key_bits, int32_t *done);
 /* the 32-bit-key form of the same sort (first stage of the two-stage initial sort) */
 int32_t sa_amd_test_sort_pairs32(uint32_t *keys, uint32_t *vals, int64_t count, int32_t begin_bit, int32_t end_bit);
+/* stage 1 of the Lempel-Ziv factorisation alone: nearest smaller values of a DEVICE array of distinct values (see sa_diag.inc) */
+int32_t sa_amd_test_lz_nsv(const uint32_t *dA, int64_t n, uint32_t *dPsv, uint32_t *dNsv, int64_t *counters);
 /* the same order through two global passes over the top 16 (or 18: nine-bit digits) key bits + the in-LDS bucket sort of the
  * rest (kernels/bucket_sort.hpp); *largest = the largest bucket; returns 1 (buffers untouched) when no workgroup shape holds it */
 int32_t sa_amd_test_bucket_sort32(uint32_t *keys, uint32_t *vals, int64_t count, int32_t top_bits, uint32_t *largest);

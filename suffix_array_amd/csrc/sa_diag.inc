@@ -256,3 +256,28 @@ SA_EXPORT int32_t sa_amd_proto_induce_l(const uint8_t *T, const uint8_t *typeL, 
     HIP_TRY(hipMemcpy(counters, dC.p, 16, hipMemcpyDeviceToHost));
     return SA_AMD_OK;
 }
+
+// stage 1 of the Lempel-Ziv factorisation (kernels/lz.hpp) alone, on a device array of n distinct uint32 values: the nearest
+// slot to the left / right that holds a smaller value to dPsv / dNsv (n entries each, device; 0xffffffff: none).  counters
+// (host, four words): slots unresolved inside their tile, words loaded from the levels, the most for one side of one slot, levels.
+SA_EXPORT int32_t sa_amd_test_lz_nsv(const uint32_t *dA, int64_t n, uint32_t *dPsv, uint32_t *dNsv, int64_t *counters)
+{
+    using namespace sa;
+    if (n <= 0 || n > 0x7fffffffLL || !dA || !dPsv || !dNsv || !counters) return SA_AMD_EINVAL;
+    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    DevBuf dl, dc;
+    int32_t rc;
+    if ((rc = dl.alloc(((size_t)n / 31 + 64) * 4))) return rc;
+    if ((rc = dc.alloc(256))) return rc;
+    HIP_TRY(hipMemset(dc.p, 0, 256));
+    rc = lz_nsv(dA, n, dPsv, dNsv, dl.as<uint32_t>(), nullptr, nullptr, dc.as<unsigned long long>(), nullptr);
+    if (rc != SA_AMD_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    unsigned long long cw[LZ_C_WORDS];
+    HIP_TRY(hipMemcpy(cw, dc.p, sizeof(cw), hipMemcpyDeviceToHost));
+    counters[0] = (int64_t)cw[LZ_C_UNRES];
+    counters[1] = (int64_t)cw[LZ_C_HSTEPS];
+    counters[2] = (int64_t)cw[LZ_C_HMAX];
+    counters[3] = lz_levels(n, nullptr).top;
+    return SA_AMD_OK;
+}
