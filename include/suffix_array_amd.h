@@ -434,6 +434,77 @@ void sa_amd_last_lz_stats(sa_amd_lz_stats *out);
 /* The parse's walk takes its route switches from sa_amd_unbwt_set_walk_limits and sa_amd_unbwt_set_splitter_spacing (the code
  * is shared); they never change a result. */
 
+/*
+ * Matching a query text against the index (an extension): matching statistics and the spans of the query that occur in the
+ * indexed text, on the device.  The index text T has n bytes and SA is in the layout of sa_amd_saca_u8;
+ * the query Q has m bytes and the cap is C = max_len >= 1.
+ *   For query position j the window is w = Q[j .. j + c), c = min(C, m - j).  Let i be the number of slots of SA[0 .. n] whose
+ *     suffix is smaller than w in slice order (the lower bound; 1 <= i <= n + 1), a = lcp(w, T[SA[i - 1] ..]) and
+ *     b = lcp(w, T[SA[i] ..]) when i <= n, else b = -1.
+ *   ML (m entries): ML[j] = max(a, b): the length, capped at C, of the longest prefix of Q[j ..] that occurs in T.
+ *   POS (m entries): SA[i - 1] if a > b, else SA[i]; SA_AMD_MATCH_NONE when ML[j] = 0.  T[POS[j] .. POS[j] + ML[j]) equals
+ *     Q[j .. j + ML[j]).  For n = 0 every ML is 0.  ML[j + 1] >= ML[j] - 1 when no window is cut by C.
+ *     T = "banana", Q = "bandana", C = 8: ML = {3, 2, 1, 0, 3, 2, 1}, POS = {0, 1, 2, NONE, 3, 4, 5}.
+ *   Where ML[j] > 0 this is what sa_amd_index_search reports as lcp_len / lcp_start for the pattern w on an index WITHOUT a
+ *     bucket table.  The answers here do not depend on whether the index has a bucket table or an LCP table: the rule by which
+ *     sa_amd_index_search answers from the top-level bucket when the pattern's bucket is empty does not apply -- the insertion
+ *     point is the same with and without the table, and its two neighbours are compared.
+ *   Shared spans, min_len = k >= 1: position j is flagged iff m - j >= k and Q[j .. j + k) occurs in T (ML[j] = k under cap k);
+ *     the spans are the union of [j, j + k) over the flagged j, as maximal intervals [start, end) in Q: ascending, disjoint and
+ *     not adjacent, pairs of uint32.  The same union as that of [j, j + ML'[j]) over all j with uncapped ML'[j] >= k.  At most
+ *     (m + 1) / (k + 1) spans (sa_amd_repeat_spans_bound(m, k)); `capacity` / *count_out as for sa_amd_repeat_spans: more spans
+ *     than fit is no error, the first `capacity` are written, *count_out and the statistics cover all of them.
+ * Errors, each with nothing written: a NULL index, m < 0, a NULL query with m > 0, max_len / min_len < 1, a negative capacity, a
+ * misaligned or short work block: SA_AMD_EINVAL.  If the resident array is not the suffix array of the text the answers are
+ * unspecified, but nothing is read outside T, Q or the tables and nothing is written outside the outputs.
+ * Cost: a position whose compares stay below the group cap (sa_amd_match_set_group_cap) loads at most
+ * (ceil(log2(n + 1)) + 3) (min(c, cap) + 4 G) text bytes, G the lanes of a group; the others take one wave each: at most
+ * 2 c + 128 log2 P bytes over the LCP table (after sa_amd_index_enable_lcp), else (ceil(log2(n + 1)) + 3) (c + 64) -- O(c log n).
+ */
+#define SA_AMD_MATCH_NONE 0xffffffffu
+/* bytes of device scratch the two device calls need for a query of m bytes: about 5 m */
+int64_t sa_amd_match_work_bytes(int32_t m);
+/* host pointers: Q goes up, ML and POS (m entries each; either may be NULL) come back */
+int32_t sa_amd_index_match_stats(const sa_amd_index *ix, const uint8_t *Q, int32_t m, int32_t max_len, uint32_t *ML, uint32_t *POS);
+/* device pointers on the index's device: dQ m bytes (any byte address), dML and dPOS m entries each (either may be NULL), dWork
+ * sa_amd_match_work_bytes(m) bytes 256-byte aligned; stream a hipStream_t (NULL = default stream).  Blocks until done. */
+int32_t sa_amd_index_match_stats_device(const sa_amd_index *ix, const uint8_t *dQ, int32_t m, int32_t max_len, uint32_t *dML,
+                                        uint32_t *dPOS, void *dWork, int64_t work_bytes, void *stream);
+/* host pointers: Q goes up, only the spans (8 bytes each) and the counters come back */
+int32_t sa_amd_index_match_spans(const sa_amd_index *ix, const uint8_t *Q, int32_t m, int32_t min_len, uint32_t *spans,
+                                 int64_t capacity, int64_t *count_out);
+/* dSpans: 2 * capacity entries of device memory (may be NULL when capacity is 0); count_out a HOST pointer */
+int32_t sa_amd_index_match_spans_device(const sa_amd_index *ix, const uint8_t *dQ, int32_t m, int32_t min_len, uint32_t *dSpans,
+                                        int64_t capacity, int64_t *count_out, void *dWork, int64_t work_bytes, void *stream);
+
+typedef struct sa_amd_match_stats {  /* of the calling thread's most recent match call */
+    int64_t positions;               /* m */
+    int64_t matched;                 /* positions with ML > 0 */
+    int64_t longest;                 /* max ML */
+    int64_t longest_pos;             /* the first j with ML[j] == longest; -1 when there is none */
+    int64_t ml_sum;                  /* sum of ML */
+    int64_t long_positions;          /* positions that left the group path: c > cap and ML >= cap */
+    int64_t compared_bytes;          /* text bytes loaded for comparison, every chunk (4 G bytes of a group, 64 of a wave) counted whole */
+    int64_t steps;                   /* suffixes probed (table steps of the LCP route included) */
+    int64_t spans;                   /* all spans, written or not (0 after a stats call, as the next two) */
+    int64_t covered_bytes;           /* query bytes inside the spans */
+    int64_t flagged;                 /* flagged positions */
+    int32_t route_long;              /* route of the long positions: 0 plain wave search, 1 LCP table */
+    int32_t readbacks;               /* blocking device -> host read-backs of counters */
+    int32_t group_lanes;             /* G */
+    int32_t group_cap;               /* the cap in effect: min(sa_amd_match_set_group_cap, 4096 -- what a workgroup stages) */
+    int32_t tile;                    /* query positions per workgroup */
+    int32_t reserved;
+} sa_amd_match_stats;
+void sa_amd_last_match_stats(sa_amd_match_stats *out);
+/* route switch of the calling thread's later match calls (never changes a result): bytes of a window a group compares before the
+ * position goes to the one-wave-per-position path, clamped to 0 .. 1 048 576 (0: every position takes it; above 4096 acts as
+ * 4096); a negative value restores the default (64).  Returns the previous value. */
+int32_t sa_amd_match_set_group_cap(int32_t bytes);
+/* the same kind of switch for G, the lanes that serve one position on the group path: rounded down to 4, 8 or 16 (default 8); a
+ * negative value restores the default.  Returns the previous value. */
+int32_t sa_amd_match_set_group_lanes(int32_t lanes);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

@@ -27,7 +27,9 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "unbwt_set_walk_limits", "unbwt_set_splitter_spacing", "UnbwtStats",
            "repeat_lengths", "repeat_spans", "last_repeat_stats", "repeats_work_bytes", "repeat_spans_bound",
            "repeat_lengths_device_ptr", "repeat_spans_device_ptr", "RepeatStats", "REPEATS_ALL", "REPEATS_KEEP_FIRST",
-           "lpf", "lz77", "lz77_decode", "lz77_literals", "last_lz_stats", "lz_work_bytes", "lpf_device_ptr", "lz77_device_ptr", "LzStats", "LZ_LITERAL"]
+           "lpf", "lz77", "lz77_decode", "lz77_literals", "last_lz_stats", "lz_work_bytes", "lpf_device_ptr", "lz77_device_ptr", "LzStats", "LZ_LITERAL",
+           "MatchStats", "last_match_stats", "match_work_bytes", "match_set_group_cap", "match_set_group_lanes", "match_stats_device_ptr", "match_spans_device_ptr",
+           "MATCH_NONE", "MATCH_TILE"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
@@ -106,6 +108,23 @@ class LzStats(ctypes.Structure):
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
+
+class MatchStats(ctypes.Structure):
+    """sa_amd_match_stats of include/suffix_array_amd.h"""
+    _fields_ = [("positions", ctypes.c_int64), ("matched", ctypes.c_int64), ("longest", ctypes.c_int64), ("longest_pos", ctypes.c_int64),
+                ("ml_sum", ctypes.c_int64), ("long_positions", ctypes.c_int64), ("compared_bytes", ctypes.c_int64), ("steps", ctypes.c_int64),
+                ("spans", ctypes.c_int64), ("covered_bytes", ctypes.c_int64), ("flagged", ctypes.c_int64), ("route_long", ctypes.c_int32),
+                ("readbacks", ctypes.c_int32), ("group_lanes", ctypes.c_int32), ("group_cap", ctypes.c_int32), ("tile", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+#: ``pos`` of a query position none of whose bytes occurs in the text (SA_AMD_MATCH_NONE of include/suffix_array_amd.h)
+MATCH_NONE = 0xFFFFFFFF
+#: query positions one workgroup of the group path owns (kernels/match.hpp)
+MATCH_TILE = 256
 
 #: the source of a literal phrase, and of a position without an earlier copy (SA_AMD_LZ_LITERAL of include/suffix_array_amd.h)
 LZ_LITERAL = 0xFFFFFFFF
@@ -259,6 +278,23 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_index_lz77.restype = ctypes.c_int32
         L.sa_amd_last_lz_stats.argtypes = [c_vp]
         L.sa_amd_last_lz_stats.restype = None
+        L.sa_amd_match_work_bytes.argtypes = [ctypes.c_int32]
+        L.sa_amd_match_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_index_match_stats.argtypes = [c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]
+        L.sa_amd_index_match_stats.restype = ctypes.c_int32
+        L.sa_amd_index_match_stats_device.argtypes = [c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_match_stats_device.restype = ctypes.c_int32
+        L.sa_amd_index_match_spans.argtypes = [c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_match_spans.restype = ctypes.c_int32
+        L.sa_amd_index_match_spans_device.argtypes = [c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int64, c_vp, c_vp,
+                                                      ctypes.c_int64, c_vp]
+        L.sa_amd_index_match_spans_device.restype = ctypes.c_int32
+        L.sa_amd_last_match_stats.argtypes = [c_vp]
+        L.sa_amd_last_match_stats.restype = None
+        L.sa_amd_match_set_group_cap.argtypes = [ctypes.c_int32]
+        L.sa_amd_match_set_group_cap.restype = ctypes.c_int32
+        L.sa_amd_match_set_group_lanes.argtypes = [ctypes.c_int32]
+        L.sa_amd_match_set_group_lanes.restype = ctypes.c_int32
         _lib = L
     return _lib
 
@@ -758,6 +794,54 @@ def lz77_device_ptr(text_ptr: int, sa_ptr: int, n: int, phrases_ptr: int, capaci
     return int(count.value)
 
 
+def last_match_stats() -> dict:
+    """positions / matched / longest / longest_pos / ml_sum / long_positions / compared_bytes / steps / spans / covered_bytes /
+    flagged / route_long / readbacks / group_lanes / group_cap / tile of this thread's most recent ``match_stats`` /
+    ``match_spans`` call (the span fields read 0 after ``match_stats``)"""
+    st = MatchStats()
+    lib().sa_amd_last_match_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def match_work_bytes(m: int) -> int:
+    return int(lib().sa_amd_match_work_bytes(m))
+
+
+def match_set_group_cap(nbytes: int) -> int:
+    """Route switch of this thread's later match calls (never changes a result): window bytes a lane group compares before the
+    position goes to the one-wave-per-position path, 0 .. 1 048 576 (0: every position; above 4096 acts as 4096); negative
+    restores the default (64).  Returns the previous value."""
+    return int(lib().sa_amd_match_set_group_cap(int(nbytes)))
+
+
+def match_set_group_lanes(lanes: int) -> int:
+    """The same kind of switch for the lanes that serve one query position on the group path: 4, 8 or 16 (default 8; negative
+    restores it).  Returns the previous value."""
+    return int(lib().sa_amd_match_set_group_lanes(int(lanes)))
+
+
+def _index_handle(index):
+    return index._h if isinstance(index, DeviceIndex) else index
+
+
+def match_stats_device_ptr(index, query_ptr: int, m: int, max_len: int, ml_ptr: int, pos_ptr: int, work_ptr: int, work_bytes: int,
+                           stream: int = 0) -> None:
+    """Device-resident matching statistics of ``m`` query bytes against ``index`` (a ``DeviceIndex``; raw device pointers on its
+    device, either output may be 0); blocks until done."""
+    _check(lib().sa_amd_index_match_stats_device(_index_handle(index), query_ptr or None, int(m), int(max_len), ml_ptr or None,
+                                                 pos_ptr or None, work_ptr, work_bytes, stream))
+
+
+def match_spans_device_ptr(index, query_ptr: int, m: int, min_len: int, spans_ptr: int, capacity: int, work_ptr: int, work_bytes: int,
+                           stream: int = 0) -> int:
+    """Device-resident shared spans (``spans_ptr``: ``2 * capacity`` uint32); blocks until done and returns the number of all
+    spans, of which the first ``capacity`` have been written."""
+    count = ctypes.c_int64(0)
+    _check(lib().sa_amd_index_match_spans_device(_index_handle(index), query_ptr or None, int(m), int(min_len), spans_ptr or None,
+                                                 int(capacity), ctypes.byref(count), work_ptr, work_bytes, stream))
+    return int(count.value)
+
+
 class DeviceIndex:
     """Text + suffix array resident in HBM (sa_amd_index of include/suffix_array_amd.h): batched
     `contains` / `search_all` / `search_lcp` (reference src/sa.rs:164-253), bucket table, integrity check.
@@ -841,6 +925,31 @@ class DeviceIndex:
             if count.value <= cap:
                 return out[:int(count.value)].copy()
             cap = int(count.value)
+
+    def match_stats(self, query, max_len: int):
+        """-> ``(ml, pos)``, uint32 arrays over the positions of ``query``: ``ml[j]`` is the length, capped at ``max_len``, of the
+        longest prefix of ``query[j:]`` that occurs in the indexed text, ``pos[j]`` a place where it occurs (``MATCH_NONE`` where
+        ``ml[j] == 0``) -- the neighbour of the window's insertion point in the suffix array with the longer match, the right
+        one on a tie.  The same answers with or without the bucket and LCP tables."""
+        q = _as_u8(query)
+        assert q.size <= MAX_LENGTH
+        cap = min(_repeat_min_len(max_len), 2**31 - 1)
+        out = np.empty((2, q.size), dtype=np.uint32)
+        _check(lib().sa_amd_index_match_stats(self._h, q.ctypes.data, q.size, cap, out[0].ctypes.data, out[1].ctypes.data))
+        return out[0], out[1]
+
+    def match_spans(self, query, min_len: int) -> np.ndarray:
+        """the byte ranges of ``query`` covered by substrings of at least ``min_len`` bytes that occur in the indexed text: a
+        ``(count, 2)`` uint32 array of ``[start, end)`` rows, ascending, disjoint and not adjacent.  Only the spans come back
+        from the device."""
+        q = _as_u8(query)
+        assert q.size <= MAX_LENGTH
+        k = _repeat_min_len(min_len)
+        cap = (q.size + 1) // (k + 1)
+        out = np.empty((cap, 2), dtype=np.uint32)
+        count = ctypes.c_int64(0)
+        _check(lib().sa_amd_index_match_spans(self._h, q.ctypes.data, q.size, k, out.ctypes.data, cap, ctypes.byref(count)))
+        return out[:min(int(count.value), cap)].copy()
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): build and keep the LCP table of the
@@ -1045,6 +1154,14 @@ class SuffixArray:
     def lz77(self) -> np.ndarray:
         """EXTENSION (the reference lacks it): the greedy LZ77 parse of the text, on the GPU (see ``lz77``)"""
         return lz77(self._s, self._sa)
+
+    def match_stats(self, query, max_len: int):
+        """EXTENSION (the reference lacks it): matching statistics of ``query`` against the text (see ``DeviceIndex.match_stats``)"""
+        return self._index().match_stats(query, max_len)
+
+    def match_spans(self, query, min_len: int) -> np.ndarray:
+        """EXTENSION (the reference lacks it): the parts of ``query`` that occur in the text (see ``DeviceIndex.match_spans``)"""
+        return self._index().match_spans(query, min_len)
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): contains / search_all / search_lcp

@@ -19,6 +19,7 @@
 #include "host/bwt.hpp"
 #include "host/repeats.hpp"
 #include "host/lz.hpp"
+#include "host/match.hpp"
 
 extern "C" {
 
@@ -859,6 +860,84 @@ SA_EXPORT int32_t sa_amd_index_lz77(const sa_amd_index *ix, uint32_t *phrases, i
 SA_EXPORT void sa_amd_last_lz_stats(sa_amd_lz_stats *out)
 {
     if (out) *out = sa::g_last_lz_stats;
+}
+
+// ---- matching statistics and shared spans of a query against the index (host/match.hpp, kernels/match.hpp) ----
+
+static sa::MatchIndex match_index(const sa_amd_index *ix)
+{
+    sa::MatchIndex mi;
+    mi.dT = ix->dT; mi.dSA = ix->dSA; mi.n = ix->n; mi.dBkt = ix->dBkt; mi.dPair = ix->dPair;
+    return mi;
+}
+
+SA_EXPORT int64_t sa_amd_match_work_bytes(int32_t m)
+{
+    if (m < 0) return -1;
+    return (int64_t)sa::match_layout(m).bytes;
+}
+
+SA_EXPORT int32_t sa_amd_index_match_stats(const sa_amd_index *ix, const uint8_t *Q, int32_t m, int32_t max_len, uint32_t *ML, uint32_t *POS)
+{
+    if (!ix || m < 0 || max_len < 1 || (m > 0 && !Q)) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    sa::DeviceGuard guard(ix->device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    return sa::match_host(match_index(ix), Q, m, max_len, false, ML, POS, nullptr, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_match_stats_device(const sa_amd_index *ix, const uint8_t *dQ, int32_t m, int32_t max_len, uint32_t *dML,
+                                                  uint32_t *dPOS, void *dWork, int64_t work_bytes, void *stream)
+{
+    if (!ix || m < 0 || max_len < 1 || (m > 0 && !dQ)) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    sa::DeviceGuard guard(ix->device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    return sa::match_device(match_index(ix), dQ, m, max_len, false, dML, dPOS, nullptr, 0, nullptr, dWork, work_bytes, (hipStream_t)stream);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_match_spans(const sa_amd_index *ix, const uint8_t *Q, int32_t m, int32_t min_len, uint32_t *spans,
+                                           int64_t capacity, int64_t *count_out)
+{
+    if (!ix || m < 0 || min_len < 1 || (m > 0 && !Q) || capacity < 0 || !count_out || (capacity > 0 && !spans)) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    sa::DeviceGuard guard(ix->device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    return sa::match_host(match_index(ix), Q, m, min_len, true, nullptr, nullptr, spans, capacity, count_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_match_spans_device(const sa_amd_index *ix, const uint8_t *dQ, int32_t m, int32_t min_len, uint32_t *dSpans,
+                                                  int64_t capacity, int64_t *count_out, void *dWork, int64_t work_bytes, void *stream)
+{
+    if (!ix || m < 0 || min_len < 1 || (m > 0 && !dQ) || capacity < 0 || !count_out || (capacity > 0 && !dSpans)) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    sa::DeviceGuard guard(ix->device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    return sa::match_device(match_index(ix), dQ, m, min_len, true, nullptr, nullptr, dSpans, capacity, count_out, dWork, work_bytes,
+                            (hipStream_t)stream);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_match_stats(sa_amd_match_stats *out)
+{
+    if (out) *out = sa::g_last_match_stats;
+}
+
+SA_EXPORT int32_t sa_amd_match_set_group_cap(int32_t bytes)
+{
+    const int32_t prev = sa::g_match_cap < 0 ? sa::MATCH_CAP_DEFAULT : sa::g_match_cap;
+    sa::g_match_cap = bytes < 0 ? -1 : (bytes > sa::MATCH_CAP_MAX ? sa::MATCH_CAP_MAX : bytes);
+    return prev;
+}
+
+SA_EXPORT int32_t sa_amd_match_set_group_lanes(int32_t lanes)
+{
+    const int32_t prev = sa::g_match_lanes;
+    sa::g_match_lanes = lanes < 0 ? 8 : (lanes >= 16 ? 16 : (lanes >= 8 ? 8 : 4));
+    return prev;
 }
 
 SA_EXPORT void sa_amd_last_unbwt_stats(sa_amd_unbwt_stats *out)
