@@ -35,6 +35,10 @@
  *   oracle_check_integrity literal restatement of reference src/sa.rs:72-84
  *   oracle_verify_sa       linear-time equivalent of the same check
  *   oracle_verify_sa_mt    the same on several host threads (full-size configs)
+ * and, for the extensions that include/suffix_array_amd.h defines on top of the array (they have no counterpart in the
+ * reference; the header's definitions are what is restated):
+ *   oracle_lz77            LPF, SRC and the greedy parse in linear time
+ *   oracle_match_stats     matching statistics of a query, O(m (C + log n)), on several host threads
  * Pinning: tests/test_oracle.py checks all of them against the known answers
  * of SURVEY.md section 8a, the reference's only literal vector
  * (`search_all(b"splend") == [0, 9]` on b"splendid splendor", reference
@@ -381,5 +385,135 @@ ORACLE_API int32_t oracle_lcp_kasai(const uint8_t *s, int64_t n, const uint32_t 
         if (h > 0) --h;
     }
     free(rank);
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* Lempel-Ziv factorisation as include/suffix_array_amd.h defines it:  */
+/* for position p with slot i (SA[i] = p), P(p) / N(p) = the entry of   */
+/* the nearest slot to the left / right that holds a smaller position   */
+/* (n: none), lp / ln the lcp of T[p..] with the suffix there;          */
+/* LPF[p] = max(lp, ln); SRC[p] = P(p) if lp >= ln, N(p) if ln > lp,    */
+/* 0xffffffff (the literal mark) if LPF[p] = 0.  Phrases: s_0 = 0,      */
+/* s_{k+1} = s_k + max(1, LPF[s_k]); phrase k = (SRC[s_k], max(1, LPF)).*/
+/* A stack pass over SA[1..n] gives P and N; the compares run in text   */
+/* order from the previous match minus one (lp(p) >= lp(p - 1) - 1:     */
+/* T[p-1..] and T[P(p-1)..] agree on lp(p-1) bytes, so T[p..] and       */
+/* T[P(p-1)+1..] agree on one less, and the nearest smaller neighbour   */
+/* on that side is at least as close in the order; ln likewise), so     */
+/* they are amortised over the text.                                    */
+/* lpf, src: n entries each; phrases: 2 * capacity entries (may be NULL */
+/* when capacity is 0).  Returns the number of ALL phrases (the first   */
+/* `capacity` are written), -1 bad arguments, -2 out of memory.         */
+/* ------------------------------------------------------------------ */
+static int64_t lz_extend(const uint8_t *t, int64_t n, int64_t p, int64_t q, int64_t h)
+{
+    if (q >= n) return 0;                   /* no neighbour on that side */
+    const int64_t lim = n - (p > q ? p : q);
+    if (h < 0) h = 0;
+    if (h > lim) h = lim;
+    while (h < lim && t[p + h] == t[q + h]) ++h;
+    return h;
+}
+
+ORACLE_API int64_t oracle_lz77(const uint8_t *t, int64_t n, const uint32_t *sa, uint32_t *lpf, uint32_t *src, uint32_t *phrases,
+                               int64_t capacity)
+{
+    if (n < 0 || n > 2147483646LL || capacity < 0 || !sa || (capacity > 0 && !phrases)) return -1;
+    if (n == 0) return 0;
+    if (!t || !lpf || !src) return -1;
+    uint32_t *P = (uint32_t *)malloc((size_t)n * 4), *N = (uint32_t *)malloc((size_t)n * 4), *st = (uint32_t *)malloc((size_t)n * 4);
+    if (!P || !N || !st) { free(P); free(N); free(st); return -2; }
+    const uint32_t *a = sa + 1;             /* the slots of the n suffixes that are not empty */
+    int64_t top = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        while (top && st[top - 1] > a[i]) N[st[--top]] = a[i];      /* the stack holds positions, ascending */
+        P[a[i]] = top ? st[top - 1] : (uint32_t)n;
+        st[top++] = a[i];
+    }
+    while (top) N[st[--top]] = (uint32_t)n;
+    int64_t lp = 0, ln = 0;
+    for (int64_t p = 0; p < n; ++p) {
+        lp = lz_extend(t, n, p, P[p], lp - 1);
+        ln = lz_extend(t, n, p, N[p], ln - 1);
+        lpf[p] = (uint32_t)(lp >= ln ? lp : ln);
+        src[p] = lpf[p] == 0 ? 0xffffffffu : (lp >= ln ? P[p] : N[p]);
+    }
+    free(P); free(N); free(st);
+    int64_t z = 0;
+    for (int64_t p = 0; p < n; ++z) {
+        const uint32_t len = lpf[p] ? lpf[p] : 1u;
+        if (z < capacity) { phrases[2 * z] = src[p]; phrases[2 * z + 1] = len; }
+        p += len;
+    }
+    return z;
+}
+
+/* ------------------------------------------------------------------ */
+/* Matching statistics as include/suffix_array_amd.h defines them: for  */
+/* query position j the window is w = Q[j .. j + c), c = min(C, m - j); */
+/* i = the number of slots of SA[0 .. n] whose suffix is smaller than w */
+/* in slice order (a proper prefix is smaller), a = lcp(w, suffix of    */
+/* slot i - 1), b = lcp(w, suffix of slot i), -1 when i = n + 1;        */
+/* ML[j] = max(a, b); POS[j] = SA[i - 1] if a > b, else SA[i];          */
+/* 0xffffffff when ML[j] = 0.  The binary search keeps the lcp of w     */
+/* with the suffixes at both ends of the open range and compares from   */
+/* the smaller of the two on; at the end they are a and b.              */
+/* ml, pos: m entries each.  Returns 0, -1 bad arguments.               */
+/* ------------------------------------------------------------------ */
+typedef struct {
+    const uint8_t *t, *q; const uint32_t *sa; uint32_t *ml, *pos; int64_t n, m, cap, lo, hi;
+} match_job;
+
+static void *match_worker(void *arg)
+{
+    const match_job *J = (const match_job *)arg;
+    const uint8_t *t = J->t;
+    const int64_t n = J->n;
+    for (int64_t j = J->lo; j < J->hi; ++j) {
+        const uint8_t *w = J->q + j;
+        const int64_t c = J->cap < J->m - j ? J->cap : J->m - j;     /* >= 1 */
+        /* slots below lo are smaller than w, slots from hi on are not; slot 0 is the empty suffix: smaller, lcp 0 */
+        int64_t lo = 1, hi = n + 1, l = 0, r = -1;
+        while (lo < hi) {
+            const int64_t mid = lo + (hi - lo) / 2, p = J->sa[mid];
+            const int64_t common = n - p < c ? n - p : c;
+            int64_t v = l < r ? l : r;
+            if (v < 0) v = 0;
+            if (v > common) v = common;      /* (cannot happen with the suffix array) */
+            while (v < common && t[p + v] == w[v]) ++v;
+            const int smaller = v < common ? t[p + v] < w[v] : common < c;
+            if (smaller) { lo = mid + 1; l = v; } else { hi = mid; r = v; }
+        }
+        const int64_t a = l, b = lo <= n ? r : -1;
+        const int64_t best = a > b ? a : b;
+        J->ml[j] = (uint32_t)best;
+        J->pos[j] = best == 0 ? 0xffffffffu : (a > b ? J->sa[lo - 1] : J->sa[lo]);
+    }
+    return NULL;
+}
+
+ORACLE_API int32_t oracle_match_stats(const uint8_t *t, int64_t n, const uint32_t *sa, const uint8_t *q, int64_t m, int64_t cap,
+                                      uint32_t *ml, uint32_t *pos)
+{
+    if (n < 0 || m < 0 || cap < 1 || !sa || (n > 0 && !t) || (m > 0 && (!q || !ml || !pos))) return -1;
+    if (m == 0) return 0;
+    int threads = (int)(m / 4096) + 1;
+    if (threads > 16) threads = 16;
+    pthread_t th[16];
+    match_job jobs[16];
+    int own[16];
+    const int64_t per = (m + threads - 1) / threads;
+    int started = 0;
+    for (int k = 0; k < threads; ++k) {
+        match_job *J = &jobs[k];
+        J->t = t; J->q = q; J->sa = sa; J->ml = ml; J->pos = pos; J->n = n; J->m = m; J->cap = cap;
+        J->lo = (int64_t)k * per; J->hi = J->lo + per > m ? m : J->lo + per;
+        if (J->lo >= J->hi) break;
+        own[k] = pthread_create(&th[k], NULL, match_worker, J) == 0;
+        if (!own[k]) match_worker(J);
+        started = k + 1;
+    }
+    for (int k = 0; k < started; ++k) if (own[k]) pthread_join(th[k], NULL);
     return 0;
 }

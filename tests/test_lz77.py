@@ -1,6 +1,7 @@
 """GPU suite for the Lempel-Ziv factorisation: every route (host pointers with and without the array, device pointers,
 DeviceIndex, SuffixArray) against the numpy definitions of test_lz77_abi.py over the oracle's suffix array; stage 1 alone on
-permutations no short text produces; the walk's resume and restart routes; capacity, errors, the top of the size range."""
+permutations no short text produces; the walk's resume and restart routes; capacity, errors, the top of the size range; texts of
+many phrases at every size where a stage changes, against the oracle library's linear-time factorisation."""
 import ctypes
 import threading
 
@@ -9,9 +10,10 @@ import pytest
 
 import suffix_array_amd as sa
 from suffix_array_amd import corpus
-from conftest import ROOT, adversarial_cases, fibonacci_word, thue_morse
+from conftest import ROOT, adversarial_cases
 from test_lcp import _Dev, _u8, kasai
-from test_lz77_abi import (LIT, decode, lpf_definition, lpf_from_lcp, neighbour_slots, parse_definition, stats_definition)
+from test_lz77_abi import (LIT, _families, decode, lpf_definition, lpf_from_lcp, neighbour_slots, oracle_lz77, parse_definition,
+                           stats_definition)
 
 pytestmark = pytest.mark.gpu
 
@@ -136,27 +138,6 @@ def check_all_routes(oracle, t, name="", offsets=(0,), arr=None):
         assert count == ph.shape[0] and np.array_equal(dev, ph), (name, off)
         assert check_stats(ph, n) == first, (name, off)
     return ph
-
-
-def _fib_text(n):
-    k, w = 1, fibonacci_word(1)
-    while len(w) < n:
-        k += 1
-        w = fibonacci_word(k)
-    return np.frombuffer(w[:n], dtype=np.uint8)
-
-
-def _families(n, seed=1):
-    rng = np.random.default_rng(seed)
-    h = rng.integers(0, 256, n // 2, dtype=np.uint8)
-    out = {
-        "one_byte": np.full(n, 0x41, dtype=np.uint8), "period2": np.resize(np.array([1, 2], dtype=np.uint8), n),
-        "fibonacci": _fib_text(n), "thue_morse": np.frombuffer(thue_morse(n), dtype=np.uint8),
-        "twice": np.resize(np.concatenate([h, h]), n), "akbak": np.concatenate([np.full(n // 2, 97), [98], np.full(n - n // 2 - 1, 97)]),
-        "random2": rng.integers(0, 2, n, dtype=np.uint8), "random4": rng.integers(0, 4, n, dtype=np.uint8),
-        "random256": rng.integers(0, 256, n, dtype=np.uint8), "zeros_ffs": rng.choice(np.array([0, 0xFF], dtype=np.uint8), n),
-    }
-    return {k: np.ascontiguousarray(v[:n], dtype=np.uint8) for k, v in out.items()}
 
 
 def test_known_answers():
@@ -413,6 +394,133 @@ def test_wrong_permutation_terminates_in_bounds():
     lpf_on_device(t, good, 0)
     count, dev = parse_on_device(t, good, n)
     assert 0 < count <= n
+
+
+# ---------------------------------------------------------------- many phrases at the sizes where a stage changes ----
+# The minima hierarchy gains a level above FAN^3 and above FAN^4 slots; k_unbwt_splitters strides once its grid is capped at
+# 16 384 workgroups of 256 lanes and k_lz_merge once its grid is capped at 65 536 (host/lz.hpp).  The reference is oracle_lz77
+# (oracle/oracle.c) over oracle.sais: the numpy definitions do not reach these sizes.
+SPLITTER_GRID_SPAN = 16384 * 256
+MERGE_GRID_SPAN = 65536 * 256
+MID_SIZES = (FAN ** 3, FAN ** 3 + 1, 2 * FAN ** 3 + 1, FAN ** 4, FAN ** 4 + 1)
+LARGE_SIZES = (SPLITTER_GRID_SPAN + 257, MERGE_GRID_SPAN + 1025)
+DEVICE_FORMS_UP_TO = 2 * FAN ** 3 + 1
+SHARED = ("english", FAN ** 4 + 1)                                    # the text of the capacity and the walk test
+_REFERENCE = {}
+
+
+def _big_text(family, n):
+    if family == "english":
+        return corpus.english_corpus(n, 17)
+    if family == "dna_repeats":
+        return corpus.dna_repeats(n, 18)
+    rng = np.random.default_rng(n)
+    if family == "random2":
+        return rng.integers(0, 2, n, dtype=np.uint8)
+    assert family == "twice"
+    h = rng.integers(0, 256, n // 2, dtype=np.uint8)
+    return np.ascontiguousarray(np.resize(np.concatenate([h, h]), n))
+
+
+def big_reference(oracle, family, n):
+    """(text, array, LPF, SRC, phrases) by oracle.sais and oracle_lz77, computed once and left unchanged"""
+    if (family, n) in _REFERENCE:
+        return _REFERENCE[family, n]
+    t = _big_text(family, n)
+    arr = oracle.sais(t)
+    lpf, src, ph, z = oracle_lz77(oracle, t, arr)
+    assert z == ph.shape[0]
+    for a in (t, arr, lpf, src, ph):
+        a.flags.writeable = False
+    if (family, n) == SHARED:
+        _REFERENCE[family, n] = (t, arr, lpf, src, ph)
+    return t, arr, lpf, src, ph
+
+
+def check_big_text(oracle, family, n):
+    t, arr, lpf, src, ph = big_reference(oracle, family, n)
+    top = levels(n)
+    assert top == (2 if n <= FAN ** 3 else 3 if n <= FAN ** 4 else 4 if n <= FAN ** 5 else 5)
+    g = sa.lpf(t, arr)
+    st = sa.last_lz_stats()
+    assert g[0].dtype == np.uint32 and g[1].dtype == np.uint32
+    assert np.array_equal(g[0], lpf), (family, n, np.flatnonzero(g[0] != lpf)[:8])
+    assert np.array_equal(g[1], src), (family, n, np.flatnonzero(g[1] != src)[:8])
+    assert st["hierarchy_max"] <= step_bound(n) and st["phrases"] == 0
+    del g
+    got = sa.lz77(t, arr)
+    assert got.shape == ph.shape, (family, n, got.shape, ph.shape)
+    assert np.array_equal(got, ph), (family, n, np.flatnonzero((got != ph).any(axis=1))[:8])
+    st = check_stats(ph, n)
+    assert st["hierarchy_max"] <= step_bound(n)
+    assert decode(got, t) == t.tobytes(), (family, n)
+    print(family, n, "levels", top, "phrases", ph.shape[0], {k: st[k] for k in ("unresolved", "hierarchy_max", "walkers", "walk_launches")})
+    if n <= DEVICE_FORMS_UP_TO:
+        a, b = lpf_on_device(t, arr, 1)
+        assert np.array_equal(a, lpf) and np.array_equal(b, src), (family, n)
+        count, dev = parse_on_device(t, arr, n, 3)
+        assert count == ph.shape[0] and np.array_equal(dev, ph), (family, n)
+        assert check_stats(ph, n) == st, (family, n)
+    return ph
+
+
+def test_stage_thresholds_follow_the_constants():
+    """the sizes above are the first at which the code takes the other path"""
+    assert (levels(FAN ** 3), levels(FAN ** 3 + 1), levels(FAN ** 4), levels(FAN ** 4 + 1)) == (2, 3, 3, 4)
+    assert FAN * FAN == TILE and sa.MATCH_TILE == 256
+    for n, span in zip(LARGE_SIZES, (SPLITTER_GRID_SPAN, MERGE_GRID_SPAN)):
+        assert -(-n // 256) > span // 256                              # more workgroups' worth of slots than the capped grid
+
+
+@pytest.mark.parametrize("n", MID_SIZES)
+@pytest.mark.parametrize("family", ["english", "dna_repeats", "random2", "twice"])
+def test_many_phrases_where_the_hierarchy_gains_a_level(oracle, family, n):
+    """a real suffix array under three and four levels of minima, k_lz_far<true> through them, thousands of walkers through the
+    doubling rounds, phrase counts summed over hundreds of emit tiles.  (oracle.sais + oracle_lz77 at 1 048 577 bytes: 0.13 s on
+    one host core.)"""
+    ph = check_big_text(oracle, family, n)
+    assert ph.shape[0] > n // 64                                      # many phrases: every emit tile holds some
+
+
+@pytest.mark.parametrize("n", LARGE_SIZES)
+@pytest.mark.parametrize("family", ["english", "random2"])
+def test_many_phrases_where_a_capped_grid_strides(oracle, family, n):
+    """k_unbwt_splitters above 16 384 workgroups' worth of positions, k_lz_merge above 65 536.  (The CPU reference takes longer
+    than the device: oracle.sais + oracle_lz77 at 16 778 241 bytes took 2.3 s + 1.4 s on one host core.)"""
+    ph = check_big_text(oracle, family, n)
+    assert ph.shape[0] > n // 64
+
+
+def test_cut_capacity_at_four_levels(oracle):
+    """fewer places than phrases at 1 048 577 bytes: the true count, the true prefix, nothing behind it"""
+    t, arr, lpf, src, ph = big_reference(oracle, *SHARED)
+    z = ph.shape[0]
+    assert z > 4096
+    for cap in (z - 1, z, z // 2):
+        count, dev = parse_on_device(t, arr, cap, 1)                  # (checks the canaries on either side and behind the phrases)
+        assert count == z and np.array_equal(dev, ph[:cap]), cap
+        check_stats(ph, t.size)
+
+
+def test_walk_resumes_at_four_levels(oracle):
+    """64 steps a launch: k_lz_walk and k_lz_flag go on where the launch before stopped, over thousands of walkers"""
+    t, arr, lpf, src, ph = big_reference(oracle, *SHARED)
+    try:
+        sa.unbwt_set_walk_limits(64, -1)
+        got = sa.lz77(t, arr)
+        assert np.array_equal(got, ph)
+        st = check_stats(ph, t.size)
+        assert st["restarts"] == 0 and st["walk_launches"] > 1 and st["splitter_spacing"] == 256
+        assert st["walkers"] > t.size // 1024
+        sa.unbwt_set_walk_limits(16, 3)                               # three launches an attempt: denser splitters, another seed
+        assert np.array_equal(sa.lz77(t, arr), ph)
+        st = check_stats(ph, t.size)
+        assert st["restarts"] >= 1 and st["splitter_spacing"] < 256
+    finally:
+        sa.unbwt_set_walk_limits(-1, -1)
+    assert np.array_equal(sa.lz77(t, arr), ph)
+    st = sa.last_lz_stats()
+    assert st["restarts"] == 0 and st["splitter_spacing"] == 256      # the defaults are back
 
 
 # ---------------------------------------------------------------- the top of the size range ----

@@ -1,8 +1,10 @@
 """CPU suite for the Lempel-Ziv factorisation: the definitions of include/suffix_array_amd.h restated in numpy (LPF with its
-sources, the greedy parse, decoding), checked against literal brute force and the known answers; the exports, the Python
-surface and the argument checks that answer without a device."""
+sources, the greedy parse, decoding), checked against literal brute force and the known answers; the oracle library's
+linear-time restatement (the reference of the GPU suite at sizes numpy does not reach) against the numpy one; the exports, the
+Python surface and the argument checks that answer without a device."""
 import ctypes
 import inspect
+import json
 import os
 import re
 
@@ -10,7 +12,7 @@ import numpy as np
 import pytest
 
 import suffix_array_amd as sa
-from conftest import ROOT
+from conftest import ROOT, adversarial_cases, fibonacci_word, thue_morse
 from test_lcp_abi import _kasai
 
 EXPORTS = ("sa_amd_lz_work_bytes", "sa_amd_lpf_device", "sa_amd_lz77_device", "sa_amd_lpf", "sa_amd_lz77", "sa_amd_index_lpf",
@@ -148,6 +150,44 @@ def stats_definition(phrases):
             "longest_pos": int(starts[np.nonzero(ph[:, 1] == longest)[0][0]])}
 
 
+def oracle_lz77(oracle, t, arr, capacity=None):
+    """oracle_lz77 of oracle/oracle.c -> (LPF, SRC, the phrases that fit `capacity` (default: all), the number of all phrases), uint32"""
+    L = oracle.L
+    L.oracle_lz77.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [ctypes.c_int64]
+    L.oracle_lz77.restype = ctypes.c_int64
+    t = _u8(t)
+    n = t.size
+    a = np.ascontiguousarray(arr, dtype=np.uint32)
+    assert a.size == n + 1
+    capacity = n if capacity is None else capacity
+    lpf, src = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+    ph = np.full((capacity + 1, 2), 0xEEEEEEEE, dtype=np.uint32)
+    z = L.oracle_lz77(t.ctypes.data, n, a.ctypes.data, lpf.ctypes.data, src.ctypes.data, ph.ctypes.data, capacity)
+    assert z >= 0 and np.all(ph[min(z, capacity):] == 0xEEEEEEEE)
+    return lpf, src, ph[:min(z, capacity)].copy(), z
+
+
+def _fib_text(n):
+    k, w = 1, fibonacci_word(1)
+    while len(w) < n:
+        k += 1
+        w = fibonacci_word(k)
+    return np.frombuffer(w[:n], dtype=np.uint8)
+
+
+def _families(n, seed=1):
+    rng = np.random.default_rng(seed)
+    h = rng.integers(0, 256, n // 2, dtype=np.uint8)
+    out = {
+        "one_byte": np.full(n, 0x41, dtype=np.uint8), "period2": np.resize(np.array([1, 2], dtype=np.uint8), n),
+        "fibonacci": _fib_text(n), "thue_morse": np.frombuffer(thue_morse(n), dtype=np.uint8),
+        "twice": np.resize(np.concatenate([h, h]), n), "akbak": np.concatenate([np.full(n // 2, 97), [98], np.full(n - n // 2 - 1, 97)]),
+        "random2": rng.integers(0, 2, n, dtype=np.uint8), "random4": rng.integers(0, 4, n, dtype=np.uint8),
+        "random256": rng.integers(0, 256, n, dtype=np.uint8), "zeros_ffs": rng.choice(np.array([0, 0xFF], dtype=np.uint8), n),
+    }
+    return {k: np.ascontiguousarray(v[:n], dtype=np.uint8) for k, v in out.items()}
+
+
 # ---------------------------------------------------------------- literal brute force ----
 
 def brute_lpf(t):
@@ -191,6 +231,34 @@ def test_definitions_against_brute_force(oracle):
         assert int(ph[:, 1].sum()) == n and decode(ph, t) == b
         st = stats_definition(ph)
         assert st["phrases"] == ph.shape[0] and 1 <= st["longest"] <= n
+
+
+def _oracle_equals_definitions(oracle, t, arr, name):
+    t = _u8(t)
+    lpf, src = lpf_from_lcp(t, arr, _kasai(oracle, t, arr))
+    ph = parse_definition(lpf, src)
+    glpf, gsrc, gph, z = oracle_lz77(oracle, t, arr)
+    assert np.array_equal(glpf, lpf) and np.array_equal(gsrc, src), name
+    assert z == ph.shape[0] and np.array_equal(gph, ph), name
+    for cap in (0, z // 2, max(z - 1, 0)):                            # a cut capacity: the true count, the true prefix
+        _, _, cut, zc = oracle_lz77(oracle, t, arr, cap)
+        assert zc == z and np.array_equal(cut, ph[:cap]), (name, cap)
+
+
+def test_oracle_lz77_equals_the_definitions(oracle):
+    for name, b in adversarial_cases().items():
+        t = _u8(b)
+        _oracle_equals_definitions(oracle, t, oracle.sais(t), name)
+    gold = os.path.join(ROOT, "tests", "golden")
+    with open(os.path.join(gold, "manifest.json")) as f:
+        names = sorted(json.load(f))
+    assert names
+    for name in names:
+        t = np.fromfile(os.path.join(gold, name + ".text"), dtype=np.uint8)
+        _oracle_equals_definitions(oracle, t, np.fromfile(os.path.join(gold, name + ".sa.u32le"), dtype="<u4"), name)
+    for name, t in _families(3001).items():
+        _oracle_equals_definitions(oracle, t, oracle.sais(t), name)
+    assert oracle_lz77(oracle, b"banana", oracle.sais(b"banana"))[2].tolist() == [[LIT, 1], [LIT, 1], [LIT, 1], [1, 3]]
 
 
 def test_known_answers():

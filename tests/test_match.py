@@ -1,8 +1,10 @@
 """GPU suite for matching a query against the device index: every route (host pointers, device pointers with misaligned queries
 and canaries, DeviceIndex, SuffixArray) against the numpy definitions of test_match_abi.py over the oracle's suffix array; the
-pin to sa_amd_index_search on the explicit windows; invariance under the bucket and LCP tables; the group-cap routes; the work
-bound; spans, capacity, errors, the top of the size range, threads."""
+pin to sa_amd_index_search on the explicit windows; invariance under the bucket and LCP tables; the group-cap routes; every
+group width; the work bound; spans, capacity, errors; a text of a million bytes against the oracle library's matching
+statistics; the top of the size range, threads."""
 import ctypes
+import hashlib
 import json
 import math
 import os
@@ -15,19 +17,28 @@ import suffix_array_amd as sa
 from suffix_array_amd import corpus
 from conftest import ROOT, adversarial_cases, fibonacci_word
 from test_lcp import _Dev
-from test_match_abi import (NONE, STAGE_MAX, _u8, long_positions_definition, match_definition, spans_definition, stats_definition)
+from test_match_abi import (CAPS, NONE, STAGE_MAX, _u8, long_positions_definition, match_definition, oracle_match_stats, queries,
+                            spans_definition, stats_definition, union_spans)
 
 pytestmark = pytest.mark.gpu
 
 TILE = sa.MATCH_TILE
 CANARY = 0xA5
-CAPS = (1, 2, 3, 7, 8, 9, 63, 64, 65, 255, 4096)
 N_ABOVE = (1 << 30) + 4097
 _CASES = adversarial_cases()
 _WANTS = ((True, True), (True, False), (False, True))
 
 
 _MEMO = {}
+LANES = (4, 8, 16)
+_ACROSS_WIDTHS = {}
+
+
+def same_for_every_width(key, lanes, *arrays):
+    """what the first group width answered for `key` is what every other width answers, bit for bit (by digest)"""
+    got = tuple(hashlib.sha256(np.asarray(a).astype(np.uint32).tobytes()).digest() for a in arrays)
+    first = _ACROSS_WIDTHS.setdefault(key, (lanes, got))
+    assert first[1] == got, (key, "lanes", first[0], lanes)
 
 
 def _memo(fn, t, arr, q, cap):
@@ -54,22 +65,6 @@ def _golden():
                    np.fromfile(os.path.join(gold, name + ".sa.u32le"), dtype="<u4")) for name in names}
 
 
-def queries(t, seed=0):
-    rng = np.random.default_rng(seed)
-    n = t.size
-    changed = t.copy()
-    changed[::37] ^= 1
-    alphabet = np.unique(t) if n else np.array([65, 66], dtype=np.uint8)
-    absent = np.setdiff1d(np.arange(256, dtype=np.uint8), np.unique(t))
-    out = {"same": t, "changed": changed, "random": alphabet[rng.integers(0, alphabet.size, min(max(n, 5), 1500))],
-           "empty": np.zeros(0, dtype=np.uint8)}
-    if absent.size:
-        out["absent"] = absent[rng.integers(0, absent.size, min(max(n, 3), 700))]
-    for m in (1, TILE - 1, TILE, TILE + 1, 2 * TILE + 1):
-        out["m%d" % m] = np.resize(changed, m) if n else np.full(m, 65, dtype=np.uint8)
-    return {k: np.ascontiguousarray(v, dtype=np.uint8) for k, v in out.items()}
-
-
 def bytes_bound(n, m, cap, st, long_mask):
     """the work bound of DESIGN.md section 15, summed over the positions: the group path for every position, the wave path on
     top for those that left it"""
@@ -87,12 +82,14 @@ def bytes_bound(n, m, cap, st, long_mask):
     return total
 
 
-def check_stats(ml, m, n, cap, group_cap=64, st=None, spans=None):
+def check_stats(ml, m, n, cap, group_cap=64, st=None, spans=None, lanes=None):
     st = sa.last_match_stats() if st is None else st
     for key, val in stats_definition(ml).items():
         assert st[key] == val, (key, st)
     ge = min(group_cap, STAGE_MAX)
     assert st["group_cap"] == ge and st["tile"] == TILE and st["group_lanes"] in (4, 8, 16)
+    if lanes is not None:
+        assert st["group_lanes"] == lanes, st
     assert st["long_positions"] == long_positions_definition(ml, m, cap, group_cap), st
     c = np.minimum(cap, m - np.arange(m))
     assert st["compared_bytes"] <= bytes_bound(n, m, cap, st, (c > ge) & (ml >= ge)), st
@@ -225,20 +222,29 @@ def test_known_answers():
     ix.close()
 
 
-def test_every_offset_and_output_choice(oracle):
+@pytest.mark.parametrize("lanes", LANES)
+def test_every_offset_and_output_choice(oracle, lanes):
     t = corpus.english_corpus(3000, 4)
     arr = oracle.sais(t)
     q = queries(t, 2)["changed"][:2 * TILE + 77]
-    ix = sa.DeviceIndex(t, arr)
-    for cap in (5, 70):
-        ml, pos = match_model(t, arr, q, cap)
-        for want in _WANTS:
-            got = host_call(ix, q, cap, want)
-            assert (not want[0] or np.array_equal(got[0], ml)) and (not want[1] or np.array_equal(got[1], pos))
-            for off in range(8):
-                dev = stats_on_device(ix, q, cap, off, want)
-                assert (not want[0] or np.array_equal(dev[0], ml)) and (not want[1] or np.array_equal(dev[1], pos)), (cap, want, off)
-    ix.close()
+    prev = sa.match_set_group_lanes(lanes)
+    try:
+        ix = sa.DeviceIndex(t, arr)
+        for cap in (5, 70):
+            ml, pos = match_model(t, arr, q, cap)
+            for want in _WANTS:
+                got = host_call(ix, q, cap, want)
+                assert (not want[0] or np.array_equal(got[0], ml)) and (not want[1] or np.array_equal(got[1], pos))
+                check_stats(ml, q.size, t.size, cap, lanes=lanes)
+                if want == (True, True):
+                    same_for_every_width(("offsets", cap), lanes, *got)
+                for off in range(8):
+                    dev = stats_on_device(ix, q, cap, off, want)
+                    assert (not want[0] or np.array_equal(dev[0], ml)) and (not want[1] or np.array_equal(dev[1], pos)), (cap, want, off)
+                    check_stats(ml, q.size, t.size, cap, lanes=lanes)
+        ix.close()
+    finally:
+        sa.match_set_group_lanes(prev)
 
 
 def _table_texts(oracle):
@@ -247,34 +253,44 @@ def _table_texts(oracle):
     return {k: (v, oracle.sais(v)) for k, v in out.items()}
 
 
-def test_answers_do_not_depend_on_the_tables(oracle):
-    for name, (t, arr) in _table_texts(oracle).items():
-        qs = queries(t, 3)
-        qs["edge"] = _u8(b"\x00\x01\x00\xff\xfe\xff\xff\x00\x00" * 30)       # windows whose bigram bucket is empty
-        for tables in ((), ("bkt",), ("lcp",), ("bkt", "lcp")):
-            ix = sa.DeviceIndex(t, arr)
-            if "bkt" in tables:
-                ix.buckets()
-            if "lcp" in tables:
-                ix.enable_lcp()
-            for qname, q in qs.items():
-                for cap in (1, 2, 3, 9, 65, 300):
-                    ml, pos = match_model(t, arr, q, cap)
-                    got = host_call(ix, q, cap)
-                    assert np.array_equal(got[0], ml) and np.array_equal(got[1], pos), (name, tables, qname, cap)
-                    st = check_stats(ml, q.size, t.size, cap)
-                    assert st["route_long"] == (1 if "lcp" in tables else 0)
-                for k in (1, 2, 5):
-                    assert np.array_equal(ix.match_spans(q, k), spans_model(t, arr, q, k)[0]), (name, tables, qname, k)
-            ix.close()
+@pytest.mark.parametrize("lanes", LANES)
+def test_answers_do_not_depend_on_the_tables(oracle, lanes):
+    prev = sa.match_set_group_lanes(lanes)
+    try:
+        for name, (t, arr) in _table_texts(oracle).items():
+            qs = queries(t, 3)
+            qs["edge"] = _u8(b"\x00\x01\x00\xff\xfe\xff\xff\x00\x00" * 30)       # windows whose bigram bucket is empty
+            for tables in ((), ("bkt",), ("lcp",), ("bkt", "lcp")):
+                ix = sa.DeviceIndex(t, arr)
+                if "bkt" in tables:
+                    ix.buckets()
+                if "lcp" in tables:
+                    ix.enable_lcp()
+                for qname, q in qs.items():
+                    for cap in (1, 2, 3, 9, 65, 300):
+                        ml, pos = match_model(t, arr, q, cap)
+                        got = host_call(ix, q, cap)
+                        assert np.array_equal(got[0], ml) and np.array_equal(got[1], pos), (name, tables, qname, cap)
+                        st = check_stats(ml, q.size, t.size, cap, lanes=lanes)
+                        assert st["route_long"] == (1 if "lcp" in tables else 0)
+                        same_for_every_width(("tables", name, tables, qname, cap), lanes, *got)
+                    for k in (1, 2, 5):
+                        sp = ix.match_spans(q, k)
+                        assert np.array_equal(sp, spans_model(t, arr, q, k)[0]), (name, tables, qname, k)
+                        same_for_every_width(("tables", name, tables, qname, "spans", k), lanes, sp)
+                ix.close()
+    finally:
+        sa.match_set_group_lanes(prev)
 
 
+@pytest.mark.parametrize("lanes", LANES)
 @pytest.mark.parametrize("group_cap", [0, 8, 64, 5000, -1])
-def test_group_cap_routes(oracle, group_cap):
+def test_group_cap_routes(oracle, group_cap, lanes):
     eff = 64 if group_cap < 0 else group_cap
     sa.match_set_group_cap(3)
     prev = sa.match_set_group_cap(group_cap)                          # (-1: a cap restored with a negative value)
     assert prev == 3
+    prev_lanes = sa.match_set_group_lanes(lanes)
     try:
         for name, (t, arr) in _table_texts(oracle).items():
             for tables in ((), ("bkt", "lcp")):
@@ -288,16 +304,20 @@ def test_group_cap_routes(oracle, group_cap):
                         ml, pos = match_model(t, arr, q, cap)
                         got = host_call(ix, q, cap)
                         assert np.array_equal(got[0], ml) and np.array_equal(got[1], pos), (name, tables, qname, cap)
-                        st = check_stats(ml, q.size, t.size, cap, eff)
+                        st = check_stats(ml, q.size, t.size, cap, eff, lanes=lanes)
                         if qname == "same" and cap > min(eff, STAGE_MAX) and t.size > cap:
                             assert st["long_positions"] > 0
+                        same_for_every_width(("group_cap", group_cap, name, tables, qname, cap), lanes, *got)
                     k = 50
                     sp = spans_model(t, arr, q, k)
-                    assert np.array_equal(ix.match_spans(q, k), sp[0])
-                    check_stats(match_model(t, arr, q, k)[0], q.size, t.size, k, eff, spans=sp)
+                    got = ix.match_spans(q, k)
+                    assert np.array_equal(got, sp[0])
+                    check_stats(match_model(t, arr, q, k)[0], q.size, t.size, k, eff, spans=sp, lanes=lanes)
+                    same_for_every_width(("group_cap", group_cap, name, tables, qname, "spans"), lanes, got)
                 ix.close()
     finally:
         sa.match_set_group_cap(-1)
+        sa.match_set_group_lanes(prev_lanes)
 
 
 def test_work_bound_one_byte_text():
@@ -439,6 +459,85 @@ def test_wrong_permutation_stays_in_bounds():
             got = stats_on_device(ix, q, cap, 3)
             assert np.all(got[0] <= cap)
         ix.close()
+
+
+# ---------------------------------------------------------------- a million bytes, exact ----
+# match_definition is a Python loop and stops at some ten thousand bytes; oracle_match_stats (oracle/oracle.c) restates the
+# header on host threads.  At this size the bigram buckets of both texts are well filled (the table's starts matter), a query
+# sends tens of thousands of positions down the long path and the descent over the LCP table runs at log_p = 21.
+MID_N = (1 << 20) + 3
+MID_M = (1 << 16) + 77
+MID_ABSENT = 2000
+_MID = {}
+
+
+def mid_case(oracle, name):
+    """(text, array, query, {cap: (ML, POS)}) computed once and left unchanged"""
+    if name in _MID:
+        return _MID[name]
+    t = corpus.english_corpus(MID_N, 21) if name == "english" else corpus.dna(MID_N, 22)
+    arr = oracle.sais(t)
+    rng = np.random.default_rng(23)
+    parts, have = [], 0
+    while have < MID_M - MID_ABSENT:                                 # slices of the text, 1 .. 6000 bytes, from anywhere in it
+        ln = int(min(rng.integers(1, 6001), MID_M - MID_ABSENT - have))
+        at = int(rng.integers(0, MID_N - ln + 1))
+        parts.append(t[at:at + ln])
+        have += ln
+    q = np.concatenate(parts)
+    flips = rng.choice(q.size, q.size // 37, replace=False)           # one byte in 37, wherever it falls: the gaps between two
+    q[flips] ^= 1                                                     # changed bytes run from nothing to some hundred bytes
+    absent = np.setdiff1d(np.arange(256, dtype=np.uint8), np.unique(t))
+    half = q.size // 2 + 1
+    q = np.ascontiguousarray(np.concatenate([q[:half], np.full(MID_ABSENT, absent[0], dtype=np.uint8), q[half:]]))
+    assert q.size == MID_M and t.size == MID_N
+    exact = {cap: oracle_match_stats(oracle, t, arr, q, cap) for cap in MID_CAPS + (50,)}
+    for a in (t, arr, q) + tuple(x for pair in exact.values() for x in pair):
+        a.flags.writeable = False
+    _MID[name] = (t, arr, q, exact)
+    return _MID[name]
+
+
+MID_CAPS = (1, 2, 3, 64, 65, 300, 4096, MID_M + 5)
+
+
+@pytest.mark.parametrize("tables", [(), ("bkt",), ("lcp",), ("bkt", "lcp")], ids=["plain", "bkt", "lcp", "bkt_lcp"])
+@pytest.mark.parametrize("name", ["english", "dna"])
+def test_mid_size_exact(oracle, name, tables):
+    t, arr, q, exact = mid_case(oracle, name)
+    n, m = t.size, q.size
+    ix = sa.DeviceIndex(t, arr)
+    if "bkt" in tables:
+        ix.buckets()
+    if "lcp" in tables:
+        ix.enable_lcp()
+    for turn, cap in enumerate(MID_CAPS):
+        ml, pos = exact[cap]
+        got = host_call(ix, q, cap)
+        assert np.array_equal(got[0], ml), (name, tables, cap, np.flatnonzero(got[0] != ml)[:8])
+        assert np.array_equal(got[1], pos), (name, tables, cap, np.flatnonzero(got[1] != pos)[:8])
+        st = check_stats(ml, m, n, cap, lanes=8)
+        assert st["long_positions"] == long_positions_definition(ml, m, cap, 64)
+        assert (st["long_positions"] > 0) == (cap > 64), (cap, st)
+        assert st["route_long"] == (1 if "lcp" in tables else 0)
+        if cap > 64:
+            print(name, tables, "cap", cap, "long positions", st["long_positions"], "bytes a position", st["compared_bytes"] / m)
+        dev = stats_on_device(ix, q, cap, 1 + 2 * (turn % 4))        # an odd byte address for the query
+        assert np.array_equal(dev[0], ml) and np.array_equal(dev[1], pos), (name, tables, cap)
+        assert check_stats(ml, m, n, cap, lanes=8)["long_positions"] == st["long_positions"]
+    assert np.all(exact[MID_M + 5][0][q == q[m // 2]] == 0)           # (the absent letter's run sits around the middle)
+    k = 50
+    ml = exact[k][0]
+    flagged = np.flatnonzero(ml == k)
+    sp = union_spans(flagged, [k] * flagged.size, m)
+    z = sp.shape[0]
+    assert z > 64
+    for capacity in (z // 2, z):
+        count, dev = spans_on_device(ix, q, k, capacity, 3)           # (checks the canaries on either side and behind the spans)
+        assert count == z and np.array_equal(dev, sp[:capacity]), (name, tables, capacity)
+        check_stats(ml, m, n, k, spans=(sp, flagged), lanes=8)
+    assert np.array_equal(ix.match_spans(q, k), sp)
+    ix.close()
 
 
 def _brute_region(region, qb):

@@ -1,6 +1,7 @@
 """CPU suite for matching a query against the index: the definitions of include/suffix_array_amd.h restated in numpy over the
 oracle's suffix array, checked against literal brute force and against the identity that the cap of the shared spans costs
-nothing; the exports, the Python surface and the argument checks that answer without a device."""
+nothing; the oracle library's threaded restatement (the reference of the GPU suite at sizes the Python loop does not reach)
+against the numpy one; the exports, the Python surface and the argument checks that answer without a device."""
 import ctypes
 import inspect
 import os
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 import suffix_array_amd as sa
+from suffix_array_amd import corpus
 from conftest import ROOT, adversarial_cases
 
 EXPORTS = ("sa_amd_match_work_bytes", "sa_amd_index_match_stats", "sa_amd_index_match_stats_device", "sa_amd_index_match_spans",
@@ -63,6 +65,22 @@ def match_definition(t, arr, q, cap):
         if ml[j] > 0:
             pos[j] = arr[i - 1] if a > b else arr[i]
     return ml, pos
+
+
+def oracle_match_stats(oracle, t, arr, q, cap):
+    """oracle_match_stats of oracle/oracle.c -> (ML, POS)"""
+    L = oracle.L
+    L.oracle_match_stats.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                     ctypes.c_void_p, ctypes.c_void_p]
+    L.oracle_match_stats.restype = ctypes.c_int32
+    t, q = np.ascontiguousarray(t, dtype=np.uint8), np.ascontiguousarray(q, dtype=np.uint8)
+    a = np.ascontiguousarray(arr, dtype=np.uint32)
+    assert a.size == t.size + 1
+    out = np.full((2, q.size + 2), 0xEEEEEEEE, dtype=np.uint32)
+    assert L.oracle_match_stats(t.ctypes.data, t.size, a.ctypes.data, q.ctypes.data, q.size, cap, out[0, 1:].ctypes.data,
+                                out[1, 1:].ctypes.data) == 0
+    assert np.all(out[:, 0] == 0xEEEEEEEE) and np.all(out[:, -1] == 0xEEEEEEEE)
+    return out[0, 1:-1].astype(np.int64), out[1, 1:-1].astype(np.int64)
 
 
 def union_spans(starts, lengths, m):
@@ -149,6 +167,40 @@ def test_definition_against_brute_force(oracle):
                 ml, pos = match_definition(t, arr, q, cap)
                 assert np.array_equal(ml, brute_ml(t.tobytes(), q.tobytes(), cap)), (name, cap)
                 check_properties(t, q, ml, pos, cap)
+
+
+CAPS = (1, 2, 3, 7, 8, 9, 63, 64, 65, 255, 4096)                     # (tests/test_match.py runs the device over the same)
+
+
+def queries(t, seed=0):
+    """the query kinds of the GPU suite for one text"""
+    tile = sa.MATCH_TILE
+    rng = np.random.default_rng(seed)
+    n = t.size
+    changed = t.copy()
+    changed[::37] ^= 1
+    alphabet = np.unique(t) if n else np.array([65, 66], dtype=np.uint8)
+    absent = np.setdiff1d(np.arange(256, dtype=np.uint8), np.unique(t))
+    out = {"same": t, "changed": changed, "random": alphabet[rng.integers(0, alphabet.size, min(max(n, 5), 1500))],
+           "empty": np.zeros(0, dtype=np.uint8)}
+    if absent.size:
+        out["absent"] = absent[rng.integers(0, absent.size, min(max(n, 3), 700))]
+    for m in (1, tile - 1, tile, tile + 1, 2 * tile + 1):
+        out["m%d" % m] = np.resize(changed, m) if n else np.full(m, 65, dtype=np.uint8)
+    return {k: np.ascontiguousarray(v, dtype=np.uint8) for k, v in out.items()}
+
+
+def test_oracle_match_stats_equals_the_definition(oracle):
+    texts = {name: _u8(b) for name, b in adversarial_cases().items() if len(b) <= 800}
+    texts["english"] = corpus.english_corpus(3000, 8)
+    texts["random2"] = np.random.default_rng(4).integers(0, 2, 2500, dtype=np.uint8)
+    for name, t in texts.items():
+        arr = oracle.sais(t)
+        for qname, q in queries(t, 6).items():
+            for cap in CAPS + (q.size + 5,):
+                ml, pos = match_definition(t, arr, q, cap)
+                got = oracle_match_stats(oracle, t, arr, q, cap)
+                assert np.array_equal(got[0], ml) and np.array_equal(got[1], pos), (name, qname, cap)
 
 
 def test_capped_union_equals_uncapped_union(oracle):

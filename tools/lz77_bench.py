@@ -1,6 +1,6 @@
 """LZ77 factorisation timing: sa_amd_lz77_device and sa_amd_lpf_device on device-resident text + suffix
 array, per workload, with the time of every stage, beside sa_amd_lcp_device and the suffix-array build of the same text, the
-stage-1 and walk counters, compared_bytes / (n log2 n), and a single-core CPU baseline (tools/lz77_cpu.c).
+stage-1 and walk counters, compared_bytes / (n log2 n), and a single-core CPU baseline (oracle_lz77 of oracle/oracle.c).
 
 python tools/lz77_bench.py [--out DIR] [--calls K] [--only NAME,...] [--cpu-max-mib M]
 Writes DIR/r09_lz77_table.txt and DIR/r09_lz77_table.csv (default DIR: profiles/).  Every parse is checked: against the CPU
@@ -46,15 +46,13 @@ WORKLOADS = {
 
 
 def cpu_lib():
-    out = os.path.join(ROOT, "tools", "bin")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "lz77_cpu.so")
-    src = os.path.join(ROOT, "tools", "lz77_cpu.c")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-o", so, src])
+    """the oracle library's linear-time factorisation: the same code the test suite checks the device against"""
+    so = os.path.join(ROOT, "oracle", "liboracle.so")
+    if not os.path.exists(so):
+        subprocess.check_call(["make", "-s", "all"], cwd=os.path.join(ROOT, "oracle"))
     L = ctypes.CDLL(so)
-    L.lz77_cpu.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [ctypes.c_int64]
-    L.lz77_cpu.restype = ctypes.c_int64
+    L.oracle_lz77.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [ctypes.c_int64]
+    L.oracle_lz77.restype = ctypes.c_int64
     return L
 
 
@@ -143,7 +141,7 @@ def main():
             lpf, src = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
             exp = np.empty((min(z, cap), 2), dtype=np.uint32)
             t0 = time.perf_counter()
-            zc = cpu.lz77_cpu(t.ctypes.data, n, arr.ctypes.data, lpf.ctypes.data, src.ctypes.data, exp.ctypes.data, exp.shape[0])
+            zc = cpu.oracle_lz77(t.ctypes.data, n, arr.ctypes.data, lpf.ctypes.data, src.ctypes.data, exp.ctypes.data, exp.shape[0])
             cpu_ms = (time.perf_counter() - t0) * 1e3
             check = "cpu" if zc == z and np.array_equal(exp, ph) else "MISMATCH"
             del lpf, src, exp
@@ -166,7 +164,7 @@ def main():
     with open(os.path.join(args.out, "r09_lz77_table.txt"), "w") as f:
         f.write(f"tools/lz77_bench.py  ({torch.cuda.get_device_name(0)}; median and spread of {args.calls} calls after one warm-up, each ending "
                 "in a device synchronise; array resident; *_ms stage columns: HIP-event time of one more call, the range pass counted with nsv; "
-                "cpu_ms = tools/lz77_cpu.c on one core, array given)\n")
+                "cpu_ms = oracle_lz77 (oracle/oracle.c) on one core, array given)\n")
         for r in rows:
             f.write("  ".join(f"{h}={v}" for h, v in zip(hdr, r)) + "\n")
     return 0 if all(r[-1] != "MISMATCH" for r in rows) else 1
