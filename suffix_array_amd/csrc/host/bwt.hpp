@@ -52,42 +52,24 @@ static int bwt_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, uint8
     return SA_AMD_OK;
 }
 
-// host buffers: the text goes up; the array is built on the device and stays there (SA == nullptr) or the caller's goes up; n
-// bytes and `primary` come back.  Device block and stream from the process-wide pool.
+// The transform of a resident text and array into a slab of the scope's block; n bytes and `primary` come back.  in.dW: the
+// scope's first slab, at least BWT_WORK_BYTES.
+static int bwt_resident(PooledScope &sc, const Inputs &in, int32_t n, uint8_t *B, int32_t *primary_out)
+{
+    uint8_t *dB = (uint8_t *)sc.take((size_t)n + 16);
+    if (sc.rc == SA_AMD_OK) sc.rc = bwt_device(in.dT, in.dSA, n, dB, primary_out, in.dW, (int64_t)in.wb, sc.st);
+    if (n > 0) sc.down(B, dB, (size_t)n);
+    return sc.finish();
+}
+
+// host buffers: the text goes up; the array is built on the device and stays there (SA == nullptr) or the caller's goes up
 static int bwt_host(const uint8_t *T, int32_t n, const uint32_t *SA, uint8_t *B, int32_t *primary_out)
 {
     if (n < 0 || !primary_out || (n > 0 && (!T || !B))) return SA_AMD_EINVAL;
     if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
-    DeviceGuard guard(pick_device());
-    if (guard.rc != SA_AMD_OK) return guard.rc;
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
-    const size_t N1 = (size_t)n + 1;
-    const size_t tb = align_up((size_t)n + 16, 256), ab = align_up(N1 * 4, 256);
-    size_t wb = BWT_WORK_BYTES;
-    if (!SA) { const size_t bb = (size_t)carve(nullptr, n).bytes; wb = bb > wb ? bb : wb; }
-    DevBlock blk;
-    hipStream_t st = nullptr;
-    int32_t rc = pool().stream(cur, &st);
-    if (rc != SA_AMD_OK) return rc;
-    rc = pool().acquire(cur, wb + 2 * tb + ab, &blk);
-    if (rc != SA_AMD_OK) { pool().release_stream(cur, st); return rc; }
-    void *dW = blk.p;                                               // (first: the block's start is 256-byte aligned)
-    uint8_t *dT = (uint8_t *)blk.p + wb;
-    uint32_t *dSA = (uint32_t *)((char *)dT + tb);
-    uint8_t *dB = (uint8_t *)dSA + ab;
-    if (n > 0) rc = hip_status(hipMemcpyAsync(dT, T, (size_t)n, hipMemcpyHostToDevice, st));
-    if (rc == SA_AMD_OK) {
-        if (!SA) rc = build_device(dT, dSA, n, dW, (int64_t)wb, st, nullptr);
-        else rc = hip_status(hipMemcpyAsync(dSA, SA, N1 * 4, hipMemcpyHostToDevice, st));
-    }
-    if (rc == SA_AMD_OK) rc = bwt_device(dT, dSA, n, dB, primary_out, dW, (int64_t)wb, st);
-    if (rc == SA_AMD_OK && n > 0) rc = hip_status(hipMemcpyAsync(B, dB, (size_t)n, hipMemcpyDeviceToHost, st));
-    const int32_t rs = hip_status(hipStreamSynchronize(st));       // (also drains the stream after a failure)
-    if (rc == SA_AMD_OK) rc = rs;
-    pool().release(blk);
-    pool().release_stream(cur, st);
-    return rc;
+    PooledScope sc(pick_device(), true);
+    const Inputs in = upload_inputs(sc, T, n, SA, BWT_WORK_BYTES, align_up((size_t)n + 16, 256));
+    return bwt_resident(sc, in, n, B, primary_out);
 }
 
 // ---------------------------------------------------------------- inverse ----
@@ -239,27 +221,15 @@ static int unbwt_host(const uint8_t *B, int32_t n, int32_t primary, uint8_t *T_o
     if (n < 0 || (n > 0 && (!B || !T_out))) return SA_AMD_EINVAL;
     if (n == 0 ? primary != 0 : (primary < 1 || primary > n)) return SA_AMD_EINVAL;
     if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
-    DeviceGuard guard(pick_device());
-    if (guard.rc != SA_AMD_OK) return guard.rc;
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
     const size_t tb = align_up((size_t)n + 16, 256), wb = unbwt_layout(n).bytes;
-    DevBlock blk;
-    hipStream_t st = nullptr;
-    int32_t rc = pool().stream(cur, &st);
-    if (rc != SA_AMD_OK) return rc;
-    rc = pool().acquire(cur, wb + 2 * tb, &blk);
-    if (rc != SA_AMD_OK) { pool().release_stream(cur, st); return rc; }
-    void *dW = blk.p;
-    uint8_t *dB = (uint8_t *)blk.p + wb, *dT = dB + tb;
-    if (n > 0) rc = hip_status(hipMemcpyAsync(dB, B, (size_t)n, hipMemcpyHostToDevice, st));
-    if (rc == SA_AMD_OK) rc = unbwt_device(dB, n, primary, dT, dW, (int64_t)wb, st);
-    if (rc == SA_AMD_OK && n > 0) rc = hip_status(hipMemcpyAsync(T_out, dT, (size_t)n, hipMemcpyDeviceToHost, st));
-    const int32_t rs = hip_status(hipStreamSynchronize(st));       // (also drains the stream after a failure)
-    if (rc == SA_AMD_OK) rc = rs;
-    pool().release(blk);
-    pool().release_stream(cur, st);
-    return rc;
+    PooledScope sc(pick_device(), true);
+    sc.acquire(wb + 2 * tb);
+    void *dW = sc.take(wb);
+    uint8_t *dB = (uint8_t *)sc.take(tb), *dT = (uint8_t *)sc.take(tb);
+    if (sc.rc == SA_AMD_OK && n > 0) sc.rc = hip_status(hipMemcpyAsync(dB, B, (size_t)n, hipMemcpyHostToDevice, sc.st));
+    if (sc.rc == SA_AMD_OK) sc.rc = unbwt_device(dB, n, primary, dT, dW, (int64_t)wb, sc.st);
+    if (n > 0) sc.down(T_out, dT, (size_t)n);
+    return sc.finish();
 }
 
 }  // namespace sa

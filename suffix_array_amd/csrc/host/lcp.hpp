@@ -3,6 +3,7 @@
 #pragma once
 #include "pipeline.hpp"
 #include "host_path.hpp"
+#include "scope.hpp"
 #include "../kernels/lcp.hpp"
 
 namespace sa {
@@ -195,41 +196,19 @@ static int lcp_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, uint3
 }
 
 // host buffers: the text and the suffix array go up (with_build: the array is built on the device instead and comes back
-// together with the LCP array), the LCP array comes back.  Device block and stream from the process-wide pool.
+// together with the LCP array), the LCP array comes back.
 static int lcp_host(const uint8_t *T, int32_t n, uint32_t *SA, uint32_t *LCP, bool with_build)
 {
     if (n < 0 || !SA || !LCP || (n > 0 && !T)) return SA_AMD_EINVAL;
     if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
-    DeviceGuard guard(pick_device());
-    if (guard.rc != SA_AMD_OK) return guard.rc;
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
     const size_t N1 = (size_t)n + 1;
-    const size_t tb = align_up((size_t)n + 16, 256), ab = align_up(N1 * 4, 256);
-    size_t wb = lcp_layout(n).bytes;
-    if (with_build) { const size_t bb = (size_t)carve(nullptr, n).bytes; wb = bb > wb ? bb : wb; }
-    DevBlock blk;
-    hipStream_t st = nullptr;
-    int32_t rc = pool().stream(cur, &st);
-    if (rc != SA_AMD_OK) return rc;
-    rc = pool().acquire(cur, wb + tb + 2 * ab, &blk);
-    if (rc != SA_AMD_OK) { pool().release_stream(cur, st); return rc; }
-    void *dW = blk.p;                                               // (first: the block's start is 256-byte aligned)
-    uint8_t *dT = (uint8_t *)blk.p + wb;
-    uint32_t *dSA = (uint32_t *)((char *)dT + tb), *dL = (uint32_t *)((char *)dSA + ab);
-    if (n > 0) rc = hip_status(hipMemcpyAsync(dT, T, (size_t)n, hipMemcpyHostToDevice, st));
-    if (rc == SA_AMD_OK) {
-        if (with_build) rc = build_device(dT, dSA, n, dW, (int64_t)wb, st, nullptr);
-        else rc = hip_status(hipMemcpyAsync(dSA, SA, N1 * 4, hipMemcpyHostToDevice, st));
-    }
-    if (rc == SA_AMD_OK) rc = lcp_device(dT, dSA, n, dL, dW, (int64_t)wb, st);
-    if (rc == SA_AMD_OK && with_build) rc = hip_status(hipMemcpyAsync(SA, dSA, N1 * 4, hipMemcpyDeviceToHost, st));
-    if (rc == SA_AMD_OK) rc = hip_status(hipMemcpyAsync(LCP, dL, N1 * 4, hipMemcpyDeviceToHost, st));
-    const int32_t rs = hip_status(hipStreamSynchronize(st));       // (also drains the stream after a failure)
-    if (rc == SA_AMD_OK) rc = rs;
-    pool().release(blk);
-    pool().release_stream(cur, st);
-    return rc;
+    PooledScope sc(pick_device(), true);
+    const Inputs in = upload_inputs(sc, T, n, with_build ? nullptr : SA, lcp_layout(n).bytes, align_up(N1 * 4, 256));
+    uint32_t *dL = (uint32_t *)sc.take(N1 * 4);
+    if (sc.rc == SA_AMD_OK) sc.rc = lcp_device(in.dT, in.dSA, n, dL, in.dW, (int64_t)in.wb, sc.st);
+    if (with_build) sc.down(SA, in.dSA, N1 * 4);
+    sc.down(LCP, dL, N1 * 4);
+    return sc.finish();
 }
 
 }  // namespace sa

@@ -218,54 +218,34 @@ static int lz_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, bool p
     return SA_AMD_OK;
 }
 
-// host buffers: the text goes up; the array is built on the device and stays there (SA == nullptr) or the caller's goes up; LPF
-// and SRC (4 n bytes each) or the first `capacity` phrases (8 bytes each) come back.  Device block and stream from the pool.
+// Either form over a resident text and array, the outputs in slabs of the scope's block: LPF and SRC (4 n bytes each, either
+// may be null: then the device call gets null and nothing comes back) or the first rows.cap phrases come back.  in.dW: the
+// scope's first slab, at least lz_layout(n).bytes.
+static int lz_resident(PooledScope &sc, const Inputs &in, int32_t n, bool parse, uint32_t *LPF, uint32_t *SRC, uint32_t *phrases, CappedRows &rows,
+                       int64_t *count_out)
+{
+    const size_t ab = ((size_t)n + 1) * 4;
+    uint32_t *dOut = (uint32_t *)sc.take(parse ? rows.bytes() : ab), *dOut2 = parse ? nullptr : (uint32_t *)sc.take(ab);
+    if (sc.rc == SA_AMD_OK)
+        sc.rc = lz_device(in.dT, in.dSA, n, parse, LPF ? dOut : nullptr, SRC ? dOut2 : nullptr, dOut, rows.cap, &rows.count, in.dW, (int64_t)in.wb, sc.st);
+    if (parse) return rows.finish(sc, phrases, dOut, count_out);
+    if (n > 0 && LPF) sc.down(LPF, dOut, (size_t)n * 4);
+    if (n > 0 && SRC) sc.down(SRC, dOut2, (size_t)n * 4);
+    return sc.finish();
+}
+
+// host buffers: the text goes up; the array is built on the device and stays there (SA == nullptr) or the caller's goes up
 static int lz_host(const uint8_t *T, int32_t n, const uint32_t *SA, bool parse, uint32_t *LPF, uint32_t *SRC, uint32_t *phrases, int64_t capacity,
                    int64_t *count_out)
 {
     if (n < 0 || (n > 0 && !T)) return SA_AMD_EINVAL;
     if (parse && (capacity < 0 || !count_out || (capacity > 0 && !phrases))) return SA_AMD_EINVAL;
     if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
-    DeviceGuard guard(pick_device());
-    if (guard.rc != SA_AMD_OK) return guard.rc;
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
-    const size_t N1 = (size_t)n + 1;
-    const size_t tb = align_up((size_t)n + 16, 256), ab = align_up(N1 * 4, 256);
-    size_t wb = lz_layout(n).bytes;
-    if (!SA) { const size_t bb = (size_t)carve(nullptr, n).bytes; wb = bb > wb ? bb : wb; }
-    const int64_t cap = parse ? (capacity < n ? capacity : n) : 0;      // no more phrases than bytes, whatever the caller's capacity
-    const size_t ob = parse ? align_up((size_t)cap * 8 + 8, 256) : 2 * ab;
-    DevBlock blk;
-    hipStream_t st = nullptr;
-    int32_t rc = pool().stream(cur, &st);
-    if (rc != SA_AMD_OK) return rc;
-    rc = pool().acquire(cur, wb + tb + ab + ob, &blk);
-    if (rc != SA_AMD_OK) { pool().release_stream(cur, st); return rc; }
-    void *dW = blk.p;                                               // (first: the block's start is 256-byte aligned)
-    uint8_t *dT = (uint8_t *)blk.p + wb;
-    uint32_t *dSA = (uint32_t *)((char *)dT + tb), *dOut = (uint32_t *)((char *)dSA + ab), *dOut2 = (uint32_t *)((char *)dOut + ab);
-    int64_t count = 0;
-    if (n > 0) rc = hip_status(hipMemcpyAsync(dT, T, (size_t)n, hipMemcpyHostToDevice, st));
-    if (rc == SA_AMD_OK) {
-        if (!SA) rc = build_device(dT, dSA, n, dW, (int64_t)wb, st, nullptr);
-        else rc = hip_status(hipMemcpyAsync(dSA, SA, N1 * 4, hipMemcpyHostToDevice, st));
-    }
-    if (rc == SA_AMD_OK) rc = lz_device(dT, dSA, n, parse, LPF ? dOut : nullptr, SRC ? dOut2 : nullptr, dOut, cap, &count, dW, (int64_t)wb, st);
-    if (rc == SA_AMD_OK && !parse && n > 0) {
-        if (LPF) rc = hip_status(hipMemcpyAsync(LPF, dOut, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        if (rc == SA_AMD_OK && SRC) rc = hip_status(hipMemcpyAsync(SRC, dOut2, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (rc == SA_AMD_OK && parse) {
-        const int64_t wr = count < cap ? count : cap;
-        if (wr > 0) rc = hip_status(hipMemcpyAsync(phrases, dOut, (size_t)wr * 8, hipMemcpyDeviceToHost, st));
-    }
-    const int32_t rsy = hip_status(hipStreamSynchronize(st));      // (also drains the stream after a failure)
-    if (rc == SA_AMD_OK) rc = rsy;
-    if (rc == SA_AMD_OK && parse) *count_out = count;
-    pool().release(blk);
-    pool().release_stream(cur, st);
-    return rc;
+    CappedRows rows;
+    if (parse) rows = CappedRows(capacity, n);                      // no more phrases than bytes
+    PooledScope sc(pick_device(), true);
+    const Inputs in = upload_inputs(sc, T, n, SA, lz_layout(n).bytes, parse ? align_up(rows.bytes(), 256) : 2 * align_up(((size_t)n + 1) * 4, 256));
+    return lz_resident(sc, in, n, parse, LPF, SRC, phrases, rows, count_out);
 }
 
 }  // namespace sa

@@ -127,46 +127,28 @@ static int match_device(const MatchIndex &ix, const uint8_t *dQ, int32_t m32, in
 }
 
 // host buffers: the query goes up, ML / POS (4 m bytes each, either may be nullptr) or the first `capacity` spans come back.
-// Device block and stream from the process-wide pool; the index's device is current.
+// The index's device is current (the caller's guard).
 static int match_host(const MatchIndex &ix, const uint8_t *Q, int32_t m, int32_t C, bool spans, uint32_t *ML, uint32_t *POS, uint32_t *out_spans,
                       int64_t capacity, int64_t *count_out)
 {
     if (m < 0 || C < 1 || (m > 0 && !Q)) return SA_AMD_EINVAL;
     if (spans && (capacity < 0 || !count_out || (capacity > 0 && !out_spans))) return SA_AMD_EINVAL;
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
     const size_t wb = match_layout(m).bytes, qb = align_up((size_t)m + 16, 256), ab = align_up(((size_t)m + 1) * 4, 256);
-    int64_t cap = 0;
-    if (spans) { cap = repeat_spans_bound(m, C); cap = capacity < cap ? capacity : cap; }
-    const size_t ob = spans ? align_up((size_t)cap * 8 + 8, 256) : 2 * ab;
-    DevBlock blk;
-    hipStream_t st = nullptr;
-    int32_t rc = pool().stream(cur, &st);
-    if (rc != SA_AMD_OK) return rc;
-    rc = pool().acquire(cur, wb + qb + ob, &blk);
-    if (rc != SA_AMD_OK) { pool().release_stream(cur, st); return rc; }
-    void *dW = blk.p;
-    uint8_t *dQ = (uint8_t *)blk.p + wb;
-    uint32_t *dOut = (uint32_t *)((char *)dQ + qb), *dOut2 = (uint32_t *)((char *)dOut + ab);
-    int64_t count = 0;
-    if (m > 0) rc = hip_status(hipMemcpyAsync(dQ, Q, (size_t)m, hipMemcpyHostToDevice, st));
-    if (rc == SA_AMD_OK)
-        rc = match_device(ix, dQ, m, C, spans, !spans && ML ? dOut : nullptr, !spans && POS ? dOut2 : nullptr, spans && cap > 0 ? dOut : nullptr, cap, &count,
-                          dW, (int64_t)wb, st);
-    if (rc == SA_AMD_OK && !spans && m > 0) {
-        if (ML) rc = hip_status(hipMemcpyAsync(ML, dOut, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-        if (rc == SA_AMD_OK && POS) rc = hip_status(hipMemcpyAsync(POS, dOut2, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (rc == SA_AMD_OK && spans) {
-        const int64_t wr = count < cap ? count : cap;
-        if (wr > 0) rc = hip_status(hipMemcpyAsync(out_spans, dOut, (size_t)wr * 8, hipMemcpyDeviceToHost, st));
-    }
-    const int32_t rsy = hip_status(hipStreamSynchronize(st));      // (also drains the stream after a failure)
-    if (rc == SA_AMD_OK) rc = rsy;
-    if (rc == SA_AMD_OK && spans) *count_out = count;
-    pool().release(blk);
-    pool().release_stream(cur, st);
-    return rc;
+    CappedRows rows;
+    if (spans) rows = CappedRows(capacity, repeat_spans_bound(m, C));
+    PooledScope sc(-1, true);
+    sc.acquire(wb + qb + (spans ? align_up(rows.bytes(), 256) : 2 * ab));
+    void *dW = sc.take(wb);
+    uint8_t *dQ = (uint8_t *)sc.take(qb);
+    uint32_t *dOut = (uint32_t *)sc.take(spans ? rows.bytes() : ab), *dOut2 = spans ? nullptr : (uint32_t *)sc.take(ab);
+    if (sc.rc == SA_AMD_OK && m > 0) sc.rc = hip_status(hipMemcpyAsync(dQ, Q, (size_t)m, hipMemcpyHostToDevice, sc.st));
+    if (sc.rc == SA_AMD_OK)
+        sc.rc = match_device(ix, dQ, m, C, spans, !spans && ML ? dOut : nullptr, !spans && POS ? dOut2 : nullptr, spans && rows.cap > 0 ? dOut : nullptr,
+                             rows.cap, &rows.count, dW, (int64_t)wb, sc.st);
+    if (spans) return rows.finish(sc, out_spans, dOut, count_out);
+    if (m > 0 && ML) sc.down(ML, dOut, (size_t)m * 4);
+    if (m > 0 && POS) sc.down(POS, dOut2, (size_t)m * 4);
+    return sc.finish();
 }
 
 }  // namespace sa

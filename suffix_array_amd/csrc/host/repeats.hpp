@@ -156,8 +156,20 @@ static int repeats_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, b
     return SA_AMD_OK;
 }
 
-// host buffers: the text goes up; the array is built on the device and stays there (SA == nullptr) or the caller's goes up; LR
-// (4 n bytes) or the first `capacity` spans (8 bytes each) come back.  Device block and stream from the process-wide pool.
+// Either form over a resident text and array, the output in a slab of the scope's block: LR (4 n bytes) or the first rows.cap
+// spans come back.  in.dW: the scope's first slab, at least rep_layout(n).bytes.
+static int repeats_resident(PooledScope &sc, const Inputs &in, int32_t n, bool spans, uint32_t *LR, int32_t min_len, int32_t mode, uint32_t *out_spans,
+                            CappedRows &rows, int64_t *count_out)
+{
+    uint32_t *dOut = (uint32_t *)sc.take(spans ? rows.bytes() : ((size_t)n + 1) * 4);
+    if (sc.rc == SA_AMD_OK)
+        sc.rc = repeats_device(in.dT, in.dSA, n, spans, dOut, min_len, mode, dOut, rows.cap, &rows.count, in.dW, (int64_t)in.wb, sc.st);
+    if (spans) return rows.finish(sc, out_spans, dOut, count_out);
+    if (n > 0) sc.down(LR, dOut, (size_t)n * 4);
+    return sc.finish();
+}
+
+// host buffers: the text goes up; the array is built on the device and stays there (SA == nullptr) or the caller's goes up
 static int repeats_host(const uint8_t *T, int32_t n, const uint32_t *SA, bool spans, uint32_t *LR, int32_t min_len, int32_t mode, uint32_t *out_spans,
                         int64_t capacity, int64_t *count_out)
 {
@@ -165,45 +177,11 @@ static int repeats_host(const uint8_t *T, int32_t n, const uint32_t *SA, bool sp
     if (spans && (min_len < 1 || (mode != REP_MODE_ALL && mode != REP_MODE_KEEP_FIRST) || capacity < 0 || !count_out ||
                   (capacity > 0 && !out_spans))) return SA_AMD_EINVAL;
     if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
-    DeviceGuard guard(pick_device());
-    if (guard.rc != SA_AMD_OK) return guard.rc;
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
-    const size_t N1 = (size_t)n + 1;
-    const size_t tb = align_up((size_t)n + 16, 256), ab = align_up(N1 * 4, 256);
-    size_t wb = rep_layout(n).bytes;
-    if (!SA) { const size_t bb = (size_t)carve(nullptr, n).bytes; wb = bb > wb ? bb : wb; }
-    // no more spans than the bound can exist, whatever the caller's capacity
-    int64_t cap = 0;
-    if (spans) { cap = repeat_spans_bound(n, min_len); cap = capacity < cap ? capacity : cap; }
-    const size_t ob = spans ? align_up((size_t)cap * 8 + 8, 256) : ab;
-    DevBlock blk;
-    hipStream_t st = nullptr;
-    int32_t rc = pool().stream(cur, &st);
-    if (rc != SA_AMD_OK) return rc;
-    rc = pool().acquire(cur, wb + tb + ab + ob, &blk);
-    if (rc != SA_AMD_OK) { pool().release_stream(cur, st); return rc; }
-    void *dW = blk.p;                                               // (first: the block's start is 256-byte aligned)
-    uint8_t *dT = (uint8_t *)blk.p + wb;
-    uint32_t *dSA = (uint32_t *)((char *)dT + tb), *dOut = (uint32_t *)((char *)dSA + ab);
-    int64_t count = 0;
-    if (n > 0) rc = hip_status(hipMemcpyAsync(dT, T, (size_t)n, hipMemcpyHostToDevice, st));
-    if (rc == SA_AMD_OK) {
-        if (!SA) rc = build_device(dT, dSA, n, dW, (int64_t)wb, st, nullptr);
-        else rc = hip_status(hipMemcpyAsync(dSA, SA, N1 * 4, hipMemcpyHostToDevice, st));
-    }
-    if (rc == SA_AMD_OK) rc = repeats_device(dT, dSA, n, spans, dOut, min_len, mode, dOut, cap, &count, dW, (int64_t)wb, st);
-    if (rc == SA_AMD_OK && !spans && n > 0) rc = hip_status(hipMemcpyAsync(LR, dOut, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (rc == SA_AMD_OK && spans) {
-        const int64_t wr = count < cap ? count : cap;
-        if (wr > 0) rc = hip_status(hipMemcpyAsync(out_spans, dOut, (size_t)wr * 8, hipMemcpyDeviceToHost, st));
-    }
-    const int32_t rsy = hip_status(hipStreamSynchronize(st));      // (also drains the stream after a failure)
-    if (rc == SA_AMD_OK) rc = rsy;
-    if (rc == SA_AMD_OK && spans) *count_out = count;
-    pool().release(blk);
-    pool().release_stream(cur, st);
-    return rc;
+    CappedRows rows;
+    if (spans) rows = CappedRows(capacity, repeat_spans_bound(n, min_len));
+    PooledScope sc(pick_device(), true);
+    const Inputs in = upload_inputs(sc, T, n, SA, rep_layout(n).bytes, align_up(spans ? rows.bytes() : ((size_t)n + 1) * 4, 256));
+    return repeats_resident(sc, in, n, spans, LR, min_len, mode, out_spans, rows, count_out);
 }
 
 }  // namespace sa

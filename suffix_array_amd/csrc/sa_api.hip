@@ -257,33 +257,21 @@ SA_EXPORT int32_t sa_amd_check_integrity_device(const uint8_t *dT, int32_t n, co
 }
 
 // enable_buckets on host buffers (reference src/sa.rs:89-119): the text goes up, 257 KiB come back; nothing else is needed --
-// the reference builds the table from the text alone.  Device block and stream come from the process-wide pool.
+// the reference builds the table from the text alone.
 static int32_t bucket_table_host(const uint8_t *T, int32_t n, uint32_t *bkt)
 {
     using namespace sa;
     if (n < 0 || !bkt || (n > 0 && !T)) return SA_AMD_EINVAL;
     if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
-    DeviceGuard guard(pick_device());
-    if (guard.rc != SA_AMD_OK) return guard.rc;
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
     const size_t tb = align_up((size_t)n + 16, 256);
-    DevBlock blk;
-    hipStream_t st = nullptr;
-    int32_t rc = pool().stream(cur, &st);
-    if (rc != SA_AMD_OK) return rc;
-    rc = pool().acquire(cur, tb + (size_t)BKT_LEN * 4, &blk);
-    if (rc != SA_AMD_OK) { pool().release_stream(cur, st); return rc; }
-    uint8_t *dT = (uint8_t *)blk.p;
-    uint32_t *dB = (uint32_t *)((char *)blk.p + tb);
-    if (n > 0) rc = hip_status(hipMemcpyAsync(dT, T, (size_t)n, hipMemcpyHostToDevice, st));
-    if (rc == SA_AMD_OK) rc = sa_amd_bucket_table_device(dT, nullptr, n, dB, st);
-    if (rc == SA_AMD_OK) rc = hip_status(hipMemcpyAsync(bkt, dB, (size_t)BKT_LEN * 4, hipMemcpyDeviceToHost, st));
-    const int32_t rs = hip_status(hipStreamSynchronize(st));       // (also drains the stream after a failure)
-    if (rc == SA_AMD_OK) rc = rs;
-    pool().release(blk);
-    pool().release_stream(cur, st);
-    return rc;
+    PooledScope sc(pick_device(), true);
+    sc.acquire(tb + (size_t)BKT_LEN * 4);
+    uint8_t *dT = (uint8_t *)sc.take(tb);
+    uint32_t *dB = (uint32_t *)sc.take((size_t)BKT_LEN * 4);
+    if (sc.rc == SA_AMD_OK && n > 0) sc.rc = hip_status(hipMemcpyAsync(dT, T, (size_t)n, hipMemcpyHostToDevice, sc.st));
+    if (sc.rc == SA_AMD_OK) sc.rc = sa_amd_bucket_table_device(dT, nullptr, n, dB, sc.st);
+    sc.down(bkt, dB, (size_t)BKT_LEN * 4);
+    return sc.finish();
 }
 
 // host buffers; which = 2: integrity check, 3: build SA (into SA, n + 1 entries) then bucket table
@@ -427,20 +415,16 @@ SA_EXPORT int32_t sa_amd_index_check_integrity(const sa_amd_index *ix)
 {
     SA_ABI_GUARD_BEGIN
     if (!ix) return SA_AMD_EINVAL;
-    sa::DeviceGuard guard(ix->device);
-    if (guard.rc != SA_AMD_OK) return guard.rc;
     // the work block of the streaming form comes from the process-wide pool (a 5.5 GB hipMalloc / hipFree per call would
     // cost more than the check); the small block if that much is not to be had
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return SA_AMD_EHIP;
-    sa::DevBlock blk;
+    sa::PooledScope sc(ix->device, false);
     int64_t wb = sa_amd_check_integrity_work_bytes(ix->n);
-    int32_t rc = sa::pool().acquire(cur, (size_t)wb, &blk);
-    if (rc == SA_AMD_ENOMEM) { wb = ((int64_t)ix->n + 1) * 4 + 256; rc = sa::pool().acquire(cur, (size_t)wb, &blk); }
-    if (rc) return rc;
-    rc = sa_amd_check_integrity_device(ix->dT, ix->n, ix->dSA, blk.p, wb, nullptr);
-    sa::pool().release(blk);
-    return rc;
+    if (sc.acquire((size_t)wb) == SA_AMD_ENOMEM) { wb = ((int64_t)ix->n + 1) * 4 + 256; sc.acquire_smaller((size_t)wb); }
+    if (sc.rc) return sc.rc;
+    const int32_t ok = sa_amd_check_integrity_device(ix->dT, ix->n, ix->dSA, sc.take((size_t)wb), wb, nullptr);      // 1 / 0, or a code
+    if (ok < 0) sc.rc = ok;
+    (void)sc.finish();
+    return ok;
     SA_ABI_GUARD_END(0)
 }
 
@@ -546,19 +530,13 @@ SA_EXPORT int32_t sa_amd_index_lcp(const sa_amd_index *ix, uint32_t *LCP)
 {
     SA_ABI_GUARD_BEGIN
     if (!ix || !LCP) return SA_AMD_EINVAL;
-    sa::DeviceGuard guard(ix->device);
-    if (guard.rc != SA_AMD_OK) return guard.rc;
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return SA_AMD_EHIP;
-    const size_t wb = sa::lcp_layout(ix->n).bytes, lb = ((size_t)ix->n + 1) * 4;
-    sa::DevBlock blk;
-    int32_t rc = sa::pool().acquire(cur, wb + lb, &blk);
-    if (rc) return rc;
-    uint32_t *dL = (uint32_t *)((char *)blk.p + wb);
-    rc = sa::lcp_device(ix->dT, ix->dSA, ix->n, dL, blk.p, (int64_t)wb, nullptr);
-    if (rc == SA_AMD_OK) rc = sa::hip_status(hipMemcpy(LCP, dL, lb, hipMemcpyDeviceToHost));
-    sa::pool().release(blk);
-    return rc;
+    const size_t lb = ((size_t)ix->n + 1) * 4;
+    sa::PooledScope sc(ix->device, false);
+    const sa::Inputs in = sa::resident_inputs(sc, ix->dT, ix->dSA, sa::lcp_layout(ix->n).bytes, lb);
+    uint32_t *dL = (uint32_t *)sc.take(lb);
+    if (sc.rc == SA_AMD_OK) sc.rc = sa::lcp_device(in.dT, in.dSA, ix->n, dL, in.dW, (int64_t)in.wb, sc.st);
+    sc.down(LCP, dL, lb);
+    return sc.finish();
     SA_ABI_GUARD_END(0)
 }
 
@@ -567,24 +545,20 @@ SA_EXPORT int32_t sa_amd_index_enable_lcp(sa_amd_index *ix)
     SA_ABI_GUARD_BEGIN
     if (!ix) return SA_AMD_EINVAL;
     if (ix->dPair) return SA_AMD_OK;
-    sa::DeviceGuard guard(ix->device);
-    if (guard.rc != SA_AMD_OK) return guard.rc;
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return SA_AMD_EHIP;
-    uint64_t *dPair = nullptr;
-    if (hipMalloc((void **)&dPair, ((size_t)ix->n + 1) * 8) != hipSuccess) { (void)hipGetLastError(); return SA_AMD_ENOMEM; }
+    sa::PooledScope sc(ix->device, false);
+    if (sc.rc) return sc.rc;
+    sa::DevBuf pair;                                             // the table outlives the call: its own allocation, not the pool's
+    if (pair.alloc(((size_t)ix->n + 1) * 8) != SA_AMD_OK) { (void)hipGetLastError(); return SA_AMD_ENOMEM; }      // (the refused allocation's error is cleared, as everywhere)
     // LCP array and its work block from the pool, as sa_amd_index_lcp; the tile minima of the table build behind them
-    const size_t wb = sa::lcp_layout(ix->n).bytes, lb = sa::align_up(((size_t)ix->n + 1) * 4, 256);
-    sa::DevBlock blk;
-    int32_t rc = sa::pool().acquire(cur, wb + lb + sa::esa_mins_elems(ix->n) * 4, &blk);
-    if (rc) { (void)hipFree(dPair); return rc; }
-    uint32_t *dL = (uint32_t *)((char *)blk.p + wb);
-    rc = sa::lcp_device(ix->dT, ix->dSA, ix->n, dL, blk.p, (int64_t)wb, nullptr);
-    if (rc == SA_AMD_OK) rc = sa::esa_build(dL, ix->n, dPair, (uint32_t *)((char *)dL + lb), nullptr);
-    if (rc == SA_AMD_OK) rc = sa::hip_status(hipDeviceSynchronize());
-    sa::pool().release(blk);
-    if (rc != SA_AMD_OK) { (void)hipFree(dPair); return rc; }
-    ix->dPair = dPair;                                           // kept: later searches take the LCP route
+    const size_t lb = sa::align_up(((size_t)ix->n + 1) * 4, 256), mb = sa::esa_mins_elems(ix->n) * 4;
+    const sa::Inputs in = sa::resident_inputs(sc, ix->dT, ix->dSA, sa::lcp_layout(ix->n).bytes, lb + mb);
+    uint32_t *dL = (uint32_t *)sc.take(lb), *dMins = (uint32_t *)sc.take(mb);
+    if (sc.rc == SA_AMD_OK) sc.rc = sa::lcp_device(in.dT, in.dSA, ix->n, dL, in.dW, (int64_t)in.wb, sc.st);
+    if (sc.rc == SA_AMD_OK) sc.rc = sa::esa_build(dL, ix->n, pair.as<uint64_t>(), dMins, sc.st);
+    if (sc.rc == SA_AMD_OK) sc.rc = sa::hip_status(hipDeviceSynchronize());      // (the route's own wait: finish() adds none on success)
+    if (sc.finish() != SA_AMD_OK) return sc.rc;
+    ix->dPair = pair.as<uint64_t>();                             // kept: later searches take the LCP route
+    pair.p = nullptr;
     return SA_AMD_OK;
     SA_ABI_GUARD_END(0)
 }
@@ -634,19 +608,9 @@ SA_EXPORT int32_t sa_amd_index_bwt(const sa_amd_index *ix, uint8_t *BWT, int32_t
 {
     SA_ABI_GUARD_BEGIN
     if (!ix || !primary_out || (ix->n > 0 && !BWT)) return SA_AMD_EINVAL;
-    sa::DeviceGuard guard(ix->device);
-    if (guard.rc != SA_AMD_OK) return guard.rc;
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return SA_AMD_EHIP;
-    const size_t wb = sa::BWT_WORK_BYTES;
-    sa::DevBlock blk;
-    int32_t rc = sa::pool().acquire(cur, wb + (size_t)ix->n + 16, &blk);
-    if (rc) return rc;
-    uint8_t *dB = (uint8_t *)blk.p + wb;
-    rc = sa::bwt_device(ix->dT, ix->dSA, ix->n, dB, primary_out, blk.p, (int64_t)wb, nullptr);
-    if (rc == SA_AMD_OK && ix->n > 0) rc = sa::hip_status(hipMemcpy(BWT, dB, (size_t)ix->n, hipMemcpyDeviceToHost));
-    sa::pool().release(blk);
-    return rc;
+    sa::PooledScope sc(ix->device, false);
+    const sa::Inputs in = sa::resident_inputs(sc, ix->dT, ix->dSA, sa::BWT_WORK_BYTES, (size_t)ix->n + 16);
+    return sa::bwt_resident(sc, in, ix->n, BWT, primary_out);
     SA_ABI_GUARD_END(0)
 }
 
@@ -721,7 +685,7 @@ SA_EXPORT int32_t sa_amd_repeat_spans(const uint8_t *T, int32_t n, const uint32_
     SA_ABI_GUARD_END(0)
 }
 
-// the index's resident text and array: the work block, and the output behind it, from the pool
+// the index's resident text and array: only the work block and the output come from the pool; on the null stream
 static int32_t index_repeats(const sa_amd_index *ix, bool spans, uint32_t *LR, int32_t min_len, int32_t mode, uint32_t *out_spans,
                              int64_t capacity, int64_t *count_out)
 {
@@ -729,27 +693,11 @@ static int32_t index_repeats(const sa_amd_index *ix, bool spans, uint32_t *LR, i
     if (spans ? (min_len < 1 || (mode != SA_AMD_REPEATS_ALL && mode != SA_AMD_REPEATS_KEEP_FIRST) || capacity < 0 || !count_out ||
                  (capacity > 0 && !out_spans))
               : (ix->n > 0 && !LR)) return SA_AMD_EINVAL;
-    sa::DeviceGuard guard(ix->device);
-    if (guard.rc != SA_AMD_OK) return guard.rc;
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return SA_AMD_EHIP;
-    int64_t cap = 0;
-    if (spans) { cap = sa::repeat_spans_bound(ix->n, min_len); cap = capacity < cap ? capacity : cap; }
-    const size_t wb = sa::rep_layout(ix->n).bytes, ob = spans ? (size_t)cap * 8 + 8 : ((size_t)ix->n + 1) * 4;
-    sa::DevBlock blk;
-    int32_t rc = sa::pool().acquire(cur, wb + ob, &blk);
-    if (rc) return rc;
-    uint32_t *dOut = (uint32_t *)((char *)blk.p + wb);
-    int64_t count = 0;
-    rc = sa::repeats_device(ix->dT, ix->dSA, ix->n, spans, dOut, min_len, mode, dOut, cap, &count, blk.p, (int64_t)wb, nullptr);
-    if (rc == SA_AMD_OK && !spans && ix->n > 0) rc = sa::hip_status(hipMemcpy(LR, dOut, (size_t)ix->n * 4, hipMemcpyDeviceToHost));
-    if (rc == SA_AMD_OK && spans) {
-        const int64_t wr = count < cap ? count : cap;
-        if (wr > 0) rc = sa::hip_status(hipMemcpy(out_spans, dOut, (size_t)wr * 8, hipMemcpyDeviceToHost));
-        if (rc == SA_AMD_OK) *count_out = count;
-    }
-    sa::pool().release(blk);
-    return rc;
+    sa::CappedRows rows;
+    if (spans) rows = sa::CappedRows(capacity, sa::repeat_spans_bound(ix->n, min_len));
+    sa::PooledScope sc(ix->device, false);
+    const sa::Inputs in = sa::resident_inputs(sc, ix->dT, ix->dSA, sa::rep_layout(ix->n).bytes, spans ? rows.bytes() : ((size_t)ix->n + 1) * 4);
+    return sa::repeats_resident(sc, in, ix->n, spans, LR, min_len, mode, out_spans, rows, count_out);
 }
 
 SA_EXPORT int32_t sa_amd_index_repeat_lengths(const sa_amd_index *ix, uint32_t *LR)
@@ -812,35 +760,17 @@ SA_EXPORT int32_t sa_amd_lz77(const uint8_t *T, int32_t n, const uint32_t *SA, u
     SA_ABI_GUARD_END(0)
 }
 
-// the index's resident text and array: the work block, and the outputs behind it, from the pool
+// the index's resident text and array: only the work block and the outputs come from the pool; on the null stream
 static int32_t index_lz(const sa_amd_index *ix, bool parse, uint32_t *LPF, uint32_t *SRC, uint32_t *phrases, int64_t capacity, int64_t *count_out)
 {
     if (!ix) return SA_AMD_EINVAL;
     if (parse && (capacity < 0 || !count_out || (capacity > 0 && !phrases))) return SA_AMD_EINVAL;
-    sa::DeviceGuard guard(ix->device);
-    if (guard.rc != SA_AMD_OK) return guard.rc;
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return SA_AMD_EHIP;
-    const int64_t cap = parse ? (capacity < ix->n ? capacity : ix->n) : 0;
-    const size_t ab = sa::align_up(((size_t)ix->n + 1) * 4, 256);
-    const size_t wb = sa::lz_layout(ix->n).bytes, ob = parse ? (size_t)cap * 8 + 8 : 2 * ab;
-    sa::DevBlock blk;
-    int32_t rc = sa::pool().acquire(cur, wb + ob, &blk);
-    if (rc) return rc;
-    uint32_t *dOut = (uint32_t *)((char *)blk.p + wb), *dOut2 = (uint32_t *)((char *)dOut + ab);
-    int64_t count = 0;
-    rc = sa::lz_device(ix->dT, ix->dSA, ix->n, parse, LPF ? dOut : nullptr, SRC ? dOut2 : nullptr, dOut, cap, &count, blk.p, (int64_t)wb, nullptr);
-    if (rc == SA_AMD_OK && !parse && ix->n > 0) {
-        if (LPF) rc = sa::hip_status(hipMemcpy(LPF, dOut, (size_t)ix->n * 4, hipMemcpyDeviceToHost));
-        if (rc == SA_AMD_OK && SRC) rc = sa::hip_status(hipMemcpy(SRC, dOut2, (size_t)ix->n * 4, hipMemcpyDeviceToHost));
-    }
-    if (rc == SA_AMD_OK && parse) {
-        const int64_t wr = count < cap ? count : cap;
-        if (wr > 0) rc = sa::hip_status(hipMemcpy(phrases, dOut, (size_t)wr * 8, hipMemcpyDeviceToHost));
-        if (rc == SA_AMD_OK) *count_out = count;
-    }
-    sa::pool().release(blk);
-    return rc;
+    sa::CappedRows rows;
+    if (parse) rows = sa::CappedRows(capacity, ix->n);
+    sa::PooledScope sc(ix->device, false);
+    const sa::Inputs in = sa::resident_inputs(sc, ix->dT, ix->dSA, sa::lz_layout(ix->n).bytes,
+                                              parse ? rows.bytes() : 2 * sa::align_up(((size_t)ix->n + 1) * 4, 256));
+    return sa::lz_resident(sc, in, ix->n, parse, LPF, SRC, phrases, rows, count_out);
 }
 
 SA_EXPORT int32_t sa_amd_index_lpf(const sa_amd_index *ix, uint32_t *LPF, uint32_t *SRC)
