@@ -94,7 +94,7 @@ struct Tuning {
     int small_max = 8192;            // SA_AMD_SMALL_MAX: texts of up to this many bytes are built by ONE launch of one workgroup (kernels/small.hpp), 0..8192
     bool no_onesweep = false;        // SA_AMD_NO_ONESWEEP: the three-kernel radix pass (histogram, spine, chunk-owned scatter) instead of the single-pass one
     int onesweep_flags = 0;          // SA_AMD_ONESWEEP_FLAGS: scheduling switches of the single-pass scatter (kernels/onesweep.hpp, OnesweepPass::flags), same result
-    int onesweep64_shape = 0;        // SA_AMD_ONESWEEP64_SHAPE / SA_AMD_ONESWEEP32_SHAPE: tile shape of the single-pass scatter (host/pipeline.hpp,
+    int onesweep64_shape = 0;        // SA_AMD_ONESWEEP64_SHAPE / SA_AMD_ONESWEEP32_SHAPE: tile shape of the single-pass scatter (host/sort.hpp,
     int onesweep32_shape = 0;        //   os_shapes64 / os_shapes32; out of range = default)
     bool no_unary_shortcut = false;  // SA_AMD_NO_UNARY_SHORTCUT: a text of one byte value goes through the sort and the rounds like any other (214 ms at 256 MiB instead of 0.3)
     int64_t count_next_min_n = 20000000;            // SA_AMD_COUNT_NEXT_MIN_N: radix sorts of fewer pairs do not count the next digit inside a pass -- all digits in front of the
@@ -113,7 +113,7 @@ struct Tuning {
     bool no_bucket_finish = false;   // SA_AMD_NO_BUCKET_FINISH: the suffixes tied on the top 32 key bits are ordered by k_finish_sorted in a pass of its own, not inside k_bucket_sort
     bool bucket_finish_always = false;   // SA_AMD_BUCKET_FINISH_ALWAYS: ... inside k_bucket_sort even with the 20-pairs-per-thread shapes (measured slower)
     int bucket_bits = 0;             // SA_AMD_BUCKET_BITS: key bits ordered by the two global passes in front of the bucket sort (0 = by text size, 16, 18)
-    int bucket_shape = -1;           // SA_AMD_BUCKET_SHAPE: workgroup shape of that sort tried first (host/pipeline.hpp, bk_shapes; -1 = the smallest default one that holds the largest bucket)
+    int bucket_shape = -1;           // SA_AMD_BUCKET_SHAPE: workgroup shape of that sort tried first (host/sort.hpp, bk_shapes; -1 = the smallest default one that holds the largest bucket)
 #ifdef SA_AMD_DIAG
     // the sample sort of the 64-bit stage (kernels/sample_sort.hpp): a measured dead end of round 4 (profiles/r04_sample_sort_64.txt),
     // kept in the diagnostic library with its tests -- correct, not faster than the eight LSD passes

@@ -1,7 +1,7 @@
 """GPU suite, top of the size range (-m gpu): texts between 2^30 and MAX_LENGTH = 2^31 - 1 through the host-pointer ABI.
 
 Above 2^30 the indices take 31 bits: the first pass of the 32-bit stage has room for ONE key bit in a value word
-(val_extra = 32 - g_bits, host/pipeline.hpp), the refinement rounds carry ranks and suffix indices >= 2^30, and the packed
+(val_extra = 32 - g_bits, host/pipeline.hpp; carried through the passes by host/sort.hpp), the refinement rounds carry ranks and suffix indices >= 2^30, and the packed
 format is 31 bits wide.  Every build names the route it is meant to cover and asserts it through last_stats(), so a later
 tuning change cannot quietly turn one case into a copy of another.  Arrays are checked against a closed form where one
 exists (periodic texts, oracle/search_model.py), otherwise with the oracle's linear-time verifier, the GPU integrity check and

@@ -1,5 +1,5 @@
 // What does one blocking read-back of a few words cost?  (a) kernel -> hipMemcpyAsync into pinned memory -> hipStreamSynchronize
-// (read_words of host/pipeline.hpp), (b) kernel -> a second tiny kernel that stores the words and then a sequence number into
+// (read_words of host/readback.hpp), (b) kernel -> a second tiny kernel that stores the words and then a sequence number into
 // MAPPED pinned host memory -> the host spins on the sequence number.  hipcc --offload-arch=gfx950 -O2 -o tools/bin/readback_probe tools/readback_probe.hip
 #include <hip/hip_runtime.h>
 #include <chrono>
