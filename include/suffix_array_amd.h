@@ -505,6 +505,69 @@ int32_t sa_amd_match_set_group_cap(int32_t bytes);
  * negative value restores the default.  Returns the previous value. */
 int32_t sa_amd_match_set_group_lanes(int32_t lanes);
 
+/*
+ * Document collections over the index (an extension): which document a position lies in, in how many documents a pattern
+ * occurs and in which ones, on the device.  The index text T has n bytes and SA is in the layout of
+ * sa_amd_saca_u8.
+ *   A collection is doc_off[0 .. ndocs], uint32: ndocs >= 1, doc_off[0] = 0, doc_off[ndocs] = n, non-decreasing -- empty documents
+ *     are legal anywhere, and so is an empty text with ndocs empty documents.  Document d is the byte range
+ *     [doc_off[d], doc_off[d + 1]).
+ *   doc(p), 0 <= p < n, is the unique d with doc_off[d] <= p < doc_off[d + 1]; for p >= n it is SA_AMD_DOC_NONE.  That covers
+ *     SA_AMD_MATCH_NONE: a POS array of sa_amd_index_match_stats can be passed straight to sa_amd_index_doc_of.
+ *   An occurrence of a pattern belongs to the document in which it STARTS.  A pattern can match across a boundary of the
+ *     concatenation; a caller who does not want that separates the documents by a byte their patterns do not contain.
+ *   For a pattern whose matches are the slots [lo, hi) -- exactly the range sa_amd_index_search reports --:
+ *     occ = hi - lo;
+ *     df = the number of distinct doc(SA[i]) over lo <= i < hi with SA[i] < n.  The empty suffix belongs to no document: the
+ *       empty pattern has occ = n + 1 and df = the number of non-empty documents;
+ *     the listing is those distinct documents, each once, in the order of the slot of their first occurrence in the range
+ *       (ordered by each document's lexicographically smallest matching suffix): deterministic, and it costs no sort.
+ *     T = "abracadabra", doc_off = {0, 4, 4, 7, 11} (documents "abra", "", "cad", "abra"): "a" has occ 5, df 3 and the listing
+ *       {3, 0, 2} (its slots hold the suffixes 10, 7, 0, 3, 5); "bra" has occ 2, df 2, listing {3, 0}; "" has df 3.
+ * sa_amd_index_set_documents checks doc_off on the host, uploads it and keeps ONE uint32 per slot next to the offsets
+ * (4 (n + 1) bytes): the previous slot of the same document + 1, 0 where there is none, 0xffffffff in slot 0 -- so "first of its
+ * document inside [lo, hi)" is the one compare `word <= lo`.  Calling it again replaces the collection; on any failure the
+ * previous collection stays.  Not to be called while another thread queries the index; queries may run concurrently.
+ * Errors, each with nothing written: a NULL index, a query before sa_amd_index_set_documents, a negative count or capacity,
+ * pat_off as sa_amd_index_search rejects it, a malformed doc_off, a device pointer of sa_amd_index_doc_of_device that is not
+ * 4-byte aligned: SA_AMD_EINVAL.  If the resident array is not the suffix array of the text the answers are unspecified, but
+ * nothing is read outside the tables and nothing is written outside the outputs.
+ * Cost: set_documents is one binary search per slot and one stable LSD sort of n pairs over the bits ndocs needs; a query
+ * streams 4 bytes per occurrence (twice for a listing) and does one binary search per listed document: O(occ), not O(df).
+ */
+#define SA_AMD_DOC_NONE 0xffffffffu
+/* bytes of device scratch sa_amd_index_set_documents takes from the pool for a text of n bytes: about 16 n */
+int64_t sa_amd_docs_work_bytes(int32_t n);
+int32_t sa_amd_index_set_documents(sa_amd_index *ix, const uint32_t *doc_off, int64_t ndocs);
+/* host pointers: pos (count entries, any values) goes up, doc(pos[i]) comes back */
+int32_t sa_amd_index_doc_of(const sa_amd_index *ix, const uint32_t *pos, int64_t count, uint32_t *doc_out);
+/* device pointers on the index's device, 4-byte aligned, count entries each; the call needs no scratch; stream a hipStream_t
+ * (NULL = default stream).  Blocks until done. */
+int32_t sa_amd_index_doc_of_device(const sa_amd_index *ix, const uint32_t *dPos, int64_t count, uint32_t *dDoc, void *stream);
+/* patterns as for sa_amd_index_search; occ and df: count entries each, either may be NULL */
+int32_t sa_amd_index_doc_search(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, uint32_t *occ,
+                                uint32_t *df);
+/* the listing of pattern q is docs[list_off[q] .. list_off[q + 1]) (list_off: count + 1 entries).  More entries than fit is no
+ * error: the first `capacity` are written, *total_out (= list_off[count]) and list_off describe all of them. */
+int32_t sa_amd_index_doc_list(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, int64_t *list_off,
+                              uint32_t *docs, int64_t capacity, int64_t *total_out);
+
+typedef struct sa_amd_docs_stats {   /* of the calling thread's most recent doc_search / doc_list call */
+    int64_t patterns;
+    int64_t occ_sum;                 /* sum of occ */
+    int64_t units;                   /* pieces of at most `chunk` slots the ranges were cut into, one wave each */
+    int64_t df_sum;                  /* sum of df = entries of the whole listing */
+    int64_t slots_scanned;           /* per-slot words streamed: occ_sum for doc_search, twice that for doc_list */
+    int32_t chunk;                   /* slots per unit in effect */
+    int32_t readbacks;               /* blocking device -> host read-backs of counters: 1 (the number of units) */
+    int32_t listed;                  /* 1 after doc_list, 0 after doc_search */
+    int32_t reserved;
+} sa_amd_docs_stats;
+void sa_amd_last_docs_stats(sa_amd_docs_stats *out);
+/* route switch of the calling thread's later doc_search / doc_list calls (never changes a result): slots per unit, clamped to
+ * 64 .. 1 048 576; a negative value restores the default (4096).  Returns the previous value. */
+int32_t sa_amd_docs_set_chunk(int32_t slots);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

@@ -10,6 +10,8 @@
 //                                           inverse_bw_transform of the C engine the reference binds)
 //   SuffixArray::repeat_lengths / repeat_spans, repeat_lengths(), repeat_spans()
 //                                           EXTENSION: the longest-repeat array and the byte ranges that are copies
+//   DocumentIndex                           EXTENSION: a device-resident index over a collection of documents: which document a
+//                                           position lies in, in how many documents a pattern occurs and in which ones
 // Rust panics (assert!, engine failure) are std::logic_error / std::runtime_error here.
 #pragma once
 #include "suffix_array_amd.h"
@@ -188,6 +190,80 @@ private:
     std::size_t n_;
     std::vector<std::uint32_t> sa_;
     std::vector<std::uint32_t> bkt_;
+};
+
+// EXTENSION (not in the reference): text + suffix array resident on the device (sa_amd_index) with a collection of documents
+// over it (suffix_array_amd.h, "Document collections over the index").  offsets: ndocs + 1 non-decreasing values from 0 to n.
+class DocumentIndex {
+public:
+    // sa == nullptr: the suffix array is built on the device and never downloaded
+    DocumentIndex(const std::uint8_t *s, std::size_t n, const std::vector<std::uint32_t> &offsets, const std::uint32_t *sa = nullptr)
+    {
+        if (n > MAX_LENGTH) throw std::logic_error("assertion failed: s.len() <= MAX_LENGTH");
+        check(sa_amd_index_create(s, static_cast<std::int32_t>(n), sa, &ix_));
+        try { set_documents(offsets); } catch (...) { sa_amd_index_destroy(ix_); throw; }
+    }
+    DocumentIndex(const DocumentIndex &) = delete;
+    DocumentIndex &operator=(const DocumentIndex &) = delete;
+    ~DocumentIndex() { sa_amd_index_destroy(ix_); }
+
+    // replaces the collection; malformed offsets throw std::invalid_argument and leave the previous one in place
+    void set_documents(const std::vector<std::uint32_t> &offsets)
+    {
+        if (offsets.size() < 2) throw std::invalid_argument("document offsets: ndocs + 1 values from 0 to n");
+        check(sa_amd_index_set_documents(ix_, offsets.data(), static_cast<std::int64_t>(offsets.size()) - 1));
+    }
+    // the document of every position; SA_AMD_DOC_NONE for positions >= n
+    std::vector<std::uint32_t> doc_of(const std::vector<std::uint32_t> &positions) const
+    {
+        std::vector<std::uint32_t> out(positions.size());
+        check(sa_amd_index_doc_of(ix_, positions.data(), static_cast<std::int64_t>(positions.size()), out.data()));
+        return out;
+    }
+    // per pattern (occ, df): occurrences, and the number of distinct documents an occurrence starts in
+    std::vector<std::pair<std::uint32_t, std::uint32_t>> doc_search(const std::vector<std::string> &patterns) const
+    {
+        const Batch b(patterns);
+        std::vector<std::uint32_t> occ(patterns.size()), df(patterns.size());
+        check(sa_amd_index_doc_search(ix_, b.data(), b.off.data(), b.count(), occ.data(), df.data()));
+        std::vector<std::pair<std::uint32_t, std::uint32_t>> out(patterns.size());
+        for (std::size_t q = 0; q < out.size(); ++q) out[q] = { occ[q], df[q] };
+        return out;
+    }
+    // per pattern the distinct documents it occurs in, ordered by the document's lexicographically smallest matching suffix
+    std::vector<std::vector<std::uint32_t>> doc_list(const std::vector<std::string> &patterns) const
+    {
+        const Batch b(patterns);
+        std::vector<std::int64_t> loff(patterns.size() + 1);
+        std::vector<std::uint32_t> docs(1 << 16);
+        std::int64_t total = 0;
+        for (;;) {
+            check(sa_amd_index_doc_list(ix_, b.data(), b.off.data(), b.count(), loff.data(), docs.data(), static_cast<std::int64_t>(docs.size()), &total));
+            if (total <= static_cast<std::int64_t>(docs.size())) break;
+            docs.resize(static_cast<std::size_t>(total));
+        }
+        std::vector<std::vector<std::uint32_t>> out(patterns.size());
+        for (std::size_t q = 0; q < out.size(); ++q) out[q].assign(docs.begin() + loff[q], docs.begin() + loff[q + 1]);
+        return out;
+    }
+
+private:
+    struct Batch {
+        std::string bytes;
+        std::vector<std::int64_t> off;
+        explicit Batch(const std::vector<std::string> &patterns) : off(patterns.size() + 1, 0)
+        {
+            for (std::size_t q = 0; q < patterns.size(); ++q) { bytes += patterns[q]; off[q + 1] = static_cast<std::int64_t>(bytes.size()); }
+        }
+        const std::uint8_t *data() const { return reinterpret_cast<const std::uint8_t *>(bytes.data()); }
+        std::int32_t count() const { return static_cast<std::int32_t>(off.size() - 1); }
+    };
+    static void check(std::int32_t rc)
+    {
+        if (rc == SA_AMD_EINVAL) throw std::invalid_argument("suffix_array_amd: invalid argument");
+        if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
+    }
+    sa_amd_index *ix_ = nullptr;
 };
 
 }  // namespace suffix_array

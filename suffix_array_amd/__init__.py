@@ -29,7 +29,9 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "repeat_lengths_device_ptr", "repeat_spans_device_ptr", "RepeatStats", "REPEATS_ALL", "REPEATS_KEEP_FIRST",
            "lpf", "lz77", "lz77_decode", "lz77_literals", "last_lz_stats", "lz_work_bytes", "lpf_device_ptr", "lz77_device_ptr", "LzStats", "LZ_LITERAL",
            "MatchStats", "last_match_stats", "match_work_bytes", "match_set_group_cap", "match_set_group_lanes", "match_stats_device_ptr", "match_spans_device_ptr",
-           "MATCH_NONE", "MATCH_TILE"]
+           "MATCH_NONE", "MATCH_TILE",
+           "DocsStats", "last_docs_stats", "docs_set_chunk", "docs_work_bytes", "doc_of_device_ptr", "DOC_NONE", "DOC_SAMPLES",
+           "DOC_CHUNK_MIN", "DOC_CHUNK_MAX", "DOC_CHUNK_DEFAULT"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
@@ -120,6 +122,25 @@ class MatchStats(ctypes.Structure):
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
+
+class DocsStats(ctypes.Structure):
+    """sa_amd_docs_stats of include/suffix_array_amd.h"""
+    _fields_ = [("patterns", ctypes.c_int64), ("occ_sum", ctypes.c_int64), ("units", ctypes.c_int64), ("df_sum", ctypes.c_int64),
+                ("slots_scanned", ctypes.c_int64), ("chunk", ctypes.c_int32), ("readbacks", ctypes.c_int32), ("listed", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+#: the document of a position behind the text (SA_AMD_DOC_NONE of include/suffix_array_amd.h); equal to ``MATCH_NONE``
+DOC_NONE = 0xFFFFFFFF
+#: entries of the sampled top level of the offset table a workgroup stages (kernels/docs.hpp)
+DOC_SAMPLES = 8192
+#: slots of a unit of ``doc_search`` / ``doc_list``: the clamp of ``docs_set_chunk`` and the default (kernels/docs.hpp)
+DOC_CHUNK_MIN = 64
+DOC_CHUNK_MAX = 1 << 20
+DOC_CHUNK_DEFAULT = 4096
 
 #: ``pos`` of a query position none of whose bytes occurs in the text (SA_AMD_MATCH_NONE of include/suffix_array_amd.h)
 MATCH_NONE = 0xFFFFFFFF
@@ -295,6 +316,22 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_match_set_group_cap.restype = ctypes.c_int32
         L.sa_amd_match_set_group_lanes.argtypes = [ctypes.c_int32]
         L.sa_amd_match_set_group_lanes.restype = ctypes.c_int32
+        L.sa_amd_docs_work_bytes.argtypes = [ctypes.c_int32]
+        L.sa_amd_docs_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_index_set_documents.argtypes = [c_vp, c_vp, ctypes.c_int64]
+        L.sa_amd_index_set_documents.restype = ctypes.c_int32
+        L.sa_amd_index_doc_of.argtypes = [c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_doc_of.restype = ctypes.c_int32
+        L.sa_amd_index_doc_of_device.argtypes = [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]
+        L.sa_amd_index_doc_of_device.restype = ctypes.c_int32
+        L.sa_amd_index_doc_search.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp]
+        L.sa_amd_index_doc_search.restype = ctypes.c_int32
+        L.sa_amd_index_doc_list.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_doc_list.restype = ctypes.c_int32
+        L.sa_amd_last_docs_stats.argtypes = [c_vp]
+        L.sa_amd_last_docs_stats.restype = None
+        L.sa_amd_docs_set_chunk.argtypes = [ctypes.c_int32]
+        L.sa_amd_docs_set_chunk.restype = ctypes.c_int32
         _lib = L
     return _lib
 
@@ -842,6 +879,39 @@ def match_spans_device_ptr(index, query_ptr: int, m: int, min_len: int, spans_pt
     return int(count.value)
 
 
+def last_docs_stats() -> dict:
+    """patterns / occ_sum / units / df_sum / slots_scanned / chunk / readbacks / listed of this thread's most recent
+    ``doc_search`` / ``doc_list`` call"""
+    st = DocsStats()
+    lib().sa_amd_last_docs_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def docs_work_bytes(n: int) -> int:
+    """device scratch ``set_documents`` takes from the pool for a text of ``n`` bytes"""
+    return int(lib().sa_amd_docs_work_bytes(n))
+
+
+def docs_set_chunk(slots: int) -> int:
+    """Route switch of this thread's later ``doc_search`` / ``doc_list`` calls (never changes a result): slots of a match range
+    one wave scans, ``DOC_CHUNK_MIN`` .. ``DOC_CHUNK_MAX``; negative restores ``DOC_CHUNK_DEFAULT``.  Returns the previous value."""
+    return int(lib().sa_amd_docs_set_chunk(int(slots)))
+
+
+def doc_of_device_ptr(index, pos_ptr: int, count: int, doc_ptr: int, stream: int = 0) -> None:
+    """Device-resident ``doc_of``: ``count`` uint32 positions at ``pos_ptr`` -> their documents at ``doc_ptr`` (raw device pointers
+    on the index's device, 4-byte aligned); needs no scratch; blocks until done."""
+    _check(lib().sa_amd_index_doc_of_device(_index_handle(index), pos_ptr or None, int(count), doc_ptr or None, stream))
+
+
+def _pattern_batch(patterns):
+    pats = [bytes(p) for p in patterns]
+    off = np.zeros(len(pats) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(p) for p in pats])
+    data = np.frombuffer(b"".join(pats), dtype=np.uint8) if off[-1] else np.zeros(1, dtype=np.uint8)
+    return data, off, len(pats)
+
+
 class DeviceIndex:
     """Text + suffix array resident in HBM (sa_amd_index of include/suffix_array_amd.h): batched
     `contains` / `search_all` / `search_lcp` (reference src/sa.rs:164-253), bucket table, integrity check.
@@ -950,6 +1020,47 @@ class DeviceIndex:
         count = ctypes.c_int64(0)
         _check(lib().sa_amd_index_match_spans(self._h, q.ctypes.data, q.size, k, out.ctypes.data, cap, ctypes.byref(count)))
         return out[:min(int(count.value), cap)].copy()
+
+    def set_documents(self, offsets) -> None:
+        """EXTENSION: make the text a collection of documents.  ``offsets``: ``ndocs + 1`` non-decreasing values from 0 to
+        ``len(text)``; document ``d`` is ``text[offsets[d]:offsets[d + 1]]`` (empty documents are legal).  Replaces an earlier
+        collection; malformed offsets raise and leave it in place."""
+        off = np.ascontiguousarray(offsets)
+        if off.ndim != 1 or off.size < 2 or (off.size and (off.min() < 0 or off.max() > 0xFFFFFFFF)):
+            raise SuffixArrayError(-1, "document offsets: ndocs + 1 values in 0 .. len(text)")
+        off = off.astype(np.uint32)
+        _check(lib().sa_amd_index_set_documents(self._h, off.ctypes.data, off.size - 1))
+
+    def doc_of(self, positions) -> np.ndarray:
+        """the document each text position lies in (uint32; ``DOC_NONE`` for positions ``>= len(text)``, so the ``pos`` of
+        ``match_stats`` can be passed as it is)"""
+        pos = np.ascontiguousarray(positions, dtype=np.uint32).ravel()
+        out = np.empty(pos.size, dtype=np.uint32)
+        _check(lib().sa_amd_index_doc_of(self._h, pos.ctypes.data, pos.size, out.ctypes.data))
+        return out
+
+    def doc_search(self, patterns):
+        """-> ``(occ, df)``, uint32 arrays over the patterns: occurrences, and the number of distinct documents an occurrence
+        starts in"""
+        data, off, cnt = _pattern_batch(patterns)
+        out = np.zeros((2, cnt), dtype=np.uint32)
+        _check(lib().sa_amd_index_doc_search(self._h, data.ctypes.data, off.ctypes.data, cnt, out[0].ctypes.data, out[1].ctypes.data))
+        return out[0], out[1]
+
+    def doc_list(self, patterns) -> list:
+        """-> per pattern the uint32 array of the distinct documents it occurs in, ordered by the document's lexicographically
+        smallest matching suffix"""
+        data, off, cnt = _pattern_batch(patterns)
+        loff = np.zeros(cnt + 1, dtype=np.int64)
+        total = ctypes.c_int64(0)
+        cap = 1 << 16
+        while True:
+            docs = np.empty(cap, dtype=np.uint32)
+            _check(lib().sa_amd_index_doc_list(self._h, data.ctypes.data, off.ctypes.data, cnt, loff.ctypes.data, docs.ctypes.data, cap,
+                                               ctypes.byref(total)))
+            if total.value <= cap:
+                return [docs[loff[q]:loff[q + 1]].copy() for q in range(cnt)]
+            cap = int(total.value)
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): build and keep the LCP table of the
@@ -1162,6 +1273,22 @@ class SuffixArray:
     def match_spans(self, query, min_len: int) -> np.ndarray:
         """EXTENSION (the reference lacks it): the parts of ``query`` that occur in the text (see ``DeviceIndex.match_spans``)"""
         return self._index().match_spans(query, min_len)
+
+    def set_documents(self, offsets) -> None:
+        """EXTENSION (the reference lacks it): make the text a collection of documents (see ``DeviceIndex.set_documents``)"""
+        self._index().set_documents(offsets)
+
+    def doc_of(self, positions) -> np.ndarray:
+        """EXTENSION (the reference lacks it): the document of each position (see ``DeviceIndex.doc_of``)"""
+        return self._index().doc_of(positions)
+
+    def doc_search(self, patterns):
+        """EXTENSION (the reference lacks it): ``(occ, df)`` per pattern (see ``DeviceIndex.doc_search``)"""
+        return self._index().doc_search(patterns)
+
+    def doc_list(self, patterns) -> list:
+        """EXTENSION (the reference lacks it): the documents each pattern occurs in (see ``DeviceIndex.doc_list``)"""
+        return self._index().doc_list(patterns)
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): contains / search_all / search_lcp

@@ -1,0 +1,232 @@
+// host/docs.hpp -- document collections over a device-resident index (kernels/docs.hpp): the build of
+// the per-slot word behind sa_amd_index_set_documents, positions to documents, document frequency and document listing.
+#pragma once
+#include "scope.hpp"
+#include "esa.hpp"
+#include "../kernels/docs.hpp"
+
+namespace sa {
+
+static thread_local sa_amd_docs_stats g_last_docs_stats;
+static thread_local int32_t g_docs_chunk = -1;          // sa_amd_docs_set_chunk of the calling thread (-1: DOC_CHUNK_DEFAULT)
+
+// what the calls need of an index (sa_api.hip owns the struct)
+struct DocIndex {
+    int device; const uint8_t *dT; const uint32_t *dSA; int32_t n; const uint32_t *dBkt; const uint64_t *dPair;
+    const uint32_t *dOff; const uint32_t *dPrev; uint32_t ndocs;
+};
+
+// layout of the build's work block: control words (the sort's error word first) | four (n + 1)-entry buffers (the document ids
+// of the slots, the sort's values and their two alternates) | sort spine | single-pass granules.  About 16 bytes per byte of text.
+struct DocsLayout { size_t ctl, keys, vals, altk, altv, alt_elems, spine, status, bytes; };
+static DocsLayout docs_layout(int32_t n)
+{
+    DocsLayout L;
+    const size_t N1 = (size_t)n + 1;
+    size_t off = 0;
+    auto take = [&](size_t b) { const size_t o = off; off = align_up(off + b, 256); return o; };
+    L.ctl = take(256);
+    L.alt_elems = (N1 + 67) & ~(size_t)3;
+    L.keys = take(L.alt_elems * 4);
+    L.vals = take(L.alt_elems * 4);
+    L.altk = take(L.alt_elems * 4);
+    L.altv = take(L.alt_elems * 4);
+    L.spine = take(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4);
+    L.status = take(((size_t)ceil_div((int64_t)N1, OS_MIN_TILE) + 1) * RADIX * 8);
+    L.bytes = off;
+    return L;
+}
+
+// doc_off[0 .. ndocs]: starts at 0 and never decreases (the caller compares the last entry with the index's n)
+static bool docs_valid(const uint32_t *doc_off, int64_t ndocs)
+{
+    if (!doc_off || ndocs < 1 || ndocs > (int64_t)0xfffffffe) return false;
+    if (doc_off[0] != 0) return false;
+    for (int64_t d = 0; d < ndocs; ++d) if (doc_off[d + 1] < doc_off[d]) return false;
+    return true;
+}
+
+static int launch_doc_of(const uint32_t *dPos, int64_t count, const uint32_t *dOff, uint32_t ndocs, int32_t n, uint32_t *dOut, hipStream_t st)
+{
+    if (count <= 0) return SA_AMD_OK;
+    const uint32_t M = ndocs + 1;
+    const uint32_t stride = (uint32_t)ceil_div((int64_t)M, DOC_SAMPLES), ns = (uint32_t)ceil_div((int64_t)M, stride);
+    int64_t g = ceil_div(count, (int64_t)DOC_THREADS * DOC_ITEMS);
+    const int64_t most = (int64_t)cu_count() * 8;
+    if (g > most) g = most;
+    PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_doc_of, dim3((unsigned)g), dim3(DOC_THREADS), 0, st, dPos, count, dOff, M, stride, ns, (uint32_t)n, dOut));
+    return SA_AMD_OK;
+}
+
+// dPrev (n + 1 entries) from dSA and the uploaded offsets; dWork: docs_layout(n).bytes, 256-byte aligned.  Blocks until done.
+static int docs_build(const uint32_t *dSA, int32_t n32, const uint32_t *dOff, uint32_t ndocs, uint32_t *dPrev, void *dWork, int64_t work_bytes,
+                      hipStream_t st)
+{
+    const int64_t n = n32;
+    const DocsLayout L = docs_layout(n32);
+    if (!dWork || work_bytes < (int64_t)L.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
+    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
+    g_posted_off = tn.no_posted_readback;
+    char *base = (char *)dWork;
+    uint32_t *ctl = (uint32_t *)(base + L.ctl);
+    uint32_t *keys = (uint32_t *)(base + L.keys), *vals = (uint32_t *)(base + L.vals);
+    HIP_TRY(hipMemsetAsync(ctl, 0, 256, st));
+    SortScratch ss;
+    ss.spine = (uint32_t *)(base + L.spine);
+    ss.digit_tot = ss.spine + (size_t)RADIX * SORT_MAX_WG;
+    ss.status = (unsigned long long *)(base + L.status);
+    ss.err = ctl;
+    // DA of slots 1 .. n (slot 0 is the empty suffix: no document), then the slots in stable order of their document
+    { const int rcd = launch_doc_of(dSA + 1, n, dOff, ndocs, n32, keys, st); if (rcd) return rcd; }
+    SortResult32 pr;
+    const int rcs = sort_pairs32(keys, vals, (uint32_t *)(base + L.altk), (uint32_t *)(base + L.altv), n, 0, bit_length((uint64_t)ndocs - 1), ss, nullptr,
+                                 st, &pr, tn, true);
+    if (rcs) return rcs;
+    int64_t g = ceil_div(n, DOC_THREADS);
+    if (g > 16384) g = 16384;
+    if (g < 1) g = 1;
+    PROF(KC_MISC, n, st, hipLaunchKernelGGL(k_doc_prev, dim3((unsigned)g), dim3(DOC_THREADS), 0, st, (const uint32_t *)pr.keys,
+                                            (const uint32_t *)(pr.passes ? pr.vals : nullptr), n, dPrev));
+    uint32_t err = 0;
+    { const int rcw = read_words(&err, ctl, 4, st); if (rcw) return rcw; }
+    HIP_TRY(hipStreamSynchronize(st));
+    g_prof.resolve();
+    if (err) return SA_AMD_EINTERNAL;               // a look-back of the sort gave up (never seen; never a silent wrong table)
+    return SA_AMD_OK;
+}
+
+// exclusive scan of v[0 .. len) in place; tsum: ceil(len / DOC_SCAN_TILE) words; last_out: see k_doc_scan_tiles
+static int docs_scan(unsigned long long *v, int64_t len, unsigned long long *tsum, unsigned long long *last_out, hipStream_t st)
+{
+    const int64_t tiles = ceil_div(len, DOC_SCAN_TILE);
+    PROF(KC_MISC, len, st, hipLaunchKernelGGL((k_doc_scan_tiles<0>), dim3((unsigned)tiles), dim3(DOC_SCAN_THREADS), 0, st, v, len, tsum,
+                                              (unsigned long long *)nullptr));
+    PROF(KC_MISC, tiles, st, hipLaunchKernelGGL(k_doc_scan_spine, dim3(1), dim3(DOC_SPINE_THREADS), 0, st, tsum, tiles));
+    PROF(KC_MISC, len, st, hipLaunchKernelGGL((k_doc_scan_tiles<1>), dim3((unsigned)tiles), dim3(DOC_SCAN_THREADS), 0, st, v, len, tsum, last_out));
+    return SA_AMD_OK;
+}
+
+static size_t docs_scan_words(int64_t len) { return (size_t)ceil_div(len, DOC_SCAN_TILE) + 1; }
+
+static unsigned docs_unit_grid(int64_t units)
+{
+    int64_t g = ceil_div(units, DOC_THREADS / WAVE);
+    const int64_t most = (int64_t)cu_count() * 16;
+    if (g > most) g = most;
+    return (unsigned)(g < 1 ? 1 : g);
+}
+
+// Document frequency (!list: occ and df, either may be nullptr) or listing (list_off: count + 1 entries, the first `capacity`
+// documents to docs, the number of all of them to *total_out) of a batch of patterns; host pointers, arguments checked by the
+// caller.  One blocking read-back: the number of units (with the summed occ and the bound of the listing).
+static int docs_query(const DocIndex &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, bool list, uint32_t *occ_out,
+                      uint32_t *df_out, int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
+{
+    sa_amd_docs_stats ds;
+    memset(&ds, 0, sizeof(ds));
+    const uint32_t chunk = (uint32_t)(g_docs_chunk < 0 ? DOC_CHUNK_DEFAULT : g_docs_chunk);
+    ds.patterns = count;
+    ds.chunk = (int32_t)chunk;
+    ds.listed = list ? 1 : 0;
+    g_last_docs_stats = ds;
+    if (count == 0) {
+        if (list) { list_off[0] = 0; *total_out = 0; }
+        return SA_AMD_OK;
+    }
+    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
+    g_posted_off = tn.no_posted_readback;
+    const int rb0 = g_readbacks;
+    const size_t C = (size_t)count, total = (size_t)pat_off[count];
+    const uint32_t N1 = (uint32_t)ix.n + 1u;
+
+    PooledScope sc(ix.device, false);
+    const size_t b_pat = align_up(total + 16, 256), b_off = align_up((C + 1) * 8, 256), b_w = align_up(C * 4 + 4, 256);
+    const size_t b_ts = align_up(docs_scan_words((int64_t)C + 1) * 8, 256);
+    sc.acquire(256 + b_pat + b_off + 4 * b_w + b_off + b_ts + (list ? b_off : 0));
+    unsigned long long *ctl = (unsigned long long *)sc.take(256);
+    uint8_t *dP = (uint8_t *)sc.take(b_pat);
+    int64_t *dO = (int64_t *)sc.take(b_off);
+    uint32_t *dLo = (uint32_t *)sc.take(b_w), *dHi = (uint32_t *)sc.take(b_w), *dOcc = (uint32_t *)sc.take(b_w), *dDf = (uint32_t *)sc.take(b_w);
+    unsigned long long *uoff = (unsigned long long *)sc.take(b_off), *tsum = (unsigned long long *)sc.take(b_ts);
+    long long *dLoff = list ? (long long *)sc.take(b_off) : nullptr;
+    if (sc.rc) return sc.rc;
+    hipStream_t st = sc.st;
+    HIP_TRY(hipMemsetAsync(ctl, 0, 256, st));
+    HIP_TRY(hipMemsetAsync(dDf, 0, C * 4, st));
+    if (total) HIP_TRY(hipMemcpyAsync(dP, pat_data, total, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dO, pat_off, (C + 1) * 8, hipMemcpyHostToDevice, st));
+
+    // ---- the ranges, by the search kernels as sa_amd_index_search runs them ----
+    g_prof.begin(KC_MISC, count, st);
+    const int rcs = launch_search(ix.dT, ix.dSA, ix.n, ix.dBkt, ix.dPair, dP, dO, count, nullptr, dLo, dHi, nullptr, nullptr, nullptr, st);
+    g_prof.end(st);
+    if (rcs) return rcs;
+    // ---- the units: ceil(occ / chunk) per pattern, scanned; the number of all of them comes back ----
+    PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_doc_ranges, dim3((unsigned)ceil_div((int64_t)count + 1, DOC_THREADS)), dim3(DOC_THREADS), 0, st, dLo,
+                                                (const uint32_t *)dHi, count, N1, chunk, ix.ndocs, dOcc, uoff, ctl));
+    { const int rcn = docs_scan(uoff, (int64_t)count + 1, tsum, &ctl[0], st); if (rcn) return rcn; }
+    unsigned long long cw[3];
+    { const int rcw = read_words(cw, ctl, sizeof(cw), st); if (rcw) return rcw; }
+    const unsigned long long units = cw[0], occ_sum = cw[1], bound = cw[2];
+    if (units > (unsigned long long)count + occ_sum / chunk || occ_sum > (unsigned long long)count * N1) return SA_AMD_EINTERNAL;
+    ds.occ_sum = (int64_t)occ_sum;
+    ds.units = (int64_t)units;
+    ds.slots_scanned = (int64_t)occ_sum * (list ? 2 : 1);
+
+    std::vector<uint32_t> df(list ? 0 : C);
+    int64_t listed = 0;
+    if (!list) {
+        if (units)
+            PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL((k_doc_count<false>), dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.dPrev,
+                                                                   (const uint32_t *)dLo, (const uint32_t *)dOcc, (const unsigned long long *)uoff, count, units,
+                                                                   chunk, dDf, (unsigned long long *)nullptr, (uint32_t *)nullptr));
+        HIP_TRY(hipStreamSynchronize(st));
+        sc.down(df.data(), dDf, C * 4);
+        if (sc.finish() != SA_AMD_OK) return sc.rc;
+        if (occ_out) HIP_TRY(hipMemcpy(occ_out, dOcc, C * 4, hipMemcpyDeviceToHost));      // the last step that can fail: nothing else is written before it
+        for (size_t q = 0; q < C; ++q) ds.df_sum += df[q];
+        if (df_out) memcpy(df_out, df.data(), C * 4);
+    } else {
+        // ---- the listing: counts per unit, one scan for the units' offsets and the patterns', ordered compaction ----
+        const int64_t cap = capacity < (int64_t)bound ? capacity : (int64_t)bound;
+        const size_t b_uc = align_up(((size_t)units + 1) * 8, 256), b_uq = align_up((size_t)units * 4 + 4, 256);
+        const size_t b_ut = align_up(docs_scan_words((int64_t)units + 1) * 8, 256), b_docs = align_up((size_t)cap * 4 + 8, 256);
+        PooledScope s2(-1, false);
+        s2.acquire(b_uc + b_uq + b_ut + b_docs);
+        unsigned long long *ucnt = (unsigned long long *)s2.take(b_uc), *utsum = (unsigned long long *)s2.take(b_ut);
+        uint32_t *uq = (uint32_t *)s2.take(b_uq), *dDocs = (uint32_t *)s2.take(b_docs);
+        if (s2.rc) return s2.rc;
+        HIP_TRY(hipMemsetAsync(ucnt + units, 0, 8, st));
+        if (units)
+            PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL((k_doc_count<true>), dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.dPrev,
+                                                                   (const uint32_t *)dLo, (const uint32_t *)dOcc, (const unsigned long long *)uoff, count, units,
+                                                                   chunk, (uint32_t *)nullptr, ucnt, uq));
+        { const int rcn = docs_scan(ucnt, (int64_t)units + 1, utsum, nullptr, st); if (rcn) return rcn; }
+        PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_doc_list_off, dim3((unsigned)ceil_div((int64_t)count + 1, DOC_THREADS)), dim3(DOC_THREADS), 0, st,
+                                                    (const unsigned long long *)uoff, (const unsigned long long *)ucnt, units, count, dLoff));
+        if (units && cap > 0)
+            PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL(k_doc_emit, dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.dPrev, ix.dSA,
+                                                                   (const uint32_t *)dLo, (const uint32_t *)dOcc, (const unsigned long long *)uoff,
+                                                                   (const uint32_t *)uq, (const unsigned long long *)ucnt, units, count, chunk, ix.dOff,
+                                                                   ix.ndocs + 1u, (uint32_t)ix.n, dDocs, (unsigned long long)cap));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<int64_t> loff(C + 1);
+        sc.down(loff.data(), dLoff, (C + 1) * 8);
+        if (sc.rc) return sc.rc;
+        listed = loff[C];
+        if (listed < 0) return SA_AMD_EINTERNAL;              // (above `bound` only for an array that is no suffix array: what fits `cap` is written)
+        const int64_t wr = listed < cap ? listed : cap;
+        if (s2.finish() != SA_AMD_OK) return s2.rc;
+        if (sc.finish() != SA_AMD_OK) return sc.rc;
+        if (wr > 0) HIP_TRY(hipMemcpy(docs, dDocs, (size_t)wr * 4, hipMemcpyDeviceToHost));    // the last step that can fail; list_off and the total behind it
+        memcpy(list_off, loff.data(), (C + 1) * 8);
+        *total_out = listed;
+        ds.df_sum = listed;
+    }
+    g_prof.resolve();
+    ds.readbacks = g_readbacks - rb0;
+    g_last_docs_stats = ds;
+    return SA_AMD_OK;
+}
+
+}  // namespace sa

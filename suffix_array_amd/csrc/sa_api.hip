@@ -20,6 +20,7 @@
 #include "host/repeats.hpp"
 #include "host/lz.hpp"
 #include "host/match.hpp"
+#include "host/docs.hpp"
 
 extern "C" {
 
@@ -341,6 +342,9 @@ struct sa_amd_index {
     uint32_t *dSA;
     uint32_t *dBkt;       // bucket table once sa_amd_index_buckets has built it (narrows the searches, src/sa.rs:123-161)
     uint64_t *dPair;      // LCP table of the search tree once sa_amd_index_enable_lcp has built it (kernels/esa.hpp)
+    uint32_t *dDocOff;    // document offsets (ndocs + 1 entries) once sa_amd_index_set_documents has taken a collection (kernels/docs.hpp)
+    uint32_t *dDocPrev;   // per slot: the previous slot of the same document + 1 (n + 1 entries)
+    uint32_t ndocs;
 };
 
 SA_EXPORT int32_t sa_amd_index_create(const uint8_t *T, int32_t n, const uint32_t *SA, sa_amd_index **out)
@@ -368,6 +372,7 @@ SA_EXPORT int32_t sa_amd_index_create(const uint8_t *T, int32_t n, const uint32_
     sa_amd_index *ix = new (std::nothrow) sa_amd_index();
     if (!ix) return SA_AMD_ENOMEM;
     ix->n = n; ix->device = 0; ix->dBkt = nullptr; ix->dPair = nullptr;
+    ix->dDocOff = nullptr; ix->dDocPrev = nullptr; ix->ndocs = 0;
     (void)hipGetDevice(&ix->device);
     ix->dT = dT.as<uint8_t>(); ix->dSA = dSA.as<uint32_t>();
     dT.p = nullptr; dSA.p = nullptr;                             // ownership moves to the index
@@ -383,6 +388,8 @@ SA_EXPORT void sa_amd_index_destroy(sa_amd_index *ix)      // (frees and deletes
     if (ix->dSA) (void)hipFree(ix->dSA);
     if (ix->dBkt) (void)hipFree(ix->dBkt);
     if (ix->dPair) (void)hipFree(ix->dPair);
+    if (ix->dDocOff) (void)hipFree(ix->dDocOff);
+    if (ix->dDocPrev) (void)hipFree(ix->dDocPrev);
     delete ix;
 }
 
@@ -434,7 +441,7 @@ SA_EXPORT int32_t sa_amd_index_search(const sa_amd_index *ix, const uint8_t *pat
 {
     SA_ABI_GUARD_BEGIN
     using namespace sa;
-    if (!ix || count < 0 || (count > 0 && !pat_off)) return SA_AMD_EINVAL;
+    if (!ix || !search_patterns_valid(pat_data, pat_off, count)) return SA_AMD_EINVAL;
     if (count == 0) {
         sa_amd_search_stats z;
         memset(&z, 0, sizeof(z));
@@ -444,8 +451,6 @@ SA_EXPORT int32_t sa_amd_index_search(const sa_amd_index *ix, const uint8_t *pat
         return SA_AMD_OK;
     }
     const int64_t total = pat_off[count];
-    if (total < 0 || (total > 0 && !pat_data)) return SA_AMD_EINVAL;
-    for (int32_t i = 0; i < count; ++i) if (pat_off[i + 1] < pat_off[i] || pat_off[i] < 0) return SA_AMD_EINVAL;
     DeviceGuard guard(ix->device);
     if (guard.rc != SA_AMD_OK) return guard.rc;
     const size_t C = (size_t)count;
@@ -458,25 +463,17 @@ SA_EXPORT int32_t sa_amd_index_search(const sa_amd_index *ix, const uint8_t *pat
     if (total) HIP_TRY(hipMemcpy(dP.p, pat_data, (size_t)total, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dO.p, pat_off, (C + 1) * 8, hipMemcpyHostToDevice));
     uint32_t *R = dR.as<uint32_t>();
-    const int64_t threads = (int64_t)count * WAVE;
-    const dim3 grid((unsigned)ceil_div(threads, SEARCH_THREADS));
     sa_amd_search_stats stats;
     memset(&stats, 0, sizeof(stats));
     stats.patterns = count;
     stats.compared_bytes = stats.steps = stats.table_steps = -1;
     DevBuf dS;
-    if (ix->dPair) {                                             // LCP route (kernels/esa.hpp)
+    if (ix->dPair) {                                             // LCP route (kernels/esa.hpp): its three counters
         if ((rc = dS.alloc(3 * 8))) return rc;
         HIP_TRY(hipMemset(dS.p, 0, 3 * 8));
-        hipLaunchKernelGGL(k_esa_search, grid, dim3(SEARCH_THREADS), 0, nullptr, (const uint8_t *)ix->dT,
-                           (const uint32_t *)ix->dSA, (int64_t)ix->n, (const uint64_t *)ix->dPair, esa_log_p(ix->n),
-                           dP.as<const uint8_t>(), dO.as<const int64_t>(), count, dC.as<uint8_t>(), R, R + C, R + 2 * C, R + 3 * C,
-                           (const uint32_t *)ix->dBkt, dS.as<unsigned long long>());
-    } else {
-        hipLaunchKernelGGL(k_search_batch, grid, dim3(SEARCH_THREADS), 0, nullptr,
-                           (const uint8_t *)ix->dT, (const uint32_t *)ix->dSA, (int64_t)ix->n, dP.as<const uint8_t>(),
-                           dO.as<const int64_t>(), count, dC.as<uint8_t>(), R, R + C, R + 2 * C, R + 3 * C, (const uint32_t *)ix->dBkt);
     }
+    if ((rc = launch_search(ix->dT, ix->dSA, ix->n, ix->dBkt, ix->dPair, dP.as<const uint8_t>(), dO.as<const int64_t>(), count, dC.as<uint8_t>(), R, R + C,
+                            R + 2 * C, R + 3 * C, ix->dPair ? dS.as<unsigned long long>() : nullptr, nullptr))) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     if (ix->dPair) {
@@ -867,6 +864,105 @@ SA_EXPORT int32_t sa_amd_match_set_group_lanes(int32_t lanes)
 {
     const int32_t prev = sa::g_match_lanes;
     sa::g_match_lanes = lanes < 0 ? 8 : (lanes >= 16 ? 16 : (lanes >= 8 ? 8 : 4));
+    return prev;
+}
+
+// ---- document collections over the index (host/docs.hpp, kernels/docs.hpp) ----
+
+static sa::DocIndex doc_index(const sa_amd_index *ix)
+{
+    sa::DocIndex di;
+    di.device = ix->device; di.dT = ix->dT; di.dSA = ix->dSA; di.n = ix->n; di.dBkt = ix->dBkt; di.dPair = ix->dPair;
+    di.dOff = ix->dDocOff; di.dPrev = ix->dDocPrev; di.ndocs = ix->ndocs;
+    return di;
+}
+
+SA_EXPORT int64_t sa_amd_docs_work_bytes(int32_t n)
+{
+    if (n < 0) return -1;
+    return (int64_t)sa::docs_layout(n).bytes;
+}
+
+SA_EXPORT int32_t sa_amd_index_set_documents(sa_amd_index *ix, const uint32_t *doc_off, int64_t ndocs)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::docs_valid(doc_off, ndocs) || doc_off[ndocs] != (uint32_t)ix->n) return SA_AMD_EINVAL;
+    const size_t M = (size_t)ndocs + 1, N1 = (size_t)ix->n + 1;
+    sa::PooledScope sc(ix->device, false);
+    if (sc.rc) return sc.rc;
+    sa::DevBuf off, prev;                                        // the tables outlive the call: their own allocations, not the pool's
+    if (off.alloc(M * 4) != SA_AMD_OK || prev.alloc(N1 * 4) != SA_AMD_OK) { (void)hipGetLastError(); return SA_AMD_ENOMEM; }
+    const size_t wb = sa::docs_layout(ix->n).bytes;
+    sc.acquire(wb);
+    void *dW = sc.take(wb);
+    if (sc.rc == SA_AMD_OK) sc.rc = sa::hip_status(hipMemcpy(off.p, doc_off, M * 4, hipMemcpyHostToDevice));
+    if (sc.rc == SA_AMD_OK) sc.rc = sa::docs_build(ix->dSA, ix->n, off.as<uint32_t>(), (uint32_t)ndocs, prev.as<uint32_t>(), dW, (int64_t)wb, sc.st);
+    if (sc.finish() != SA_AMD_OK) return sc.rc;                  // (a previous collection stays)
+    if (ix->dDocOff) (void)hipFree(ix->dDocOff);
+    if (ix->dDocPrev) (void)hipFree(ix->dDocPrev);
+    ix->dDocOff = off.as<uint32_t>(); ix->dDocPrev = prev.as<uint32_t>(); ix->ndocs = (uint32_t)ndocs;
+    off.p = nullptr; prev.p = nullptr;
+    return SA_AMD_OK;
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_doc_of(const sa_amd_index *ix, const uint32_t *pos, int64_t count, uint32_t *doc_out)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || count < 0 || (count > 0 && (!pos || !doc_out)) || !ix->dDocOff) return SA_AMD_EINVAL;
+    if (count == 0) return SA_AMD_OK;
+    const size_t b = sa::align_up((size_t)count * 4, 256);
+    sa::PooledScope sc(ix->device, false);
+    sc.acquire(2 * b);
+    uint32_t *dPos = (uint32_t *)sc.take(b), *dOut = (uint32_t *)sc.take(b);
+    if (sc.rc == SA_AMD_OK) sc.rc = sa::hip_status(hipMemcpyAsync(dPos, pos, (size_t)count * 4, hipMemcpyHostToDevice, sc.st));
+    if (sc.rc == SA_AMD_OK) sc.rc = sa::launch_doc_of(dPos, count, ix->dDocOff, ix->ndocs, ix->n, dOut, sc.st);
+    sc.down(doc_out, dOut, (size_t)count * 4);
+    return sc.finish();
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_doc_of_device(const sa_amd_index *ix, const uint32_t *dPos, int64_t count, uint32_t *dDoc, void *stream)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || count < 0 || (count > 0 && (!dPos || !dDoc)) || ((((uintptr_t)dPos) | ((uintptr_t)dDoc)) & 3u) || !ix->dDocOff) return SA_AMD_EINVAL;
+    if (count == 0) return SA_AMD_OK;
+    sa::DeviceGuard guard(ix->device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    const int32_t rc = sa::launch_doc_of(dPos, count, ix->dDocOff, ix->ndocs, ix->n, dDoc, (hipStream_t)stream);
+    if (rc) return rc;
+    return sa::hip_status(hipStreamSynchronize((hipStream_t)stream));
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_doc_search(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, uint32_t *occ,
+                                          uint32_t *df)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::search_patterns_valid(pat_data, pat_off, count) || !ix->dDocOff) return SA_AMD_EINVAL;
+    return sa::docs_query(doc_index(ix), pat_data, pat_off, count, false, occ, df, nullptr, nullptr, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_doc_list(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, int64_t *list_off,
+                                        uint32_t *docs, int64_t capacity, int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::search_patterns_valid(pat_data, pat_off, count)) return SA_AMD_EINVAL;
+    if (capacity < 0 || !list_off || !total_out || (capacity > 0 && !docs) || !ix->dDocOff) return SA_AMD_EINVAL;
+    return sa::docs_query(doc_index(ix), pat_data, pat_off, count, true, nullptr, nullptr, list_off, docs, capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_docs_stats(sa_amd_docs_stats *out)
+{
+    if (out) *out = sa::g_last_docs_stats;
+}
+
+SA_EXPORT int32_t sa_amd_docs_set_chunk(int32_t slots)
+{
+    const int32_t prev = sa::g_docs_chunk < 0 ? sa::DOC_CHUNK_DEFAULT : sa::g_docs_chunk;
+    sa::g_docs_chunk = slots < 0 ? -1 : (slots < sa::DOC_CHUNK_MIN ? sa::DOC_CHUNK_MIN : (slots > sa::DOC_CHUNK_MAX ? sa::DOC_CHUNK_MAX : slots));
     return prev;
 }
 
