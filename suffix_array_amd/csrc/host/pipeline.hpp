@@ -345,6 +345,13 @@ struct DeviceBuild {
     bool flat_text = false;             // short text whose byte values are equally frequent: narrower initial keys (geometry_and_probes)
     bool bucket_finished = false;       // ... and k_bucket_sort has already ordered the suffixes tied on those 32 bits by their low key bits
     uint64_t *sorted0 = nullptr;        // the initial keys in SA order (kept for the rank look-ups)
+    // Group-start flags (kernels/common.hpp, OS_HF_*): != nullptr: the last pass of the 64-bit initial sort wrote one flag byte per
+    // slot here instead of the sorted keys, and sr.keys holds true keys only at the ends of that pass's digit runs.  The first
+    // re-rank (group_heads, the rank set-up of the dense route) reads the flags; every other reader of the sorted keys gets them
+    // rebuilt first (rebuild_sorted_keys).  The flags live in w.keysC, which nothing else touches between the last sort pass and
+    // the end of the first k_rr_apply.
+    uint8_t *head_flags = nullptr;
+    bool flags_slab_ok = true;          // w.keysC is device memory (reduced-memory route: it may be the pinned host block -- then the key route is taken)
     // ---- the tied list and its buffers (from first_round_from_sorted_keys on) ----
     TiedList L;
     int64_t tiles = 0, depth = 0;       // tiles: RR_TILE-element tiles of the whole array (the re-rank steps straight from the initial order)
@@ -425,12 +432,14 @@ struct DeviceBuild {
 
     // ---- the re-rank step: k_rr_count, k_rr_scan (a round: k_rr_scan_round, finish_round), k_rr_apply (kernels/rerank.hpp) ----
     // One launcher each, over the RR_TILE-element tiles of m elements; tile_cnt / tile_head / total == nullptr: the workspace's.
-    template <bool FIRST, typename KeyT = uint64_t, bool PARENTS = false>
+    // FLAGS: the groups come from head_flags, not from the keys (the first re-rank behind a flags pass of the initial sort)
+    template <bool FIRST, typename KeyT = uint64_t, bool PARENTS = false, bool FLAGS = false>
     int rr_count(const KeyT *keys, const uint32_t *U, int64_t m, uint32_t *tile_first = nullptr, int g_shift = 0, const uint32_t *gate = nullptr,
                  uint32_t *tile_cnt = nullptr, uint32_t *tile_head = nullptr)
     {
-        PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_rr_count<FIRST, KeyT, PARENTS>), dim3((unsigned)ceil_div(m, RR_TILE)), dim3(RR_THREADS), 0, st, keys, U, m,
-                                                    tile_cnt ? tile_cnt : w.tcnt, tile_head ? tile_head : w.thead, 0, tile_first, g_shift, gate));
+        PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_rr_count<FIRST, KeyT, PARENTS, FLAGS>), dim3((unsigned)ceil_div(m, RR_TILE)), dim3(RR_THREADS), 0, st, keys, U, m,
+                                                    tile_cnt ? tile_cnt : w.tcnt, tile_head ? tile_head : w.thead, 0, tile_first, g_shift, gate,
+                                                    FLAGS ? (const uint8_t *)head_flags : (const uint8_t *)nullptr));
         return SA_AMD_OK;
     }
     int rr_scan(int64_t m, uint32_t *tile_cnt = nullptr, uint32_t *tile_head = nullptr, uint32_t *total = nullptr)
@@ -439,14 +448,38 @@ struct DeviceBuild {
                                                                       tile_head ? tile_head : w.thead, ceil_div(m, RR_TILE), total ? total : w.total));
         return SA_AMD_OK;
     }
-    template <bool FIRST, bool WRITE_SA, int ISA_MODE, typename KeyT = uint64_t, bool FTAIL = false>
+    template <bool FIRST, bool WRITE_SA, int ISA_MODE, typename KeyT = uint64_t, bool FTAIL = false, bool FLAGS = false>
     int rr_apply(const KeyT *keys, const RrApply &a)
     {
-        PROF(KC_RR_APPLY, a.m, st, hipLaunchKernelGGL((k_rr_apply<FIRST, WRITE_SA, ISA_MODE, KeyT, FTAIL>), dim3((unsigned)ceil_div(a.m, RR_TILE)), dim3(RR_THREADS), 0, st,
+        PROF(KC_RR_APPLY, a.m, st, hipLaunchKernelGGL((k_rr_apply<FIRST, WRITE_SA, ISA_MODE, KeyT, FTAIL, FLAGS>), dim3((unsigned)ceil_div(a.m, RR_TILE)), dim3(RR_THREADS), 0, st,
                                                       keys, a.V, a.U, a.m, a.tile_cnt ? a.tile_cnt : (const uint32_t *)w.tcnt,
                                                       a.tile_head ? a.tile_head : (const uint32_t *)w.thead, a.SA, a.ISA, a.Uo, a.Go, a.Vo, a.n_text, a.has_isa, a.g_shift,
                                                       a.pair_k, a.pair_v, a.tile_total ? a.tile_total : (const uint32_t *)w.total, a.key_shift, a.tile_next,
-                                                      a.parent_tail, a.changed_cnt, a.gate, a.sa_final));
+                                                      a.parent_tail, a.changed_cnt, a.gate, a.sa_final,
+                                                      FLAGS ? (const uint8_t *)head_flags : (const uint8_t *)nullptr));
+        return SA_AMD_OK;
+    }
+    // the rank set-up of the dense route (ISA_MODE 0: direct ISA stores, 2: ranks for the binned scatter): tail or head ranks,
+    // groups from the flags or from the sorted keys
+    template <int ISA_MODE>
+    int rr_apply_setup(const RrApply &a)
+    {
+        const uint64_t *k = sr.keys;
+        if (head_flags)
+            return isa_tail_ranks ? rr_apply<true, false, ISA_MODE, uint64_t, true, true>(k, a) : rr_apply<true, false, ISA_MODE, uint64_t, false, true>(k, a);
+        return isa_tail_ranks ? rr_apply<true, false, ISA_MODE, uint64_t, true>(k, a) : rr_apply<true, false, ISA_MODE>(k, a);
+    }
+    // Flags were emitted but the route that follows reads the sorted keys (compaction for the text rounds, rank look-ups of the
+    // sparse rounds): sr.keys[i] = the initial key of suffix SA[i], by the device function those look-ups compare with.  Rare in
+    // real use (the flags are asked for only when the dense route is expected) and dear: about 50 ms at 256 MiB with gram keys.
+    int rebuild_sorted_keys()
+    {
+        if (!head_flags) return SA_AMD_OK;
+        int64_t blocks = ceil_div(n, GK_THREADS);
+        if (blocks > 65536) blocks = 65536;
+        PROF(KC_GATHER, n, st, hipLaunchKernelGGL((k_keys_of_suffixes), dim3((unsigned)blocks), dim3(GK_THREADS), 0, st, dT, P, n, (const uint32_t *)SA, sr.keys));
+        head_flags = nullptr;
+        if (trace) fprintf(stderr, "suffix_array_amd: sorted keys rebuilt from the suffix array (the route taken reads them)\n");
         return SA_AMD_OK;
     }
     // what every re-rank straight from the initial order shares: all n slots in, the first tied list out
@@ -1030,6 +1063,7 @@ struct DeviceBuild {
         // 3. packed keys, 4. initial sort: all key bits as (u64 key, u32 suffix) pairs, or only the top 32 bits as
         //    (u32, u32) pairs in 12 Ki-element tiles -- two thirds of the bytes per pass and half the passes
         sr.keys = w.keysA; sr.vals = w.valsA; sr.passes = 0;
+        head_flags = nullptr;
         sorted32 = nullptr;               // top-32 stage: the sorted 32-bit keys (no 64-bit sorted array exists)
         bucket_finished = false;
         // value of pair i = i: not stored by k_build_keys, the first sort pass takes the index (saves 8 B / suffix)
@@ -1072,8 +1106,17 @@ struct DeviceBuild {
             }
 #endif
             if (!ss_done) {
-            rc = sort_pairs(w.keysA, w.valsA, w.keysB, w.valsB, n, 0, key_bits, w.ss, SA, st, &sr, tn, iota, sigma == 1, counted);
+            // Group-start flags instead of sorted keys from the last pass (head_flags above): asked for when the dense route is
+            // expected -- its first re-rank is the only reader of the sorted keys then.  Tuning::head_flags 0: never, 2: always
+            // (the routes that need the keys rebuild them: rebuild_sorted_keys); diagnostic library only.
+            const bool dense_expected = force_dense || probe_dense || !text_ok;
+            const bool want_flags = tn.head_flags != 0 && (tn.head_flags == 2 || dense_expected) && flags_slab_ok && onesweep_on(w.ss, tn) && !timing_only() &&
+                                    !tn.fused64 && n >= 2 && key_bits > 0;
+            rc = sort_pairs(w.keysA, w.valsA, w.keysB, w.valsB, n, 0, key_bits, w.ss, SA, st, &sr, tn, iota, sigma == 1, counted,
+                            want_flags ? (uint8_t *)w.keysC : (uint8_t *)nullptr);
             if (rc) return rc;
+            if (want_flags && sr.passes > 0 && sr.vals == SA) head_flags = (uint8_t *)w.keysC;      // (the last pass always runs: it delivers into SA)
+            if (trace && head_flags) fprintf(stderr, "suffix_array_amd: initial sort: the last pass wrote group-start flags, not the sorted keys\n");
             local.sort_passes += sr.passes; local.sorted_elements += (int64_t)sr.passes * n;
             }
         }
@@ -1229,7 +1272,9 @@ struct DeviceBuild {
         int rc = SA_AMD_OK; (void)rc;
         if (!finished32 && !fused64) {
         // (64-bit keys: also every tile's first group start: the dense route's first ranks are tail ranks, k_rr_apply FTAIL)
-        rc = top_shift ? rr_count<true, uint32_t>(sorted32, nullptr, n) : rr_count<true, uint64_t, true>((const uint64_t *)sr.keys, nullptr, n, w.tnext);
+        rc = top_shift ? rr_count<true, uint32_t>(sorted32, nullptr, n)
+           : head_flags ? rr_count<true, uint64_t, true, true>((const uint64_t *)sr.keys, nullptr, n, w.tnext)
+                        : rr_count<true, uint64_t, true>((const uint64_t *)sr.keys, nullptr, n, w.tnext);
         if (rc) return rc;
         if ((rc = rr_scan(n))) return rc;
         { const int rcw = read_words(&m32, w.total, 4, st); if (rcw) return rcw; }
@@ -1299,8 +1344,7 @@ struct DeviceBuild {
                 uint64_t *pk_out = from_sa ? (uint64_t *)nullptr : pk;
                 uint32_t *pv_out = from_sa ? pk32 + H + 1 : w.U1;
                 a.pair_k = pk_out; a.pair_v = pv_out;
-                rc = isa_tail_ranks ? rr_apply<true, false, 2, uint64_t, true>(sr.keys, a) : rr_apply<true, false, 2>(sr.keys, a);
-                if (rc) return rc;
+                if ((rc = rr_apply_setup<2>(a))) return rc;
                 if (from_sa) {
                     hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, st, dSA, (uint32_t)n);
                     LAUNCH_CHECK(st);
@@ -1308,9 +1352,10 @@ struct DeviceBuild {
                 } else
                     rc = scatter_binned((uint32_t *)pk, w.U1, (uint32_t *)sr.keys, w.G1, n, n, w, st, &local, tn);
                 if (rc) return rc;
-            } else if ((rc = isa_tail_ranks ? rr_apply<true, false, 0, uint64_t, true>(sr.keys, a) : rr_apply<true, false, 0>(sr.keys, a))) return rc;
+            } else if ((rc = rr_apply_setup<0>(a))) return rc;
         } else if (L.m > 0) {
             // compaction only; the sorted initial keys stay intact for the rank look-ups
+            if ((rc = rebuild_sorted_keys())) return rc;
             HIP_TRY(hipMemsetAsync(w.has_isa, 0, ((size_t)n + 31) / 32 * 4, st));
             if (!lists_ready) {
                 L.keys_beside(w, sr.keys);
@@ -1483,6 +1528,7 @@ static int build_device(const uint8_t *dT, uint32_t *dSA, int32_t n32, void *dWo
     B.w = dWork2 ? carve(dWork, n, (size_t)work_bytes, dWork2) : carve(dWork, n);
     const Workspace &w = B.w;
     if ((int64_t)w.bytes > work_bytes || (int64_t)w.bytes2 > work2_bytes) return SA_AMD_EINVAL;
+    B.flags_slab_ok = !dWork2 || ((char *)w.keysC >= (char *)dWork && (char *)w.keysC + n <= (char *)dWork + work_bytes);
     if (n <= tn.small_max) {
         // small texts: the whole construction in one launch of one workgroup, everything in LDS (kernels/small.hpp)
         if (n <= SM_LITE_SINGLE_N)

@@ -173,7 +173,10 @@ static int sort_pairs_onesweep(KeyT *keys_in, uint32_t *vals_in, KeyT *keys_alt,
                                const uint8_t *text = nullptr, int64_t text_n = 0,      // != nullptr (32-bit keys only): the FIRST pass reads its keys from the text (k_onesweep<..., TEXT_KEYS>)
                                int text_bits = 8,                                      //   8: the text itself (all 256 byte values), 2: the bit-packed text of a four-symbol alphabet
                                int val_extra = 0,                                      //   the first pass puts that many key bits below the 32 into the top bits of the values (OnesweepPass::val_extra)
-                               KeyT *keys_out2 = nullptr)                              // != nullptr: keys_in is read-only -- the second pass writes its keys here, not into keys_in
+                               KeyT *keys_out2 = nullptr,                              // != nullptr: keys_in is read-only -- the second pass writes its keys here, not into keys_in
+                               uint8_t *head_flags = nullptr,                          // != nullptr (64-bit keys, final_vals): the last pass writes `count` group-start flags here and only the keys at
+                                                                                       //   the ends of its tiles' digit runs (k_onesweep<..., HEAD_FLAGS>); the rest of *keys_res is then unspecified
+                               bool poison_keys = false)                               // diagnostic library: fill that pass's key buffer with 0xA5 bytes first (sa_amd_test_sort_pairs_flags)
 {
     constexpr int TILE = THREADS * ITEMS;
     constexpr int R = 1 << RBITS;
@@ -259,7 +262,19 @@ static int sort_pairs_onesweep(KeyT *keys_in, uint32_t *vals_in, KeyT *keys_alt,
         P.flags = (uint32_t)tn.onesweep_flags;
         P.text = text; P.text_n = text_n; P.text_bits = text_bits;
         P.val_extra = (text && *passes == 0 && iota) ? val_extra : 0;
-        if (!K64 && !SEQ && text && *passes == 0)
+        // (the flags pass exists for 64-bit keys only: a 32-bit sort ignores head_flags, and so does every pass but the last)
+        constexpr bool FLAGS_OK = K64 && RBITS == RADIX_BITS;
+        P.head_flags = (FLAGS_OK && last && final_vals) ? head_flags : nullptr;
+        if (P.head_flags) {
+            if constexpr (FLAGS_OK) {
+#ifdef SA_AMD_DIAG
+                if (poison_keys) HIP_TRY(hipMemsetAsync(kout, 0xA5, (size_t)count * sizeof(KeyT), st));
+#endif
+                PROF(KC_ONESWEEP, count, st,
+                     hipLaunchKernelGGL((k_onesweep<THREADS, ITEMS, KeyT, SEQ, WG_PER_CU, RBITS, false, true>), dim3(grid), dim3(THREADS), 0, st, (const KeyT *)kin,
+                                        (const uint32_t *)((iota && *passes == 0) ? nullptr : vin), kout, vdst, P));
+            }
+        } else if (!K64 && !SEQ && text && *passes == 0)
             PROF(KC_ONESWEEP32, count, st,
                  hipLaunchKernelGGL((k_onesweep<THREADS, ITEMS, KeyT, SEQ, WG_PER_CU, RBITS, !K64 && !SEQ>), dim3(grid), dim3(THREADS), 0, st, (const KeyT *)kin,
                                     (const uint32_t *)((iota && *passes == 0) ? nullptr : vin), kout, vdst, P));
@@ -289,13 +304,15 @@ static int sort_pairs(uint64_t *keys_in, uint32_t *vals_in, uint64_t *keys_alt, 
                       int begin_bit, int end_bit, const SortScratch &ss, uint32_t *final_vals,
                       hipStream_t st, SortResult *res, const Tuning &tn, bool iota = false,   // iota: value i = index i, vals_in is scratch only
                       bool may_skip = false,                                                   // look for passes that are the identity (costs a read-back per pass)
-                      bool first_counted = false)                                              // the producer of keys_in has histogrammed the first digit (sort_first_counts says where and how)
+                      bool first_counted = false,                                              // the producer of keys_in has histogrammed the first digit (sort_first_counts says where and how)
+                      uint8_t *head_flags = nullptr, bool poison_keys = false)                 // single-pass engine only, with final_vals: see sort_pairs_onesweep
 {
     res->keys = keys_in; res->vals = vals_in; res->passes = 0; res->skipped = 0;
     if (count <= 1 || end_bit <= begin_bit) return SA_AMD_OK;
     if (onesweep_on(ss, tn)) {
 #define OS_CALL64(T, I, S) sort_pairs_onesweep<uint64_t, T, I, S>(keys_in, vals_in, keys_alt, vals_alt, count, begin_bit, end_bit, ss, final_vals, st, \
-                                                                 &res->keys, &res->vals, &res->passes, &res->skipped, tn, iota, may_skip, first_counted)
+                                                                 &res->keys, &res->vals, &res->passes, &res->skipped, tn, iota, may_skip, first_counted, \
+                                                                 nullptr, 0, 8, 0, nullptr, head_flags, poison_keys)
         switch (tn.onesweep64_shape) {
         case 1: return OS_CALL64(512, 16, true);
         case 2: return OS_CALL64(512, 8, false);

@@ -47,6 +47,8 @@ inline int env_small_max() { return (int)env_int("SA_AMD_SMALL_MAX", 8192, 0, 81
 #ifdef SA_AMD_DIAG
 // the old forms of the re-rank writes (Tuning::sa_every_round / setup_key_copy), set by sa_amd_debug_rerank_routes
 inline std::atomic<int> g_rerank_routes{0};
+// when the last pass of the 64-bit initial sort writes group-start flags (Tuning::head_flags), set by sa_amd_debug_head_flags
+inline std::atomic<int> g_head_flags_mode{1};
 #endif
 
 struct Tuning {
@@ -69,6 +71,9 @@ struct Tuning {
     bool no_run_skip = false;        // SA_AMD_NO_RUN_SKIP: never skip a radix pass whose digit is the same for every element
     int64_t run_skip_min = (int64_t)1 << 25;   // SA_AMD_RUN_SKIP_MIN: smallest refinement sort that looks for such passes
     int64_t dense_rekey_min = (int64_t)1 << 22;   // SA_AMD_DENSE_REKEY_MIN: smallest whole-list global sort that is re-keyed by group index
+    int head_flags = 1;              // the last pass of the 64-bit initial sort writes group-start flags instead of the sorted keys: 0 never, 1 when the dense
+                                     //   route is expected (its first re-rank is then the keys' only reader), 2 always (the keys are rebuilt where needed).
+                                     //   The product library has no switch (always 1); diag library: sa_amd_debug_head_flags, for A/B and the route tests
     bool no_first_tail = false;      // SA_AMD_NO_FIRST_TAIL: the dense route's first ranks are head ranks (the first doubling round then rewrites every rank)
     // the re-rank writes of round 4 (diag library only, sa_amd_debug_rerank_routes: A/B and route tests; the product library has no switch)
     bool sa_every_round = false;     // bit 0: the dense rounds write SA for every listed element each round, not only when it leaves the list
@@ -203,6 +208,8 @@ struct Tuning {
             const int r = g_rerank_routes.load(std::memory_order_relaxed);
             t.sa_every_round = (r & 1) != 0;
             t.setup_key_copy = (r & 2) != 0;
+            const int hf = g_head_flags_mode.load(std::memory_order_relaxed);
+            t.head_flags = hf < 0 ? 0 : (hf > 2 ? 2 : hf);
         }
 #endif
         return t;

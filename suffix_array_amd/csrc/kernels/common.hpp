@@ -37,6 +37,20 @@ __device__ __forceinline__ uint32_t wave_incl_max(uint32_t v)
     return v;
 }
 
+// 64-bit value of lane `src` (two 32-bit shuffles; executed by every lane of the wave)
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
+{
+    return ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src, WAVE) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src, WAVE);
+}
+
+// Group-start flags: one byte per position of the sorted initial order, written by the last pass of the 64-bit initial sort
+// (k_onesweep<..., HEAD_FLAGS>, kernels/onesweep.hpp) and read by the first re-rank (rr_wave_classify_flags, kernels/rerank.hpp)
+// in place of the sorted keys.  A group = a maximal run of equal keys.
+constexpr uint8_t OS_HF_SAME = 0;   // position p continues the group of p - 1
+constexpr uint8_t OS_HF_START = 1;  // p starts a group (always so at p = 0)
+constexpr uint8_t OS_HF_SEAM = 2;   // p is the first element of a tile's digit run: the pass could not see p - 1, but it stored the true
+                                    // keys of p and p - 1 in its key buffer -- p starts a group iff they differ
+
 // Exclusive block sum over THREADS threads; *total receives the block sum. lds: THREADS/64 + 1 words.
 template <int THREADS>
 __device__ __forceinline__ uint32_t block_excl_sum(uint32_t v, uint32_t *lds, uint32_t *total)

@@ -440,6 +440,19 @@ __device__ __forceinline__ uint64_t text_key(const uint8_t *__restrict__ T, cons
     return tk;
 }
 
+// keys[i] = the initial key of suffix sa[i]: the sorted keys again, for a build whose last sort pass wrote group-start flags
+// instead of them (DeviceBuild::rebuild_sorted_keys) and that turns out to need them.  Same zero padding as k_build_keys.
+__global__ __launch_bounds__(GK_THREADS) void k_keys_of_suffixes(const uint8_t *__restrict__ T, KeyParams P, int64_t n, const uint32_t *__restrict__ sa,
+                                                                  uint64_t *__restrict__ keys)
+{
+    __shared__ uint8_t lcode[256];
+    lcode[threadIdx.x] = P.code[threadIdx.x];
+    __syncthreads();
+    const bool al = (((uintptr_t)T) & 7) == 0;
+    for (int64_t i = (int64_t)blockIdx.x * GK_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * GK_THREADS)
+        keys[i] = text_key(T, lcode, P, n, (int64_t)sa[i], P.k, al);
+}
+
 // ---- entropy probe + two-stage initial sort ---------------------------------------------------
 // When the top 32 bits of the packed key already separate almost all suffixes (random bytes, DNA),
 // the initial sort only needs those 32 bits (two global passes + kernels/bucket_sort.hpp, or four global passes); the few ties are finished by a refinement round on the

@@ -198,14 +198,23 @@ struct OnesweepPass {
                                     //   32 - e: host-checked), so that the bucket sort orders 32 + e key bits (kernels/bucket_sort.hpp); e <= 2
     uint32_t flags;                 // bit 0: look at the predecessors' granules before the staging, not after (scheduling A/B, same
                                     // result); bit 7 (diagnostic library only): phase stamps
+    uint8_t *head_flags;            // HEAD_FLAGS instances (last pass of the 64-bit initial sort): one byte per output position, see k_onesweep
 };
+
 
 // THREADS x ITEMS elements per tile.  SEQ = false: keys and values are staged in LDS side by side (one workgroup per CU at the
 // sizes in use); SEQ = true: the values go through the keys' buffer once the keys are out, which leaves room for TWO
 // workgroups per CU -- while one waits (look-back, barriers, the ranking's ALU work) the other one's loads and stores flow.
 // RBITS: digit width (8, or 9 for the two global passes in front of the bucket sort of a text of more than 2^29 suffixes)
 // TEXT_KEYS: the first pass of the 32-bit stage over a text of all 256 byte values -- key of element i = text_key32(P.text, i)
-template <int THREADS, int ITEMS, typename KeyT, bool SEQ, int WG_PER_CU, int RBITS = RADIX_BITS, bool TEXT_KEYS = false>
+// HEAD_FLAGS: the LAST pass of the 64-bit initial sort, whose sorted keys are only ever compared with their left neighbours
+// (group heads, kernels/rerank.hpp).  The tile is staged in output order, so the pass answers that itself: it writes one byte per
+// output position to P.head_flags (OS_HF_*) instead of the 8-byte key.  Two slots adjacent inside a digit run of the tile are
+// adjacent in the output; only the FIRST slot of a digit run has its output predecessor elsewhere -- the last slot of the same
+// digit's run in whichever earlier tile or segment held that digit last.  So the first and the last slot of every digit run
+// still store their keys (32 of 8192 on a five-bit last digit), the first slot gets OS_HF_SEAM, and the reader compares
+// keys_out[p] with keys_out[p - 1] there.  Every other entry of keys_out is left unwritten: nothing may read it.
+template <int THREADS, int ITEMS, typename KeyT, bool SEQ, int WG_PER_CU, int RBITS = RADIX_BITS, bool TEXT_KEYS = false, bool HEAD_FLAGS = false>
 __global__ __launch_bounds__(THREADS, WG_PER_CU * THREADS / 256) void k_onesweep(
     const KeyT *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, KeyT *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
     OnesweepPass P)
@@ -214,6 +223,7 @@ __global__ __launch_bounds__(THREADS, WG_PER_CU * THREADS / 256) void k_onesweep
     constexpr int RADIX_BITS = RBITS;
     static_assert(RBITS == 8 || !SEQ, "the digits of the sequential shapes travel as bytes");
     static_assert(!TEXT_KEYS || sizeof(KeyT) == 4, "text keys are the top 32 key bits");
+    static_assert(!HEAD_FLAGS || (sizeof(KeyT) == 8 && !TEXT_KEYS && RBITS == 8), "group-start flags: last pass of the 64-bit sort");
     constexpr int TILE = THREADS * ITEMS;
     constexpr int NWAVES = THREADS / WAVE;
     constexpr int WAVE_ELEMS = WAVE * ITEMS;
@@ -521,9 +531,21 @@ __global__ __launch_bounds__(THREADS, WG_PER_CU * THREADS / 256) void k_onesweep
                 kx = lds_k[idx];
                 d = digit_of(kx, P.shift, P.dmask);
                 gp = goff[d] + (uint32_t)idx;
-                keys_out[gp] = kx;
+                if (!HEAD_FLAGS) keys_out[gp] = kx;
                 if (!SEQ) vals_out[gp] = lds_v[idx];
                 else dpack[j >> 2] |= d << (8 * (j & 3));
+            }
+            if constexpr (HEAD_FLAGS) {
+                // slot idx - 1 is the neighbouring lane's (its key comes by shuffle, executed by every lane); lane 0 reads it from the stage
+                uint64_t left = shfl64((uint64_t)kx, l ? l - 1 : 0);
+                if (ok) {
+                    const uint32_t run_begin = digit_base[d];
+                    const uint32_t run_end = d + 1 < (uint32_t)RADIX ? digit_base[(d + 1) & (RADIX - 1)] : (uint32_t)valid;
+                    const bool first = (uint32_t)idx == run_begin;
+                    if (l == 0 && !first) left = (uint64_t)lds_k[idx - 1];
+                    P.head_flags[gp] = gp == 0 ? OS_HF_START : (first ? OS_HF_SEAM : ((uint64_t)kx != left ? OS_HF_START : OS_HF_SAME));
+                    if (first || (uint32_t)idx + 1u == run_end) keys_out[gp] = kx;
+                }
             }
             if (count_next) {
                 // (segment-major in LDS: neighbouring lanes carry different digits, i.e. different banks -- digit-major put the whole

@@ -33,11 +33,6 @@ constexpr int RR_WAVE_ELEMS = WAVE * RR_ITEMS;   // 512 consecutive elements per
 // last subgroup alone (see k_rr_apply)
 struct WaveGroups { uint64_t head[RR_ITEMS], tied[RR_ITEMS], valid[RR_ITEMS], phead[RR_ITEMS]; };
 
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
-{
-    return ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src, WAVE) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src, WAVE);
-}
-
 template <typename KeyT, bool PARENTS = false>
 __device__ __forceinline__ WaveGroups rr_wave_classify(const KeyT *__restrict__ keys, int64_t m, int64_t wbase, int key_shift, int g_shift = 0,
                                                        uint64_t *kout = nullptr)      // kout: the wave's keys, [RR_ITEMS] = the key before the wave
@@ -81,6 +76,64 @@ __device__ __forceinline__ WaveGroups rr_wave_classify(const KeyT *__restrict__ 
     return g;
 }
 
+// The same masks from the group-start flags of the initial sort's last pass (OS_HF_*, kernels/common.hpp) -- the FIRST re-rank
+// behind a k_onesweep<..., HEAD_FLAGS> pass: one byte per element instead of its 8-byte key.  `keys` is that pass's key buffer and
+// is read only at OS_HF_SEAM positions (p and p - 1: the two entries the pass guarantees).  phead == head: the first ranks
+// have no parent groups (g_shift == 0).
+// A wave's 512 flag bytes come in ONE load of 8 bytes per lane (lane l: elements 8 l .. 8 l + 7 of the wave; the flag slab is
+// 8-byte aligned and 8 (n + 64) bytes long, so the last wave reads, and masks, a few bytes behind the n flags); every lane turns
+// its bytes into 8 head bits, and the wave's 64 such bytes ARE head[0 .. 7] in order: four lanes' bytes are joined into a word
+// and sixteen v_readlane fetch them.  (Measured on C3, 2^28 slots: byte loads in the wave-striped layout of the keys -- eight
+// 64-byte loads per wave -- left k_rr_count at 427 us, 0.63 TB/s: bound by load instructions, not bytes.)
+template <bool PARENTS = false>
+__device__ __forceinline__ WaveGroups rr_wave_classify_flags(const uint8_t *__restrict__ flags, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase)
+{
+    const int l = lane_id();
+    WaveGroups g;
+    const int64_t i0 = wbase + 8 * l;                           // this lane's eight elements
+    const int64_t a = wbase + RR_WAVE_ELEMS;                    // (uniform) the element behind the wave
+    // (its flag is loaded here, next to the wave's own: the kernels that call this do so little per tile that the memory round
+    // trips in a row, not the bytes, are their time)
+    const uint8_t fa = a < m ? flags[a] : OS_HF_START;
+    uint32_t hb = 0;                                            // bit k: element i0 + k starts a group
+    if (i0 < m) {
+        const uint2 w = *(const uint2 *)(flags + i0);
+        // bit 0 of every byte (OS_HF_START) -> four bits per word
+        hb = (((w.x & 0x01010101u) * 0x01020408u) >> 24 & 15u) | ((((w.y & 0x01010101u) * 0x01020408u) >> 24 & 15u) << 4);
+        if ((w.x | w.y) & 0x02020202u) {                        // (rare: the first element of a digit run of a tile of the sort)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const uint32_t f = ((k < 4 ? w.x : w.y) >> (8 * (k & 3))) & 255u;
+                if (f == OS_HF_SEAM && i0 + k < m && i0 + k > 0 && keys[i0 + k] != keys[i0 + k - 1]) hb |= 1u << k;
+            }
+        }
+        if (i0 == 0) hb |= 1u;
+        if (i0 + 8 > m) hb &= (1u << (int)(m - i0)) - 1u;       // (elements behind the end are no heads)
+    }
+    // lane 4 q: the head bytes of lanes 4 q .. 4 q + 3 as one word (shuffles executed by every lane)
+    const uint32_t h1 = (uint32_t)__shfl_down((int)hb, 1, WAVE), h2 = (uint32_t)__shfl_down((int)hb, 2, WAVE), h3 = (uint32_t)__shfl_down((int)hb, 3, WAVE);
+    const uint32_t quad = hb | (h1 << 8) | (h2 << 16) | (h3 << 24);
+    const int64_t left = m - wbase;                             // (uniform) elements of the wave that exist: all 512, or fewer in the last one
+#pragma unroll
+    for (int r = 0; r < RR_ITEMS; ++r) {
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)quad, 8 * r), hi = (uint32_t)__builtin_amdgcn_readlane((int)quad, 8 * r + 4);
+        const int64_t here = left - 64 * r;
+        g.valid[r] = here >= 64 ? ~0ull : (here <= 0 ? 0ull : ((1ull << here) - 1ull));
+        g.head[r] = (((uint64_t)hi << 32) | lo) & g.valid[r];
+        g.phead[r] = PARENTS ? g.head[r] : 0ull;
+    }
+    const bool boundary_after = fa == OS_HF_START || (fa == OS_HF_SEAM && keys[a] != keys[a - 1]);
+#pragma unroll
+    for (int r = 0; r < RR_ITEMS; ++r) {
+        const uint64_t bnd = g.head[r] | ~g.valid[r];
+        const uint64_t bnd_next0 = (r + 1 < RR_ITEMS) ? ((g.head[(r + 1) % RR_ITEMS] | ~g.valid[(r + 1) % RR_ITEMS]) & 1ull)
+                                                      : (boundary_after ? 1ull : 0ull);
+        const uint64_t next = (bnd >> 1) | (bnd_next0 << 63);
+        g.tied[r] = g.valid[r] & ~(g.head[r] & next);
+    }
+    return g;
+}
+
 // "head code" of the dense doubling rounds: (list index of a group start << 1) | (it also starts a parent group);
 // RR_NO_HEAD: there is none (list indices are below 2^31, so the code of index m with the parent bit set is the same word)
 constexpr uint32_t RR_NO_HEAD = 0xffffffffu;
@@ -101,19 +154,24 @@ __device__ __forceinline__ uint32_t rr_first_head_code(const WaveGroups &g, int6
 
 // PARENTS (dense doubling rounds): also tile_first, the head code of the tile's first group start (g_shift: the parent
 // group is the key above that bit)
-template <bool FIRST, typename KeyT = uint64_t, bool PARENTS = false>
+// FLAGS (FIRST only): the groups come from head_flags (rr_wave_classify_flags), `keys` is the flag pass's sparsely written key buffer
+template <bool FIRST, typename KeyT = uint64_t, bool PARENTS = false, bool FLAGS = false>
 __global__ __launch_bounds__(RR_THREADS) void k_rr_count(const KeyT *__restrict__ keys,
                                                           const uint32_t *__restrict__ U, int64_t m,
                                                           uint32_t *__restrict__ tile_cnt,
                                                           uint32_t *__restrict__ tile_head, int key_shift,
                                                           uint32_t *__restrict__ tile_first, int g_shift,
-                                                          const uint32_t *__restrict__ gate = nullptr)      // != nullptr: the launch does nothing when *gate != 0 (see RoundCtl, host/pipeline.hpp)
+                                                          const uint32_t *__restrict__ gate = nullptr,      // != nullptr: the launch does nothing when *gate != 0 (see RoundCtl, host/pipeline.hpp)
+                                                          const uint8_t *__restrict__ head_flags = nullptr)
 {
+    static_assert(!FLAGS || (FIRST && sizeof(KeyT) == 8), "group-start flags come from the 64-bit initial sort");
     __shared__ uint32_t wcnt[RR_THREADS / WAVE], whead[RR_THREADS / WAVE], wfirst[RR_THREADS / WAVE];
     if (gate && *gate) return;
     const int64_t wbase = (int64_t)blockIdx.x * RR_TILE + (int64_t)wave_id() * RR_WAVE_ELEMS;
     uint64_t kk[RR_ITEMS + 1];
-    const WaveGroups g = rr_wave_classify<KeyT, false>(keys, m, wbase, key_shift, 0, PARENTS ? kk : nullptr);
+    WaveGroups g;
+    if constexpr (FLAGS) g = rr_wave_classify_flags<false>(head_flags, (const uint64_t *)keys, m, wbase);
+    else g = rr_wave_classify<KeyT, false>(keys, m, wbase, key_shift, 0, PARENTS ? kk : nullptr);
     uint32_t cnt = 0, lasthead = 0;
 #pragma unroll
     for (int r = 0; r < RR_ITEMS; ++r) {
@@ -133,11 +191,14 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_count(const KeyT *__restrict_
             if (!found && g.head[r]) {                          // (uniform)
                 found = true;
                 const int b = __builtin_ctzll(g.head[r]);
+                const int64_t i = wbase + 64 * r + b;
+                if constexpr (FLAGS) first_code = ((uint32_t)i << 1) | 1u;      // (no parent groups yet: every group start starts its parent too)
+                else {
                 const uint64_t mine = shfl64(kk[r], b);
                 const uint64_t left = b ? shfl64(kk[r], b - 1) : (r ? shfl64(kk[r ? r - 1 : 0], 63) : kk[RR_ITEMS]);
-                const int64_t i = wbase + 64 * r + b;
                 const uint32_t ph = (i == 0 || ((mine ^ left) >> g_shift) != 0ull) ? 1u : 0u;
                 first_code = ((uint32_t)i << 1) | ph;
+                }
             }
         }
     }
@@ -272,7 +333,8 @@ __global__ __launch_bounds__(SPINE_THREADS) void k_rr_scan_round(uint32_t *__res
 // (ISA = group heads, has_isa = bitmap, pair_v = counts per tile) instead of being listed, 2 = write (suffix, rank) pairs in slot order; the host bins them by suffix position
 // with one radix pass and k_scatter_pairs then writes the ISA window by window (a random 4-byte
 // store costs a whole 64-byte memory transaction, a binned one is merged in the caches).
-template <bool FIRST, bool WRITE_SA, int ISA_MODE, typename KeyT = uint64_t, bool FTAIL = false>
+// FLAGS (FIRST only): as in k_rr_count
+template <bool FIRST, bool WRITE_SA, int ISA_MODE, typename KeyT = uint64_t, bool FTAIL = false, bool FLAGS = false>
 __global__ __launch_bounds__(RR_THREADS) void k_rr_apply(
     const KeyT *__restrict__ keys, const uint32_t *__restrict__ V, const uint32_t *__restrict__ U, int64_t m,
     const uint32_t *__restrict__ tile_cnt, const uint32_t *__restrict__ tile_head, uint32_t *__restrict__ SA,
@@ -281,8 +343,10 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_apply(
     uint32_t *__restrict__ pair_v, const uint32_t *__restrict__ tile_total, int key_shift,
     const uint32_t *__restrict__ tile_next, int parent_tail, uint32_t *__restrict__ changed_cnt,
     const uint32_t *__restrict__ gate = nullptr,      // != nullptr: the launch does nothing when *gate != 0
-    int sa_final = 0)                                 // 1: SA[slot] = suffix only for the elements that leave the tied list (see below)
+    int sa_final = 0,                                 // 1: SA[slot] = suffix only for the elements that leave the tied list (see below)
+    const uint8_t *__restrict__ head_flags = nullptr)
 {
+    static_assert(!FLAGS || (FIRST && sizeof(KeyT) == 8), "group-start flags come from the 64-bit initial sort");
     constexpr bool SPARSE = ISA_MODE == 1;
     if (gate && *gate) return;
     // Dense doubling rounds (TAIL): the rank of a group is its LAST slot + 1 (Larsson-Sadakane's group number).  When a
@@ -310,7 +374,9 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_apply(
     }
     const int l = lane_id(), w = wave_id();
     const int64_t wbase = (int64_t)blockIdx.x * RR_TILE + (int64_t)w * RR_WAVE_ELEMS;
-    const WaveGroups g = rr_wave_classify<KeyT, TAIL>(keys, m, wbase, key_shift, g_shift);
+    WaveGroups g;
+    if constexpr (FLAGS) g = rr_wave_classify_flags<TAIL>(head_flags, (const uint64_t *)keys, m, wbase);
+    else g = rr_wave_classify<KeyT, TAIL>(keys, m, wbase, key_shift, g_shift);
     uint32_t slot[RR_ITEMS], v[RR_ITEMS];
 #pragma unroll
     for (int r = 0; r < RR_ITEMS; ++r) {

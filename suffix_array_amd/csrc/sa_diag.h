@@ -19,10 +19,20 @@ int32_t sa_amd_debug_group_sort_stamps(int32_t on);
  * bit 0: dense rounds write SA for every listed suffix each round (not only in the round it leaves the list),
  * bit 1: the binned rank set-up copies SA into its pair keys (instead of binning straight from the suffix array) */
 int32_t sa_amd_debug_rerank_routes(int32_t flags);
+/* when the last pass of the 64-bit initial sort writes group-start flags instead of the sorted keys (process-wide; returns the
+ * previous mode): 0 never (the key route), 1 when the dense route is expected (what the product library always does), 2 whenever
+ * that sort runs -- the routes that read the sorted keys then rebuild them.  Every mode gives the same array and statistics. */
+int32_t sa_amd_debug_head_flags(int32_t mode);
 int32_t sa_amd_debug_sort_variant_count(void);
 const char *sa_amd_debug_sort_variant_name(int32_t index);
 /* stable LSD radix sort of (u64 key, u32 value) pairs on bits [begin_bit, end_bit); host buffers */
 int32_t sa_amd_test_sort_pairs(uint64_t *keys, uint32_t *vals, int64_t count, int32_t begin_bit, int32_t end_bit);
+/* the same sort (single-pass engine) with the flags variant of its last pass: vals = the sorted order; flags_out[count] = one byte
+ * per output position p: 0 = p continues the group (run of equal keys) of p - 1, 1 = p starts a group, 2 = compare
+ * keys_out[p] with keys_out[p - 1] (both are true sorted keys there); keys_out[count] = that pass's key buffer, 0xA5 bytes wherever
+ * the pass stored nothing; keys is read only */
+int32_t sa_amd_test_sort_pairs_flags(const uint64_t *keys, uint32_t *vals, int64_t count, int32_t begin_bit, int32_t end_bit,
+                                     uint8_t *flags_out, uint64_t *keys_out);
 /* the sample sort of the 64-bit stage (kernels/sample_sort.hpp; count >= 262 144): keys in order out, vals[i] = the index key i came
  * from; *done = 0: a bucket that is no equality bucket did not fit a workgroup -- the pipeline then takes the LSD sort */
 int32_t sa_amd_test_sample_sort64(uint64_t *keys, uint32_t *vals, int64_t count, int32_t key_bits, int32_t *done);

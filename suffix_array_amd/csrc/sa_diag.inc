@@ -24,6 +24,11 @@ SA_EXPORT int32_t sa_amd_debug_rerank_routes(int32_t flags)
     return sa::g_rerank_routes.exchange(flags & 3);
 }
 
+SA_EXPORT int32_t sa_amd_debug_head_flags(int32_t mode)
+{
+    return sa::g_head_flags_mode.exchange(mode < 0 ? 0 : (mode > 2 ? 2 : mode));
+}
+
 SA_EXPORT int32_t sa_amd_debug_sort_variant_count(void) { return sa::N_SORT_VARIANTS; }
 SA_EXPORT const char *sa_amd_debug_sort_variant_name(int32_t i)
 {
@@ -57,6 +62,46 @@ SA_EXPORT int32_t sa_amd_test_sort_pairs(uint64_t *keys, uint32_t *vals, int64_t
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(keys, sr.keys, N * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(vals, sr.vals, N * 4, hipMemcpyDeviceToHost));
+    { uint32_t e = 0; HIP_TRY(hipMemcpy(&e, ss.err, 4, hipMemcpyDeviceToHost)); if (e) return SA_AMD_EINTERNAL; }
+    return SA_AMD_OK;
+}
+
+// The same sort with the flags variant of the last pass (k_onesweep<..., HEAD_FLAGS>; single-pass engine only): vals = the sorted
+// order, flags_out[count] = the group-start flags, keys_out[count] = that pass's key buffer, filled with 0xA5 bytes in front of it
+// (only the keys at the ends of the tiles' digit runs are stored).  `keys` is not written.  count == 1: no pass runs, flag 1.
+SA_EXPORT int32_t sa_amd_test_sort_pairs_flags(const uint64_t *keys, uint32_t *vals, int64_t count, int32_t begin_bit, int32_t end_bit,
+                                               uint8_t *flags_out, uint64_t *keys_out)
+{
+    using namespace sa;
+    if (count <= 0 || !keys || !vals || !flags_out || !keys_out || begin_bit < 0 || end_bit > 64 || end_bit <= begin_bit) return SA_AMD_EINVAL;
+    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
+    const size_t N = (size_t)count;
+    memset(keys_out, 0xA5, N * 8);
+    if (count == 1) { flags_out[0] = OS_HF_START; return SA_AMD_OK; }
+    DevBuf dk, dv, dsp, dst, df;
+    int32_t rc;
+    if ((rc = dk.alloc(N * 8 * 2))) return rc;
+    if ((rc = dv.alloc(N * 4 * 3))) return rc;
+    if ((rc = df.alloc(N))) return rc;
+    if ((rc = dsp.alloc(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4))) return rc;
+    if ((rc = dst.alloc(((size_t)ceil_div(count, OS_MIN_TILE) + 1) * RADIX * 8 + 256))) return rc;
+    uint64_t *k = dk.as<uint64_t>(); uint32_t *v = dv.as<uint32_t>(), *spine = dsp.as<uint32_t>();
+    HIP_TRY(hipMemcpy(k, keys, N * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(v, vals, N * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(df.p, 0xff, N));
+    HIP_TRY(hipMemset(dst.p, 0, 256));
+    SortScratch ss; ss.spine = spine; ss.digit_tot = spine + (size_t)RADIX * SORT_MAX_WG;
+    ss.err = dst.as<uint32_t>(); ss.status = (unsigned long long *)(dst.as<char>() + 256);
+    if (!onesweep_on(ss, tn)) return SA_AMD_EINVAL;      // (the three-kernel engine has no flags variant)
+    SortResult sr;
+    rc = sort_pairs(k, v, k + N, v + N, count, begin_bit, end_bit, ss, v + 2 * N, nullptr, &sr, tn, false, false, false, df.as<uint8_t>(), true);
+    if (rc != SA_AMD_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (sr.vals != v + 2 * N) return SA_AMD_EINTERNAL;
+    HIP_TRY(hipMemcpy(keys_out, sr.keys, N * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(vals, sr.vals, N * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flags_out, df.p, N, hipMemcpyDeviceToHost));
     { uint32_t e = 0; HIP_TRY(hipMemcpy(&e, ss.err, 4, hipMemcpyDeviceToHost)); if (e) return SA_AMD_EINTERNAL; }
     return SA_AMD_OK;
 }
