@@ -568,6 +568,68 @@ void sa_amd_last_docs_stats(sa_amd_docs_stats *out);
  * 64 .. 1 048 576; a negative value restores the default (4096).  Returns the previous value. */
 int32_t sa_amd_docs_set_chunk(int32_t slots);
 
+/*
+ * Document-aware duplicate spans (an extension): the byte ranges that are copies, with the document boundaries of the
+ * collection respected, and how many bytes of every document they cover, on the device.  T has n bytes,
+ * SA is in the layout of sa_amd_saca_u8, the collection is doc_off[0 .. ndocs] as sa_amd_index_set_documents took it and
+ * min_len = k >= 1.  Write ds(p) = doc_off[doc(p)] and de(p) = doc_off[doc(p) + 1].
+ *   Window and member: the window of p is T[p .. p + k).  p is a MEMBER iff the window lies inside its document:
+ *     p + k <= de(p).  A window cut by a document end does not exist here: it is never flagged and never serves as somebody's copy.
+ *   Scope SA_AMD_DOCREP_ANY: another member q != p with the same window, in any document.
+ *   Scope SA_AMD_DOCREP_OTHER: such a q with doc(q) != doc(p).
+ *   Mode SA_AMD_REPEATS_ALL: p is flagged iff such a q exists.
+ *   Mode SA_AMD_REPEATS_KEEP_FIRST: p is flagged iff such a q exists with q < p.  Under OTHER this is the same as
+ *     doc(q) < doc(p), because documents are ordered by position: the first copy survives, under OTHER the copy in the first
+ *     document that has it.
+ *   Equivalently, over the maximal slot runs [a, b] with LCP[a + 1 .. b] >= k (those of sa_amd_repeat_spans' KEEP_FIRST):
+ *     non-members are transparent -- they break no run and contribute nothing --; with mn / mx the smallest / largest member
+ *     position of the run, a member p is flagged iff
+ *                      ANY                    OTHER
+ *       KEEP_FIRST     mn < p                 mn < ds(p)
+ *       ALL            mn < p or mx > p       mn < ds(p) or mx >= de(p)
+ *   Spans: the union of [p, p + k) over the flagged p, as maximal intervals [start, end): ascending, disjoint, not adjacent,
+ *     pairs of uint32 -- the form of sa_amd_repeat_spans; at most sa_amd_repeat_spans_bound(n, k) of them.  Every covered byte
+ *     lies in a window inside its own document, but two spans that touch a document boundary from both sides merge into one:
+ *     spans are not split at boundaries, doc_bytes carries the per-document accounting.
+ *   doc_bytes[d] (ndocs entries, optional): the covered bytes inside document d; they sum to covered_bytes.
+ *   "abracadabra", doc_off = {0, 4, 4, 7, 11}: KEEP_FIRST, ANY, k = 1 flags {3, 5, 7, 8, 9, 10}: spans {[3,4), [5,6), [7,11)};
+ *     KEEP_FIRST, OTHER, k = 1 flags {5, 7, 8, 9, 10} (the 'a' at 3 has its first copy in its own document):
+ *     doc_bytes = {0, 0, 1, 4}; ALL, k = 3, either scope, flags {0, 1, 7, 8}.
+ *   "aaaa", doc_off = {0, 2, 4}, k = 2 (the members are 0 and 2): KEEP_FIRST gives {[2, 4)} where the boundary-blind
+ *     sa_amd_repeat_spans gives {[1, 4)}; ALL gives the single span {[0, 4)}, merged across the boundary, doc_bytes = {2, 2}.
+ *   With ndocs = 1: scope ANY gives exactly the spans, span count, flagged count and covered bytes of
+ *     sa_amd_index_repeat_spans for the same mode (for ALL the union of the k-windows equals the union of the
+ *     [p, p + LR[p]), since LR[p + 1] >= LR[p] - 1); scope OTHER gives nothing.
+ * `capacity` / *count_out as for sa_amd_repeat_spans: more spans than fit is no error, the first `capacity` are written,
+ * *count_out and the statistics cover all of them.
+ * Errors, each with nothing written: a NULL index, no collection set, min_len < 1, an unknown mode or scope, a negative
+ * capacity, a NULL count_out, capacity > 0 with NULL spans: SA_AMD_EINVAL.  The array's range errors are those of
+ * sa_amd_index_repeat_spans.  With a wrong permutation the answers are unspecified, but nothing is read outside the tables and
+ * nothing is written outside the outputs.  Every position is below n + 1 < 2^31 and every sum with min_len is taken in 64 bits.
+ * sa_amd_last_repeat_stats and sa_amd_last_lcp_stats are filled as by sa_amd_index_repeat_spans (the LCP front end runs).
+ * Cost: the LCP front end, one search of doc_off per slot (a sampled level in LDS, then a few loads), and passes that stream
+ * 12 to 16 bytes per slot.
+ */
+#define SA_AMD_DOCREP_ANY   0
+#define SA_AMD_DOCREP_OTHER 1
+/* bytes of device scratch the call takes from the pool: sa_amd_repeats_work_bytes(n) plus 4 bytes per document; -1 when n < 0
+ * or ndocs < 1 */
+int64_t sa_amd_doc_repeats_work_bytes(int32_t n, int64_t ndocs);
+/* host pointers: only the spans (8 bytes each), doc_bytes (ndocs entries, or NULL: the accounting pass does not run) and the
+ * counters come back */
+int32_t sa_amd_index_doc_repeat_spans(const sa_amd_index *ix, int32_t min_len, int32_t mode, int32_t scope, uint32_t *spans,
+                                      int64_t capacity, int64_t *count_out, uint32_t *doc_bytes);
+
+typedef struct sa_amd_doc_repeat_stats { /* of the calling thread's most recent sa_amd_index_doc_repeat_spans */
+    int64_t members;                 /* positions whose window lies inside their document */
+    int64_t flagged;                 /* flagged positions */
+    int64_t spans;                   /* all spans, written or not */
+    int64_t covered_bytes;           /* bytes inside the spans */
+    int64_t docs_touched;            /* documents with at least one covered byte; -1 when doc_bytes was NULL (no accounting pass) */
+    int32_t readbacks, reserved;     /* blocking device -> host read-backs of counters: the front end's and one more */
+} sa_amd_doc_repeat_stats;
+void sa_amd_last_doc_repeat_stats(sa_amd_doc_repeat_stats *out);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

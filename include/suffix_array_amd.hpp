@@ -11,7 +11,8 @@
 //   SuffixArray::repeat_lengths / repeat_spans, repeat_lengths(), repeat_spans()
 //                                           EXTENSION: the longest-repeat array and the byte ranges that are copies
 //   DocumentIndex                           EXTENSION: a device-resident index over a collection of documents: which document a
-//                                           position lies in, in how many documents a pattern occurs and in which ones
+//                                           position lies in, in how many documents a pattern occurs and in which ones,
+//                                           and (repeat_spans) the duplicate byte ranges that respect the document boundaries
 // Rust panics (assert!, engine failure) are std::logic_error / std::runtime_error here.
 #pragma once
 #include "suffix_array_amd.h"
@@ -201,6 +202,7 @@ public:
     {
         if (n > MAX_LENGTH) throw std::logic_error("assertion failed: s.len() <= MAX_LENGTH");
         check(sa_amd_index_create(s, static_cast<std::int32_t>(n), sa, &ix_));
+        n_ = n;
         try { set_documents(offsets); } catch (...) { sa_amd_index_destroy(ix_); throw; }
     }
     DocumentIndex(const DocumentIndex &) = delete;
@@ -212,6 +214,7 @@ public:
     {
         if (offsets.size() < 2) throw std::invalid_argument("document offsets: ndocs + 1 values from 0 to n");
         check(sa_amd_index_set_documents(ix_, offsets.data(), static_cast<std::int64_t>(offsets.size()) - 1));
+        ndocs_ = offsets.size() - 1;
     }
     // the document of every position; SA_AMD_DOC_NONE for positions >= n
     std::vector<std::uint32_t> doc_of(const std::vector<std::uint32_t> &positions) const
@@ -246,6 +249,23 @@ public:
         for (std::size_t q = 0; q < out.size(); ++q) out[q].assign(docs.begin() + loff[q], docs.begin() + loff[q + 1]);
         return out;
     }
+    // the duplicate spans [start, end) that respect the document boundaries (suffix_array_amd.h, "Document-aware duplicate
+    // spans"): a window of min_len bytes counts only inside its document.  mode: SA_AMD_REPEATS_ALL / _KEEP_FIRST; scope:
+    // SA_AMD_DOCREP_ANY / _OTHER.  doc_bytes != nullptr: resized to one entry per document, the covered bytes inside it.
+    std::vector<std::pair<std::uint32_t, std::uint32_t>> repeat_spans(std::int32_t min_len, std::int32_t mode = SA_AMD_REPEATS_KEEP_FIRST,
+                                                                      std::int32_t scope = SA_AMD_DOCREP_OTHER,
+                                                                      std::vector<std::uint32_t> *doc_bytes = nullptr) const
+    {
+        const std::int64_t cap = sa_amd_repeat_spans_bound(static_cast<std::int32_t>(n_), min_len);
+        if (cap < 0) throw std::invalid_argument("min_len must be at least 1");
+        std::vector<std::uint32_t> flat(2 * static_cast<std::size_t>(cap) + 2);
+        if (doc_bytes) doc_bytes->assign(ndocs_, 0u);
+        std::int64_t count = 0;
+        check(sa_amd_index_doc_repeat_spans(ix_, min_len, mode, scope, flat.data(), cap, &count, doc_bytes ? doc_bytes->data() : nullptr));
+        std::vector<std::pair<std::uint32_t, std::uint32_t>> out(static_cast<std::size_t>(count < cap ? count : cap));
+        for (std::size_t i = 0; i < out.size(); ++i) out[i] = { flat[2 * i], flat[2 * i + 1] };
+        return out;
+    }
 
 private:
     struct Batch {
@@ -264,6 +284,7 @@ private:
         if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
     }
     sa_amd_index *ix_ = nullptr;
+    std::size_t n_ = 0, ndocs_ = 0;
 };
 
 }  // namespace suffix_array

@@ -30,6 +30,7 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "lpf", "lz77", "lz77_decode", "lz77_literals", "last_lz_stats", "lz_work_bytes", "lpf_device_ptr", "lz77_device_ptr", "LzStats", "LZ_LITERAL",
            "MatchStats", "last_match_stats", "match_work_bytes", "match_set_group_cap", "match_set_group_lanes", "match_stats_device_ptr", "match_spans_device_ptr",
            "MATCH_NONE", "MATCH_TILE",
+           "DocRepeatStats", "last_doc_repeat_stats", "doc_repeats_work_bytes", "DOCREP_ANY", "DOCREP_OTHER",
            "DocsStats", "last_docs_stats", "docs_set_chunk", "docs_work_bytes", "doc_of_device_ptr", "DOC_NONE", "DOC_SAMPLES",
            "DOC_CHUNK_MIN", "DOC_CHUNK_MAX", "DOC_CHUNK_DEFAULT"]
 
@@ -133,6 +134,15 @@ class DocsStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class DocRepeatStats(ctypes.Structure):
+    """sa_amd_doc_repeat_stats of include/suffix_array_amd.h"""
+    _fields_ = [("members", ctypes.c_int64), ("flagged", ctypes.c_int64), ("spans", ctypes.c_int64), ("covered_bytes", ctypes.c_int64),
+                ("docs_touched", ctypes.c_int64), ("readbacks", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 #: the document of a position behind the text (SA_AMD_DOC_NONE of include/suffix_array_amd.h); equal to ``MATCH_NONE``
 DOC_NONE = 0xFFFFFFFF
 #: entries of the sampled top level of the offset table a workgroup stages (kernels/docs.hpp)
@@ -153,6 +163,9 @@ LZ_LITERAL = 0xFFFFFFFF
 #: span modes of ``repeat_spans_device_ptr`` (SA_AMD_REPEATS_* of include/suffix_array_amd.h)
 REPEATS_ALL = 0
 REPEATS_KEEP_FIRST = 1
+#: scopes of ``DeviceIndex.doc_repeat_spans`` (SA_AMD_DOCREP_* of include/suffix_array_amd.h): a copy anywhere / in another document
+DOCREP_ANY = 0
+DOCREP_OTHER = 1
 
 
 def library_path() -> str:
@@ -328,6 +341,12 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_index_doc_search.restype = ctypes.c_int32
         L.sa_amd_index_doc_list.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.c_int64, c_vp]
         L.sa_amd_index_doc_list.restype = ctypes.c_int32
+        L.sa_amd_doc_repeats_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64]
+        L.sa_amd_doc_repeats_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_index_doc_repeat_spans.argtypes = [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int64, c_vp, c_vp]
+        L.sa_amd_index_doc_repeat_spans.restype = ctypes.c_int32
+        L.sa_amd_last_doc_repeat_stats.argtypes = [c_vp]
+        L.sa_amd_last_doc_repeat_stats.restype = None
         L.sa_amd_last_docs_stats.argtypes = [c_vp]
         L.sa_amd_last_docs_stats.restype = None
         L.sa_amd_docs_set_chunk.argtypes = [ctypes.c_int32]
@@ -897,6 +916,19 @@ def docs_work_bytes(n: int) -> int:
     return int(lib().sa_amd_docs_work_bytes(n))
 
 
+def last_doc_repeat_stats() -> dict:
+    """members / flagged / spans / covered_bytes / docs_touched / readbacks of this thread's most recent ``doc_repeat_spans``
+    call (``docs_touched`` is -1 when the call did not ask for ``doc_bytes``)"""
+    st = DocRepeatStats()
+    lib().sa_amd_last_doc_repeat_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def doc_repeats_work_bytes(n: int, ndocs: int) -> int:
+    """device scratch ``doc_repeat_spans`` takes from the pool for a text of ``n`` bytes in ``ndocs`` documents"""
+    return int(lib().sa_amd_doc_repeats_work_bytes(int(n), int(ndocs)))
+
+
 def docs_set_chunk(slots: int) -> int:
     """Route switch of this thread's later ``doc_search`` / ``doc_list`` calls (never changes a result): slots of a match range
     one wave scans, ``DOC_CHUNK_MIN`` .. ``DOC_CHUNK_MAX``; negative restores ``DOC_CHUNK_DEFAULT``.  Returns the previous value."""
@@ -1035,6 +1067,7 @@ class DeviceIndex:
             raise SuffixArrayError(-1, "document offsets: ndocs + 1 values in 0 .. len(text)")
         off = off.astype(np.uint32)
         _check(lib().sa_amd_index_set_documents(self._h, off.ctypes.data, off.size - 1))
+        self._ndocs = off.size - 1
 
     def doc_of(self, positions) -> np.ndarray:
         """the document each text position lies in (uint32; ``DOC_NONE`` for positions ``>= len(text)``, so the ``pos`` of
@@ -1051,6 +1084,25 @@ class DeviceIndex:
         out = np.zeros((2, cnt), dtype=np.uint32)
         _check(lib().sa_amd_index_doc_search(self._h, data.ctypes.data, off.ctypes.data, cnt, out[0].ctypes.data, out[1].ctypes.data))
         return out[0], out[1]
+
+    def doc_repeat_spans(self, min_len: int, mode: int = REPEATS_KEEP_FIRST, scope: int = DOCREP_OTHER, doc_bytes: bool = False):
+        """EXTENSION: duplicate spans that respect the document boundaries, in the form ``repeat_spans`` returns them.  A window
+        of ``min_len`` bytes counts only where it lies inside its document; it is flagged when the same window occurs at
+        another such position (``DOCREP_ANY``) or in another document (``DOCREP_OTHER``) -- anywhere (``REPEATS_ALL``) or earlier
+        (``REPEATS_KEEP_FIRST``: the first copy survives).  ``doc_bytes=True`` returns ``(spans, doc_bytes)`` with the covered
+        bytes of every document (uint32, ``ndocs`` entries)."""
+        k = _repeat_min_len(min_len)
+        ndocs = getattr(self, "_ndocs", 0)
+        if ndocs < 1:
+            raise SuffixArrayError(-1, "doc_repeat_spans: set_documents first")
+        cap = (self._s.size + 1) // (k + 1)
+        out = np.empty((cap, 2), dtype=np.uint32)
+        db = np.zeros(ndocs, dtype=np.uint32) if doc_bytes else None
+        count = ctypes.c_int64(0)
+        _bwt_rc(lib().sa_amd_index_doc_repeat_spans(self._h, k, int(mode), int(scope), out.ctypes.data, cap, ctypes.byref(count),
+                                                    None if db is None else db.ctypes.data))
+        spans = out[:min(int(count.value), cap)].copy()
+        return (spans, db) if doc_bytes else spans
 
     def doc_list(self, patterns) -> list:
         """-> per pattern the uint32 array of the distinct documents it occurs in, ordered by the document's lexicographically
@@ -1286,6 +1338,11 @@ class SuffixArray:
     def doc_of(self, positions) -> np.ndarray:
         """EXTENSION (the reference lacks it): the document of each position (see ``DeviceIndex.doc_of``)"""
         return self._index().doc_of(positions)
+
+    def doc_repeat_spans(self, min_len: int, mode: int = REPEATS_KEEP_FIRST, scope: int = DOCREP_OTHER, doc_bytes: bool = False):
+        """EXTENSION (the reference lacks it): duplicate spans that respect the document boundaries (see
+        ``DeviceIndex.doc_repeat_spans``)"""
+        return self._index().doc_repeat_spans(min_len, mode, scope, doc_bytes)
 
     def doc_search(self, patterns):
         """EXTENSION (the reference lacks it): ``(occ, df)`` per pattern (see ``DeviceIndex.doc_search``)"""

@@ -21,6 +21,7 @@
 #include "host/lz.hpp"
 #include "host/match.hpp"
 #include "host/docs.hpp"
+#include "host/doc_repeats.hpp"
 
 extern "C" {
 
@@ -964,6 +965,28 @@ SA_EXPORT int32_t sa_amd_docs_set_chunk(int32_t slots)
     const int32_t prev = sa::g_docs_chunk < 0 ? sa::DOC_CHUNK_DEFAULT : sa::g_docs_chunk;
     sa::g_docs_chunk = slots < 0 ? -1 : (slots < sa::DOC_CHUNK_MIN ? sa::DOC_CHUNK_MIN : (slots > sa::DOC_CHUNK_MAX ? sa::DOC_CHUNK_MAX : slots));
     return prev;
+}
+
+// ---- document-aware duplicate spans (host/doc_repeats.hpp, kernels/doc_repeats.hpp) ----
+
+SA_EXPORT int64_t sa_amd_doc_repeats_work_bytes(int32_t n, int64_t ndocs)
+{
+    if (n < 0 || ndocs < 1 || ndocs > (int64_t)0xfffffffe) return -1;
+    return (int64_t)sa::docrep_layout(n, ndocs).bytes;
+}
+
+SA_EXPORT int32_t sa_amd_index_doc_repeat_spans(const sa_amd_index *ix, int32_t min_len, int32_t mode, int32_t scope, uint32_t *spans,
+                                                int64_t capacity, int64_t *count_out, uint32_t *doc_bytes)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !ix->dDocOff || !sa::docrep_args_valid(min_len, mode, scope, spans, capacity, count_out)) return SA_AMD_EINVAL;
+    return sa::doc_repeats_index(doc_index(ix), min_len, mode, scope, spans, capacity, count_out, doc_bytes);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_doc_repeat_stats(sa_amd_doc_repeat_stats *out)
+{
+    if (out) *out = sa::g_last_doc_repeat_stats;
 }
 
 SA_EXPORT void sa_amd_last_unbwt_stats(sa_amd_unbwt_stats *out)
