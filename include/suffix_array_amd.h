@@ -630,6 +630,70 @@ typedef struct sa_amd_doc_repeat_stats { /* of the calling thread's most recent 
 } sa_amd_doc_repeat_stats;
 void sa_amd_last_doc_repeat_stats(sa_amd_doc_repeat_stats *out);
 
+/*
+ * Per-document term frequencies and top-k documents (an extension): how often a pattern occurs in each document it occurs in,
+ * and the k documents that hold most of its occurrences, on the device.  The collection is
+ * doc_off[0 .. ndocs] as sa_amd_index_set_documents took it; a pattern's matches are the slots [lo, hi) that
+ * sa_amd_index_search reports; an occurrence belongs to the document it starts in.
+ *   Term frequency: tf(d) = the number of slots i in [lo, hi) with SA[i] < n and doc(SA[i]) = d.  The sum of tf over the listing
+ *     equals occ -- less one for the empty pattern, because slot 0 belongs to no document.  For the empty pattern tf(d) is
+ *     the length of document d.
+ *   sa_amd_index_doc_tf returns the listing of sa_amd_index_doc_list -- the same documents, in the same first-slot order, with
+ *     the same list_off -- and a tf entry next to every document.
+ *   sa_amd_index_doc_topk takes 1 <= k <= SA_AMD_DOC_TOPK_MAX and returns, per pattern, the min(k, df) documents with the
+ *     greatest tf, ordered by tf descending and then by document id ascending.  Entry t of pattern q stands at top_off[q] + t;
+ *     top_off[count] is the sum of min(k, df).  The order on (tf descending, id ascending) is strict: the answer is unique.
+ *   T = "abracadabra", doc_off = {0, 4, 4, 7, 11}: "a" has the listing {3, 0, 2} with tf {2, 2, 1}; its top-1 is (0, 2), its
+ *     top-2 is (0, 2), (3, 2), its top-5 is (0, 2), (3, 2), (2, 1).  "bra" has tf {1, 1}.  "" has the listing {3, 0, 2} with
+ *     tf {4, 4, 3}.
+ * sa_amd_index_enable_doc_freq keeps one more uint32 per byte of text in the index (4 n bytes): the array S of the slots 1 .. n
+ * ordered by document, ascending inside a document.  Document d owns exactly S[doc_off[d] .. doc_off[d + 1]) -- every position
+ * of d has one slot -- so tf(d) = lb(S_d, hi) - lb(S_d, lo), lb the lower bound in S_d.  It is the order the stable sort of
+ * sa_amd_index_set_documents produces (same scratch, sa_amd_docs_work_bytes).  A no-op when the table exists; SA_AMD_EINVAL
+ * when no collection is set, SA_AMD_ENOMEM when the table does not fit.  sa_amd_index_set_documents drops the table when it
+ * replaces the collection: the caller enables it again.  The threading rule of sa_amd_index_set_documents applies.
+ * Errors, each with nothing written: a NULL index, no collection, no frequency table, a negative count or capacity, pat_off as
+ * sa_amd_index_search rejects it, k outside 1 .. SA_AMD_DOC_TOPK_MAX, a NULL list_off, top_off or total_out: SA_AMD_EINVAL.
+ * The downloads into tf and then docs are the last two steps that can fail; list_off / top_off and *total_out are written
+ * behind both: a failing call can leave tf (partly) written and everything else untouched.  With an array that is no suffix array the answers are unspecified, but nothing is read outside the tables and nothing
+ * is written outside the outputs.
+ * Cost: the listing's 2 occ streamed words, O(log |d| + log tf) loads of S per listed document, and for the top-k a sort in
+ * LDS of pieces of the listing: pieces of P keys keep their first k, the kept keys are cut into pieces again until every
+ * pattern is one piece.
+ */
+#define SA_AMD_DOC_TOPK_MAX 1024
+int32_t sa_amd_index_enable_doc_freq(sa_amd_index *ix);
+/* capacity, list_off and *total_out exactly as for sa_amd_index_doc_list: more entries than fit is no error, the first `capacity`
+ * entries of docs and of tf are written.  Either of docs and tf may be NULL. */
+int32_t sa_amd_index_doc_tf(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, int64_t *list_off,
+                            uint32_t *docs, uint32_t *tf, int64_t capacity, int64_t *total_out);
+/* top_off: count + 1 entries; docs and tf: count * k entries each (a 64-bit product), written compactly up to top_off[count].
+ * Either of docs and tf may be NULL. */
+int32_t sa_amd_index_doc_topk(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, int32_t k,
+                              int64_t *top_off, uint32_t *docs, uint32_t *tf);
+
+typedef struct sa_amd_doc_tf_stats { /* of the calling thread's most recent doc_tf / doc_topk call (sa_amd_last_docs_stats is not touched) */
+    int64_t patterns;
+    int64_t occ_sum;                 /* sum of occ */
+    int64_t df_sum;                  /* entries of the whole listing */
+    int64_t tf_sum;                  /* sum of the tf computed: of the whole listing, or of its first `capacity` entries */
+    int64_t table_loads;             /* loads of S, all lanes */
+    int64_t topk_entries;            /* top_off[count]; 0 after doc_tf */
+    int64_t pieces;                  /* workgroups of all reduction rounds */
+    int32_t rounds;                  /* reduction rounds: the last leaves one piece per pattern (at least 1 for a doc_topk with patterns) */
+    int32_t k;                       /* 0 after doc_tf */
+    int32_t piece;                   /* the effective P; 0 after doc_tf */
+    int32_t chunk;                   /* slots per unit of the listing in effect (sa_amd_docs_set_chunk) */
+    int32_t readbacks;               /* blocking device -> host read-backs of counters: the listing's and the tf kernel's */
+    int32_t reserved;
+} sa_amd_doc_tf_stats;
+void sa_amd_last_doc_tf_stats(sa_amd_doc_tf_stats *out);
+/* route switch of the calling thread's later doc_topk calls (never changes a result): keys per piece P, rounded down to a power
+ * of two in 64 .. 4096; a negative value restores the default (1024).  Returns the previous value.  A call raises P to at least
+ * twice the next power of two >= k, so that every round at least halves a list longer than P.  sa_amd_docs_set_chunk applies to
+ * doc_tf and doc_topk as it does to doc_list. */
+int32_t sa_amd_docs_set_topk_piece(int32_t entries);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

@@ -12,7 +12,9 @@
 //                                           EXTENSION: the longest-repeat array and the byte ranges that are copies
 //   DocumentIndex                           EXTENSION: a device-resident index over a collection of documents: which document a
 //                                           position lies in, in how many documents a pattern occurs and in which ones,
-//                                           and (repeat_spans) the duplicate byte ranges that respect the document boundaries
+//                                           (term_frequencies, top_k) how often in each and the k documents with the most
+//                                           occurrences, and (repeat_spans) the duplicate byte ranges that respect the
+//                                           document boundaries
 // Rust panics (assert!, engine failure) are std::logic_error / std::runtime_error here.
 #pragma once
 #include "suffix_array_amd.h"
@@ -249,6 +251,36 @@ public:
         for (std::size_t q = 0; q < out.size(); ++q) out[q].assign(docs.begin() + loff[q], docs.begin() + loff[q + 1]);
         return out;
     }
+    // keeps the slots ordered by document (4 bytes per byte of text) that term_frequencies and top_k need; a no-op when they
+    // exist.  set_documents drops them: enable again after replacing the collection.
+    void enable_frequencies() { check(sa_amd_index_enable_doc_freq(ix_)); }
+    // per pattern the listing of doc_list as (doc, tf) pairs: tf = the occurrences that start in the document
+    std::vector<std::vector<std::pair<std::uint32_t, std::uint32_t>>> term_frequencies(const std::vector<std::string> &patterns) const
+    {
+        const Batch b(patterns);
+        std::vector<std::int64_t> loff(patterns.size() + 1);
+        std::vector<std::uint32_t> docs(1 << 16), tf(1 << 16);
+        std::int64_t total = 0;
+        for (;;) {
+            check(sa_amd_index_doc_tf(ix_, b.data(), b.off.data(), b.count(), loff.data(), docs.data(), tf.data(),
+                                      static_cast<std::int64_t>(docs.size()), &total));
+            if (total <= static_cast<std::int64_t>(docs.size())) break;
+            docs.resize(static_cast<std::size_t>(total));
+            tf.resize(static_cast<std::size_t>(total));
+        }
+        return pairs(loff, docs, tf);
+    }
+    // per pattern the min(k, df) documents with the most occurrences as (doc, tf) pairs, by tf descending and then by document id
+    // ascending; 1 <= k <= SA_AMD_DOC_TOPK_MAX
+    std::vector<std::vector<std::pair<std::uint32_t, std::uint32_t>>> top_k(const std::vector<std::string> &patterns, std::int32_t k) const
+    {
+        if (k < 1 || k > SA_AMD_DOC_TOPK_MAX) throw std::invalid_argument("k must be in 1 .. SA_AMD_DOC_TOPK_MAX");
+        const Batch b(patterns);
+        std::vector<std::int64_t> toff(patterns.size() + 1);
+        std::vector<std::uint32_t> docs(patterns.size() * static_cast<std::size_t>(k) + 1), tf(docs.size());
+        check(sa_amd_index_doc_topk(ix_, b.data(), b.off.data(), b.count(), k, toff.data(), docs.data(), tf.data()));
+        return pairs(toff, docs, tf);
+    }
     // the duplicate spans [start, end) that respect the document boundaries (suffix_array_amd.h, "Document-aware duplicate
     // spans"): a window of min_len bytes counts only inside its document.  mode: SA_AMD_REPEATS_ALL / _KEEP_FIRST; scope:
     // SA_AMD_DOCREP_ANY / _OTHER.  doc_bytes != nullptr: resized to one entry per document, the covered bytes inside it.
@@ -278,6 +310,14 @@ private:
         const std::uint8_t *data() const { return reinterpret_cast<const std::uint8_t *>(bytes.data()); }
         std::int32_t count() const { return static_cast<std::int32_t>(off.size() - 1); }
     };
+    static std::vector<std::vector<std::pair<std::uint32_t, std::uint32_t>>> pairs(const std::vector<std::int64_t> &off, const std::vector<std::uint32_t> &docs,
+                                                                                    const std::vector<std::uint32_t> &tf)
+    {
+        std::vector<std::vector<std::pair<std::uint32_t, std::uint32_t>>> out(off.size() - 1);
+        for (std::size_t q = 0; q < out.size(); ++q)
+            for (std::int64_t e = off[q]; e < off[q + 1]; ++e) out[q].emplace_back(docs[static_cast<std::size_t>(e)], tf[static_cast<std::size_t>(e)]);
+        return out;
+    }
     static void check(std::int32_t rc)
     {
         if (rc == SA_AMD_EINVAL) throw std::invalid_argument("suffix_array_amd: invalid argument");

@@ -32,7 +32,9 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "MATCH_NONE", "MATCH_TILE",
            "DocRepeatStats", "last_doc_repeat_stats", "doc_repeats_work_bytes", "DOCREP_ANY", "DOCREP_OTHER",
            "DocsStats", "last_docs_stats", "docs_set_chunk", "docs_work_bytes", "doc_of_device_ptr", "DOC_NONE", "DOC_SAMPLES",
-           "DOC_CHUNK_MIN", "DOC_CHUNK_MAX", "DOC_CHUNK_DEFAULT"]
+           "DOC_CHUNK_MIN", "DOC_CHUNK_MAX", "DOC_CHUNK_DEFAULT",
+           "DocTfStats", "last_doc_tf_stats", "docs_set_topk_piece", "DOC_TOPK_MAX", "DOC_TOPK_PIECE_MIN", "DOC_TOPK_PIECE_MAX",
+           "DOC_TOPK_PIECE_DEFAULT"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
@@ -134,6 +136,17 @@ class DocsStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class DocTfStats(ctypes.Structure):
+    """sa_amd_doc_tf_stats of include/suffix_array_amd.h"""
+    _fields_ = [("patterns", ctypes.c_int64), ("occ_sum", ctypes.c_int64), ("df_sum", ctypes.c_int64), ("tf_sum", ctypes.c_int64),
+                ("table_loads", ctypes.c_int64), ("topk_entries", ctypes.c_int64), ("pieces", ctypes.c_int64), ("rounds", ctypes.c_int32),
+                ("k", ctypes.c_int32), ("piece", ctypes.c_int32), ("chunk", ctypes.c_int32), ("readbacks", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 class DocRepeatStats(ctypes.Structure):
     """sa_amd_doc_repeat_stats of include/suffix_array_amd.h"""
     _fields_ = [("members", ctypes.c_int64), ("flagged", ctypes.c_int64), ("spans", ctypes.c_int64), ("covered_bytes", ctypes.c_int64),
@@ -151,6 +164,12 @@ DOC_SAMPLES = 8192
 DOC_CHUNK_MIN = 64
 DOC_CHUNK_MAX = 1 << 20
 DOC_CHUNK_DEFAULT = 4096
+#: the largest ``k`` of ``doc_topk`` (SA_AMD_DOC_TOPK_MAX of include/suffix_array_amd.h)
+DOC_TOPK_MAX = 1024
+#: keys of a piece of the top-k reduction: the clamp of ``docs_set_topk_piece`` and the default (kernels/doc_tf.hpp)
+DOC_TOPK_PIECE_MIN = 64
+DOC_TOPK_PIECE_MAX = 4096
+DOC_TOPK_PIECE_DEFAULT = 1024
 
 #: ``pos`` of a query position none of whose bytes occurs in the text (SA_AMD_MATCH_NONE of include/suffix_array_amd.h)
 MATCH_NONE = 0xFFFFFFFF
@@ -351,6 +370,16 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_last_docs_stats.restype = None
         L.sa_amd_docs_set_chunk.argtypes = [ctypes.c_int32]
         L.sa_amd_docs_set_chunk.restype = ctypes.c_int32
+        L.sa_amd_index_enable_doc_freq.argtypes = [c_vp]
+        L.sa_amd_index_enable_doc_freq.restype = ctypes.c_int32
+        L.sa_amd_index_doc_tf.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_doc_tf.restype = ctypes.c_int32
+        L.sa_amd_index_doc_topk.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp]
+        L.sa_amd_index_doc_topk.restype = ctypes.c_int32
+        L.sa_amd_last_doc_tf_stats.argtypes = [c_vp]
+        L.sa_amd_last_doc_tf_stats.restype = None
+        L.sa_amd_docs_set_topk_piece.argtypes = [ctypes.c_int32]
+        L.sa_amd_docs_set_topk_piece.restype = ctypes.c_int32
         _lib = L
     return _lib
 
@@ -935,6 +964,21 @@ def docs_set_chunk(slots: int) -> int:
     return int(lib().sa_amd_docs_set_chunk(int(slots)))
 
 
+def last_doc_tf_stats() -> dict:
+    """patterns / occ_sum / df_sum / tf_sum / table_loads / topk_entries / pieces / rounds / k / piece / chunk / readbacks of this
+    thread's most recent ``doc_tf`` / ``doc_topk`` call"""
+    st = DocTfStats()
+    lib().sa_amd_last_doc_tf_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def docs_set_topk_piece(entries: int) -> int:
+    """Route switch of this thread's later ``doc_topk`` calls (never changes a result): keys of a piece of the reduction, rounded
+    down to a power of two in ``DOC_TOPK_PIECE_MIN`` .. ``DOC_TOPK_PIECE_MAX``; negative restores ``DOC_TOPK_PIECE_DEFAULT``.
+    Returns the previous value."""
+    return int(lib().sa_amd_docs_set_topk_piece(int(entries)))
+
+
 def doc_of_device_ptr(index, pos_ptr: int, count: int, doc_ptr: int, stream: int = 0) -> None:
     """Device-resident ``doc_of``: ``count`` uint32 positions at ``pos_ptr`` -> their documents at ``doc_ptr`` (raw device pointers
     on the index's device, 4-byte aligned); needs no scratch; blocks until done."""
@@ -1118,6 +1162,39 @@ class DeviceIndex:
             if total.value <= cap:
                 return [docs[loff[q]:loff[q + 1]].copy() for q in range(cnt)]
             cap = int(total.value)
+
+    def enable_doc_freq(self) -> None:
+        """EXTENSION: build and keep the slots ordered by document (4 bytes per byte of text) that ``doc_tf`` and ``doc_topk``
+        need.  A no-op when the table exists; ``set_documents`` drops it, so enable it again after replacing the collection."""
+        _check(lib().sa_amd_index_enable_doc_freq(self._h))
+
+    def doc_tf(self, patterns) -> list:
+        """-> per pattern ``(docs, tf)``: the listing of ``doc_list`` and, next to every document, the number of occurrences
+        that start in it (uint32 arrays)"""
+        data, off, cnt = _pattern_batch(patterns)
+        loff = np.zeros(cnt + 1, dtype=np.int64)
+        total = ctypes.c_int64(0)
+        cap = 1 << 16
+        while True:
+            out = np.empty((2, cap), dtype=np.uint32)
+            _check(lib().sa_amd_index_doc_tf(self._h, data.ctypes.data, off.ctypes.data, cnt, loff.ctypes.data, out[0].ctypes.data,
+                                             out[1].ctypes.data, cap, ctypes.byref(total)))
+            if total.value <= cap:
+                return [(out[0, loff[q]:loff[q + 1]].copy(), out[1, loff[q]:loff[q + 1]].copy()) for q in range(cnt)]
+            cap = int(total.value)
+
+    def doc_topk(self, patterns, k: int) -> list:
+        """-> per pattern ``(docs, tf)``: the ``min(k, df)`` documents with the most occurrences, by ``tf`` descending and then by
+        document id ascending (uint32 arrays); ``1 <= k <= DOC_TOPK_MAX``"""
+        data, off, cnt = _pattern_batch(patterns)
+        k = int(k)
+        if not 1 <= k <= DOC_TOPK_MAX:
+            raise SuffixArrayError(-1, "doc_topk: k in 1 .. DOC_TOPK_MAX")
+        toff = np.zeros(cnt + 1, dtype=np.int64)
+        out = np.empty((2, max(cnt * k, 1)), dtype=np.uint32)
+        _check(lib().sa_amd_index_doc_topk(self._h, data.ctypes.data, off.ctypes.data, cnt, k, toff.ctypes.data, out[0].ctypes.data,
+                                           out[1].ctypes.data))
+        return [(out[0, toff[q]:toff[q + 1]].copy(), out[1, toff[q]:toff[q + 1]].copy()) for q in range(cnt)]
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): build and keep the LCP table of the
@@ -1351,6 +1428,19 @@ class SuffixArray:
     def doc_list(self, patterns) -> list:
         """EXTENSION (the reference lacks it): the documents each pattern occurs in (see ``DeviceIndex.doc_list``)"""
         return self._index().doc_list(patterns)
+
+    def enable_doc_freq(self) -> None:
+        """EXTENSION (the reference lacks it): keep the table ``doc_tf`` / ``doc_topk`` need (see ``DeviceIndex.enable_doc_freq``)"""
+        self._index().enable_doc_freq()
+
+    def doc_tf(self, patterns) -> list:
+        """EXTENSION (the reference lacks it): ``(docs, tf)`` per pattern (see ``DeviceIndex.doc_tf``)"""
+        return self._index().doc_tf(patterns)
+
+    def doc_topk(self, patterns, k: int) -> list:
+        """EXTENSION (the reference lacks it): the ``k`` documents with the most occurrences per pattern (see
+        ``DeviceIndex.doc_topk``)"""
+        return self._index().doc_topk(patterns, k)
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): contains / search_all / search_lcp

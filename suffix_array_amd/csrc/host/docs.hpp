@@ -14,6 +14,7 @@ static thread_local int32_t g_docs_chunk = -1;          // sa_amd_docs_set_chunk
 struct DocIndex {
     int device; const uint8_t *dT; const uint32_t *dSA; int32_t n; const uint32_t *dBkt; const uint64_t *dPair;
     const uint32_t *dOff; const uint32_t *dPrev; uint32_t ndocs;
+    const uint32_t *dSlots;       // the slots ordered by document once sa_amd_index_enable_doc_freq has built them (host/doc_tf.hpp), else nullptr
 };
 
 // layout of the build's work block: control words (the sort's error word first) | four (n + 1)-entry buffers (the document ids
@@ -58,9 +59,12 @@ static int launch_doc_of(const uint32_t *dPos, int64_t count, const uint32_t *dO
     return SA_AMD_OK;
 }
 
-// dPrev (n + 1 entries) from dSA and the uploaded offsets; dWork: docs_layout(n).bytes, 256-byte aligned.  Blocks until done.
-static int docs_build(const uint32_t *dSA, int32_t n32, const uint32_t *dOff, uint32_t ndocs, uint32_t *dPrev, void *dWork, int64_t work_bytes,
-                      hipStream_t st)
+// The front half of every table build: DA of slots 1 .. n (slot 0 is the empty suffix: no document), then the slots in stable
+// order of their document.  pr->keys: the document ids in that order, pr->vals: the slots less one (only when pr->passes: one
+// document sorts nothing and the order is that of the slots).  dWork: docs_layout(n).bytes, 256-byte aligned; *ctl_out: its
+// control words, the sort's error word first.
+static int docs_sorted_slots(const uint32_t *dSA, int32_t n32, const uint32_t *dOff, uint32_t ndocs, void *dWork, int64_t work_bytes, hipStream_t st,
+                             SortResult32 *pr, uint32_t **ctl_out)
 {
     const int64_t n = n32;
     const DocsLayout L = docs_layout(n32);
@@ -76,23 +80,41 @@ static int docs_build(const uint32_t *dSA, int32_t n32, const uint32_t *dOff, ui
     ss.digit_tot = ss.spine + (size_t)RADIX * SORT_MAX_WG;
     ss.status = (unsigned long long *)(base + L.status);
     ss.err = ctl;
-    // DA of slots 1 .. n (slot 0 is the empty suffix: no document), then the slots in stable order of their document
     { const int rcd = launch_doc_of(dSA + 1, n, dOff, ndocs, n32, keys, st); if (rcd) return rcd; }
-    SortResult32 pr;
-    const int rcs = sort_pairs32(keys, vals, (uint32_t *)(base + L.altk), (uint32_t *)(base + L.altv), n, 0, bit_length((uint64_t)ndocs - 1), ss, nullptr,
-                                 st, &pr, tn, true);
-    if (rcs) return rcs;
-    int64_t g = ceil_div(n, DOC_THREADS);
-    if (g > 16384) g = 16384;
-    if (g < 1) g = 1;
-    PROF(KC_MISC, n, st, hipLaunchKernelGGL(k_doc_prev, dim3((unsigned)g), dim3(DOC_THREADS), 0, st, (const uint32_t *)pr.keys,
-                                            (const uint32_t *)(pr.passes ? pr.vals : nullptr), n, dPrev));
+    *ctl_out = ctl;
+    return sort_pairs32(keys, vals, (uint32_t *)(base + L.altk), (uint32_t *)(base + L.altv), n, 0, bit_length((uint64_t)ndocs - 1), ss, nullptr, st, pr, tn,
+                        true);
+}
+
+// the end of every table build: the sort's error word comes back; blocks until the table is written
+static int docs_built(const uint32_t *ctl, hipStream_t st)
+{
     uint32_t err = 0;
     { const int rcw = read_words(&err, ctl, 4, st); if (rcw) return rcw; }
     HIP_TRY(hipStreamSynchronize(st));
     g_prof.resolve();
     if (err) return SA_AMD_EINTERNAL;               // a look-back of the sort gave up (never seen; never a silent wrong table)
     return SA_AMD_OK;
+}
+
+static unsigned docs_slot_grid(int64_t n)
+{
+    int64_t g = ceil_div(n, DOC_THREADS);
+    if (g > 16384) g = 16384;
+    return (unsigned)(g < 1 ? 1 : g);
+}
+
+// dPrev (n + 1 entries) from dSA and the uploaded offsets; dWork: docs_layout(n).bytes, 256-byte aligned.  Blocks until done.
+static int docs_build(const uint32_t *dSA, int32_t n32, const uint32_t *dOff, uint32_t ndocs, uint32_t *dPrev, void *dWork, int64_t work_bytes,
+                      hipStream_t st)
+{
+    const int64_t n = n32;
+    SortResult32 pr;
+    uint32_t *ctl = nullptr;
+    { const int rcs = docs_sorted_slots(dSA, n32, dOff, ndocs, dWork, work_bytes, st, &pr, &ctl); if (rcs) return rcs; }
+    PROF(KC_MISC, n, st, hipLaunchKernelGGL(k_doc_prev, dim3(docs_slot_grid(n)), dim3(DOC_THREADS), 0, st, (const uint32_t *)pr.keys,
+                                            (const uint32_t *)(pr.passes ? pr.vals : nullptr), n, dPrev));
+    return docs_built(ctl, st);
 }
 
 // exclusive scan of v[0 .. len) in place; tsum: ceil(len / DOC_SCAN_TILE) words; last_out: see k_doc_scan_tiles
@@ -116,43 +138,45 @@ static unsigned docs_unit_grid(int64_t units)
     return (unsigned)(g < 1 ? 1 : g);
 }
 
-// Document frequency (!list: occ and df, either may be nullptr) or listing (list_off: count + 1 entries, the first `capacity`
-// documents to docs, the number of all of them to *total_out) of a batch of patterns; host pointers, arguments checked by the
-// caller.  One blocking read-back: the number of units (with the summed occ and the bound of the listing).
-static int docs_query(const DocIndex &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, bool list, uint32_t *occ_out,
-                      uint32_t *df_out, int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
+// The device side of a batch of patterns after its ranges: lo (clamped), occ, the scanned units and their totals.  With `list`
+// the block has room for the listing's offsets as well.
+struct DocsBatch {
+    PooledScope sc;
+    unsigned long long *ctl = nullptr, *uoff = nullptr;
+    uint32_t *dLo = nullptr, *dOcc = nullptr, *dDf = nullptr;
+    long long *dLoff = nullptr;
+    uint32_t chunk = 0;
+    unsigned long long units = 0, occ_sum = 0, bound = 0;
+    explicit DocsBatch(int device) : sc(device, false) {}
+};
+
+// patterns up, the ranges by the search kernels, the units.  One blocking read-back: the number of units (with the summed occ
+// and the bound of the listing).  count >= 1.
+static int docs_ranges(DocsBatch &b, const DocIndex &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, bool list)
 {
-    sa_amd_docs_stats ds;
-    memset(&ds, 0, sizeof(ds));
-    const uint32_t chunk = (uint32_t)(g_docs_chunk < 0 ? DOC_CHUNK_DEFAULT : g_docs_chunk);
-    ds.patterns = count;
-    ds.chunk = (int32_t)chunk;
-    ds.listed = list ? 1 : 0;
-    g_last_docs_stats = ds;
-    if (count == 0) {
-        if (list) { list_off[0] = 0; *total_out = 0; }
-        return SA_AMD_OK;
-    }
     const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
     g_posted_off = tn.no_posted_readback;
-    const int rb0 = g_readbacks;
     const size_t C = (size_t)count, total = (size_t)pat_off[count];
     const uint32_t N1 = (uint32_t)ix.n + 1u;
+    b.chunk = (uint32_t)(g_docs_chunk < 0 ? DOC_CHUNK_DEFAULT : g_docs_chunk);
+    const uint32_t chunk = b.chunk;
 
-    PooledScope sc(ix.device, false);
+    PooledScope &sc = b.sc;
     const size_t b_pat = align_up(total + 16, 256), b_off = align_up((C + 1) * 8, 256), b_w = align_up(C * 4 + 4, 256);
     const size_t b_ts = align_up(docs_scan_words((int64_t)C + 1) * 8, 256);
     sc.acquire(256 + b_pat + b_off + 4 * b_w + b_off + b_ts + (list ? b_off : 0));
-    unsigned long long *ctl = (unsigned long long *)sc.take(256);
+    unsigned long long *ctl = b.ctl = (unsigned long long *)sc.take(256);
     uint8_t *dP = (uint8_t *)sc.take(b_pat);
     int64_t *dO = (int64_t *)sc.take(b_off);
-    uint32_t *dLo = (uint32_t *)sc.take(b_w), *dHi = (uint32_t *)sc.take(b_w), *dOcc = (uint32_t *)sc.take(b_w), *dDf = (uint32_t *)sc.take(b_w);
-    unsigned long long *uoff = (unsigned long long *)sc.take(b_off), *tsum = (unsigned long long *)sc.take(b_ts);
-    long long *dLoff = list ? (long long *)sc.take(b_off) : nullptr;
+    uint32_t *dLo = b.dLo = (uint32_t *)sc.take(b_w), *dHi = (uint32_t *)sc.take(b_w);
+    b.dOcc = (uint32_t *)sc.take(b_w);
+    b.dDf = (uint32_t *)sc.take(b_w);
+    unsigned long long *uoff = b.uoff = (unsigned long long *)sc.take(b_off), *tsum = (unsigned long long *)sc.take(b_ts);
+    b.dLoff = list ? (long long *)sc.take(b_off) : nullptr;
     if (sc.rc) return sc.rc;
     hipStream_t st = sc.st;
     HIP_TRY(hipMemsetAsync(ctl, 0, 256, st));
-    HIP_TRY(hipMemsetAsync(dDf, 0, C * 4, st));
+    HIP_TRY(hipMemsetAsync(b.dDf, 0, C * 4, st));
     if (total) HIP_TRY(hipMemcpyAsync(dP, pat_data, total, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dO, pat_off, (C + 1) * 8, hipMemcpyHostToDevice, st));
 
@@ -163,65 +187,111 @@ static int docs_query(const DocIndex &ix, const uint8_t *pat_data, const int64_t
     if (rcs) return rcs;
     // ---- the units: ceil(occ / chunk) per pattern, scanned; the number of all of them comes back ----
     PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_doc_ranges, dim3((unsigned)ceil_div((int64_t)count + 1, DOC_THREADS)), dim3(DOC_THREADS), 0, st, dLo,
-                                                (const uint32_t *)dHi, count, N1, chunk, ix.ndocs, dOcc, uoff, ctl));
+                                                (const uint32_t *)dHi, count, N1, chunk, ix.ndocs, b.dOcc, uoff, ctl));
     { const int rcn = docs_scan(uoff, (int64_t)count + 1, tsum, &ctl[0], st); if (rcn) return rcn; }
     unsigned long long cw[3];
     { const int rcw = read_words(cw, ctl, sizeof(cw), st); if (rcw) return rcw; }
-    const unsigned long long units = cw[0], occ_sum = cw[1], bound = cw[2];
-    if (units > (unsigned long long)count + occ_sum / chunk || occ_sum > (unsigned long long)count * N1) return SA_AMD_EINTERNAL;
-    ds.occ_sum = (int64_t)occ_sum;
-    ds.units = (int64_t)units;
-    ds.slots_scanned = (int64_t)occ_sum * (list ? 2 : 1);
+    b.units = cw[0]; b.occ_sum = cw[1]; b.bound = cw[2];
+    if (b.units > (unsigned long long)count + b.occ_sum / chunk || b.occ_sum > (unsigned long long)count * N1) return SA_AMD_EINTERNAL;
+    return SA_AMD_OK;
+}
 
-    std::vector<uint32_t> df(list ? 0 : C);
-    int64_t listed = 0;
+// The listing of a batch on the device: the first `cap` = min(capacity, bound) documents in dDocs, the offsets of all of them in
+// loff (count + 1 entries, on the host), their number in `listed`.  Its scratch is a block of its own, sized by the units.
+struct DocsListing {
+    PooledScope s2;
+    uint32_t *dDocs = nullptr;
+    int64_t cap = 0, listed = 0;
+    std::vector<int64_t> loff;
+    DocsListing() : s2(-1, false) {}
+};
+
+// counts per unit, one scan for the units' offsets and the patterns', ordered compaction; waits for the stream
+static int docs_listing(DocsBatch &b, DocsListing &ls, const DocIndex &ix, int32_t count, int64_t capacity)
+{
+    const size_t C = (size_t)count;
+    const unsigned long long units = b.units, occ_sum = b.occ_sum;
+    const uint32_t chunk = b.chunk;
+    hipStream_t st = b.sc.st;
+    const int64_t cap = ls.cap = capacity < (int64_t)b.bound ? capacity : (int64_t)b.bound;
+    const size_t b_uc = align_up(((size_t)units + 1) * 8, 256), b_uq = align_up((size_t)units * 4 + 4, 256);
+    const size_t b_ut = align_up(docs_scan_words((int64_t)units + 1) * 8, 256), b_docs = align_up((size_t)cap * 4 + 8, 256);
+    PooledScope &s2 = ls.s2;
+    s2.acquire(b_uc + b_uq + b_ut + b_docs);
+    unsigned long long *ucnt = (unsigned long long *)s2.take(b_uc), *utsum = (unsigned long long *)s2.take(b_ut);
+    uint32_t *uq = (uint32_t *)s2.take(b_uq), *dDocs = ls.dDocs = (uint32_t *)s2.take(b_docs);
+    if (s2.rc) return s2.rc;
+    HIP_TRY(hipMemsetAsync(ucnt + units, 0, 8, st));
+    if (units)
+        PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL((k_doc_count<true>), dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.dPrev,
+                                                               (const uint32_t *)b.dLo, (const uint32_t *)b.dOcc, (const unsigned long long *)b.uoff, count, units,
+                                                               chunk, (uint32_t *)nullptr, ucnt, uq));
+    { const int rcn = docs_scan(ucnt, (int64_t)units + 1, utsum, nullptr, st); if (rcn) return rcn; }
+    PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_doc_list_off, dim3((unsigned)ceil_div((int64_t)count + 1, DOC_THREADS)), dim3(DOC_THREADS), 0, st,
+                                                (const unsigned long long *)b.uoff, (const unsigned long long *)ucnt, units, count, b.dLoff));
+    if (units && cap > 0)
+        PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL(k_doc_emit, dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.dPrev, ix.dSA,
+                                                               (const uint32_t *)b.dLo, (const uint32_t *)b.dOcc, (const unsigned long long *)b.uoff,
+                                                               (const uint32_t *)uq, (const unsigned long long *)ucnt, units, count, chunk, ix.dOff,
+                                                               ix.ndocs + 1u, (uint32_t)ix.n, dDocs, (unsigned long long)cap));
+    HIP_TRY(hipStreamSynchronize(st));
+    ls.loff.resize(C + 1);
+    b.sc.down(ls.loff.data(), b.dLoff, (C + 1) * 8);
+    if (b.sc.rc) return b.sc.rc;
+    ls.listed = ls.loff[C];
+    if (ls.listed < 0) return SA_AMD_EINTERNAL;               // (above `bound` only for an array that is no suffix array: what fits `cap` is written)
+    return SA_AMD_OK;
+}
+
+// Document frequency (!list: occ and df, either may be nullptr) or listing (list_off: count + 1 entries, the first `capacity`
+// documents to docs, the number of all of them to *total_out) of a batch of patterns; host pointers, arguments checked by the
+// caller.
+static int docs_query(const DocIndex &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, bool list, uint32_t *occ_out,
+                      uint32_t *df_out, int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
+{
+    sa_amd_docs_stats ds;
+    memset(&ds, 0, sizeof(ds));
+    ds.patterns = count;
+    ds.chunk = (int32_t)(g_docs_chunk < 0 ? DOC_CHUNK_DEFAULT : g_docs_chunk);
+    ds.listed = list ? 1 : 0;
+    g_last_docs_stats = ds;
+    if (count == 0) {
+        if (list) { list_off[0] = 0; *total_out = 0; }
+        return SA_AMD_OK;
+    }
+    const int rb0 = g_readbacks;
+    const size_t C = (size_t)count;
+    DocsBatch b(ix.device);
+    { const int rcr = docs_ranges(b, ix, pat_data, pat_off, count, list); if (rcr) return rcr; }
+    PooledScope &sc = b.sc;
+    hipStream_t st = sc.st;
+    ds.occ_sum = (int64_t)b.occ_sum;
+    ds.units = (int64_t)b.units;
+    ds.slots_scanned = (int64_t)b.occ_sum * (list ? 2 : 1);
+
     if (!list) {
-        if (units)
-            PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL((k_doc_count<false>), dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.dPrev,
-                                                                   (const uint32_t *)dLo, (const uint32_t *)dOcc, (const unsigned long long *)uoff, count, units,
-                                                                   chunk, dDf, (unsigned long long *)nullptr, (uint32_t *)nullptr));
+        std::vector<uint32_t> df(C);
+        if (b.units)
+            PROF(KC_MISC, (int64_t)b.occ_sum, st, hipLaunchKernelGGL((k_doc_count<false>), dim3(docs_unit_grid((int64_t)b.units)), dim3(DOC_THREADS), 0, st,
+                                                                     ix.dPrev, (const uint32_t *)b.dLo, (const uint32_t *)b.dOcc,
+                                                                     (const unsigned long long *)b.uoff, count, b.units, b.chunk, b.dDf,
+                                                                     (unsigned long long *)nullptr, (uint32_t *)nullptr));
         HIP_TRY(hipStreamSynchronize(st));
-        sc.down(df.data(), dDf, C * 4);
+        sc.down(df.data(), b.dDf, C * 4);
         if (sc.finish() != SA_AMD_OK) return sc.rc;
-        if (occ_out) HIP_TRY(hipMemcpy(occ_out, dOcc, C * 4, hipMemcpyDeviceToHost));      // the last step that can fail: nothing else is written before it
+        if (occ_out) HIP_TRY(hipMemcpy(occ_out, b.dOcc, C * 4, hipMemcpyDeviceToHost));      // the last step that can fail: nothing else is written before it
         for (size_t q = 0; q < C; ++q) ds.df_sum += df[q];
         if (df_out) memcpy(df_out, df.data(), C * 4);
     } else {
-        // ---- the listing: counts per unit, one scan for the units' offsets and the patterns', ordered compaction ----
-        const int64_t cap = capacity < (int64_t)bound ? capacity : (int64_t)bound;
-        const size_t b_uc = align_up(((size_t)units + 1) * 8, 256), b_uq = align_up((size_t)units * 4 + 4, 256);
-        const size_t b_ut = align_up(docs_scan_words((int64_t)units + 1) * 8, 256), b_docs = align_up((size_t)cap * 4 + 8, 256);
-        PooledScope s2(-1, false);
-        s2.acquire(b_uc + b_uq + b_ut + b_docs);
-        unsigned long long *ucnt = (unsigned long long *)s2.take(b_uc), *utsum = (unsigned long long *)s2.take(b_ut);
-        uint32_t *uq = (uint32_t *)s2.take(b_uq), *dDocs = (uint32_t *)s2.take(b_docs);
-        if (s2.rc) return s2.rc;
-        HIP_TRY(hipMemsetAsync(ucnt + units, 0, 8, st));
-        if (units)
-            PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL((k_doc_count<true>), dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.dPrev,
-                                                                   (const uint32_t *)dLo, (const uint32_t *)dOcc, (const unsigned long long *)uoff, count, units,
-                                                                   chunk, (uint32_t *)nullptr, ucnt, uq));
-        { const int rcn = docs_scan(ucnt, (int64_t)units + 1, utsum, nullptr, st); if (rcn) return rcn; }
-        PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_doc_list_off, dim3((unsigned)ceil_div((int64_t)count + 1, DOC_THREADS)), dim3(DOC_THREADS), 0, st,
-                                                    (const unsigned long long *)uoff, (const unsigned long long *)ucnt, units, count, dLoff));
-        if (units && cap > 0)
-            PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL(k_doc_emit, dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.dPrev, ix.dSA,
-                                                                   (const uint32_t *)dLo, (const uint32_t *)dOcc, (const unsigned long long *)uoff,
-                                                                   (const uint32_t *)uq, (const unsigned long long *)ucnt, units, count, chunk, ix.dOff,
-                                                                   ix.ndocs + 1u, (uint32_t)ix.n, dDocs, (unsigned long long)cap));
-        HIP_TRY(hipStreamSynchronize(st));
-        std::vector<int64_t> loff(C + 1);
-        sc.down(loff.data(), dLoff, (C + 1) * 8);
-        if (sc.rc) return sc.rc;
-        listed = loff[C];
-        if (listed < 0) return SA_AMD_EINTERNAL;              // (above `bound` only for an array that is no suffix array: what fits `cap` is written)
-        const int64_t wr = listed < cap ? listed : cap;
-        if (s2.finish() != SA_AMD_OK) return s2.rc;
+        DocsListing ls;
+        { const int rcl = docs_listing(b, ls, ix, count, capacity); if (rcl) return rcl; }
+        const int64_t wr = ls.listed < ls.cap ? ls.listed : ls.cap;
+        if (ls.s2.finish() != SA_AMD_OK) return ls.s2.rc;
         if (sc.finish() != SA_AMD_OK) return sc.rc;
-        if (wr > 0) HIP_TRY(hipMemcpy(docs, dDocs, (size_t)wr * 4, hipMemcpyDeviceToHost));    // the last step that can fail; list_off and the total behind it
-        memcpy(list_off, loff.data(), (C + 1) * 8);
-        *total_out = listed;
-        ds.df_sum = listed;
+        if (wr > 0) HIP_TRY(hipMemcpy(docs, ls.dDocs, (size_t)wr * 4, hipMemcpyDeviceToHost));    // the last step that can fail; list_off and the total behind it
+        memcpy(list_off, ls.loff.data(), (C + 1) * 8);
+        *total_out = ls.listed;
+        ds.df_sum = ls.listed;
     }
     g_prof.resolve();
     ds.readbacks = g_readbacks - rb0;

@@ -22,6 +22,7 @@
 #include "host/match.hpp"
 #include "host/docs.hpp"
 #include "host/doc_repeats.hpp"
+#include "host/doc_tf.hpp"
 
 extern "C" {
 
@@ -346,6 +347,7 @@ struct sa_amd_index {
     uint32_t *dDocOff;    // document offsets (ndocs + 1 entries) once sa_amd_index_set_documents has taken a collection (kernels/docs.hpp)
     uint32_t *dDocPrev;   // per slot: the previous slot of the same document + 1 (n + 1 entries)
     uint32_t ndocs;
+    uint32_t *dDocSlots;  // the slots 1 .. n ordered by document once sa_amd_index_enable_doc_freq has built them (kernels/doc_tf.hpp)
 };
 
 SA_EXPORT int32_t sa_amd_index_create(const uint8_t *T, int32_t n, const uint32_t *SA, sa_amd_index **out)
@@ -373,7 +375,7 @@ SA_EXPORT int32_t sa_amd_index_create(const uint8_t *T, int32_t n, const uint32_
     sa_amd_index *ix = new (std::nothrow) sa_amd_index();
     if (!ix) return SA_AMD_ENOMEM;
     ix->n = n; ix->device = 0; ix->dBkt = nullptr; ix->dPair = nullptr;
-    ix->dDocOff = nullptr; ix->dDocPrev = nullptr; ix->ndocs = 0;
+    ix->dDocOff = nullptr; ix->dDocPrev = nullptr; ix->ndocs = 0; ix->dDocSlots = nullptr;
     (void)hipGetDevice(&ix->device);
     ix->dT = dT.as<uint8_t>(); ix->dSA = dSA.as<uint32_t>();
     dT.p = nullptr; dSA.p = nullptr;                             // ownership moves to the index
@@ -391,6 +393,7 @@ SA_EXPORT void sa_amd_index_destroy(sa_amd_index *ix)      // (frees and deletes
     if (ix->dPair) (void)hipFree(ix->dPair);
     if (ix->dDocOff) (void)hipFree(ix->dDocOff);
     if (ix->dDocPrev) (void)hipFree(ix->dDocPrev);
+    if (ix->dDocSlots) (void)hipFree(ix->dDocSlots);
     delete ix;
 }
 
@@ -874,7 +877,7 @@ static sa::DocIndex doc_index(const sa_amd_index *ix)
 {
     sa::DocIndex di;
     di.device = ix->device; di.dT = ix->dT; di.dSA = ix->dSA; di.n = ix->n; di.dBkt = ix->dBkt; di.dPair = ix->dPair;
-    di.dOff = ix->dDocOff; di.dPrev = ix->dDocPrev; di.ndocs = ix->ndocs;
+    di.dOff = ix->dDocOff; di.dPrev = ix->dDocPrev; di.ndocs = ix->ndocs; di.dSlots = ix->dDocSlots;
     return di;
 }
 
@@ -901,6 +904,8 @@ SA_EXPORT int32_t sa_amd_index_set_documents(sa_amd_index *ix, const uint32_t *d
     if (sc.finish() != SA_AMD_OK) return sc.rc;                  // (a previous collection stays)
     if (ix->dDocOff) (void)hipFree(ix->dDocOff);
     if (ix->dDocPrev) (void)hipFree(ix->dDocPrev);
+    if (ix->dDocSlots) (void)hipFree(ix->dDocSlots);             // the frequency table was the old collection's: enabled again by the caller
+    ix->dDocSlots = nullptr;
     ix->dDocOff = off.as<uint32_t>(); ix->dDocPrev = prev.as<uint32_t>(); ix->ndocs = (uint32_t)ndocs;
     off.p = nullptr; prev.p = nullptr;
     return SA_AMD_OK;
@@ -987,6 +992,63 @@ SA_EXPORT int32_t sa_amd_index_doc_repeat_spans(const sa_amd_index *ix, int32_t 
 SA_EXPORT void sa_amd_last_doc_repeat_stats(sa_amd_doc_repeat_stats *out)
 {
     if (out) *out = sa::g_last_doc_repeat_stats;
+}
+
+// ---- per-document term frequencies and top-k documents (host/doc_tf.hpp, kernels/doc_tf.hpp) ----
+
+SA_EXPORT int32_t sa_amd_index_enable_doc_freq(sa_amd_index *ix)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !ix->dDocOff) return SA_AMD_EINVAL;
+    if (ix->dDocSlots) return SA_AMD_OK;
+    sa::PooledScope sc(ix->device, false);
+    if (sc.rc) return sc.rc;
+    sa::DevBuf slots;                                            // the table outlives the call: its own allocation, not the pool's
+    if (slots.alloc(((size_t)ix->n + 1) * 4) != SA_AMD_OK) { (void)hipGetLastError(); return SA_AMD_ENOMEM; }      // (n entries; never empty)
+    const size_t wb = sa::docs_layout(ix->n).bytes;
+    sc.acquire(wb);
+    void *dW = sc.take(wb);
+    if (sc.rc == SA_AMD_OK) sc.rc = sa::docs_freq_build(ix->dSA, ix->n, ix->dDocOff, ix->ndocs, slots.as<uint32_t>(), dW, (int64_t)wb, sc.st);
+    if (sc.finish() != SA_AMD_OK) return sc.rc;
+    ix->dDocSlots = slots.as<uint32_t>();
+    slots.p = nullptr;
+    return SA_AMD_OK;
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_doc_tf(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, int64_t *list_off,
+                                      uint32_t *docs, uint32_t *tf, int64_t capacity, int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    // (in this order: everything that can be refused without the index is, before the index is looked at)
+    if (!ix || !sa::search_patterns_valid(pat_data, pat_off, count) || capacity < 0 || !list_off || !total_out) return SA_AMD_EINVAL;
+    if (!ix->dDocOff || !ix->dDocSlots) return SA_AMD_EINVAL;
+    return sa::doc_tf_query(doc_index(ix), pat_data, pat_off, count, 0, list_off, docs, tf, capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_doc_topk(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, int32_t k,
+                                        int64_t *top_off, uint32_t *docs, uint32_t *tf)
+{
+    SA_ABI_GUARD_BEGIN
+    // (in this order: everything that can be refused without the index is, before the index is looked at)
+    if (!ix || k < 1 || k > SA_AMD_DOC_TOPK_MAX || !sa::search_patterns_valid(pat_data, pat_off, count) || !top_off) return SA_AMD_EINVAL;
+    if (!ix->dDocOff || !ix->dDocSlots) return SA_AMD_EINVAL;
+    return sa::doc_tf_query(doc_index(ix), pat_data, pat_off, count, k, top_off, docs, tf, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_doc_tf_stats(sa_amd_doc_tf_stats *out)
+{
+    if (out) *out = sa::g_last_doc_tf_stats;
+}
+
+SA_EXPORT int32_t sa_amd_docs_set_topk_piece(int32_t entries)
+{
+    const int32_t prev = sa::g_topk_piece < 0 ? sa::DOC_TOPK_PIECE_DEFAULT : sa::g_topk_piece;
+    const int32_t e = entries < sa::DOC_TOPK_PIECE_MIN ? sa::DOC_TOPK_PIECE_MIN : (entries > sa::DOC_TOPK_PIECE_MAX ? sa::DOC_TOPK_PIECE_MAX : entries);
+    sa::g_topk_piece = entries < 0 ? -1 : (int32_t)sa::topk_pow2_floor((uint32_t)e);
+    return prev;
 }
 
 SA_EXPORT void sa_amd_last_unbwt_stats(sa_amd_unbwt_stats *out)

@@ -23,6 +23,9 @@ int32_t sa_amd_debug_rerank_routes(int32_t flags);
  * previous mode): 0 never (the key route), 1 when the dense route is expected (what the product library always does), 2 whenever
  * that sort runs -- the routes that read the sorted keys then rebuild them.  Every mode gives the same array and statistics. */
 int32_t sa_amd_debug_head_flags(int32_t mode);
+/* the second bound of the term-frequency kernel (process-wide; returns the previous mode): 0 galloping from the first bound (what
+ * the product library always does), 1 a plain binary search of the document's part.  Both give the same answers. */
+int32_t sa_amd_debug_doc_tf_bounds(int32_t mode);
 int32_t sa_amd_debug_sort_variant_count(void);
 const char *sa_amd_debug_sort_variant_name(int32_t index);
 /* stable LSD radix sort of (u64 key, u32 value) pairs on bits [begin_bit, end_bit); host buffers */

@@ -24,6 +24,11 @@ SA_EXPORT int32_t sa_amd_debug_rerank_routes(int32_t flags)
     return sa::g_rerank_routes.exchange(flags & 3);
 }
 
+SA_EXPORT int32_t sa_amd_debug_doc_tf_bounds(int32_t mode)
+{
+    return sa::g_doc_tf_plain_bounds.exchange(mode ? 1 : 0);
+}
+
 SA_EXPORT int32_t sa_amd_debug_head_flags(int32_t mode)
 {
     return sa::g_head_flags_mode.exchange(mode < 0 ? 0 : (mode > 2 ? 2 : mode));
