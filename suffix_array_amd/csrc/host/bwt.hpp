@@ -3,6 +3,8 @@
 #pragma once
 #include "pipeline.hpp"
 #include "host_path.hpp"
+#include "scope.hpp"
+#include "index.hpp"
 #include "../kernels/bwt.hpp"
 
 namespace sa {
@@ -25,8 +27,7 @@ static int bwt_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, uint8
     const int64_t n = n32;
     if (work_bytes < (int64_t)BWT_WORK_BYTES || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
     if (n > 0 && (const uint8_t *)dB == dT) return SA_AMD_EINVAL;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
-    g_posted_off = tn.no_posted_readback;
+    route_tuning();                                             // (the posted read-backs' switch; nothing else of the tuning is used here)
     uint32_t *ctl = (uint32_t *)dWork;
     HIP_TRY(hipMemsetAsync(ctl, 0, 256, st));
 
@@ -66,7 +67,7 @@ static int bwt_resident(PooledScope &sc, const Inputs &in, int32_t n, uint8_t *B
 static int bwt_host(const uint8_t *T, int32_t n, const uint32_t *SA, uint8_t *B, int32_t *primary_out)
 {
     if (n < 0 || !primary_out || (n > 0 && (!T || !B))) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    if (device_count() <= 0) return SA_AMD_ENODEVICE;
     PooledScope sc(pick_device(), true);
     const Inputs in = upload_inputs(sc, T, n, SA, BWT_WORK_BYTES, align_up((size_t)n + 16, 256));
     return bwt_resident(sc, in, n, B, primary_out);
@@ -109,8 +110,7 @@ static int unbwt_device(const uint8_t *dB, int32_t n32, int32_t primary32, uint8
     if (primary32 < 1 || primary32 > n32) return SA_AMD_EINVAL;
     const UnbwtLayout L = unbwt_layout(n32);
     if (work_bytes < (int64_t)L.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
-    g_posted_off = tn.no_posted_readback;
+    const Tuning tn = route_tuning();
     const int rb0 = g_readbacks;
     const uint32_t primary = (uint32_t)primary32;
     char *base = (char *)dWork;
@@ -220,7 +220,7 @@ static int unbwt_host(const uint8_t *B, int32_t n, int32_t primary, uint8_t *T_o
 {
     if (n < 0 || (n > 0 && (!B || !T_out))) return SA_AMD_EINVAL;
     if (n == 0 ? primary != 0 : (primary < 1 || primary > n)) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    if (device_count() <= 0) return SA_AMD_ENODEVICE;
     const size_t tb = align_up((size_t)n + 16, 256), wb = unbwt_layout(n).bytes;
     PooledScope sc(pick_device(), true);
     sc.acquire(wb + 2 * tb);
@@ -230,6 +230,14 @@ static int unbwt_host(const uint8_t *B, int32_t n, int32_t primary, uint8_t *T_o
     if (sc.rc == SA_AMD_OK) sc.rc = unbwt_device(dB, n, primary, dT, dW, (int64_t)wb, sc.st);
     if (n > 0) sc.down(T_out, dT, (size_t)n);
     return sc.finish();
+}
+
+// the index's resident text and array: only the work block and the output come from the pool; on the null stream
+static int32_t bwt_index(const sa_amd_index &ix, uint8_t *BWT, int32_t *primary_out)
+{
+    PooledScope sc(ix.device, false);
+    const Inputs in = resident_inputs(sc, ix.text(), ix.sa(), BWT_WORK_BYTES, (size_t)ix.n + 16);
+    return bwt_resident(sc, in, ix.n, BWT, primary_out);
 }
 
 }  // namespace sa

@@ -45,7 +45,7 @@ static int launch_docrep_mark(int scope, unsigned g, hipStream_t st, const uint3
 // ix: the resident text, array and collection (device memory on the current device); dWork: docrep_layout(n, ndocs).bytes,
 // 256-byte aligned.  The first `capacity` spans to dSpans, the number of all of them to *count_out (host); account: doc_bytes
 // (ndocs words) stand in the work block's doc_bytes slab afterwards.  Arguments checked by the caller.  Blocks until done.
-static int doc_repeats_device(const DocIndex &ix, int32_t min_len, int32_t mode, int32_t scope, uint32_t *dSpans, int64_t capacity,
+static int doc_repeats_device(const sa_amd_index &ix, int32_t min_len, int32_t mode, int32_t scope, uint32_t *dSpans, int64_t capacity,
                               int64_t *count_out, bool account, void *dWork, int64_t work_bytes, hipStream_t st)
 {
     const int64_t n = ix.n;
@@ -62,12 +62,11 @@ static int doc_repeats_device(const DocIndex &ix, int32_t min_len, int32_t mode,
     const DocRepLayout D = docrep_layout(ix.n, ix.ndocs);
     const LcpLayout &L = D.rep.lcp;
     if (work_bytes < (int64_t)D.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
-    g_posted_off = tn.no_posted_readback;
+    const Tuning tn = route_tuning();
     const int rb0 = g_readbacks;
     char *base = (char *)dWork;
     uint32_t *dDocBytes = (uint32_t *)(base + D.doc_bytes);
-    { const int rcf = lcp_front(ix.dT, ix.dSA, n, dWork, L, st, tn, stats); if (rcf) return rcf; }
+    { const int rcf = lcp_front(ix.text(), ix.sa(), n, dWork, L, st, tn, stats); if (rcf) return rcf; }
     stats.readbacks = g_readbacks - rb0;
     g_last_lcp_stats = stats;
     if (account) HIP_TRY(hipMemsetAsync(dDocBytes, 0, (size_t)ix.ndocs * 4, st));
@@ -103,13 +102,13 @@ static int doc_repeats_device(const DocIndex &ix, int32_t min_len, int32_t mode,
         const uint32_t stride = (uint32_t)ceil_div((int64_t)M, DOC_SAMPLES), ns = (uint32_t)ceil_div((int64_t)M, stride);
         int64_t sg = (int64_t)cu_count() * 4;
         if (sg > tiles) sg = tiles;
-        PROF(KC_REP_LR, n, st, hipLaunchKernelGGL(k_docrep_slots, dim3((unsigned)sg), dim3(REP_THREADS), 0, st, ix.dSA, n, plcp, ix.dOff, M, stride, ns, k_min,
+        PROF(KC_REP_LR, n, st, hipLaunchKernelGGL(k_docrep_slots, dim3((unsigned)sg), dim3(REP_THREADS), 0, st, ix.sa(), n, plcp, ix.doc_off(), M, stride, ns, k_min,
                                                   lcps, dsv, dev, agg, ctl, dctl));
     }
     PROF(KC_REP_LR, tiles, st, hipLaunchKernelGGL(k_docrep_seg_spine, dim3(4), dim3(REP_SPINE_THREADS), 0, st, (const uint32_t *)agg, tiles, carry));
     {
-        const int rcm = mode == REP_MODE_ALL ? launch_docrep_mark<REP_MODE_ALL>(scope, g, st, ix.dSA, n, lcps, dsv, dev, k_min, carry, flag)
-                                             : launch_docrep_mark<REP_MODE_KEEP_FIRST>(scope, g, st, ix.dSA, n, lcps, dsv, dev, k_min, carry, flag);
+        const int rcm = mode == REP_MODE_ALL ? launch_docrep_mark<REP_MODE_ALL>(scope, g, st, ix.sa(), n, lcps, dsv, dev, k_min, carry, flag)
+                                             : launch_docrep_mark<REP_MODE_KEEP_FIRST>(scope, g, st, ix.sa(), n, lcps, dsv, dev, k_min, carry, flag);
         if (rcm) return rcm;
     }
 
@@ -119,7 +118,7 @@ static int doc_repeats_device(const DocIndex &ix, int32_t min_len, int32_t mode,
     // ---- per-document accounting (tile_max: still the exclusive running maximum of the tiles' reach) ----
     if (account) {
         PROF(KC_REP_SPANS, n, st, hipLaunchKernelGGL(k_docrep_account, dim3(g), dim3(REP_THREADS), 0, st, (const uint8_t *)flag, n, k_min,
-                                                     (const uint32_t *)tile_max, ix.dOff, M, dDocBytes));
+                                                     (const uint32_t *)tile_max, ix.doc_off(), M, dDocBytes));
         int64_t tg = ceil_div((int64_t)ix.ndocs, REP_THREADS);
         if (tg > 4096) tg = 4096;
         PROF(KC_MISC, (int64_t)ix.ndocs, st, hipLaunchKernelGGL(k_docrep_touched, dim3((unsigned)tg), dim3(REP_THREADS), 0, st, (const uint32_t *)dDocBytes,
@@ -153,13 +152,13 @@ static int doc_repeats_device(const DocIndex &ix, int32_t min_len, int32_t mode,
 }
 
 // host pointers; the work block and the spans' slab come from the pool, on the null stream as the index's other routes
-static int doc_repeats_index(const DocIndex &ix, int32_t min_len, int32_t mode, int32_t scope, uint32_t *spans, int64_t capacity, int64_t *count_out,
+static int doc_repeats_index(const sa_amd_index &ix, int32_t min_len, int32_t mode, int32_t scope, uint32_t *spans, int64_t capacity, int64_t *count_out,
                              uint32_t *doc_bytes)
 {
     CappedRows rows(capacity, repeat_spans_bound(ix.n, min_len));
     PooledScope sc(ix.device, false);
     const DocRepLayout D = docrep_layout(ix.n, ix.ndocs);
-    const Inputs in = resident_inputs(sc, ix.dT, ix.dSA, D.bytes, rows.bytes());
+    const Inputs in = resident_inputs(sc, ix.text(), ix.sa(), D.bytes, rows.bytes());
     uint32_t *dOut = (uint32_t *)sc.take(rows.bytes());
     if (sc.rc == SA_AMD_OK)
         sc.rc = doc_repeats_device(ix, min_len, mode, scope, dOut, rows.cap, &rows.count, doc_bytes != nullptr, in.dW, (int64_t)in.wb, sc.st);

@@ -30,6 +30,23 @@ static int docs_freq_build(const uint32_t *dSA, int32_t n32, const uint32_t *dOf
     return docs_built(ctl, st);
 }
 
+// sa_amd_index_enable_doc_freq: the table of the index's collection (there is one: checked by the caller); built once
+static int32_t docs_freq_enable(sa_amd_index &ix)
+{
+    if (ix.doc_slots()) return SA_AMD_OK;
+    PooledScope sc(ix.device, false);
+    if (sc.rc) return sc.rc;
+    DevBuf slots;
+    if (index_table_alloc(slots, ((size_t)ix.n + 1) * 4) != SA_AMD_OK) return SA_AMD_ENOMEM;      // (n entries; never empty)
+    const size_t wb = docs_layout(ix.n).bytes;
+    sc.acquire(wb);
+    void *dW = sc.take(wb);
+    if (sc.rc == SA_AMD_OK) sc.rc = docs_freq_build(ix.sa(), ix.n, ix.doc_off(), ix.ndocs, slots.as<uint32_t>(), dW, (int64_t)wb, sc.st);
+    if (sc.finish() != SA_AMD_OK) return sc.rc;
+    ix.dDocSlots = std::move(slots);
+    return SA_AMD_OK;
+}
+
 static uint32_t topk_pow2_floor(uint32_t v) { uint32_t p = 1; while (p * 2 <= v) p *= 2; return p; }
 static uint32_t topk_pow2_ceil(uint64_t v) { uint32_t p = 1; while (p < v) p *= 2; return p; }
 
@@ -70,7 +87,7 @@ static std::vector<TopkRound> topk_rounds(std::vector<unsigned long long> &len, 
 // k >= 1: the top k documents of every pattern (off_out = top_off; docs / tf compact, count * k entries at most).
 // Host pointers, docs and tf may be nullptr, arguments checked by the caller.  Read-backs: the listing's (units, list_off),
 // the counters of k_doc_tf.
-static int doc_tf_query(const DocIndex &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, int32_t k, int64_t *off_out,
+static int doc_tf_query(const sa_amd_index &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, int32_t k, int64_t *off_out,
                         uint32_t *docs, uint32_t *tf, int64_t capacity, int64_t *total_out)
 {
     sa_amd_doc_tf_stats ts;
@@ -132,12 +149,12 @@ static int doc_tf_query(const DocIndex &ix, const uint8_t *pat_data, const int64
         if (g > most) g = most;
 #ifdef SA_AMD_DIAG
         if (g_doc_tf_plain_bounds.load(std::memory_order_relaxed))
-            PROF(KC_MISC, entries, st, hipLaunchKernelGGL((k_doc_tf<false>), dim3((unsigned)g), dim3(DOC_THREADS), 0, st, ix.dSlots, ix.dOff, ix.ndocs,
+            PROF(KC_MISC, entries, st, hipLaunchKernelGGL((k_doc_tf<false>), dim3((unsigned)g), dim3(DOC_THREADS), 0, st, ix.doc_slots(), ix.doc_off(), ix.ndocs,
                                                           (uint32_t)ix.n, (const uint32_t *)b.dLo, (const uint32_t *)b.dOcc, (const long long *)b.dLoff, count,
                                                           (const uint32_t *)ls.dDocs, entries, dTf, keysA, b.ctl));
         else
 #endif
-            PROF(KC_MISC, entries, st, hipLaunchKernelGGL((k_doc_tf<true>), dim3((unsigned)g), dim3(DOC_THREADS), 0, st, ix.dSlots, ix.dOff, ix.ndocs,
+            PROF(KC_MISC, entries, st, hipLaunchKernelGGL((k_doc_tf<true>), dim3((unsigned)g), dim3(DOC_THREADS), 0, st, ix.doc_slots(), ix.doc_off(), ix.ndocs,
                                                           (uint32_t)ix.n, (const uint32_t *)b.dLo, (const uint32_t *)b.dOcc, (const long long *)b.dLoff, count,
                                                           (const uint32_t *)ls.dDocs, entries, dTf, keysA, b.ctl));
     }

@@ -3,19 +3,13 @@
 #pragma once
 #include "scope.hpp"
 #include "esa.hpp"
+#include "index.hpp"
 #include "../kernels/docs.hpp"
 
 namespace sa {
 
 static thread_local sa_amd_docs_stats g_last_docs_stats;
 static thread_local int32_t g_docs_chunk = -1;          // sa_amd_docs_set_chunk of the calling thread (-1: DOC_CHUNK_DEFAULT)
-
-// what the calls need of an index (sa_api.hip owns the struct)
-struct DocIndex {
-    int device; const uint8_t *dT; const uint32_t *dSA; int32_t n; const uint32_t *dBkt; const uint64_t *dPair;
-    const uint32_t *dOff; const uint32_t *dPrev; uint32_t ndocs;
-    const uint32_t *dSlots;       // the slots ordered by document once sa_amd_index_enable_doc_freq has built them (host/doc_tf.hpp), else nullptr
-};
 
 // layout of the build's work block: control words (the sort's error word first) | four (n + 1)-entry buffers (the document ids
 // of the slots, the sort's values and their two alternates) | sort spine | single-pass granules.  About 16 bytes per byte of text.
@@ -69,8 +63,7 @@ static int docs_sorted_slots(const uint32_t *dSA, int32_t n32, const uint32_t *d
     const int64_t n = n32;
     const DocsLayout L = docs_layout(n32);
     if (!dWork || work_bytes < (int64_t)L.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
-    g_posted_off = tn.no_posted_readback;
+    const Tuning tn = route_tuning();
     char *base = (char *)dWork;
     uint32_t *ctl = (uint32_t *)(base + L.ctl);
     uint32_t *keys = (uint32_t *)(base + L.keys), *vals = (uint32_t *)(base + L.vals);
@@ -152,10 +145,9 @@ struct DocsBatch {
 
 // patterns up, the ranges by the search kernels, the units.  One blocking read-back: the number of units (with the summed occ
 // and the bound of the listing).  count >= 1.
-static int docs_ranges(DocsBatch &b, const DocIndex &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, bool list)
+static int docs_ranges(DocsBatch &b, const sa_amd_index &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, bool list)
 {
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
-    g_posted_off = tn.no_posted_readback;
+    route_tuning();                                             // (the posted read-backs' switch; nothing else of the tuning is used here)
     const size_t C = (size_t)count, total = (size_t)pat_off[count];
     const uint32_t N1 = (uint32_t)ix.n + 1u;
     b.chunk = (uint32_t)(g_docs_chunk < 0 ? DOC_CHUNK_DEFAULT : g_docs_chunk);
@@ -182,7 +174,7 @@ static int docs_ranges(DocsBatch &b, const DocIndex &ix, const uint8_t *pat_data
 
     // ---- the ranges, by the search kernels as sa_amd_index_search runs them ----
     g_prof.begin(KC_MISC, count, st);
-    const int rcs = launch_search(ix.dT, ix.dSA, ix.n, ix.dBkt, ix.dPair, dP, dO, count, nullptr, dLo, dHi, nullptr, nullptr, nullptr, st);
+    const int rcs = launch_search(ix.text(), ix.sa(), ix.n, ix.bkt(), ix.pair(), dP, dO, count, nullptr, dLo, dHi, nullptr, nullptr, nullptr, st);
     g_prof.end(st);
     if (rcs) return rcs;
     // ---- the units: ceil(occ / chunk) per pattern, scanned; the number of all of them comes back ----
@@ -207,7 +199,7 @@ struct DocsListing {
 };
 
 // counts per unit, one scan for the units' offsets and the patterns', ordered compaction; waits for the stream
-static int docs_listing(DocsBatch &b, DocsListing &ls, const DocIndex &ix, int32_t count, int64_t capacity)
+static int docs_listing(DocsBatch &b, DocsListing &ls, const sa_amd_index &ix, int32_t count, int64_t capacity)
 {
     const size_t C = (size_t)count;
     const unsigned long long units = b.units, occ_sum = b.occ_sum;
@@ -223,16 +215,16 @@ static int docs_listing(DocsBatch &b, DocsListing &ls, const DocIndex &ix, int32
     if (s2.rc) return s2.rc;
     HIP_TRY(hipMemsetAsync(ucnt + units, 0, 8, st));
     if (units)
-        PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL((k_doc_count<true>), dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.dPrev,
+        PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL((k_doc_count<true>), dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.doc_prev(),
                                                                (const uint32_t *)b.dLo, (const uint32_t *)b.dOcc, (const unsigned long long *)b.uoff, count, units,
                                                                chunk, (uint32_t *)nullptr, ucnt, uq));
     { const int rcn = docs_scan(ucnt, (int64_t)units + 1, utsum, nullptr, st); if (rcn) return rcn; }
     PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_doc_list_off, dim3((unsigned)ceil_div((int64_t)count + 1, DOC_THREADS)), dim3(DOC_THREADS), 0, st,
                                                 (const unsigned long long *)b.uoff, (const unsigned long long *)ucnt, units, count, b.dLoff));
     if (units && cap > 0)
-        PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL(k_doc_emit, dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.dPrev, ix.dSA,
+        PROF(KC_MISC, (int64_t)occ_sum, st, hipLaunchKernelGGL(k_doc_emit, dim3(docs_unit_grid((int64_t)units)), dim3(DOC_THREADS), 0, st, ix.doc_prev(), ix.sa(),
                                                                (const uint32_t *)b.dLo, (const uint32_t *)b.dOcc, (const unsigned long long *)b.uoff,
-                                                               (const uint32_t *)uq, (const unsigned long long *)ucnt, units, count, chunk, ix.dOff,
+                                                               (const uint32_t *)uq, (const unsigned long long *)ucnt, units, count, chunk, ix.doc_off(),
                                                                ix.ndocs + 1u, (uint32_t)ix.n, dDocs, (unsigned long long)cap));
     HIP_TRY(hipStreamSynchronize(st));
     ls.loff.resize(C + 1);
@@ -246,7 +238,7 @@ static int docs_listing(DocsBatch &b, DocsListing &ls, const DocIndex &ix, int32
 // Document frequency (!list: occ and df, either may be nullptr) or listing (list_off: count + 1 entries, the first `capacity`
 // documents to docs, the number of all of them to *total_out) of a batch of patterns; host pointers, arguments checked by the
 // caller.
-static int docs_query(const DocIndex &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, bool list, uint32_t *occ_out,
+static int docs_query(const sa_amd_index &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, bool list, uint32_t *occ_out,
                       uint32_t *df_out, int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
 {
     sa_amd_docs_stats ds;
@@ -273,7 +265,7 @@ static int docs_query(const DocIndex &ix, const uint8_t *pat_data, const int64_t
         std::vector<uint32_t> df(C);
         if (b.units)
             PROF(KC_MISC, (int64_t)b.occ_sum, st, hipLaunchKernelGGL((k_doc_count<false>), dim3(docs_unit_grid((int64_t)b.units)), dim3(DOC_THREADS), 0, st,
-                                                                     ix.dPrev, (const uint32_t *)b.dLo, (const uint32_t *)b.dOcc,
+                                                                     ix.doc_prev(), (const uint32_t *)b.dLo, (const uint32_t *)b.dOcc,
                                                                      (const unsigned long long *)b.uoff, count, b.units, b.chunk, b.dDf,
                                                                      (unsigned long long *)nullptr, (uint32_t *)nullptr));
         HIP_TRY(hipStreamSynchronize(st));
@@ -297,6 +289,52 @@ static int docs_query(const DocIndex &ix, const uint8_t *pat_data, const int64_t
     ds.readbacks = g_readbacks - rb0;
     g_last_docs_stats = ds;
     return SA_AMD_OK;
+}
+
+// sa_amd_index_set_documents: the collection's two tables, built from the caller's offsets (checked by the caller) and handed to
+// the index.  A failure leaves the previous collection and its frequency table; a success drops that table, which was the old
+// collection's: the caller enables it again.
+static int32_t docs_set(sa_amd_index &ix, const uint32_t *doc_off, int64_t ndocs)
+{
+    const size_t M = (size_t)ndocs + 1, N1 = (size_t)ix.n + 1;
+    PooledScope sc(ix.device, false);
+    if (sc.rc) return sc.rc;
+    DevBuf off, prev;
+    if (index_table_alloc(off, M * 4) != SA_AMD_OK || index_table_alloc(prev, N1 * 4) != SA_AMD_OK) return SA_AMD_ENOMEM;
+    const size_t wb = docs_layout(ix.n).bytes;
+    sc.acquire(wb);
+    void *dW = sc.take(wb);
+    if (sc.rc == SA_AMD_OK) sc.rc = hip_status(hipMemcpy(off.p, doc_off, M * 4, hipMemcpyHostToDevice));
+    if (sc.rc == SA_AMD_OK) sc.rc = docs_build(ix.sa(), ix.n, off.as<uint32_t>(), (uint32_t)ndocs, prev.as<uint32_t>(), dW, (int64_t)wb, sc.st);
+    if (sc.finish() != SA_AMD_OK) return sc.rc;                  // (a previous collection stays)
+    ix.dDocOff = std::move(off);
+    ix.dDocPrev = std::move(prev);
+    ix.dDocSlots.reset();
+    ix.ndocs = (uint32_t)ndocs;
+    return SA_AMD_OK;
+}
+
+// sa_amd_index_doc_of: host pointers, count >= 1
+static int32_t doc_of_host(const sa_amd_index &ix, const uint32_t *pos, int64_t count, uint32_t *doc_out)
+{
+    const size_t b = align_up((size_t)count * 4, 256);
+    PooledScope sc(ix.device, false);
+    sc.acquire(2 * b);
+    uint32_t *dPos = (uint32_t *)sc.take(b), *dOut = (uint32_t *)sc.take(b);
+    if (sc.rc == SA_AMD_OK) sc.rc = hip_status(hipMemcpyAsync(dPos, pos, (size_t)count * 4, hipMemcpyHostToDevice, sc.st));
+    if (sc.rc == SA_AMD_OK) sc.rc = launch_doc_of(dPos, count, ix.doc_off(), ix.ndocs, ix.n, dOut, sc.st);
+    sc.down(doc_out, dOut, (size_t)count * 4);
+    return sc.finish();
+}
+
+// sa_amd_index_doc_of_device: pointers on the index's device, count >= 1.  Blocks until done.
+static int32_t doc_of_device(const sa_amd_index &ix, const uint32_t *dPos, int64_t count, uint32_t *dDoc, hipStream_t st)
+{
+    DeviceGuard guard(ix.device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    const int32_t rc = launch_doc_of(dPos, count, ix.doc_off(), ix.ndocs, ix.n, dDoc, st);
+    if (rc) return rc;
+    return hip_status(hipStreamSynchronize(st));
 }
 
 }  // namespace sa

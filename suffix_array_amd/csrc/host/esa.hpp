@@ -74,4 +74,78 @@ static int launch_search(const uint8_t *dT, const uint32_t *dSA, int32_t n, cons
     return SA_AMD_OK;
 }
 
+// sa_amd_index_search behind its argument checks: the patterns go up in buffers of the call's own, the outputs (each may be
+// nullptr) come back by blocking copies; the thread's search statistics are those of this call
+static int32_t index_search(const sa_amd_index &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, uint8_t *contains,
+                            uint32_t *range_lo, uint32_t *range_hi, uint32_t *lcp_start, uint32_t *lcp_len)
+{
+    if (count == 0) {
+        sa_amd_search_stats z;
+        memset(&z, 0, sizeof(z));
+        z.route = ix.pair() ? 1 : 0;
+        if (!ix.pair()) z.compared_bytes = z.steps = z.table_steps = -1;
+        g_last_search_stats = z;
+        return SA_AMD_OK;
+    }
+    const int64_t total = pat_off[count];
+    DeviceGuard guard(ix.device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    const size_t C = (size_t)count;
+    DevBuf dP, dO, dC, dR;
+    int32_t rc;
+    if ((rc = dP.alloc((size_t)total))) return rc;
+    if ((rc = dO.alloc((C + 1) * 8))) return rc;
+    if ((rc = dC.alloc(C))) return rc;
+    if ((rc = dR.alloc(C * 4 * 4))) return rc;
+    if (total) HIP_TRY(hipMemcpy(dP.p, pat_data, (size_t)total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dO.p, pat_off, (C + 1) * 8, hipMemcpyHostToDevice));
+    uint32_t *R = dR.as<uint32_t>();
+    sa_amd_search_stats stats;
+    memset(&stats, 0, sizeof(stats));
+    stats.patterns = count;
+    stats.compared_bytes = stats.steps = stats.table_steps = -1;
+    DevBuf dS;
+    if (ix.pair()) {                                             // LCP route (kernels/esa.hpp): its three counters
+        if ((rc = dS.alloc(3 * 8))) return rc;
+        HIP_TRY(hipMemset(dS.p, 0, 3 * 8));
+    }
+    if ((rc = launch_search(ix.text(), ix.sa(), ix.n, ix.bkt(), ix.pair(), dP.as<const uint8_t>(), dO.as<const int64_t>(), count, dC.as<uint8_t>(), R, R + C,
+                            R + 2 * C, R + 3 * C, ix.pair() ? dS.as<unsigned long long>() : nullptr, nullptr))) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    if (ix.pair()) {
+        int64_t cw[3];
+        HIP_TRY(hipMemcpy(cw, dS.p, sizeof(cw), hipMemcpyDeviceToHost));
+        stats.compared_bytes = cw[0]; stats.steps = cw[1]; stats.table_steps = cw[2];
+        stats.route = 1;
+    }
+    g_last_search_stats = stats;
+    if (contains) HIP_TRY(hipMemcpy(contains, dC.p, C, hipMemcpyDeviceToHost));
+    if (range_lo) HIP_TRY(hipMemcpy(range_lo, R, C * 4, hipMemcpyDeviceToHost));
+    if (range_hi) HIP_TRY(hipMemcpy(range_hi, R + C, C * 4, hipMemcpyDeviceToHost));
+    if (lcp_start) HIP_TRY(hipMemcpy(lcp_start, R + 2 * C, C * 4, hipMemcpyDeviceToHost));
+    if (lcp_len) HIP_TRY(hipMemcpy(lcp_len, R + 3 * C, C * 4, hipMemcpyDeviceToHost));
+    return SA_AMD_OK;
+}
+
+// sa_amd_index_enable_lcp: the pair table, built once from the LCP array and kept
+static int32_t index_enable_lcp(sa_amd_index &ix)
+{
+    if (ix.pair()) return SA_AMD_OK;
+    PooledScope sc(ix.device, false);
+    if (sc.rc) return sc.rc;
+    DevBuf pair;
+    if (index_table_alloc(pair, ((size_t)ix.n + 1) * 8) != SA_AMD_OK) return SA_AMD_ENOMEM;
+    // LCP array and its work block from the pool, as sa_amd_index_lcp; the tile minima of the table build behind them
+    const size_t lb = align_up(((size_t)ix.n + 1) * 4, 256), mb = esa_mins_elems(ix.n) * 4;
+    const Inputs in = resident_inputs(sc, ix.text(), ix.sa(), lcp_layout(ix.n).bytes, lb + mb);
+    uint32_t *dL = (uint32_t *)sc.take(lb), *dMins = (uint32_t *)sc.take(mb);
+    if (sc.rc == SA_AMD_OK) sc.rc = lcp_device(in.dT, in.dSA, ix.n, dL, in.dW, (int64_t)in.wb, sc.st);
+    if (sc.rc == SA_AMD_OK) sc.rc = esa_build(dL, ix.n, pair.as<uint64_t>(), dMins, sc.st);
+    if (sc.rc == SA_AMD_OK) sc.rc = hip_status(hipDeviceSynchronize());      // (the route's own wait: finish() adds none on success)
+    if (sc.finish() != SA_AMD_OK) return sc.rc;
+    ix.dPair = std::move(pair);                                 // kept: later searches take the LCP route
+    return SA_AMD_OK;
+}
+
 }  // namespace sa

@@ -553,7 +553,7 @@ struct BuildBlock {
 
 static int acquire_build_block(int32_t n, int node, const HostTuning &ht, BuildBlock &b)
 {
-    const size_t wb = (size_t)sa_amd_workspace_bytes(n);
+    const size_t wb = (size_t)carve(nullptr, n).bytes;
     b.tb = align_up((size_t)n, 256);
     b.sb = align_up(((size_t)n + 1) * 4, 256);
     b.ws_dev = wb;
@@ -743,6 +743,80 @@ static int build_host_small_batch(const uint8_t *const *T, uint32_t *const *SA, 
         for (size_t k = k0; k < k1; ++k) status[items[k]] = rcc;
         if (first == SA_AMD_OK) first = rcc;
         k0 = k1;
+    }
+    return first;
+}
+
+// sa_amd_saca_batch behind its argument checks: `count` texts over `ndev` > 0 devices (device[i], or round robin), status[i]
+// (may be nullptr) per text; returns the first failure.
+static int32_t saca_batch(const uint8_t *const *T, uint32_t *const *SA, const int32_t *n, const int32_t *device, int32_t count, int32_t *status,
+                          int ndev)
+{
+    std::vector<int32_t> st((size_t)count, SA_AMD_OK);
+    std::vector<std::vector<int>> per_dev((size_t)ndev), small_dev((size_t)ndev);
+    // texts of up to SA_AMD_SMALL_MAX bytes (the one-workgroup kernel's) are built together, one launch per device and chunk
+    // (host/host_path.hpp, build_host_small_batch) -- unless a device has a single one, which takes the single-call path
+    const HostTuning ht = HostTuning::from_env();
+    for (int i = 0; i < count; ++i) {
+        const int d = device ? device[i] : i % ndev;
+        if (d < 0 || d >= ndev) { st[(size_t)i] = SA_AMD_EINVAL; continue; }
+        if (n[i] > 0 && n[i] <= ht.small_max && T[i] && SA[i]) small_dev[(size_t)d].push_back(i);
+        else per_dev[(size_t)d].push_back(i);
+    }
+    for (int d = 0; d < ndev; ++d)
+        if (small_dev[(size_t)d].size() == 1) { per_dev[(size_t)d].push_back(small_dev[(size_t)d][0]); small_dev[(size_t)d].clear(); }
+    std::vector<std::atomic<int>> small_taken((size_t)ndev);
+    for (auto &a : small_taken) a.store(0);
+    // Two host threads per device (SA_AMD_BATCH_THREADS, 1..16), each with its own stream and device block, take the
+    // device's items in turn: while one waits for its 4(n+1)-byte copy back over PCIe the other uploads and computes,
+    // so the link and the GPU overlap instead of alternating.
+    // (SA_AMD_BATCH_THREADS = 0, the default: two per device; six for a device whose texts are all below SA_AMD_LANES_MIN_N, twelve
+    // when they are all below 8 MiB -- those builds leave most of the GPU idle and take no turns, host/host_path.hpp; measured,
+    // one GPU: 128 x 1 MiB of English 196 ms with two threads and turns, 67 with eight, 58 with twelve; 16 x 16 MiB 75 / 65 / 71)
+    const int per_env = (int)env_int("SA_AMD_BATCH_THREADS", 0, 0, 16);
+    const int64_t lanes_min = ht.lanes_min_n;
+    std::vector<int> per_of((size_t)ndev, 2);
+    for (int d = 0; d < ndev; ++d) {
+        int64_t largest = 0;
+        for (int i : per_dev[(size_t)d]) largest = n[i] > largest ? n[i] : largest;
+        per_of[(size_t)d] = per_env > 0 ? per_env : (largest < lanes_min ? (largest < ((int64_t)8 << 20) ? 12 : 6) : 2);
+    }
+    std::vector<std::atomic<size_t>> next((size_t)ndev);
+    for (auto &a : next) a.store(0);
+    auto work = [&](int d) {
+        if (!small_dev[(size_t)d].empty() && small_taken[(size_t)d].exchange(1) == 0) {
+            // (the first worker of the device to get here; the others go on with the large texts meanwhile)
+            try { (void)build_host_small_batch(T, SA, n, small_dev[(size_t)d].data(), small_dev[(size_t)d].size(), d, st.data()); }
+            catch (const std::bad_alloc &) { for (int i : small_dev[(size_t)d]) st[(size_t)i] = SA_AMD_ENOMEM; }
+            catch (...) { for (int i : small_dev[(size_t)d]) st[(size_t)i] = SA_AMD_EINTERNAL; }
+        }
+        for (;;) {
+            const size_t q = next[(size_t)d].fetch_add(1);
+            if (q >= per_dev[(size_t)d].size()) break;
+            const int i = per_dev[(size_t)d][q];
+            int32_t rc;
+            try { rc = build_host(T[i], SA[i], n[i], true, d); }
+            catch (const std::bad_alloc &) { rc = SA_AMD_ENOMEM; }
+            catch (...) { rc = SA_AMD_EINTERNAL; }
+            st[(size_t)i] = rc;
+        }
+    };
+    std::vector<std::thread> workers;
+    bool spawn_failed = false;
+    for (int d = 0; d < ndev && !spawn_failed; ++d) {
+        const size_t items = per_dev[(size_t)d].size() + (small_dev[(size_t)d].empty() ? 0 : 1);
+        for (int k = 0; k < per_of[(size_t)d] && (size_t)k < items; ++k) {
+            try { workers.emplace_back(work, d); }
+            catch (...) { spawn_failed = true; break; }         // (std::system_error: no more threads)
+        }
+    }
+    for (auto &t : workers) t.join();
+    if (spawn_failed)
+        for (int d = 0; d < ndev; ++d) work(d);                  // whatever the started workers left is done here, serially
+    int32_t first = SA_AMD_OK;
+    for (int i = 0; i < count; ++i) {
+        if (status) status[i] = st[(size_t)i];
+        if (first == SA_AMD_OK && st[(size_t)i] != SA_AMD_OK) first = st[(size_t)i];
     }
     return first;
 }

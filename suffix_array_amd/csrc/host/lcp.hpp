@@ -4,6 +4,7 @@
 #include "pipeline.hpp"
 #include "host_path.hpp"
 #include "scope.hpp"
+#include "index.hpp"
 #include "../kernels/lcp.hpp"
 
 namespace sa {
@@ -171,8 +172,7 @@ static int lcp_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, uint3
     g_last_lcp_stats = stats;
     const LcpLayout L = lcp_layout(n32);
     if (work_bytes < (int64_t)L.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
-    g_posted_off = tn.no_posted_readback;
+    const Tuning tn = route_tuning();
     const int rb0 = g_readbacks;
     { const int rcf = lcp_front(dT, dSA, n, dWork, L, st, tn, stats); if (rcf) return rcf; }
     if (n == 0) {
@@ -200,7 +200,7 @@ static int lcp_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, uint3
 static int lcp_host(const uint8_t *T, int32_t n, uint32_t *SA, uint32_t *LCP, bool with_build)
 {
     if (n < 0 || !SA || !LCP || (n > 0 && !T)) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    if (device_count() <= 0) return SA_AMD_ENODEVICE;
     const size_t N1 = (size_t)n + 1;
     PooledScope sc(pick_device(), true);
     const Inputs in = upload_inputs(sc, T, n, with_build ? nullptr : SA, lcp_layout(n).bytes, align_up(N1 * 4, 256));
@@ -208,6 +208,18 @@ static int lcp_host(const uint8_t *T, int32_t n, uint32_t *SA, uint32_t *LCP, bo
     if (sc.rc == SA_AMD_OK) sc.rc = lcp_device(in.dT, in.dSA, n, dL, in.dW, (int64_t)in.wb, sc.st);
     if (with_build) sc.down(SA, in.dSA, N1 * 4);
     sc.down(LCP, dL, N1 * 4);
+    return sc.finish();
+}
+
+// the index's resident text and array: only the work block and the output come from the pool; on the null stream
+static int32_t lcp_index(const sa_amd_index &ix, uint32_t *LCP)
+{
+    const size_t lb = ((size_t)ix.n + 1) * 4;
+    PooledScope sc(ix.device, false);
+    const Inputs in = resident_inputs(sc, ix.text(), ix.sa(), lcp_layout(ix.n).bytes, lb);
+    uint32_t *dL = (uint32_t *)sc.take(lb);
+    if (sc.rc == SA_AMD_OK) sc.rc = lcp_device(in.dT, in.dSA, ix.n, dL, in.dW, (int64_t)in.wb, sc.st);
+    sc.down(LCP, dL, lb);
     return sc.finish();
 }
 

@@ -81,8 +81,7 @@ static int lz_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, bool p
     const LcpLayout &L = Z.lcp;
     if (work_bytes < (int64_t)Z.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
     if (parse && (capacity < 0 || !count_out || (capacity > 0 && !dPhrases))) return SA_AMD_EINVAL;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
-    g_posted_off = tn.no_posted_readback;
+    route_tuning();                                             // (the posted read-backs' switch; nothing else of the tuning is used here)
     const int rb0 = g_readbacks;
     { const int rcr = lcp_range(dSA, n, dWork, L, st); if (rcr) return rcr; }
     if (n == 0) {
@@ -240,12 +239,23 @@ static int lz_host(const uint8_t *T, int32_t n, const uint32_t *SA, bool parse, 
 {
     if (n < 0 || (n > 0 && !T)) return SA_AMD_EINVAL;
     if (parse && (capacity < 0 || !count_out || (capacity > 0 && !phrases))) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    if (device_count() <= 0) return SA_AMD_ENODEVICE;
     CappedRows rows;
     if (parse) rows = CappedRows(capacity, n);                      // no more phrases than bytes
     PooledScope sc(pick_device(), true);
     const Inputs in = upload_inputs(sc, T, n, SA, lz_layout(n).bytes, parse ? align_up(rows.bytes(), 256) : 2 * align_up(((size_t)n + 1) * 4, 256));
     return lz_resident(sc, in, n, parse, LPF, SRC, phrases, rows, count_out);
+}
+
+// the index's resident text and array: only the work block and the outputs come from the pool; on the null stream
+static int32_t lz_index(const sa_amd_index &ix, bool parse, uint32_t *LPF, uint32_t *SRC, uint32_t *phrases, int64_t capacity, int64_t *count_out)
+{
+    if (parse && (capacity < 0 || !count_out || (capacity > 0 && !phrases))) return SA_AMD_EINVAL;
+    CappedRows rows;
+    if (parse) rows = CappedRows(capacity, ix.n);
+    PooledScope sc(ix.device, false);
+    const Inputs in = resident_inputs(sc, ix.text(), ix.sa(), lz_layout(ix.n).bytes, parse ? rows.bytes() : 2 * align_up(((size_t)ix.n + 1) * 4, 256));
+    return lz_resident(sc, in, ix.n, parse, LPF, SRC, phrases, rows, count_out);
 }
 
 }  // namespace sa

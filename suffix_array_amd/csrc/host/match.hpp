@@ -3,6 +3,7 @@
 #pragma once
 #include "repeats.hpp"
 #include "esa.hpp"
+#include "index.hpp"
 #include "../kernels/match.hpp"
 
 namespace sa {
@@ -10,9 +11,6 @@ namespace sa {
 static thread_local sa_amd_match_stats g_last_match_stats;
 static thread_local int32_t g_match_cap = -1;          // sa_amd_match_set_group_cap of the calling thread (-1: MATCH_CAP_DEFAULT)
 static thread_local int32_t g_match_lanes = 8;         // sa_amd_match_set_group_lanes of the calling thread: 4, 8 or 16
-
-// what the calls need of an index (sa_api.hip owns the struct)
-struct MatchIndex { const uint8_t *dT; const uint32_t *dSA; int32_t n; const uint32_t *dBkt; const uint64_t *dPair; };
 
 // layout of the work block: control words | the long list (m entries) | the flag bytes (m) | the span passes' words per tile
 struct MatchLayout { size_t ctl, list, flag, tile_max, cnt, bytes; };
@@ -33,18 +31,18 @@ static MatchLayout match_layout(int32_t m)
 static_assert((MATCH_C_WORDS + REP_C_WORDS) * 8 <= 256, "control slab");
 
 template <int G>
-static void launch_match_tile(const MatchIndex &ix, const uint8_t *dQ, int64_t m, int64_t C, int ge, uint32_t *dML, uint32_t *dPOS, uint8_t *flag,
+static void launch_match_tile(const sa_amd_index &ix, const uint8_t *dQ, int64_t m, int64_t C, int ge, uint32_t *dML, uint32_t *dPOS, uint8_t *flag,
                               uint32_t *list, unsigned long long *ctl, hipStream_t st)
 {
     const unsigned g = (unsigned)ceil_div(m, MATCH_TILE);
-    hipLaunchKernelGGL((k_match_tile<G>), dim3(g), dim3(MATCH_THREADS), (size_t)match_stage_words(ge) * 4, st, ix.dT, ix.dSA, (int64_t)ix.n, ix.dBkt,
+    hipLaunchKernelGGL((k_match_tile<G>), dim3(g), dim3(MATCH_THREADS), (size_t)match_stage_words(ge) * 4, st, ix.text(), ix.sa(), (int64_t)ix.n, ix.bkt(),
                        dQ, m, C, ge, dML, dPOS, flag, list, ctl);
 }
 
 // dQ: m bytes on the index's device (any byte address); dWork: match_layout(m).bytes, 256-byte aligned.  !spans: ML and POS
 // (either may be nullptr) for cap C.  spans: those of min_len = C, the first `capacity` of them to dSpans, the number of all of
 // them to *count_out (host).  Blocks until done.
-static int match_device(const MatchIndex &ix, const uint8_t *dQ, int32_t m32, int32_t C32, bool spans, uint32_t *dML, uint32_t *dPOS,
+static int match_device(const sa_amd_index &ix, const uint8_t *dQ, int32_t m32, int32_t C32, bool spans, uint32_t *dML, uint32_t *dPOS,
                         uint32_t *dSpans, int64_t capacity, int64_t *count_out, void *dWork, int64_t work_bytes, hipStream_t st)
 {
     const int64_t m = m32, C = C32;
@@ -58,7 +56,7 @@ static int match_device(const MatchIndex &ix, const uint8_t *dQ, int32_t m32, in
     const int G = g_match_lanes;
     ms.positions = m;
     ms.longest_pos = -1;
-    ms.route_long = ix.dPair ? 1 : 0;
+    ms.route_long = ix.pair() ? 1 : 0;
     ms.group_cap = cap < MATCH_STAGE_MAX ? cap : MATCH_STAGE_MAX;
     ms.group_lanes = G >= 16 ? 16 : (G >= 8 ? 8 : 4);
     ms.tile = MATCH_TILE;
@@ -67,8 +65,7 @@ static int match_device(const MatchIndex &ix, const uint8_t *dQ, int32_t m32, in
         if (spans) *count_out = 0;
         return SA_AMD_OK;
     }
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
-    g_posted_off = tn.no_posted_readback;
+    route_tuning();                                             // (the posted read-backs' switch; nothing else of the tuning is used here)
     const int rb0 = g_readbacks;
     char *base = (char *)dWork;
     unsigned long long *ctl = (unsigned long long *)(base + L.ctl), *rctl = ctl + MATCH_C_WORDS;
@@ -91,11 +88,11 @@ static int match_device(const MatchIndex &ix, const uint8_t *dQ, int32_t m32, in
     // ---- pass 2: one wave per listed position ----
     if (longs > 0) {
         const unsigned g = (unsigned)ceil_div(longs * WAVE, MATCH_THREADS);
-        if (ix.dPair)
-            PROF(KC_MISC, longs, st, hipLaunchKernelGGL((k_match_long<true>), dim3(g), dim3(MATCH_THREADS), 0, st, ix.dT, ix.dSA, (int64_t)ix.n, ix.dPair,
+        if (ix.pair())
+            PROF(KC_MISC, longs, st, hipLaunchKernelGGL((k_match_long<true>), dim3(g), dim3(MATCH_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n, ix.pair(),
                                                         esa_log_p(ix.n), dQ, m, C, (const uint32_t *)list, longs, dML, dPOS, flag, ctl));
         else
-            PROF(KC_MISC, longs, st, hipLaunchKernelGGL((k_match_long<false>), dim3(g), dim3(MATCH_THREADS), 0, st, ix.dT, ix.dSA, (int64_t)ix.n,
+            PROF(KC_MISC, longs, st, hipLaunchKernelGGL((k_match_long<false>), dim3(g), dim3(MATCH_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n,
                                                         (const uint64_t *)nullptr, 0, dQ, m, C, (const uint32_t *)list, longs, dML, dPOS, flag, ctl));
     }
 
@@ -128,7 +125,7 @@ static int match_device(const MatchIndex &ix, const uint8_t *dQ, int32_t m32, in
 
 // host buffers: the query goes up, ML / POS (4 m bytes each, either may be nullptr) or the first `capacity` spans come back.
 // The index's device is current (the caller's guard).
-static int match_host(const MatchIndex &ix, const uint8_t *Q, int32_t m, int32_t C, bool spans, uint32_t *ML, uint32_t *POS, uint32_t *out_spans,
+static int match_host(const sa_amd_index &ix, const uint8_t *Q, int32_t m, int32_t C, bool spans, uint32_t *ML, uint32_t *POS, uint32_t *out_spans,
                       int64_t capacity, int64_t *count_out)
 {
     if (m < 0 || C < 1 || (m > 0 && !Q)) return SA_AMD_EINVAL;

@@ -13,6 +13,16 @@
 
 namespace sa {
 
+// The tuning of one call, read from the environment: the one place that passes the engines' variant counts (host/sort.hpp).
+static inline Tuning env_tuning() { return Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32); }
+// The same for a route that reads words back (read_words): the calling thread's posted read-backs follow the tuning.
+static inline Tuning route_tuning()
+{
+    const Tuning tn = env_tuning();
+    g_posted_off = tn.no_posted_readback;
+    return tn;
+}
+
 constexpr size_t GRAM_MAX_ENTRIES = (size_t)1 << 24;   // gram keys: the rank table has sigma^g <= min(n, 2^24) entries
 static_assert(GROUP_CAP_MAX == GS_CAP, "Tuning clamps SA_AMD_GROUP_CAP to the kernel's cap");
 
@@ -1511,12 +1521,11 @@ static int build_device(const uint8_t *dT, uint32_t *dSA, int32_t n32, void *dWo
     DeviceBuild B;
     B.dT = dT; B.dSA = dSA; B.SA = dSA + 1; B.n = n; B.st = st;
     B.early = early;
-    B.tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
+    B.tn = route_tuning();
     B.trace = env_int("SA_AMD_VERBOSE", 0, 0, 9) >= 3;      // one line per refinement round on stderr
     B.trace_t = now_ms();
     memset(&B.local, 0, sizeof(B.local));
     g_readbacks = 0;
-    g_posted_off = B.tn.no_posted_readback;
     const Tuning &tn = B.tn;
     sa_amd_stats &local = B.local;
     if (n == 0) {

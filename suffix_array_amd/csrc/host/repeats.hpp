@@ -64,8 +64,7 @@ static int repeats_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, b
     const LcpLayout &L = R.lcp;
     if (work_bytes < (int64_t)R.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
     if (spans && (min_len < 1 || (mode != REP_MODE_ALL && mode != REP_MODE_KEEP_FIRST) || capacity < 0 || !count_out)) return SA_AMD_EINVAL;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
-    g_posted_off = tn.no_posted_readback;
+    const Tuning tn = route_tuning();
     const int rb0 = g_readbacks;
     { const int rcf = lcp_front(dT, dSA, n, dWork, L, st, tn, stats); if (rcf) return rcf; }
     stats.readbacks = g_readbacks - rb0;
@@ -176,12 +175,26 @@ static int repeats_host(const uint8_t *T, int32_t n, const uint32_t *SA, bool sp
     if (n < 0 || (n > 0 && !T)) return SA_AMD_EINVAL;
     if (spans && (min_len < 1 || (mode != REP_MODE_ALL && mode != REP_MODE_KEEP_FIRST) || capacity < 0 || !count_out ||
                   (capacity > 0 && !out_spans))) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    if (device_count() <= 0) return SA_AMD_ENODEVICE;
     CappedRows rows;
     if (spans) rows = CappedRows(capacity, repeat_spans_bound(n, min_len));
     PooledScope sc(pick_device(), true);
     const Inputs in = upload_inputs(sc, T, n, SA, rep_layout(n).bytes, align_up(spans ? rows.bytes() : ((size_t)n + 1) * 4, 256));
     return repeats_resident(sc, in, n, spans, LR, min_len, mode, out_spans, rows, count_out);
+}
+
+// the index's resident text and array: only the work block and the output come from the pool; on the null stream
+static int32_t repeats_index(const sa_amd_index &ix, bool spans, uint32_t *LR, int32_t min_len, int32_t mode, uint32_t *out_spans, int64_t capacity,
+                             int64_t *count_out)
+{
+    if (spans ? (min_len < 1 || (mode != SA_AMD_REPEATS_ALL && mode != SA_AMD_REPEATS_KEEP_FIRST) || capacity < 0 || !count_out ||
+                 (capacity > 0 && !out_spans))
+              : (ix.n > 0 && !LR)) return SA_AMD_EINVAL;
+    CappedRows rows;
+    if (spans) rows = CappedRows(capacity, repeat_spans_bound(ix.n, min_len));
+    PooledScope sc(ix.device, false);
+    const Inputs in = resident_inputs(sc, ix.text(), ix.sa(), rep_layout(ix.n).bytes, spans ? rows.bytes() : ((size_t)ix.n + 1) * 4);
+    return repeats_resident(sc, in, ix.n, spans, LR, min_len, mode, out_spans, rows, count_out);
 }
 
 }  // namespace sa

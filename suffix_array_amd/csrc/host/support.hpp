@@ -23,6 +23,7 @@
 #include <new>
 #include <atomic>
 #include <thread>
+#include <utility>
 #include <vector>
 #include <chrono>
 #include <sys/syscall.h>
@@ -66,11 +67,24 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf &operator=(DevBuf &&o) noexcept      // what this held is freed, what `o` held is this one's: `o` is left empty
+    {
+        if (this != &o) { reset(); p = o.p; o.p = nullptr; }
+        return *this;
+    }
     ~DevBuf() { reset(); }
     int alloc(size_t bytes) { reset(); return hip_status(hipMalloc(&p, bytes ? bytes : 1)); }
     void reset() { if (p) (void)hipFree(p); p = nullptr; }
     template <typename T> T *as() const { return (T *)p; }
 };
+
+// the number of HIP devices (0 where the runtime cannot tell): what sa_amd_device_count answers
+static inline int device_count()
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess) return 0;
+    return ndev;
+}
 
 // makes `device` current for the scope and restores the caller's device afterwards (device < 0: leave it alone)
 struct DeviceGuard {

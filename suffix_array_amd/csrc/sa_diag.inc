@@ -44,9 +44,9 @@ SA_EXPORT int32_t sa_amd_test_sort_pairs(uint64_t *keys, uint32_t *vals, int64_t
 {
     using namespace sa;
     if (count < 0 || (count > 0 && (!keys || !vals)) || begin_bit < 0 || end_bit > 64) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
     if (count == 0) return SA_AMD_OK;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
+    const Tuning tn = env_tuning();
     const size_t N = (size_t)count;
     DevBuf dk, dv, dsp;
     int32_t rc;
@@ -79,8 +79,8 @@ SA_EXPORT int32_t sa_amd_test_sort_pairs_flags(const uint64_t *keys, uint32_t *v
 {
     using namespace sa;
     if (count <= 0 || !keys || !vals || !flags_out || !keys_out || begin_bit < 0 || end_bit > 64 || end_bit <= begin_bit) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
+    const Tuning tn = env_tuning();
     const size_t N = (size_t)count;
     memset(keys_out, 0xA5, N * 8);
     if (count == 1) { flags_out[0] = OS_HF_START; return SA_AMD_OK; }
@@ -117,8 +117,8 @@ SA_EXPORT int32_t sa_amd_test_sample_sort64(uint64_t *keys, uint32_t *vals, int6
 {
     using namespace sa;
     if (count <= 0 || !keys || !vals || !done || key_bits < 1 || key_bits > 64) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
+    const Tuning tn = env_tuning();
     const size_t N = (size_t)count;
     DevBuf dk, dv, dsp, dst, dbig, dsmall;
     int32_t rc;
@@ -155,9 +155,9 @@ SA_EXPORT int32_t sa_amd_test_sort_pairs32(uint32_t *keys, uint32_t *vals, int64
 {
     using namespace sa;
     if (count < 0 || (count > 0 && (!keys || !vals)) || begin_bit < 0 || end_bit > 32) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
     if (count == 0) return SA_AMD_OK;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
+    const Tuning tn = env_tuning();
     const size_t N = ((size_t)count + 3) & ~(size_t)3;
     DevBuf dk, dv, dsp;
     int32_t rc;
@@ -194,10 +194,10 @@ SA_EXPORT int32_t sa_amd_test_bucket_sort32(uint32_t *keys, uint32_t *vals, int6
 {
     using namespace sa;
     if (count < 0 || (count > 0 && (!keys || !vals)) || !largest || (top_bits != 16 && top_bits != 18)) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
     *largest = 0;
     if (count == 0) return SA_AMD_OK;
-    const Tuning tn = Tuning::from_env(N_SORT_VARIANTS, N_SORT32_VARIANTS, N_OS_SHAPES64, N_OS_SHAPES32);
+    const Tuning tn = env_tuning();
     const size_t N = ((size_t)count + 3) & ~(size_t)3;
     DevBuf dk, dv, dsp, dst, dbs;
     int32_t rc;
@@ -241,7 +241,7 @@ SA_EXPORT int32_t sa_amd_test_build_keys(const uint8_t *T, int32_t n, uint64_t *
 {
     using namespace sa;
     if (n <= 0 || !T || !keys) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
     DevBuf dT, dk, dv, dh;
     int32_t rc;
     if ((rc = dT.alloc((size_t)n))) return rc;
@@ -276,7 +276,7 @@ SA_EXPORT int32_t sa_amd_proto_induce_l(const uint8_t *T, const uint8_t *typeL, 
 {
     using namespace sa;
     if (n <= 0 || !T || !typeL || !SA || !head || !ms || !counters) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
     const size_t N = (size_t)n;
     DevBuf dT, dL, dS, dH, dC;
     int32_t rc;
@@ -314,7 +314,7 @@ SA_EXPORT int32_t sa_amd_test_lz_nsv(const uint32_t *dA, int64_t n, uint32_t *dP
 {
     using namespace sa;
     if (n <= 0 || n > 0x7fffffffLL || !dA || !dPsv || !dNsv || !counters) return SA_AMD_EINVAL;
-    if (sa_amd_device_count() <= 0) return SA_AMD_ENODEVICE;
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
     DevBuf dl, dc;
     int32_t rc;
     if ((rc = dl.alloc(((size_t)n / 31 + 64) * 4))) return rc;
