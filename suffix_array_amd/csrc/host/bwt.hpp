@@ -91,8 +91,8 @@ static UnbwtLayout unbwt_layout(int32_t n)
     L.alt_elems = (N1 + 67) & ~(size_t)3;
     L.widx = take(L.alt_elems * 4);
     L.wk = take(2 * L.alt_elems * 4);
-    L.spine = take(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4);
-    L.status = take(((size_t)ceil_div((int64_t)N1, OS_MIN_TILE) + 1) * RADIX * 8);
+    L.spine = take(SortScratch::SPINE_BYTES);
+    L.status = take(SortScratch::granule_bytes((int64_t)N1));
     L.bytes = off;
     return L;
 }
@@ -122,18 +122,16 @@ static int unbwt_device(const uint8_t *dB, int32_t n32, int32_t primary32, uint8
 
     // ---- phase 1: ψ by one stable digit sort of the indices of B ----
     {
-        SortScratch ss;
-        ss.spine = (uint32_t *)(base + L.spine);
-        ss.digit_tot = ss.spine + (size_t)RADIX * SORT_MAX_WG;
-        ss.status = (unsigned long long *)(base + L.status);
-        ss.err = ctl;
+        const SortScratch ss = SortScratch::make(base + L.spine, base + L.status, ctl);
         uint32_t *keys = wk, *altv = wk + L.alt_elems, *altk = widx;
         int64_t gb = ceil_div(ceil_div(n, 4), BWT_THREADS);
         if (gb > 65536) gb = 65536;
         PROF(KC_MISC, n, st, hipLaunchKernelGGL(k_unbwt_keys, dim3((unsigned)gb), dim3(BWT_THREADS), 0, st, dB, n, keys,
                                                 (((uintptr_t)dB) & 3u) == 0 ? 1 : 0));
-        SortResult32 pr;
-        const int rcs = sort_pairs32(keys, nullptr, altk, altv, n, 0, RADIX_BITS, ss, nullptr, st, &pr, tn, true);
+        SortJob<uint32_t> job{ keys, nullptr, altk, altv, n, 0, RADIX_BITS };
+        job.iota = true;
+        SortResult<uint32_t> pr;
+        const int rcs = sort_pairs32(job, ss, st, tn, &pr);
         if (rcs) return rcs;
         if (pr.passes > 1) return SA_AMD_EINTERNAL;
         int64_t pb = ceil_div(n, BWT_THREADS);

@@ -21,7 +21,7 @@ static int docs_freq_build(const uint32_t *dSA, int32_t n32, const uint32_t *dOf
                            hipStream_t st)
 {
     const int64_t n = n32;
-    SortResult32 pr;
+    SortResult<uint32_t> pr;
     uint32_t *ctl = nullptr;
     { const int rcs = docs_sorted_slots(dSA, n32, dOff, ndocs, dWork, work_bytes, st, &pr, &ctl); if (rcs) return rcs; }
     if (n > 0)

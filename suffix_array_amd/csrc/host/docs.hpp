@@ -26,8 +26,8 @@ static DocsLayout docs_layout(int32_t n)
     L.vals = take(L.alt_elems * 4);
     L.altk = take(L.alt_elems * 4);
     L.altv = take(L.alt_elems * 4);
-    L.spine = take(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4);
-    L.status = take(((size_t)ceil_div((int64_t)N1, OS_MIN_TILE) + 1) * RADIX * 8);
+    L.spine = take(SortScratch::SPINE_BYTES);
+    L.status = take(SortScratch::granule_bytes((int64_t)N1));
     L.bytes = off;
     return L;
 }
@@ -58,7 +58,7 @@ static int launch_doc_of(const uint32_t *dPos, int64_t count, const uint32_t *dO
 // document sorts nothing and the order is that of the slots).  dWork: docs_layout(n).bytes, 256-byte aligned; *ctl_out: its
 // control words, the sort's error word first.
 static int docs_sorted_slots(const uint32_t *dSA, int32_t n32, const uint32_t *dOff, uint32_t ndocs, void *dWork, int64_t work_bytes, hipStream_t st,
-                             SortResult32 *pr, uint32_t **ctl_out)
+                             SortResult<uint32_t> *pr, uint32_t **ctl_out)
 {
     const int64_t n = n32;
     const DocsLayout L = docs_layout(n32);
@@ -68,15 +68,12 @@ static int docs_sorted_slots(const uint32_t *dSA, int32_t n32, const uint32_t *d
     uint32_t *ctl = (uint32_t *)(base + L.ctl);
     uint32_t *keys = (uint32_t *)(base + L.keys), *vals = (uint32_t *)(base + L.vals);
     HIP_TRY(hipMemsetAsync(ctl, 0, 256, st));
-    SortScratch ss;
-    ss.spine = (uint32_t *)(base + L.spine);
-    ss.digit_tot = ss.spine + (size_t)RADIX * SORT_MAX_WG;
-    ss.status = (unsigned long long *)(base + L.status);
-    ss.err = ctl;
+    const SortScratch ss = SortScratch::make(base + L.spine, base + L.status, ctl);
     { const int rcd = launch_doc_of(dSA + 1, n, dOff, ndocs, n32, keys, st); if (rcd) return rcd; }
     *ctl_out = ctl;
-    return sort_pairs32(keys, vals, (uint32_t *)(base + L.altk), (uint32_t *)(base + L.altv), n, 0, bit_length((uint64_t)ndocs - 1), ss, nullptr, st, pr, tn,
-                        true);
+    SortJob<uint32_t> job{ keys, vals, (uint32_t *)(base + L.altk), (uint32_t *)(base + L.altv), n, 0, bit_length((uint64_t)ndocs - 1) };
+    job.iota = true;
+    return sort_pairs32(job, ss, st, tn, pr);
 }
 
 // the end of every table build: the sort's error word comes back; blocks until the table is written
@@ -102,7 +99,7 @@ static int docs_build(const uint32_t *dSA, int32_t n32, const uint32_t *dOff, ui
                       hipStream_t st)
 {
     const int64_t n = n32;
-    SortResult32 pr;
+    SortResult<uint32_t> pr;
     uint32_t *ctl = nullptr;
     { const int rcs = docs_sorted_slots(dSA, n32, dOff, ndocs, dWork, work_bytes, st, &pr, &ctl); if (rcs) return rcs; }
     PROF(KC_MISC, n, st, hipLaunchKernelGGL(k_doc_prev, dim3(docs_slot_grid(n)), dim3(DOC_THREADS), 0, st, (const uint32_t *)pr.keys,

@@ -41,8 +41,8 @@ static CiLayout ci_layout(int32_t n)
     L.rank = take(N1 * 4);
     L.alt_elems = (N1 + 67) & ~(size_t)3;
     L.alt = take(4 * L.alt_elems * 4);
-    L.spine = take(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4);
-    L.status = take(((size_t)ceil_div((int64_t)N1, OS_MIN_TILE) + 1) * RADIX * 8);
+    L.spine = take(SortScratch::SPINE_BYTES);
+    L.status = take(SortScratch::granule_bytes((int64_t)N1));
     L.err = take(256);
     L.starts = take(257 * 4);
     L.bitmap_bytes = ((N1 + 31) / 32 + 1) * 4;
@@ -70,21 +70,15 @@ static int32_t check_integrity_device(const uint8_t *dT, int32_t n, const uint32
         if (f & 1u) return SA_AMD_ERANGE;
         if (f & 2u) return 0;
         char *base = (char *)dWork;
-        Workspace w;
-        memset(&w, 0, sizeof(w));
-        w.isa = (uint32_t *)(base + L.rank);
-        w.spine = (uint32_t *)(base + L.spine);
-        w.digit_tot = w.spine + (size_t)RADIX * SORT_MAX_WG;
-        w.os_status = (unsigned long long *)(base + L.status);
-        w.os_err = (uint32_t *)(base + L.err);
-        w.ss.spine = w.spine; w.ss.digit_tot = w.digit_tot; w.ss.status = w.os_status; w.ss.err = w.os_err;
-        HIP_TRY(hipMemsetAsync(w.os_err, 0, 16, st));
+        uint32_t *rank_of = (uint32_t *)(base + L.rank);
+        const SortScratch ss = SortScratch::make(base + L.spine, base + L.status, (uint32_t *)(base + L.err));
+        HIP_TRY(hipMemsetAsync(ss.err, 0, 16, st));
         uint32_t *alt = (uint32_t *)(base + L.alt);
         const Tuning tn = env_tuning();
         sa_amd_stats local;
         memset(&local, 0, sizeof(local));
         // pairs (SA[i], i), i = 0 .. n, binned by the suffix position; the scatter skips the empty suffix (value n)
-        const int rcs = scatter_binned((uint32_t *)dSA, nullptr, alt, alt + L.alt_elems, (int64_t)n + 1, (int64_t)n, w, st, &local, tn, true,
+        const int rcs = scatter_binned(ss, rank_of, (uint32_t *)dSA, nullptr, alt, alt + L.alt_elems, (int64_t)n + 1, (int64_t)n, st, &local, tn, true,
                                        alt + 2 * L.alt_elems, alt + 3 * L.alt_elems);
         if (rcs) return rcs;
         // first bytes: boundaries proposed from the array, proved in text order (streaming); then the slot-order check
@@ -93,14 +87,14 @@ static int32_t check_integrity_device(const uint8_t *dT, int32_t n, const uint32
         hipLaunchKernelGGL(k_ci_starts, dim3(1), dim3(512), 0, st, dT, dSA, (int64_t)n, starts, bitmap);
         int64_t fblocks = ceil_div((int64_t)n, 256 * 16);
         if (fblocks > 16384) fblocks = 16384;
-        hipLaunchKernelGGL(k_ci_first_bytes, dim3((unsigned)fblocks), dim3(256), 0, st, dT, (int64_t)n, (const uint32_t *)w.isa, (const uint32_t *)starts, flags);
+        hipLaunchKernelGGL(k_ci_first_bytes, dim3((unsigned)fblocks), dim3(256), 0, st, dT, (int64_t)n, (const uint32_t *)rank_of, (const uint32_t *)starts, flags);
         const int64_t cblocks = ceil_div((int64_t)n, (int64_t)CI_THREADS * CI_ITEMS);
-        hipLaunchKernelGGL(k_ci_check_shared, dim3((unsigned)cblocks), dim3(CI_THREADS), 0, st, dSA, (int64_t)n, (const uint32_t *)w.isa,
+        hipLaunchKernelGGL(k_ci_check_shared, dim3((unsigned)cblocks), dim3(CI_THREADS), 0, st, dSA, (int64_t)n, (const uint32_t *)rank_of,
                            (const uint32_t *)bitmap, flags);
         HIP_TRY(hipGetLastError());
         uint32_t words[2] = { 0, 0 };
         { const int rcw = read_words(&words[0], flags, 4, st); if (rcw) return rcw; }
-        { const int rcw = read_words(&words[1], w.os_err, 4, st); if (rcw) return rcw; }
+        { const int rcw = read_words(&words[1], ss.err, 4, st); if (rcw) return rcw; }
         if (words[1]) return SA_AMD_EINTERNAL;
         return (words[0] & 2u) ? 0 : 1;
     }

@@ -26,8 +26,8 @@ static LcpLayout lcp_layout(int32_t n)
     L.phi = take(N1 * 4);
     L.alt_elems = (N1 + 67) & ~(size_t)3;
     L.alt = take(4 * L.alt_elems * 4);
-    L.spine = take(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4);
-    L.status = take(((size_t)ceil_div((int64_t)N1, OS_MIN_TILE) + 1) * RADIX * 8);
+    L.spine = take(SortScratch::SPINE_BYTES);
+    L.status = take(SortScratch::granule_bytes((int64_t)N1));
     L.tiles = take(((size_t)ceil_div((int64_t)N1, LCP_TILE) + 1) * 4);
     L.bytes = off;
     return L;
@@ -64,19 +64,12 @@ static int lcp_partner_phi(const uint32_t *dSA, int64_t n, void *dWork, const Lc
     if (binned(n, n, tn)) {
         // the binned scatter of the ISA writes, keyed by SA[i] with the value SA[i-1]: the sort passes move the pairs, so they
         // are copies (the caller's array is read-only)
-        Workspace w;
-        memset(&w, 0, sizeof(w));
-        w.isa = phi;
-        w.spine = (uint32_t *)(base + L.spine);
-        w.digit_tot = w.spine + (size_t)RADIX * SORT_MAX_WG;
-        w.os_status = (unsigned long long *)(base + L.status);
-        w.os_err = err;
-        w.ss.spine = w.spine; w.ss.digit_tot = w.digit_tot; w.ss.status = w.os_status; w.ss.err = w.os_err;
+        const SortScratch ss = SortScratch::make(base + L.spine, base + L.status, err);
         HIP_TRY(hipMemcpyAsync(alt, dSA + 1, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(alt + ae, dSA, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
         sa_amd_stats local;
         memset(&local, 0, sizeof(local));
-        const int rcs = scatter_binned(alt, alt + ae, alt + 2 * ae, alt + 3 * ae, n, n, w, st, &local, tn);
+        const int rcs = scatter_binned(ss, phi, alt, alt + ae, alt + 2 * ae, alt + 3 * ae, n, n, st, &local, tn);
         if (rcs) return rcs;
     } else {
         int64_t pb = ceil_div(n, 256);

@@ -30,16 +30,15 @@ static_assert(GROUP_CAP_MAX == GS_CAP, "Tuning clamps SA_AMD_GROUP_CAP to the ke
 struct Workspace {
     uint64_t *keysA, *keysB, *keysC;
     uint32_t *valsA, *valsB, *isa, *U0, *U1, *G0, *G1;
-    uint32_t *spine, *digit_tot, *tcnt, *thead, *tnext, *hist, *total, *chg, *has_isa;
+    uint32_t *tcnt, *thead, *tnext, *hist, *total, *chg, *has_isa;
     uint8_t *packed;           // bit-packed text (alphabets of 2, 4 or 16 symbols): n / 2 + 64 bytes
     uint8_t *gram_flags;       // gram keys: which g-grams occur (sigma^g <= min(n, 2^24) flags) and
     uint4 *gram_table;         //   the rank directory over them (16 bytes per 64 indices)
     uint32_t *surv_bits, *surv_cnt, *todo_bits, *ft_cnt, *ft_head;   // first refinement round straight from the sorted keys (k_finish_sorted)
-    unsigned long long *os_status;  // look-back granules of the single-pass tile scatter: 2 KiB per 8192-element tile
-    uint32_t *os_err;
     uint32_t *bk_start;             // bucket sort of the 32-bit first stage: 2^16 + 1 or 2^18 + 1 bucket starts
     uint32_t *early_bits, *early_cnt;    // early download: bitmap over the n + 1 entries of the downloaded array, marked entries per tile
-    SortScratch ss;
+    SortScratch ss;                 // spine, digit totals and look-back granules of the radix sorts (2 KiB per 8192-element tile); ss.err: 64 words, the
+                                    //   sorts' give-ups in word 0, the bucket sort's two words from word 2
     size_t bytes, bytes2;           // in the first (device) block, in the second (reduced-memory route: pinned host) block
 };
 
@@ -62,10 +61,10 @@ static Workspace carve(void *base, int64_t n, size_t cap = ~(size_t)0, void *bas
     const size_t ft_tiles = (size_t)ceil_div((int64_t)N, FT_TILE) + 1;
     const size_t gram_entries = N < GRAM_MAX_ENTRIES ? N : GRAM_MAX_ENTRIES;
     // ---- small, shared between workgroups ----
-    w.spine = (uint32_t *)take((size_t)RADIX * SORT_MAX_WG * 4);
-    w.digit_tot = (uint32_t *)take(RADIX * 4);
-    w.os_status = (unsigned long long *)take(((size_t)ceil_div((int64_t)N, OS_MIN_TILE) + 1) * RADIX * 8);
-    w.os_err = (uint32_t *)take(256);
+    {
+        void *spine = take(SortScratch::SPINE_BYTES), *granules = take(SortScratch::granule_bytes((int64_t)N));
+        w.ss = SortScratch::make(spine, granules, (uint32_t *)take(256));
+    }
     w.hist = (uint32_t *)take(256 * 4);
     w.total = (uint32_t *)take(256);
     w.chg = (uint32_t *)take((size_t)RR_CHG_COUNTERS * 32 * 4);      // (directly behind w.total: read back together)
@@ -96,7 +95,6 @@ static Workspace carve(void *base, int64_t n, size_t cap = ~(size_t)0, void *bas
     w.U1 = (uint32_t *)take(N * 4);
     w.G1 = (uint32_t *)take(N * 4);
     w.keysC = (uint64_t *)take((N + 64) * 8);
-    w.ss.spine = w.spine; w.ss.digit_tot = w.digit_tot; w.ss.status = w.os_status; w.ss.err = w.os_err;
     w.bytes = off;
     w.bytes2 = off2;
     return w;
@@ -155,8 +153,8 @@ static bool binned(int64_t n, int64_t count, const Tuning &tn)
 // iota: the value of pair i is i and pk is READ-ONLY (the suffix array itself): the passes then go pk -> (altk, altv) ->
 // (altk2, altv2) and never write into pk.  Without iota, altk2 != nullptr: pk is read-only likewise (the keys of the rank set-up
 // are the suffix array), the second pass writes its keys to altk2 and its values back into pv.
-static int scatter_binned(uint32_t *pk, uint32_t *pv, uint32_t *altk, uint32_t *altv, int64_t count, int64_t n,
-                          const Workspace &w, hipStream_t st, sa_amd_stats *local, const Tuning &tn, bool iota = false,
+static int scatter_binned(const SortScratch &ss, uint32_t *isa, uint32_t *pk, uint32_t *pv, uint32_t *altk, uint32_t *altv, int64_t count, int64_t n,
+                          hipStream_t st, sa_amd_stats *local, const Tuning &tn, bool iota = false,
                           uint32_t *altk2 = nullptr, uint32_t *altv2 = nullptr)
 {
     const int nb = bit_length((uint64_t)(n > 1 ? n : 1));          // (the sentinel value n may be among the keys)
@@ -165,40 +163,42 @@ static int scatter_binned(uint32_t *pk, uint32_t *pv, uint32_t *altk, uint32_t *
     if (wlog > 15) wlog = 15;                                        // (n < 2^31, so nb <= 31)
     // (a text of fewer than 2^10 bytes has no bits above the window: the one-pass form below does it)
     const bool two = nb > wlog && (tn.scatter_levels == 2 || (tn.scatter_levels == 0 && count >= ((int64_t)1 << 25)));
-    SortResult32 pr;
+    SortResult<uint32_t> pr;
     if (two) {
         int rc;
         if (iota) {
             const int mid = wlog + RADIX_BITS < nb ? wlog + RADIX_BITS : nb;
-            rc = sort_pairs32(pk, nullptr, altk, altv, count, wlog, mid, w.ss, nullptr, st, &pr, tn, true);
+            SortJob<uint32_t> first{ pk, nullptr, altk, altv, count, wlog, mid };
+            first.iota = true;
+            rc = sort_pairs32(first, ss, st, tn, &pr, local);
             if (rc) return rc;
             if (pr.passes != 1) return SA_AMD_EINTERNAL;            // (cannot happen: nb > wlog whenever count > 1)
-            local->sort_passes += 1; local->sorted_elements += count;
             if (mid < nb) {
-                rc = sort_pairs32(altk, altv, altk2, altv2, count, mid, nb, w.ss, nullptr, st, &pr, tn);
+                rc = sort_pairs32(SortJob<uint32_t>{ altk, altv, altk2, altv2, count, mid, nb }, ss, st, tn, &pr, local);
                 if (rc) return rc;
-                local->sort_passes += pr.passes; local->sorted_elements += (int64_t)pr.passes * count;
             }
         } else {
-            rc = sort_pairs32(pk, pv, altk, altv, count, wlog, nb, w.ss, nullptr, st, &pr, tn, false, false, RADIX_BITS, nullptr, 0, 8, 0, altk2);
+            SortJob<uint32_t> both{ pk, pv, altk, altv, count, wlog, nb };
+            both.keys_out2 = altk2;
+            rc = sort_pairs32(both, ss, st, tn, &pr, local);
             if (rc) return rc;
-            local->sort_passes += pr.passes; local->sorted_elements += (int64_t)pr.passes * count;
         }
         const unsigned grid = (unsigned)ceil_div(count, SW_CHUNK);
         if (wlog <= 13)
             PROF(KC_SCATTER, count, st, hipLaunchKernelGGL((k_scatter_windows<13>), dim3(grid), dim3(SW_THREADS), 0, st, (const uint32_t *)pr.keys,
-                                                           (const uint32_t *)pr.vals, w.isa, count, (uint32_t)n, wlog));
+                                                           (const uint32_t *)pr.vals, isa, count, (uint32_t)n, wlog));
         else
             PROF(KC_SCATTER, count, st, hipLaunchKernelGGL((k_scatter_windows<15>), dim3(grid), dim3(SW_THREADS), 0, st, (const uint32_t *)pr.keys,
-                                                           (const uint32_t *)pr.vals, w.isa, count, (uint32_t)n, wlog));
+                                                           (const uint32_t *)pr.vals, isa, count, (uint32_t)n, wlog));
         return SA_AMD_OK;
     }
     const int shift = nb > RADIX_BITS ? nb - RADIX_BITS : 0;
-    int rc = sort_pairs32(pk, pv, altk, altv, count, shift, shift + RADIX_BITS, w.ss, nullptr, st, &pr, tn, iota);
+    SortJob<uint32_t> one{ pk, pv, altk, altv, count, shift, shift + RADIX_BITS };
+    one.iota = iota;
+    const int rc = sort_pairs32(one, ss, st, tn, &pr, local);
     if (rc) return rc;
-    local->sort_passes += pr.passes; local->sorted_elements += (int64_t)pr.passes * count;
     PROF(KC_SCATTER, count, st, hipLaunchKernelGGL((k_scatter_pairs<uint32_t>), dim3((unsigned)ceil_div(count, 1024)), dim3(256), 0, st,
-                                                   (const uint32_t *)pr.keys, (const uint32_t *)pr.vals, w.isa, count, (uint32_t)n));
+                                                   (const uint32_t *)pr.keys, (const uint32_t *)pr.vals, isa, count, (uint32_t)n));
     return SA_AMD_OK;
 }
 
@@ -349,7 +349,7 @@ struct DeviceBuild {
     int sigma = 0, key_bits = 0, g_bits = 0, top_shift = 0;
     bool force_dense = false, text_ok = false, local_ok = false, probe_dense = false;
     // ---- initial order (initial_sort) ----
-    SortResult sr;
+    SortResult<uint64_t> sr;
     const uint32_t *sorted32 = nullptr; // top-32 stage: the sorted 32-bit keys (no 64-bit sorted array exists)
     int bucket_top_bits = 0;            // key bits the two global passes in front of the bucket sort order (0: four global passes)
     bool flat_text = false;             // short text whose byte values are equally frequent: narrower initial keys (geometry_and_probes)
@@ -582,10 +582,9 @@ struct DeviceBuild {
                                                     (const uint64_t *)L.rkA, (const uint32_t *)L.V, m, kb, (const uint64_t *)pivot,
                                                     (const uint32_t *)w.tcnt, (const uint32_t *)starts, groups, mps, (const uint32_t *)w.total,
                                                     mk, mv, (const uint32_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr));
-        SortResult s2;
-        const int rc = sort_pairs(mk, mv, mk_alt, mv_alt, minor, 0, sort_bits, w.ss, nullptr, st, &s2, tn);
+        SortResult<uint64_t> s2;
+        const int rc = sort_pairs(SortJob<uint64_t>{ mk, mv, mk_alt, mv_alt, minor, 0, sort_bits }, w.ss, st, tn, &s2, &local);
         if (rc) return rc;
-        local.sort_passes += s2.passes; local.sorted_elements += (int64_t)s2.passes * minor;
         PROF(KC_MISC, groups, st, hipLaunchKernelGGL((k_split_less), dim3((unsigned)ceil_div((int64_t)groups, 256)), dim3(256), 0, st,
                                                  (const uint64_t *)s2.keys, (const uint32_t *)mps, (const uint64_t *)pivot, groups, kb, Lless));
         PROF(KC_RR_APPLY, m, st, hipLaunchKernelGGL((k_split_pass<true>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
@@ -614,7 +613,7 @@ struct DeviceBuild {
         const bool resume = ctl && ctl->resume_tot;
         const int64_t tiles = ceil_div(m, RR_TILE);
         const int kb = K.kb;
-        SortResult sr;
+        SortResult<uint64_t> sr;
         int rc;
         // sparse look-up: its own kernel, one suffix per thread (a chain of ~60 dependent loads each)
         auto gather_sparse = [&]() -> int {
@@ -701,9 +700,10 @@ struct DeviceBuild {
                     PROF(KC_RR_APPLY, m, st, hipLaunchKernelGGL((k_flag_gather), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
                                                                 (const uint8_t *)flags, (const uint64_t *)L.rkA, (const uint32_t *)L.V, L.U, L.G, m,
                                                                 (const uint32_t *)w.tcnt, (const uint32_t *)w.ft_cnt, kb, L.rkB, Valt, L.Un));
-                    rc = sort_pairs(L.rkB, Valt, L.rkB + half, Valt + half, m_big, 0, kb + idx_bits, w.ss, nullptr, st, &sr, tn, false, true);
+                    SortJob<uint64_t> big{ L.rkB, Valt, L.rkB + half, Valt + half, m_big, 0, kb + idx_bits };
+                    big.may_skip = true;
+                    rc = sort_pairs(big, w.ss, st, tn, &sr, &local);
                     if (rc) return rc;
-                    local.sort_passes += sr.passes; local.sorted_elements += (int64_t)sr.passes * m_big;
                     PROF(KC_SCATTER, m_big, st, hipLaunchKernelGGL((k_scatter_back), dim3((unsigned)ceil_div(m_big, 256)), dim3(256), 0, st,
                                                                    (const uint64_t *)sr.keys, (const uint32_t *)sr.vals,
                                                                    (const uint32_t *)L.Un, L.G, kb, m_big, L.rkA, L.V));
@@ -770,9 +770,10 @@ struct DeviceBuild {
             if (rc || taken) return rc;
             if (split_rest) *split_rest = 3;              // (a Fibonacci word's groups fall into parts of similar size round after round)
         }
-        rc = sort_pairs(L.rkA, L.V, L.rkB, Valt, m, 0, sort_bits, w.ss, nullptr, st, &sr, tn, false, true);
+        SortJob<uint64_t> whole{ L.rkA, L.V, L.rkB, Valt, m, 0, sort_bits };
+        whole.may_skip = true;
+        rc = sort_pairs(whole, w.ss, st, tn, &sr, &local);
         if (rc) return rc;
-        local.sort_passes += sr.passes; local.sorted_elements += (int64_t)sr.passes * m;
         out->keys = sr.keys; out->vals = sr.vals; out->m_global = m;
         out->vnext = (sr.vals == L.V) ? Valt : L.V;
         return SA_AMD_OK;
@@ -806,7 +807,7 @@ struct DeviceBuild {
                 // (only the ranks that change became pairs; their number is in the counters)
                 int64_t pairs = 0;
                 for (int c = 0; c < RR_CHG_COUNTERS; ++c) pairs += words[64 + c * 32];
-                if (pairs > 0 && (rc = scatter_binned((uint32_t *)a.pair_k, a.pair_v, (uint32_t *)rf.keys, (uint32_t *)rf.vals, pairs, n, w, st, &local, tn))) return rc;
+                if (pairs > 0 && (rc = scatter_binned(w.ss, w.isa, (uint32_t *)a.pair_k, a.pair_v, (uint32_t *)rf.keys, (uint32_t *)rf.vals, pairs, n, st, &local, tn))) return rc;
             }
             if (!ctl.deferred) return SA_AMD_OK;
             if (words[RC_FLAGGED] == 0) {
@@ -1021,12 +1022,16 @@ struct DeviceBuild {
             PROF(KC_BUILD_KEYS, n, st, hipLaunchKernelGGL((k_build_keys<true>), dim3((unsigned)ceil_div(ceil_div(n, KB_TILE), KB_TPW)), dim3(KB_THREADS), 0, st, dT, n, P,
                                                           (uint64_t *)nullptr, vals0, k32a, top_shift, packed_out,
                                                           counted ? fc.counts : (uint32_t *)nullptr, fc.chunk_elems, fc.G, (1u << rbits) - 1u, top_bits ? 32 - top_bits : 0));
-            SortResult32 s32;
+            SortResult<uint32_t> s32;
+            SortJob<uint32_t> job{ k32a, w.valsA, k32b, w.valsB, n, top_bits ? 32 - top_bits : 0, 32 };
+            job.iota = iota; job.first_counted = counted;
             if (top_bits) {
-                rc = sort_pairs32(k32a, w.valsA, k32b, w.valsB, n, 32 - top_bits, 32, w.ss, nullptr, st, &s32, tn, iota, counted, rbits,
-                                  text_keys ? dT : (packed_keys ? (const uint8_t *)packed_out : (const uint8_t *)nullptr), n, packed_keys ? 2 : 8, val_extra);
+                job.rbits = rbits;
+                job.text = text_keys ? dT : (packed_keys ? (const uint8_t *)packed_out : (const uint8_t *)nullptr);
+                job.text_n = n; job.text_bits = packed_keys ? 2 : 8;
+                job.val_extra = val_extra;
+                rc = sort_pairs32(job, w.ss, st, tn, &s32, &local);
                 if (rc) return rc;
-                local.sort_passes += s32.passes; local.sorted_elements += (int64_t)s32.passes * n;
                 uint32_t *kout = (s32.keys == k32a) ? k32b : k32a;
                 bool done = false, fused = false;
                 uint32_t largest = 0;
@@ -1041,7 +1046,7 @@ struct DeviceBuild {
                 }
                 KeyParams Pf = P;
                 Pf.packed = packed_out;             // (written by now: the fused round's text look-ups take the bit-packed text, a quarter of the lines)
-                rc = bucket_sort32(s32.keys, s32.vals, kout, SA, n, top_bits, w.bk_start, w.os_err + 2, st, tn, &done, &largest,
+                rc = bucket_sort32(s32.keys, s32.vals, kout, SA, n, top_bits, w.bk_start, w.ss.err + 2, st, tn, &done, &largest,
                                    fuse ? &F : nullptr, &Pf, &K, &fused, val_extra);
                 if (rc) return rc;
                 bucket_finished = done && fused;
@@ -1055,9 +1060,9 @@ struct DeviceBuild {
                 sr.keys = (kout == k32a) ? w.keysA : w.keysB;
                 break;
             }
-            rc = sort_pairs32(k32a, w.valsA, k32b, w.valsB, n, 0, 32, w.ss, SA, st, &s32, tn, iota, counted);
+            job.final_vals = SA;
+            rc = sort_pairs32(job, w.ss, st, tn, &s32, &local);
             if (rc) return rc;
-            local.sort_passes += s32.passes; local.sorted_elements += (int64_t)s32.passes * n;
             sorted32 = s32.keys;
             sr.vals = s32.vals; sr.passes = s32.passes;
             sr.keys = (s32.keys == k32a) ? w.keysA : w.keysB;      // the 8n-byte buffer that now holds the sorted 32-bit keys
@@ -1122,12 +1127,14 @@ struct DeviceBuild {
             const bool dense_expected = force_dense || probe_dense || !text_ok;
             const bool want_flags = tn.head_flags != 0 && (tn.head_flags == 2 || dense_expected) && flags_slab_ok && onesweep_on(w.ss, tn) && !timing_only() &&
                                     !tn.fused64 && n >= 2 && key_bits > 0;
-            rc = sort_pairs(w.keysA, w.valsA, w.keysB, w.valsB, n, 0, key_bits, w.ss, SA, st, &sr, tn, iota, sigma == 1, counted,
-                            want_flags ? (uint8_t *)w.keysC : (uint8_t *)nullptr);
+            SortJob<uint64_t> job{ w.keysA, w.valsA, w.keysB, w.valsB, n, 0, key_bits };
+            job.final_vals = SA;
+            job.iota = iota; job.may_skip = sigma == 1; job.first_counted = counted;
+            job.head_flags = want_flags ? (uint8_t *)w.keysC : (uint8_t *)nullptr;
+            rc = sort_pairs(job, w.ss, st, tn, &sr, &local);
             if (rc) return rc;
             if (want_flags && sr.passes > 0 && sr.vals == SA) head_flags = (uint8_t *)w.keysC;      // (the last pass always runs: it delivers into SA)
             if (trace && head_flags) fprintf(stderr, "suffix_array_amd: initial sort: the last pass wrote group-start flags, not the sorted keys\n");
-            local.sort_passes += sr.passes; local.sorted_elements += (int64_t)sr.passes * n;
             }
         }
         P.packed = packed_out;
@@ -1358,9 +1365,9 @@ struct DeviceBuild {
                 if (from_sa) {
                     hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, st, dSA, (uint32_t)n);
                     LAUNCH_CHECK(st);
-                    rc = scatter_binned(dSA, pk32 + H, sk32, sk32 + H, n + 1, n, w, st, &local, tn, false, pk32);
+                    rc = scatter_binned(w.ss, w.isa, dSA, pk32 + H, sk32, sk32 + H, n + 1, n, st, &local, tn, false, pk32);
                 } else
-                    rc = scatter_binned((uint32_t *)pk, w.U1, (uint32_t *)sr.keys, w.G1, n, n, w, st, &local, tn);
+                    rc = scatter_binned(w.ss, w.isa, (uint32_t *)pk, w.U1, (uint32_t *)sr.keys, w.G1, n, n, st, &local, tn);
                 if (rc) return rc;
             } else if ((rc = rr_apply_setup<0>(a))) return rc;
         } else if (L.m > 0) {
@@ -1407,7 +1414,7 @@ struct DeviceBuild {
                     hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, st, dSA, (uint32_t)n);
                     LAUNCH_CHECK(st);
                     const size_t H = ((size_t)n + 1 + 3) & ~(size_t)3;      // keys in the first half of an 8(n + 64)-byte buffer, values in the second
-                    rc = scatter_binned(dSA, nullptr, (uint32_t *)L.rkB, (uint32_t *)L.rkB + H, n + 1, n, w, st, &local, tn, true,
+                    rc = scatter_binned(w.ss, w.isa, dSA, nullptr, (uint32_t *)L.rkB, (uint32_t *)L.rkB + H, n + 1, n, st, &local, tn, true,
                                         (uint32_t *)L.rkA, (uint32_t *)L.rkA + H);
                     if (rc) return rc;
                 } else
@@ -1553,7 +1560,7 @@ static int build_device(const uint8_t *dT, uint32_t *dSA, int32_t n32, void *dWo
         if (stats) *stats = local;
         return SA_AMD_OK;
     }
-    HIP_TRY(hipMemsetAsync(w.os_err, 0, 16, st));          // look-back give-ups of the single-pass scatter: checked at the end
+    HIP_TRY(hipMemsetAsync(w.ss.err, 0, 16, st));          // look-back give-ups of the single-pass scatter: checked at the end
     int rc;
     if ((rc = B.geometry_and_probes())) return rc;
     if (!B.unary_done) {
@@ -1571,7 +1578,7 @@ static int build_device(const uint8_t *dT, uint32_t *dSA, int32_t n32, void *dWo
         // (synchronises the stream) a look-back that gave up means a tile scatter wrote nothing useful: never a silent wrong array
         // (word 3: a bucket larger than the shape the host picked for k_bucket_sort)
         uint32_t gave_up[4] = { 0, 0, 0, 0 };
-        const int rcw = read_words(gave_up, w.os_err, 16, st); if (rcw) return rcw;
+        const int rcw = read_words(gave_up, w.ss.err, 16, st); if (rcw) return rcw;
         if (gave_up[0] || gave_up[3]) return SA_AMD_EINTERNAL;
     }
     local.readbacks = g_readbacks;

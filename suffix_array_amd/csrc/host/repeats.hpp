@@ -102,19 +102,12 @@ static int repeats_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, b
         uint32_t *dst = spans ? lrbuf : dLR;
         if (binned(n, n, tn)) {
             // the random 4-byte stores of LR go through the binned scatter, as those of Φ do: the pass writes the pairs in slot order
-            Workspace w;
-            memset(&w, 0, sizeof(w));
-            w.isa = dst;
-            w.spine = (uint32_t *)(base + L.spine);
-            w.digit_tot = w.spine + (size_t)RADIX * SORT_MAX_WG;
-            w.os_status = (unsigned long long *)(base + L.status);
-            w.os_err = err;
-            w.ss.spine = w.spine; w.ss.digit_tot = w.digit_tot; w.ss.status = w.os_status; w.ss.err = w.os_err;
+            const SortScratch ss = SortScratch::make(base + L.spine, base + L.status, err);
             PROF(KC_REP_LR, n, st, hipLaunchKernelGGL((k_rep_slots<REP_OUT_PAIRS>), dim3((unsigned)tiles), dim3(REP_THREADS), 0, st, dSA, n, plcp,
                                                       alt, alt + ae, k_min, (uint32_t *)nullptr, ctl));
             sa_amd_stats local;
             memset(&local, 0, sizeof(local));
-            const int rcs = scatter_binned(alt, alt + ae, alt + 2 * ae, alt + 3 * ae, n, n, w, st, &local, tn);
+            const int rcs = scatter_binned(ss, dst, alt, alt + ae, alt + 2 * ae, alt + 3 * ae, n, n, st, &local, tn);
             if (rcs) return rcs;
         } else {
             PROF(KC_REP_LR, n, st, hipLaunchKernelGGL((k_rep_slots<REP_OUT_PLAIN>), dim3((unsigned)tiles), dim3(REP_THREADS), 0, st, dSA, n, plcp,

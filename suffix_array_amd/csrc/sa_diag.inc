@@ -52,17 +52,16 @@ SA_EXPORT int32_t sa_amd_test_sort_pairs(uint64_t *keys, uint32_t *vals, int64_t
     int32_t rc;
     if ((rc = dk.alloc(N * 8 * 2))) return rc;
     if ((rc = dv.alloc(N * 4 * 2))) return rc;
-    if ((rc = dsp.alloc(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4))) return rc;
-    uint64_t *k = dk.as<uint64_t>(); uint32_t *v = dv.as<uint32_t>(), *spine = dsp.as<uint32_t>();
+    if ((rc = dsp.alloc(SortScratch::SPINE_BYTES))) return rc;
+    uint64_t *k = dk.as<uint64_t>(); uint32_t *v = dv.as<uint32_t>();
     HIP_TRY(hipMemcpy(k, keys, N * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(v, vals, N * 4, hipMemcpyHostToDevice));
-    SortResult sr;
+    SortResult<uint64_t> sr;
     DevBuf dst;
-    if ((rc = dst.alloc(((size_t)ceil_div(count, OS_MIN_TILE) + 1) * RADIX * 8 + 256))) return rc;
+    if ((rc = dst.alloc(256 + SortScratch::granule_bytes(count)))) return rc;
     HIP_TRY(hipMemset(dst.p, 0, 256));
-    SortScratch ss; ss.spine = spine; ss.digit_tot = spine + (size_t)RADIX * SORT_MAX_WG;
-    ss.err = dst.as<uint32_t>(); ss.status = (unsigned long long *)(dst.as<char>() + 256);
-    rc = sort_pairs(k, v, k + N, v + N, count, begin_bit, end_bit, ss, nullptr, nullptr, &sr, tn);
+    const SortScratch ss = SortScratch::make(dsp.p, dst.as<char>() + 256, dst.as<uint32_t>());      // (the error words in front of the granules)
+    rc = sort_pairs(SortJob<uint64_t>{ k, v, k + N, v + N, count, begin_bit, end_bit }, ss, nullptr, tn, &sr);
     if (rc != SA_AMD_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(keys, sr.keys, N * 8, hipMemcpyDeviceToHost));
@@ -89,18 +88,20 @@ SA_EXPORT int32_t sa_amd_test_sort_pairs_flags(const uint64_t *keys, uint32_t *v
     if ((rc = dk.alloc(N * 8 * 2))) return rc;
     if ((rc = dv.alloc(N * 4 * 3))) return rc;
     if ((rc = df.alloc(N))) return rc;
-    if ((rc = dsp.alloc(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4))) return rc;
-    if ((rc = dst.alloc(((size_t)ceil_div(count, OS_MIN_TILE) + 1) * RADIX * 8 + 256))) return rc;
-    uint64_t *k = dk.as<uint64_t>(); uint32_t *v = dv.as<uint32_t>(), *spine = dsp.as<uint32_t>();
+    if ((rc = dsp.alloc(SortScratch::SPINE_BYTES))) return rc;
+    if ((rc = dst.alloc(256 + SortScratch::granule_bytes(count)))) return rc;
+    uint64_t *k = dk.as<uint64_t>(); uint32_t *v = dv.as<uint32_t>();
     HIP_TRY(hipMemcpy(k, keys, N * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(v, vals, N * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(df.p, 0xff, N));
     HIP_TRY(hipMemset(dst.p, 0, 256));
-    SortScratch ss; ss.spine = spine; ss.digit_tot = spine + (size_t)RADIX * SORT_MAX_WG;
-    ss.err = dst.as<uint32_t>(); ss.status = (unsigned long long *)(dst.as<char>() + 256);
+    const SortScratch ss = SortScratch::make(dsp.p, dst.as<char>() + 256, dst.as<uint32_t>());      // (the error words in front of the granules)
     if (!onesweep_on(ss, tn)) return SA_AMD_EINVAL;      // (the three-kernel engine has no flags variant)
-    SortResult sr;
-    rc = sort_pairs(k, v, k + N, v + N, count, begin_bit, end_bit, ss, v + 2 * N, nullptr, &sr, tn, false, false, false, df.as<uint8_t>(), true);
+    SortJob<uint64_t> job{ k, v, k + N, v + N, count, begin_bit, end_bit };
+    job.final_vals = v + 2 * N;
+    job.head_flags = df.as<uint8_t>(); job.poison_keys = true;
+    SortResult<uint64_t> sr;
+    rc = sort_pairs(job, ss, nullptr, tn, &sr);
     if (rc != SA_AMD_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
     if (sr.vals != v + 2 * N) return SA_AMD_EINTERNAL;
@@ -124,16 +125,15 @@ SA_EXPORT int32_t sa_amd_test_sample_sort64(uint64_t *keys, uint32_t *vals, int6
     int32_t rc;
     if ((rc = dk.alloc((N + 64) * 8 * 3))) return rc;
     if ((rc = dv.alloc(N * 4 * 5))) return rc;
-    if ((rc = dsp.alloc(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4))) return rc;
-    if ((rc = dst.alloc(((size_t)ceil_div(count, OS_MIN_TILE) + 1) * RADIX * 8 + 256))) return rc;
+    if ((rc = dsp.alloc(SortScratch::SPINE_BYTES))) return rc;
+    if ((rc = dst.alloc(256 + SortScratch::granule_bytes(count)))) return rc;
     if ((rc = dbig.alloc(((size_t)ceil_div(count, SS_TILE) + SS_WAYS) * SS_IDS2 * 4))) return rc;
     if ((rc = dsmall.alloc((size_t)8 << 20))) return rc;
     HIP_TRY(hipMemset(dst.p, 0, 256));
     uint64_t *k = dk.as<uint64_t>();
-    uint32_t *v = dv.as<uint32_t>(), *spine = dsp.as<uint32_t>();
+    uint32_t *v = dv.as<uint32_t>();
     HIP_TRY(hipMemcpy(k, keys, N * 8, hipMemcpyHostToDevice));
-    SortScratch ss; ss.spine = spine; ss.digit_tot = spine + (size_t)RADIX * SORT_MAX_WG;
-    ss.err = dst.as<uint32_t>(); ss.status = (unsigned long long *)(dst.as<char>() + 256);
+    const SortScratch ss = SortScratch::make(dsp.p, dst.as<char>() + 256, dst.as<uint32_t>());      // (the error words in front of the granules)
     sa_amd_stats local;
     memset(&local, 0, sizeof(local));
     bool ok = false;
@@ -163,17 +163,16 @@ SA_EXPORT int32_t sa_amd_test_sort_pairs32(uint32_t *keys, uint32_t *vals, int64
     int32_t rc;
     if ((rc = dk.alloc(N * 4 * 2))) return rc;
     if ((rc = dv.alloc(N * 4 * 2))) return rc;
-    if ((rc = dsp.alloc(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4))) return rc;
-    uint32_t *k = dk.as<uint32_t>(), *v = dv.as<uint32_t>(), *spine = dsp.as<uint32_t>();
+    if ((rc = dsp.alloc(SortScratch::SPINE_BYTES))) return rc;
+    uint32_t *k = dk.as<uint32_t>(), *v = dv.as<uint32_t>();
     HIP_TRY(hipMemcpy(k, keys, (size_t)count * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(v, vals, (size_t)count * 4, hipMemcpyHostToDevice));
-    SortResult32 sr;
+    SortResult<uint32_t> sr;
     DevBuf dst;
-    if ((rc = dst.alloc(((size_t)ceil_div(count, OS_MIN_TILE) + 1) * RADIX * 8 + 256))) return rc;
+    if ((rc = dst.alloc(256 + SortScratch::granule_bytes(count)))) return rc;
     HIP_TRY(hipMemset(dst.p, 0, 256));
-    SortScratch ss; ss.spine = spine; ss.digit_tot = spine + (size_t)RADIX * SORT_MAX_WG;
-    ss.err = dst.as<uint32_t>(); ss.status = (unsigned long long *)(dst.as<char>() + 256);
-    rc = sort_pairs32(k, v, k + N, v + N, count, begin_bit, end_bit, ss, nullptr, nullptr, &sr, tn);
+    const SortScratch ss = SortScratch::make(dsp.p, dst.as<char>() + 256, dst.as<uint32_t>());      // (the error words in front of the granules)
+    rc = sort_pairs32(SortJob<uint32_t>{ k, v, k + N, v + N, count, begin_bit, end_bit }, ss, nullptr, tn, &sr);
     if (rc != SA_AMD_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(keys, sr.keys, (size_t)count * 4, hipMemcpyDeviceToHost));
@@ -203,16 +202,15 @@ SA_EXPORT int32_t sa_amd_test_bucket_sort32(uint32_t *keys, uint32_t *vals, int6
     int32_t rc;
     if ((rc = dk.alloc(N * 4 * 2))) return rc;
     if ((rc = dv.alloc(N * 4 * 3))) return rc;
-    if ((rc = dsp.alloc(((size_t)RADIX * SORT_MAX_WG + RADIX) * 4))) return rc;
-    if ((rc = dst.alloc(((size_t)ceil_div(count, OS_MIN_TILE) + 1) * RADIX * 8 + 256))) return rc;
+    if ((rc = dsp.alloc(SortScratch::SPINE_BYTES))) return rc;
+    if ((rc = dst.alloc(256 + SortScratch::granule_bytes(count)))) return rc;
     if ((rc = dbs.alloc(((size_t)BK_BUCKETS_MAX + 1) * 4))) return rc;
-    uint32_t *k = dk.as<uint32_t>(), *v = dv.as<uint32_t>(), *spine = dsp.as<uint32_t>();
+    uint32_t *k = dk.as<uint32_t>(), *v = dv.as<uint32_t>();
     HIP_TRY(hipMemcpy(k, keys, (size_t)count * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(v, vals, (size_t)count * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(dst.p, 0, 256));
-    SortScratch ss; ss.spine = spine; ss.digit_tot = spine + (size_t)RADIX * SORT_MAX_WG;
-    ss.err = dst.as<uint32_t>(); ss.status = (unsigned long long *)(dst.as<char>() + 256);
-    SortResult32 sr;
+    const SortScratch ss = SortScratch::make(dsp.p, dst.as<char>() + 256, dst.as<uint32_t>());      // (the error words in front of the granules)
+    SortResult<uint32_t> sr;
     const int rbits = top_bits == 18 ? 9 : RADIX_BITS;
     bool counted = false;
     if (rbits == 9) {
@@ -223,7 +221,9 @@ SA_EXPORT int32_t sa_amd_test_bucket_sort32(uint32_t *keys, uint32_t *vals, int6
         HIP_TRY(hipGetLastError());
         counted = true;
     }
-    rc = sort_pairs32(k, v, k + N, v + N, count, 32 - top_bits, 32, ss, nullptr, nullptr, &sr, tn, false, counted, rbits);
+    SortJob<uint32_t> job{ k, v, k + N, v + N, count, 32 - top_bits, 32 };
+    job.first_counted = counted; job.rbits = rbits;
+    rc = sort_pairs32(job, ss, nullptr, tn, &sr);
     if (rc != SA_AMD_OK) return rc;
     uint32_t *kout = sr.keys == k ? k + N : k, *vout = v + 2 * N;
     bool done = false;

@@ -430,6 +430,39 @@ def test_gpu_verifiers_64_mib(oracle):
     assert run_gpu(oracle, t, False, seed=64, cpu_too=True) > 20
 
 
+# sizes at which the window arithmetic of the streaming form's binned inverse permutation changes (scatter_binned,
+# host/pipeline.hpp: window 2^10 entries for these sizes, 8 bits per pass above it): 1023 has no bit above the window, so a
+# two-pass request is answered by the one-pass form; 1024 is the first size with one; 65 537 has 17 bits, the first pass
+# covers them all and the second is skipped; 300 000 has 19, both passes run
+LEVEL_N = (1023, 1024, 65537, 300000)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("levels", (1, 2))
+@pytest.mark.parametrize("n", LEVEL_N)
+@pytest.mark.parametrize("kind", ("dna", "english"))
+def test_gpu_verifiers_scatter_levels(oracle, monkeypatch, kind, n, levels):
+    """the streaming form with its inverse permutation binned by one radix pass and by two (SA_AMD_SCATTER_LEVELS): by size it
+    takes one below 2^25 entries, so only test_gpu_verifiers_64_mib reaches the two-pass form with this form's own buffers.
+    run_gpu drives sa_amd_check_integrity_device itself with a 256-byte aligned block of sa_amd_check_integrity_work_bytes(n)
+    bytes ("streaming/*"); that this is the streaming form is checked first: the call writes behind the 4 (n + 1) + 256 bytes
+    that are all the small form touches."""
+    monkeypatch.setenv("SA_AMD_SCATTER_LEVELS", str(levels))
+    t = make_text(kind, n)
+    good = oracle.sais(t)
+    dev = DeviceForms(t, n)
+    try:
+        dev._fill("ff")
+        assert dev.hip.h.hipMemcpy(dev.ds, good.ctypes.data, 4 * (n + 1), 1) == 0
+        assert dev.L.sa_amd_check_integrity_device(dev.dt, n, dev.ds, dev.work, dev.big, None) == 1
+        tail = np.empty(dev.big - dev.small, dtype=np.uint8)
+        assert dev.hip.h.hipMemcpy(tail.ctypes.data, dev.work + dev.small, tail.size, 2) == 0
+        assert (tail != 0xff).any()
+    finally:
+        dev.close()
+    assert run_gpu(oracle, t, n <= 2050, seed=n) > 20
+
+
 @pytest.mark.gpu
 def test_gpu_empty_text():
     """n = 0 on every GPU form: [0] is right, any other single entry is out of range (see test_empty_text)"""
