@@ -12,7 +12,8 @@
 // streaming speed instead of 32 at scatter speed.  The first pass (the low 10 of the 16 bits) takes its places from one LDS
 // counter per digit (one atomic per pair; the order among equal digits is whatever the atomics give, which is enough: the
 // second pass is stable and pairs equal in ALL low bits are equal keys); the second (the top 6 bits) is the stable ranking of
-// the tile scatter (6 ballots + mbcnt per key, per-wave digit counts in LDS).  The kernel is instruction-bound, not
+// the tile scatter (6 ballots + mbcnt per key, per-wave digit counts in LDS); both passes are templates of kernels/lds_sort.hpp
+// (lds_count_pass, lds_stable_pass), shared with k_group_sort_big.  The kernel is instruction-bound, not
 // memory-bound -- with two 8-bit ballot passes it took 1.40 ms for 2^28 pairs.
 //   k_bucket_starts  start[b] = first pair whose key >> lbits is >= b, by binary search in the grouped keys
 //                    (65 537 searches; the first levels are shared and cache-resident), and the largest bucket
@@ -32,6 +33,7 @@
 #include "radix_sort.hpp"
 #include "rerank.hpp"
 #include "refine.hpp"
+#include "lds_sort.hpp"
 
 namespace sa {
 
@@ -140,10 +142,8 @@ __global__ __launch_bounds__(THREADS, MINW) void k_bucket_sort(const uint32_t *_
     if (size > CAP) { if (tid == 0) atomicAdd(err, 1u); return; }      // (the host picked the shape from the largest bucket: cannot happen)
     const int J = (size + THREADS - 1) / THREADS;
     const int e0 = w * J * WAVE + l;
-    uint16_t *my_hist = wave_hist[w];
 
-    uint32_t key[ITEMS], val[ITEMS], pp[ITEMS / 2];
-#define BK_POS(j) ((pp[(j) >> 1] >> (16 * ((j) & 1))) & 0xffffu)
+    uint32_t key[ITEMS], val[ITEMS], pp[ITEMS / 2];    // pp: places in the bucket, two to a register
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
         // (register arrays are only ever assigned unconditionally, from scalars: conditional element stores make the compiler keep
@@ -157,45 +157,14 @@ __global__ __launch_bounds__(THREADS, MINW) void k_bucket_sort(const uint32_t *_
     }
     const uint32_t hi_bits = (keys_in[lo] >> lbits) << lbits;      // the bucket's number, as key bits (1 <= lbits, lbits + xbits <= 16, host-checked)
     const int sbits = lbits + xbits;                               // key bits ordered here
-    const uint32_t lo_mask = (1u << sbits) - 1u;
     const int bbits = sbits < BK_BBITS ? sbits : BK_BBITS;        // second pass: the top bits of the staged key, stable
     const int abits = sbits - bbits;                               // first pass: the bits below them
 
     if (abits > 0) {
-        // ---- first pass: a counter per digit hands out the places.  Which of two pairs with the same digit comes first is left
-        // to the order the atomics arrive in: the second pass keeps whatever order this one leaves (it is stable), and pairs
-        // that agree in all low bits have the same 32-bit key -- their order is the later rounds' business, not the sort's ----
-        const uint32_t amask = (1u << abits) - 1u;
-        for (int i = tid; i < NB_A; i += THREADS) cnt_a[i] = 0;
-        __syncthreads();                           // (also: the keys have arrived)
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            uint32_t r = 0;
-            if (j < J && (e0 + j * WAVE) < size) r = atomicAdd(&cnt_a[key[j] & amask], 1u);
-            if ((j & 1) == 0) pp[j >> 1] = r; else pp[j >> 1] |= r << 16;
-        }
-        lds_barrier();
-        {
-            // exclusive sums over the NB_A counters, in place
-            constexpr int BPT = NB_A >= THREADS ? NB_A / THREADS : 1;
-            const bool scans = tid * BPT < NB_A;
-            uint32_t c[BPT], sum = 0;
-#pragma unroll
-            for (int i = 0; i < BPT; ++i) { c[i] = scans ? cnt_a[tid * BPT + i] : 0u; sum += c[i]; }
-            uint32_t all;
-            uint32_t run = block_excl_sum_b<THREADS, true>(sum, scan_lds, &all);
-#pragma unroll
-            for (int i = 0; i < BPT; ++i) { if (scans) cnt_a[tid * BPT + i] = run; run += c[i]; }
-        }
-        lds_barrier();
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            if (j < J && (e0 + j * WAVE) < size) {
-                const uint32_t ps = BK_POS(j) + cnt_a[key[j] & amask];
-                lds_k[ps] = (uint16_t)(key[j] & lo_mask);
-                lds_v[ps] = val[j];
-            }
-        }
+        // ---- first pass (lds_count_pass, lds_sort.hpp): a counter per digit hands out the places.  Which of two pairs with the same
+        // digit comes first is left to the order the atomics arrive in: the second pass keeps whatever order this one leaves (it is
+        // stable), and pairs that agree in all low bits have the same 32-bit key -- their order is the later rounds' business ----
+        lds_count_pass<THREADS, ITEMS, NB_A>(key, val, pp, J, e0, size, (1u << abits) - 1u, lds_k, lds_v, cnt_a, scan_lds);
         lds_barrier();
         // the order of the first pass: back into registers, wave-striped
 #pragma unroll
@@ -206,61 +175,8 @@ __global__ __launch_bounds__(THREADS, MINW) void k_bucket_sort(const uint32_t *_
             key[j] = kx; val[j] = vx;
         }
     }
-    {
-        // ---- second pass, stable: rank inside the wave (lanes with my digit below me + earlier items: ballots + mbcnt), per-wave
-        // digit counts in LDS ----
-        const uint32_t dmask = (1u << bbits) - 1u;
-        for (int i = tid; i < NWAVES * NB_B / 2; i += THREADS) ((uint32_t *)&wave_hist[0][0])[i] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            uint32_t r = 0;
-            if (j < J) {                           // (uniform)
-                const bool ok = (e0 + j * WAVE) < size;
-                const uint32_t d = (key[j] >> abits) & dmask;
-                const uint64_t okm = __ballot(ok);
-                uint32_t xlo = ~(uint32_t)okm, xhi = ~(uint32_t)(okm >> 32);
-#pragma unroll
-                for (int bb = 0; bb < BK_BBITS; ++bb) {
-                    const uint32_t sel = (uint32_t)((int32_t)(d << (31 - bb)) >> 31);
-                    const uint64_t bal = __ballot(sel != 0);
-                    xlo |= (uint32_t)bal ^ sel;
-                    xhi |= (uint32_t)(bal >> 32) ^ sel;
-                }
-                const uint32_t mlo = ~xlo, mhi = ~xhi;
-                const uint32_t below = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
-                const uint32_t prior = my_hist[d];
-                if (ok && below == 0) my_hist[d] = (uint16_t)(prior + (uint32_t)(__popc(mlo) + __popc(mhi)));
-                r = prior + below;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if ((j & 1) == 0) pp[j >> 1] = r; else pp[j >> 1] |= r << 16;
-        }
-        lds_barrier();
-        // ---- wave 0, lane d: per-wave offsets of digit d, its start in the bucket ----
-        if (w == 0) {
-            uint32_t tot = 0;
-#pragma unroll
-            for (int ww = 0; ww < NWAVES; ++ww) {
-                const uint32_t cnt = wave_hist[ww][l];
-                wave_hist[ww][l] = (uint16_t)tot;
-                tot += cnt;
-            }
-            digit_base[l] = wave_incl_sum(tot) - tot;
-        }
-        lds_barrier();
-        // ---- into LDS in the order of this digit (stable) ----
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            if (j < J && (e0 + j * WAVE) < size) {
-                const uint32_t d = (key[j] >> abits) & dmask;
-                const uint32_t ps = BK_POS(j) + digit_base[d] + my_hist[d];
-                lds_k[ps] = (uint16_t)(key[j] & lo_mask);
-                lds_v[ps] = val[j];
-            }
-        }
-    }
-#undef BK_POS
+    // ---- second pass, stable (lds_stable_pass, lds_sort.hpp): rank inside the wave, per-wave digit counts in LDS ----
+    lds_stable_pass<THREADS, ITEMS, BK_BBITS>(key, val, pp, J, e0, size, abits, (1u << bbits) - 1u, lds_k, lds_v, wave_hist, digit_base);
     __syncthreads();
     if (FINISH) {
         // ---- suffixes tied on all 32 key bits: ordered by their low key bits, inside the staged bucket ----

@@ -28,6 +28,7 @@
 #pragma once
 #include "common.hpp"
 #include "radix_sort.hpp"
+#include "lds_sort.hpp"
 
 namespace sa {
 
@@ -315,9 +316,8 @@ __global__ __launch_bounds__(THREADS, WG_PER_CU * THREADS / 256) void k_onesweep
         const int valid = (P.n - base) >= TILE ? TILE : (int)(P.n - base);
         const bool full = valid == TILE;
         KeyT key[ITEMS];
-        uint32_t val[ITEMS], pp[ITEMS / 2];    // pp: tile positions (< 65536), two to a register
+        uint32_t val[ITEMS], pp[ITEMS / 2];    // pp: tile positions (< 65536), two to a register (place_put / place_get, lds_sort.hpp)
         uint32_t xpack = 0;                    // TEXT_KEYS: the two key bits below key[j] in bits [2j, 2j + 2)
-#define OS_POS(j) ((pp[(j) >> 1] >> (16 * ((j) & 1))) & 0xffffu)
         if (TEXT_KEYS && P.text_bits == 2) {
             // four symbols: 12 consecutive suffixes = 24 + 30 stream bits from byte (base + first position) / 4 on (the zero bytes behind
             // the packed text and the slab's slack cover the reads of the last tile; positions behind the text are masked below)
@@ -372,25 +372,11 @@ __global__ __launch_bounds__(THREADS, WG_PER_CU * THREADS / 256) void k_onesweep
         for (int i = tid; i < NWAVES * RADIX / 2; i += THREADS) ((uint32_t *)&wave_hist[0][0])[i] = 0;
         __syncthreads();
         stamp(0);      // ticket, key loads issued, segment switch, counters zeroed, barrier (waits for the keys)
-        // ---- rank inside the wave: lanes with my digit below me (8 ballots + mbcnt), wave totals in LDS ----
+        // ---- rank inside the wave: lanes with my digit below me, wave totals in LDS (wave_digit_rank, lds_sort.hpp) ----
 #pragma unroll
         for (int j = 0; j < ITEMS; ++j) {
             const bool ok = full || OS_ELEM(j) < valid;
-            const uint32_t d = digit_of(key[j], P.shift, P.dmask);
-            const uint64_t okm = __ballot(ok);
-            uint32_t xlo = ~(uint32_t)okm, xhi = ~(uint32_t)(okm >> 32);
-#pragma unroll
-            for (int b = 0; b < RADIX_BITS; ++b) {
-                const uint32_t sel = (uint32_t)((int32_t)(d << (31 - b)) >> 31);
-                const uint64_t bal = __ballot(sel != 0);
-                xlo |= (uint32_t)bal ^ sel;
-                xhi |= (uint32_t)(bal >> 32) ^ sel;
-            }
-            const uint32_t mlo = ~xlo, mhi = ~xhi;
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
-            const uint32_t prior = my_hist[d];
-            if (ok && below == 0) my_hist[d] = (uint16_t)(prior + (uint32_t)(__popc(mlo) + __popc(mhi)));
-            if ((j & 1) == 0) pp[j >> 1] = prior + below; else pp[j >> 1] |= (prior + below) << 16;
+            place_put(pp, j, wave_digit_rank<RADIX_BITS>(digit_of(key[j], P.shift, P.dmask), ok, my_hist));
             __builtin_amdgcn_sched_barrier(0);
         }
         stamp(1);      // ranking
@@ -453,14 +439,14 @@ __global__ __launch_bounds__(THREADS, WG_PER_CU * THREADS / 256) void k_onesweep
 #pragma unroll
         for (int j = 0; j < ITEMS; ++j) {
             const uint32_t d = digit_of(key[j], P.shift, P.dmask);
-            const uint32_t ps = OS_POS(j) + digit_base[d] + my_hist[d];
+            const uint32_t ps = place_get(pp, j) + digit_base[d] + my_hist[d];
             if ((j & 1) == 0) pp[j >> 1] = (pp[j >> 1] & 0xffff0000u) | ps; else pp[j >> 1] = (pp[j >> 1] & 0xffffu) | (ps << 16);
             if (full || OS_ELEM(j) < valid) lds_k[ps] = key[j];
         }
         if (!SEQ) {
 #pragma unroll
             for (int j = 0; j < ITEMS; ++j)
-                if (full || OS_ELEM(j) < valid) lds_v[OS_POS(j)] = val[j];
+                if (full || OS_ELEM(j) < valid) lds_v[place_get(pp, j)] = val[j];
         } else load_vals();                    // (the keys' registers are free: the values travel while the keys go out)
         if (walk && late_look) {
 #pragma unroll
@@ -566,7 +552,7 @@ __global__ __launch_bounds__(THREADS, WG_PER_CU * THREADS / 256) void k_onesweep
             lds_barrier();                     // every key has been read
 #pragma unroll
             for (int j = 0; j < ITEMS; ++j)
-                if (full || OS_ELEM(j) < valid) lds_v[OS_POS(j)] = val[j];
+                if (full || OS_ELEM(j) < valid) lds_v[place_get(pp, j)] = val[j];
             lds_barrier();
 #pragma unroll
             for (int j = 0; j < ITEMS; ++j) {
@@ -578,7 +564,6 @@ __global__ __launch_bounds__(THREADS, WG_PER_CU * THREADS / 256) void k_onesweep
             }
         }
         stamp(7);      // values through the stage (SEQ)
-#undef OS_POS
 #undef OS_ELEM
         if (tid == 0) {                        // the ticket asked for at the top of this tile
             if (pend_s >= 0 && pend_k < seg_tiles(pend_s)) { next_t = pend_s * P.tiles_per_seg + pend_k; next_seg = pend_s; }

@@ -4,6 +4,7 @@
 // Part of the MI355X-native suffix-array engine (gfx950 / CDNA4, wave64); see DESIGN.md section 3.
 #pragma once
 #include "radix_sort.hpp"
+#include "lds_sort.hpp"
 
 namespace sa {
 
@@ -314,20 +315,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_radix_downsweep_wcl(
         for (int j = 0; j < ITEMS; ++j) {
             const bool ok = full || (e0 + j * WAVE) < valid;
             const uint32_t d = digit_of(key[j], shift, dmask);
-            const uint64_t okm = __ballot(ok);
-            uint32_t xlo = ~(uint32_t)okm, xhi = ~(uint32_t)(okm >> 32);
-#pragma unroll
-            for (int b = 0; b < RADIX_BITS; ++b) {
-                const uint32_t sel = (uint32_t)((int32_t)(d << (31 - b)) >> 31);
-                const uint64_t bal = __ballot(sel != 0);
-                xlo |= (uint32_t)bal ^ sel;
-                xhi |= (uint32_t)(bal >> 32) ^ sel;
-            }
-            const uint32_t mlo = ~xlo, mhi = ~xhi;
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
-            const uint32_t prior = my_hist[d];
-            if (ok && below == 0) my_hist[d] = (uint16_t)(prior + (uint32_t)(__popc(mlo) + __popc(mhi)));
-            pos[j] = prior + below;
+            pos[j] = wave_digit_rank<RADIX_BITS>(d, ok, my_hist);      // (lds_sort.hpp)
             __builtin_amdgcn_sched_barrier(0);
         }
         stamp(1);      // ranking (includes the wait for the keys)

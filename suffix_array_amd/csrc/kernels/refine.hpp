@@ -5,6 +5,7 @@
 #include "keys.hpp"
 #include "rerank.hpp"
 #include "radix_sort.hpp"
+#include "lds_sort.hpp"
 
 namespace sa {
 
@@ -257,6 +258,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, 
     // more than one member: they fetch the next rank, count inside their subgroup (not the whole group) and move to their
     // new place.  A group that is still tied after K.iters steps shares (K.iters + 1) * h symbols: when no group of the
     // round went through the global sort, the host multiplies h by K.iters + 1 instead of 2 (long repeats: 15 rounds -> 6).
+    // The count inside a subgroup and the steps 2 .. K.iters: count_rank_lt_le and chase_steps, kernels/lds_sort.hpp.
     constexpr bool CHASE = MODE == KS_CHASE;
     __shared__ uint32_t s_val2[CHASE ? GS_TILE : 1];              // second value buffer + subgroup extents (first << 16 | size)
     __shared__ uint32_t s_rng[CHASE ? 2 : 1][CHASE ? GS_TILE : 1];
@@ -272,7 +274,8 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, 
     // a thousand, 100 us on the one compute unit that has the tile, which is what a launch over a few hundred tiles (a text of a
     // few MiB) then takes.  Such a tile sorts (first place of the member's group or, not owned, its own place | key | place)
     // composites through a bitonic network instead: 66 steps of 1 024 exchanges, 5 us whatever the groups -- every owned group
-    // comes out ordered in its own places, everything else stays where it is.  (Keys of up to 42 bits: 11 + 42 + 11.)
+    // comes out ordered in its own places, everything else stays where it is.  (Keys of up to 42 bits: 11 + 42 + 11.)  The network
+    // and the reason most of its steps need no workgroup barrier: lds_bitonic_sort, kernels/lds_sort.hpp.
     bool by_network = false;
     uint16_t *s_place = (uint16_t *)s_val;                       // (s_val is written only behind the barrier that follows the ranks)
     if (!CHASE && K.kb <= 42 && K.net_min > 0) {
@@ -293,22 +296,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, 
                 s_key[jl] = ((uint64_t)(owned ? start : jl) << 53) | (owned ? key[r] << 11 : 0ull) | (uint64_t)jl;
             }
             __syncthreads();
-            // (exchange x of a step pairs elements inside the 128-element block x / 64 as long as the distance is at most 64, and a
-            // wave's 64 exchanges are one such block: 56 of the 66 steps need no workgroup barrier, only the wave's own LDS traffic
-            // to have landed)
-            for (int k = 2; k <= GS_TILE; k <<= 1) {
-                for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-                    for (int x = t; x < GS_TILE / 2; x += GS_THREADS) {
-                        const int lo = ((x & ~(j - 1)) << 1) | (x & (j - 1)), hi = lo | j;
-                        const uint64_t a = s_key[lo], c = s_key[hi];
-                        if ((a > c) == ((lo & k) == 0)) { s_key[lo] = c; s_key[hi] = a; }
-                    }
-                    const int next_j = j > 1 ? (j >> 1) : k;                 // (the next step's distance; behind the last step: a barrier)
-                    if (j > 64 || next_j > 64 || (j == 1 && k == GS_TILE)) __syncthreads();
-                    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                }
-            }
+            lds_bitonic_sort<GS_THREADS, GS_TILE>(s_key, GS_TILE, t);       // (56 of the 66 steps without a workgroup barrier: lds_sort.hpp)
 #pragma unroll
             for (int r = 0; r < GS_ITEMS; ++r) {
                 const int p = r * GS_THREADS + t;
@@ -339,14 +327,8 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, 
             const int lt = lt_a + lt_b, le = le_a + le_b + 1;          // (+1: myself)
             rng = ((uint32_t)(start + lt) << 16) | (uint32_t)(le - lt);
         } else if (owned && CHASE) {
-            const uint64_t mine = (key[r] << 11) | (uint64_t)jl;
-            int lt = 0, le = 0;
-            for (int i = start; i < end; ++i) {
-                const uint64_t k = s_key[i];
-                rank += k < mine ? 1 : 0;
-                lt += (k >> 11) < key[r] ? 1 : 0;
-                le += (k >> 11) <= key[r] ? 1 : 0;
-            }
+            int lt, le;
+            count_rank_lt_le<11>(s_key, start, end - start, (key[r] << 11) | (uint64_t)jl, key[r], rank, lt, le);
             rng = ((uint32_t)(start + lt) << 16) | (uint32_t)(le - lt);
         } else if (owned && MODE == KS_RANK && K.kb <= 32) {
             const uint32_t *k32 = (const uint32_t *)s_key;
@@ -376,61 +358,12 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, 
         if (CHASE) { s_val[dest[r]] = v[r]; s_rng[0][dest[r]] = rng; }      // (s_val / s_rng are not read by the counts above)
     }
     stamp(3);      // group extents + rank loops
-    if (CHASE) {
+    if constexpr (CHASE) {
         // from here on a thread works on PLACES jl = r * GS_THREADS + t of the sorted tile, not on the members it loaded
         static_assert(!CHASE || GS_TILE <= 2048, "subgroup extents are packed as 16 + 16 bits, places as 11");
-        uint32_t *val_cur = s_val, *val_nxt = s_val2;
-        int cur = 0;
         __syncthreads();
-        for (int it = 2; it <= K.iters; ++it) {
-            uint32_t rg[GS_ITEMS], vq[GS_ITEMS];
-            uint64_t mine[GS_ITEMS];
-            bool any = false;
-#pragma unroll
-            for (int r = 0; r < GS_ITEMS; ++r) {
-                const int q = r * GS_THREADS + t;
-                rg[r] = s_rng[cur][q];
-                vq[r] = val_cur[q];
-                any |= (rg[r] & 0xffffu) > 1u;
-            }
-            if (!__syncthreads_or(any)) break;
-#pragma unroll
-            for (int r = 0; r < GS_ITEMS; ++r) {
-                const int q = r * GS_THREADS + t;
-                mine[r] = 0;
-                if ((rg[r] & 0xffffu) > 1u) {
-                    const int64_t p = (int64_t)vq[r] + (int64_t)it * K.h;
-                    const uint64_t comp = p < n ? (uint64_t)n + (uint64_t)K.isa[p] : (uint64_t)(n - 1 - (int64_t)vq[r]);
-                    mine[r] = (comp << 11) | (uint64_t)q;
-                    s_key[q] = mine[r];
-                }
-            }
-            __syncthreads();
-            const int nxt = cur ^ 1;
-#pragma unroll
-            for (int r = 0; r < GS_ITEMS; ++r) {
-                const int q = r * GS_THREADS + t;
-                const int e = (int)(rg[r] & 0xffffu), a = (int)(rg[r] >> 16);
-                if (e > 1) {
-                    int rank = 0, lt = 0, le = 0;
-                    const uint64_t comp = mine[r] >> 11;
-                    for (int i = a; i < a + e; ++i) {
-                        const uint64_t k = s_key[i];
-                        rank += k < mine[r] ? 1 : 0;
-                        lt += (k >> 11) < comp ? 1 : 0;
-                        le += (k >> 11) <= comp ? 1 : 0;
-                    }
-                    val_nxt[a + rank] = vq[r];
-                    s_rng[nxt][a + rank] = ((uint32_t)(a + lt) << 16) | (uint32_t)(le - lt);
-                } else {
-                    val_nxt[q] = vq[r];
-                    s_rng[nxt][q] = rg[r];
-                }
-            }
-            __syncthreads();
-            { uint32_t *tmp = val_cur; val_cur = val_nxt; val_nxt = tmp; }
-            cur = nxt;
-        }
+        const int cur = chase_steps<GS_THREADS, GS_ITEMS, 11>(s_key, s_val, s_val2, s_rng, GS_TILE, t, K.iters, K.h, K.isa, n);   // (lds_sort.hpp)
+        const uint32_t *val_cur = cur ? s_val2 : s_val;
         stamp(4);
 #pragma unroll
         for (int r = 0; r < GS_ITEMS; ++r) {
@@ -518,7 +451,8 @@ __global__ __launch_bounds__(GX_THREADS) void k_group_sort_straddle(uint64_t *__
     if (!chase && size > GX_BITONIC_MIN && K.kb <= 54) {
         // A group of a thousand members ranked by counting is a million comparisons on ONE compute unit (100 us: at 1 MiB of English
         // text this kernel took longer than k_group_sort itself): (key2 << 10 | member) composites -- distinct, so the order is the
-        // stable one -- go through a bitonic network in LDS instead, 55 steps of 512 exchanges for 1 024 members.
+        // stable one -- go through a bitonic network in LDS instead (lds_bitonic_sort, kernels/lds_sort.hpp), 55 steps of 512
+        // exchanges for 1 024 members.
         int P = 128;
         while (P < size) P <<= 1;
 #pragma unroll
@@ -528,19 +462,7 @@ __global__ __launch_bounds__(GX_THREADS) void k_group_sort_straddle(uint64_t *__
             else if (i < P) s_key[i] = ~0ull;
         }
         __syncthreads();
-        for (int k = 2; k <= P; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int x = t; x < P / 2; x += GX_THREADS) {
-                    const int lo = ((x & ~(j - 1)) << 1) | (x & (j - 1)), hi = lo | j;
-                    const uint64_t a = s_key[lo], c = s_key[hi];
-                    if ((a > c) == ((lo & k) == 0)) { s_key[lo] = c; s_key[hi] = a; }
-                }
-                // (distances of at most 64 stay inside a wave's own 128-element blocks: see k_group_sort)
-                const int next_j = j > 1 ? (j >> 1) : k;
-                if (j > 64 || next_j > 64 || (j == 1 && k == P)) __syncthreads();
-                else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            }
-        }
+        lds_bitonic_sort<GX_THREADS, GS_CAP>(s_key, P, t);               // (lds_sort.hpp)
         __shared__ uint64_t s_ghead;                                // the bits above the secondary key: the group's head, the same for every member
         if (t == 0) s_ghead = key[0] & ~kmask;
         __syncthreads();
@@ -577,69 +499,15 @@ __global__ __launch_bounds__(GX_THREADS) void k_group_sort_straddle(uint64_t *__
     for (int r = 0; r < GX_ITEMS; ++r) {
         const int i = r * GX_THREADS + t;
         if (i < size) {
-            const uint64_t comp = key[r] & kmask, mine = (comp << 10) | (uint64_t)i;
-            int rank = 0, lt = 0, le = 0;
-            for (int q = 0; q < size; ++q) {
-                const uint64_t k = s_key[q];
-                rank += k < mine ? 1 : 0;
-                lt += (k >> 10) < comp ? 1 : 0;
-                le += (k >> 10) <= comp ? 1 : 0;
-            }
+            const uint64_t comp = key[r] & kmask;
+            int rank, lt, le;
+            count_rank_lt_le<10>(s_key, 0, size, (comp << 10) | (uint64_t)i, comp, rank, lt, le);
             s_v[0][rank] = v[r];
             s_rg[0][rank] = ((uint32_t)lt << 16) | (uint32_t)(le - lt);
         }
     }
     __syncthreads();
-    int cur = 0;
-    for (int it = 2; it <= K.iters; ++it) {
-        uint32_t rg[GX_ITEMS], vq[GX_ITEMS];
-        uint64_t mine[GX_ITEMS];
-        bool any = false;
-#pragma unroll
-        for (int r = 0; r < GX_ITEMS; ++r) {
-            const int q = r * GX_THREADS + t;
-            rg[r] = q < size ? s_rg[cur][q] : 1u;
-            vq[r] = q < size ? s_v[cur][q] : 0u;
-            any |= (rg[r] & 0xffffu) > 1u;
-        }
-        if (!__syncthreads_or(any)) break;
-#pragma unroll
-        for (int r = 0; r < GX_ITEMS; ++r) {
-            const int q = r * GX_THREADS + t;
-            mine[r] = 0;
-            if ((rg[r] & 0xffffu) > 1u) {
-                const int64_t p = (int64_t)vq[r] + (int64_t)it * K.h;
-                const uint64_t comp = p < n ? (uint64_t)n + (uint64_t)K.isa[p] : (uint64_t)(n - 1 - (int64_t)vq[r]);
-                mine[r] = (comp << 10) | (uint64_t)q;
-                s_key[q] = mine[r];
-            }
-        }
-        __syncthreads();
-        const int nxt = cur ^ 1;
-#pragma unroll
-        for (int r = 0; r < GX_ITEMS; ++r) {
-            const int q = r * GX_THREADS + t;
-            if (q >= size) continue;
-            const int e = (int)(rg[r] & 0xffffu), a = (int)(rg[r] >> 16);
-            if (e > 1) {
-                int rank = 0, lt = 0, le = 0;
-                const uint64_t comp = mine[r] >> 10;
-                for (int i = a; i < a + e; ++i) {
-                    const uint64_t k = s_key[i];
-                    rank += k < mine[r] ? 1 : 0;
-                    lt += (k >> 10) < comp ? 1 : 0;
-                    le += (k >> 10) <= comp ? 1 : 0;
-                }
-                s_v[nxt][a + rank] = vq[r];
-                s_rg[nxt][a + rank] = ((uint32_t)(a + lt) << 16) | (uint32_t)(le - lt);
-            } else {
-                s_v[nxt][q] = vq[r];
-                s_rg[nxt][q] = rg[r];
-            }
-        }
-        __syncthreads();
-        cur = nxt;
-    }
+    const int cur = chase_steps<GX_THREADS, GX_ITEMS, 10>(s_key, s_v[0], s_v[1], s_rg, size, t, K.iters, K.h, K.isa, n);   // (lds_sort.hpp)
     const uint64_t ghead = ((uint64_t)gb) << K.kb;
 #pragma unroll
     for (int r = 0; r < GX_ITEMS; ++r) {
@@ -658,7 +526,8 @@ __global__ __launch_bounds__(GX_THREADS) void k_group_sort_straddle(uint64_t *__
 // compaction in front and a scatter behind.  The members' secondary keys (at most 32 bits) are where k_group_sort left them:
 // keys[j] = group head << kb | key2, V[j] = suffix, in list order.  First pass on the low 10 key bits by one LDS counter per
 // digit (the order among equal digits is left to the atomics: members that agree in ALL key bits stay tied, and which of them
-// takes which slot of the subgroup is nobody's business), then stable 6-bit passes (6 ballots + mbcnt) over the rest.
+// takes which slot of the subgroup is nobody's business), then stable 6-bit passes (6 ballots + mbcnt) over the rest: the two
+// passes are lds_count_pass and lds_stable_pass of kernels/lds_sort.hpp, shared with k_bucket_sort.
 // heads: the list k_group_sort wrote (first members of groups it could not own); a group of at most `cap` members is
 // k_group_sort_straddle's, one of more than GB_CAP stays flagged for the global sort.  sorted_members: members ordered here
 // (the host counts them with the members of the global sort: no chasing after a round that had such groups).
@@ -689,7 +558,6 @@ __global__ __launch_bounds__(GB_THREADS) void k_group_sort_big(uint64_t *__restr
     __shared__ uint32_t scan_lds[NWAVES + 1];
     __shared__ int s_size;
     const int tid = threadIdx.x, l = lane_id(), w = wave_id();
-    uint16_t *my_hist = wave_hist[w];
     const uint32_t count = *n_heads;
     const int lo_size = size_lo;                                   // smaller groups are not this instance's
     for (uint32_t ent = blockIdx.x; ent < count; ent += gridDim.x) {
@@ -721,8 +589,7 @@ __global__ __launch_bounds__(GB_THREADS) void k_group_sort_big(uint64_t *__restr
         const int J = (size + GB_THREADS - 1) / GB_THREADS;
         const int e0 = w * J * WAVE + l;
         const uint32_t kmask = kb >= 32 ? 0xffffffffu : ((1u << kb) - 1u);
-        uint32_t key[GB_ITEMS], val[GB_ITEMS], pp[GB_ITEMS / 2];
-#define GB_POS(j) ((pp[(j) >> 1] >> (16 * ((j) & 1))) & 0xffffu)
+        uint32_t key[GB_ITEMS], val[GB_ITEMS], pp[GB_ITEMS / 2];       // pp: places in the group, two to a register
 #pragma unroll
         for (int j = 0; j < GB_ITEMS; ++j) {
             const int e = e0 + j * WAVE;
@@ -731,38 +598,8 @@ __global__ __launch_bounds__(GB_THREADS) void k_group_sort_big(uint64_t *__restr
             key[j] = kx; val[j] = vx;
         }
         const int abits = kb < GB_ABITS ? kb : GB_ABITS;
-        {
-            // ---- first pass: one counter per digit hands out the places ----
-            const uint32_t amask = (1u << abits) - 1u;
-            for (int i = tid; i < NB_A; i += GB_THREADS) cnt_a[i] = 0;
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < GB_ITEMS; ++j) {
-                uint32_t r = 0;
-                if (j < J && (e0 + j * WAVE) < size) r = atomicAdd(&cnt_a[key[j] & amask], 1u);
-                if ((j & 1) == 0) pp[j >> 1] = r; else pp[j >> 1] |= r << 16;
-            }
-            lds_barrier();
-            {
-                constexpr int BPT = NB_A / GB_THREADS;
-                uint32_t c[BPT], sum = 0;
-#pragma unroll
-                for (int i = 0; i < BPT; ++i) { c[i] = cnt_a[tid * BPT + i]; sum += c[i]; }
-                uint32_t all;
-                uint32_t run = block_excl_sum_b<GB_THREADS, true>(sum, scan_lds, &all);
-#pragma unroll
-                for (int i = 0; i < BPT; ++i) { cnt_a[tid * BPT + i] = run; run += c[i]; }
-            }
-            lds_barrier();
-#pragma unroll
-            for (int j = 0; j < GB_ITEMS; ++j) {
-                if (j < J && (e0 + j * WAVE) < size) {
-                    const uint32_t ps = GB_POS(j) + cnt_a[key[j] & amask];
-                    lds_k[ps] = key[j];
-                    lds_v[ps] = val[j];
-                }
-            }
-        }
+        // ---- first pass: one counter per digit hands out the places (lds_count_pass, lds_sort.hpp) ----
+        lds_count_pass<GB_THREADS, GB_ITEMS, NB_A>(key, val, pp, J, e0, size, (1u << abits) - 1u, lds_k, lds_v, cnt_a, scan_lds);
         // ---- stable passes over the remaining key bits, 6 at a time ----
 #pragma unroll
         for (int p = 0; p < (32 - 1 + GB_BBITS - 1) / GB_BBITS; ++p) {
@@ -785,55 +622,8 @@ __global__ __launch_bounds__(GB_THREADS) void k_group_sort_big(uint64_t *__restr
                     if (j < J && (e0 + j * WAVE) < size) same = same && ((key[j] >> shift) & (uint32_t)(NB_B - 1)) == dref;
                 if (__syncthreads_and(same ? 1 : 0)) continue;     // (uniform; the bucket stays in LDS as it is)
             }
-            for (int i = tid; i < NWAVES * NB_B / 2; i += GB_THREADS) ((uint32_t *)&wave_hist[0][0])[i] = 0;
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < GB_ITEMS; ++j) {
-                uint32_t r = 0;
-                if (j < J) {                                       // (uniform)
-                    const bool ok = (e0 + j * WAVE) < size;
-                    const uint32_t d = (key[j] >> shift) & (uint32_t)(NB_B - 1);
-                    const uint64_t okm = __ballot(ok);
-                    uint32_t xlo = ~(uint32_t)okm, xhi = ~(uint32_t)(okm >> 32);
-#pragma unroll
-                    for (int bb = 0; bb < GB_BBITS; ++bb) {
-                        const uint32_t sel = (uint32_t)((int32_t)(d << (31 - bb)) >> 31);
-                        const uint64_t bal = __ballot(sel != 0);
-                        xlo |= (uint32_t)bal ^ sel;
-                        xhi |= (uint32_t)(bal >> 32) ^ sel;
-                    }
-                    const uint32_t mlo = ~xlo, mhi = ~xhi;
-                    const uint32_t below = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
-                    const uint32_t prior = my_hist[d];
-                    if (ok && below == 0) my_hist[d] = (uint16_t)(prior + (uint32_t)(__popc(mlo) + __popc(mhi)));
-                    r = prior + below;
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if ((j & 1) == 0) pp[j >> 1] = r; else pp[j >> 1] |= r << 16;
-            }
-            lds_barrier();
-            if (w == 0) {
-                uint32_t tot = 0;
-#pragma unroll
-                for (int ww = 0; ww < NWAVES; ++ww) {
-                    const uint32_t cnt = wave_hist[ww][l];
-                    wave_hist[ww][l] = (uint16_t)tot;
-                    tot += cnt;
-                }
-                digit_base[l] = wave_incl_sum(tot) - tot;
-            }
-            lds_barrier();
-#pragma unroll
-            for (int j = 0; j < GB_ITEMS; ++j) {
-                if (j < J && (e0 + j * WAVE) < size) {
-                    const uint32_t d = (key[j] >> shift) & (uint32_t)(NB_B - 1);
-                    const uint32_t ps = GB_POS(j) + digit_base[d] + my_hist[d];
-                    lds_k[ps] = key[j];
-                    lds_v[ps] = val[j];
-                }
-            }
+            lds_stable_pass<GB_THREADS, GB_ITEMS, GB_BBITS>(key, val, pp, J, e0, size, shift, (uint32_t)(NB_B - 1), lds_k, lds_v, wave_hist, digit_base);
         }
-#undef GB_POS
         __syncthreads();
         const uint64_t ghead = (uint64_t)g0 << kb;
 #pragma unroll

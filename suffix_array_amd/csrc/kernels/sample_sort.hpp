@@ -27,6 +27,7 @@
 #pragma once
 #include "common.hpp"
 #include "rerank.hpp"
+#include "lds_sort.hpp"
 
 namespace sa {
 
@@ -461,8 +462,7 @@ __global__ __launch_bounds__(THREADS, 4) void k_ss_bucket_sort(const uint64_t *_
     const int J = (size + THREADS - 1) / THREADS;
     const int e0 = w * J * WAVE + l;                   // element e = wave w, item j, lane l -> w * 64 J + 64 j + l (wave-striped)
     uint64_t key[ITEMS];
-    uint32_t val[ITEMS], pp[ITEMS / 2];
-#define SB_POS(j) ((pp[(j) >> 1] >> (16 * ((j) & 1))) & 0xffffu)
+    uint32_t val[ITEMS], pp[ITEMS / 2];                // pp: places in the bucket, two to a register (place_put / place_get, lds_sort.hpp)
     uint64_t diff = 0;
     const uint64_t k0 = keys_in[lo];
 #pragma unroll
@@ -499,7 +499,7 @@ __global__ __launch_bounds__(THREADS, 4) void k_ss_bucket_sort(const uint64_t *_
         for (int j = 0; j < ITEMS; ++j) {
             uint32_t r = 0;
             if (j < J && (e0 + j * WAVE) < size) r = atomicAdd(&cnt_a[(uint32_t)key[j] & amask], 1u);
-            if ((j & 1) == 0) pp[j >> 1] = r; else pp[j >> 1] |= r << 16;
+            place_put(pp, j, r);
         }
         __syncthreads();
         {
@@ -517,13 +517,13 @@ __global__ __launch_bounds__(THREADS, 4) void k_ss_bucket_sort(const uint64_t *_
 #pragma unroll
         for (int j = 0; j < ITEMS; ++j) {
             if (j < J && (e0 + j * WAVE) < size) {
-                const uint32_t ps = SB_POS(j) + cnt_a[(uint32_t)key[j] & amask];
+                const uint32_t ps = place_get(pp, j) + cnt_a[(uint32_t)key[j] & amask];
                 lds_k[ps] = key[j]; lds_v[ps] = val[j];
             }
         }
         shift = abits;
     }
-    // ---- stable passes of SB_BBITS bits over the rest: rank inside the wave (ballots + mbcnt), per-wave digit counts in LDS ----
+    // ---- stable passes of SB_BBITS bits over the rest: rank inside the wave (wave_digit_rank, lds_sort.hpp), per-wave digit counts in LDS ----
     while (shift < sig) {
         __syncthreads();
         const int nb = sig - shift < SB_BBITS ? sig - shift : SB_BBITS;
@@ -544,25 +544,10 @@ __global__ __launch_bounds__(THREADS, 4) void k_ss_bucket_sort(const uint64_t *_
         for (int j = 0; j < ITEMS; ++j) {
             uint32_t r = 0;
             if (j < J) {                           // (uniform)
-                const bool ok = (e0 + j * WAVE) < size;
-                const uint32_t d = (uint32_t)(key[j] >> shift) & dmask;
-                const uint64_t okm = __ballot(ok);
-                uint32_t xlo = ~(uint32_t)okm, xhi = ~(uint32_t)(okm >> 32);
-#pragma unroll
-                for (int bb = 0; bb < SB_BBITS; ++bb) {
-                    const uint32_t sel = (uint32_t)((int32_t)(d << (31 - bb)) >> 31);
-                    const uint64_t bal = __ballot(sel != 0);
-                    xlo |= (uint32_t)bal ^ sel;
-                    xhi |= (uint32_t)(bal >> 32) ^ sel;
-                }
-                const uint32_t mlo = ~xlo, mhi = ~xhi;
-                const uint32_t below = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
-                const uint32_t prior = my_hist[d];
-                if (ok && below == 0) my_hist[d] = (uint16_t)(prior + (uint32_t)(__popc(mlo) + __popc(mhi)));
-                r = prior + below;
+                r = wave_digit_rank<SB_BBITS>((uint32_t)(key[j] >> shift) & dmask, (e0 + j * WAVE) < size, my_hist);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if ((j & 1) == 0) pp[j >> 1] = r; else pp[j >> 1] |= r << 16;
+            place_put(pp, j, r);
         }
         __syncthreads();
         uint32_t tot = 0;
@@ -582,13 +567,12 @@ __global__ __launch_bounds__(THREADS, 4) void k_ss_bucket_sort(const uint64_t *_
         for (int j = 0; j < ITEMS; ++j) {
             if (j < J && (e0 + j * WAVE) < size) {
                 const uint32_t d = (uint32_t)(key[j] >> shift) & dmask;
-                const uint32_t ps = SB_POS(j) + digit_base[d] + my_hist[d];
+                const uint32_t ps = place_get(pp, j) + digit_base[d] + my_hist[d];
                 lds_k[ps] = key[j]; lds_v[ps] = val[j];
             }
         }
         shift += nb;
     }
-#undef SB_POS
     __syncthreads();
     for (int i = tid; i < size; i += THREADS) { keys_out[lo + i] = lds_k[i]; vals_out[lo + i] = lds_v[i]; }
 }

@@ -967,6 +967,31 @@ def test_groups_across_tile_boundaries(oracle, monkeypatch, period, copies):
                 monkeypatch.delenv(k)
 
 
+def test_tile_network_and_counting_loops_give_the_same_array(oracle, monkeypatch):
+    """k_group_sort orders the groups a tile owns either by its counting loops (SA_AMD_NETWORK_MIN=0: never the network) or by
+    the bitonic network over the whole tile (SA_AMD_NETWORK_MIN=1: whenever a tile owns a group of two) -- the same array
+    either way, and the oracle's.  The texts of test_groups_across_tile_boundaries at groups of 97 members (below the straddle
+    kernel's own network threshold), 700 (between the two thresholds) and 1 024 (the largest group a tile owns); text-keyed
+    rounds, rank rounds with the chase (which never takes the network), and 24-bit keys without gram ranks."""
+    for period, copies in ((700, 97), (333, 700), (211, 1024)):
+        rng = np.random.default_rng(period * 7 + copies)
+        block = rng.integers(0, 256, period, dtype=np.uint8)
+        text = np.tile(block, copies)
+        mixed = np.concatenate([np.tile(block, copies // 2), corpus.english(50_000, 3), np.tile(block[: period // 3], copies), rng.integers(0, 3, 20_000, dtype=np.uint8)])
+        for t in (text, mixed):
+            exp = oracle.sais(t)
+            for env in ({}, {"SA_AMD_FORCE_DENSE": "1", "SA_AMD_CHASE": "1"},
+                        {"SA_AMD_NO_REPEAT_PROBE": "1", "SA_AMD_NO_GRAM_KEYS": "1", "SA_AMD_KEY_BITS": "24"}):
+                for net_min in ("0", "1"):
+                    monkeypatch.setenv("SA_AMD_NETWORK_MIN", net_min)
+                    for k, v in env.items():
+                        monkeypatch.setenv(k, v)
+                    assert np.array_equal(build(t), exp), (period, copies, env, net_min)
+                    for k in env:
+                        monkeypatch.delenv(k)
+        monkeypatch.delenv("SA_AMD_NETWORK_MIN")
+
+
 def test_bucket_route_is_not_tried_on_a_text_with_one_huge_bucket(oracle, monkeypatch):
     """a text the entropy probe sends to the 32-bit first stage (its 4-byte prefixes are nearly unique) although one value of
     the top 16 key bits holds 1/32 of the suffixes: the probe's samples, counted per bucket, say so and the two global passes
