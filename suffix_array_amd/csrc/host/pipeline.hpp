@@ -1279,6 +1279,7 @@ struct DeviceBuild {
             depth += s_sym;
             local.text_rounds++;
             local.rounds++;
+            if (trace) fprintf(stderr, "suffix_array_amd: text round %d depth %lld: tied %lld -> %lld  (%.2f ms)\n", local.text_rounds, (long long)depth, (long long)cnt4[2], (long long)L.m, lap());
         }
         return SA_AMD_OK;
     }
