@@ -694,6 +694,83 @@ void sa_amd_last_doc_tf_stats(sa_amd_doc_tf_stats *out);
  * doc_tf and doc_topk as it does to doc_list. */
 int32_t sa_amd_docs_set_topk_piece(int32_t entries);
 
+/*
+ * Repeated substrings (an extension): which substrings occur at least twice, how often, and the most frequent, the longest or
+ * the most covering of them, on the device.  The table a unigram tokeniser trainer seeds its vocabulary
+ * from and a curator lists boilerplate with, without downloading the suffix array or the LCP array.
+ * SA and LCP are in the layout of sa_amd_saca_u8 and sa_amd_lcp: n + 1 entries, LCP[0] = LCP[1] = 0.
+ *   A slot i with 2 <= i <= n is a REPRESENTATIVE when both hold: d = LCP[i] > 0; the nearest j < i with LCP[j] <= d has
+ *     LCP[j] < d.  That j is lo, and lo >= 1.  hi is the nearest j > i with LCP[j] < d, or n + 1 when there is none.
+ *   The NODE of a representative is the row (lo, count, depth, parent): lo as above; count = hi - lo, which is at least 2;
+ *     depth = d; parent = max(LCP[lo], LCP[hi]), with LCP[n + 1] read as 0.  This gives parent < depth.
+ *   Its substring is T[SA[lo] .. SA[lo] + depth), and it occurs at exactly SA[lo .. lo + count).
+ *   The nodes are the internal nodes of the suffix tree below the root: there are at most max(n - 1, 0) of them
+ *     (sa_amd_substrings_bound); every substring that occurs at least twice, of length L, lies in exactly one node with
+ *     parent < L <= depth and has that node's count; for one node every length in (parent, depth] has the same occurrence set,
+ *     so a caller can cut the table at any length without another query.
+ *   "banana": LCP = {0, 0, 1, 3, 0, 0, 2}; the nodes are (1, 3, 1, 0) "a", (2, 2, 3, 1) "ana" (and "an") and (5, 2, 2, 0) "na"
+ *     (and "n"), at the representatives 2, 3 and 6; pos = {5, 3, 4}.
+ * Query: min_len >= 1, max_len (0: none, otherwise >= min_len), min_count >= 2, order and k.  A node is SELECTED when
+ *   depth >= min_len, (max_len == 0 or parent < max_len) and count >= min_count.  Its effective length is len = depth when
+ *   max_len == 0, otherwise min(depth, max_len).
+ * Orders: SA_AMD_SUBSTR_ALL returns every selected node by representative slot ascending and ignores k.  The ranked orders
+ *   return the best min(k, selected) nodes by a 64-bit key, descending, equal keys by representative slot ascending:
+ *   SA_AMD_SUBSTR_BY_COUNT key = count, SA_AMD_SUBSTR_BY_LENGTH key = len, SA_AMD_SUBSTR_BY_COVER key = count * len (uint64).
+ *   They require k >= 1.  The order is strict, so the answer is unique.
+ * Outputs: rows of 4 uint32 (lo, count, depth, parent); pos (optional, may be NULL): pos[r] = SA[lo_r], where the substring of
+ *   row r can be read in the text.  *total is the number of rows the query has: selected, or min(k, selected) for the ranked
+ *   orders.  The first min(capacity, *total) rows are written and nothing behind them; more rows than fit is no error.
+ * Errors, as for sa_amd_lcp: an entry > n is SA_AMD_ERANGE, SA[0] != n is SA_AMD_EINVAL (range pass before anything is read
+ * through the entries).  A query outside the ranges above, an unknown order, capacity < 0, a NULL total, NULL rows with
+ * capacity > 0 and a misaligned or short work block are SA_AMD_EINVAL with nothing written; they are answered before a
+ * device is looked for.  SA_AMD_ENOMEM as elsewhere.  With an array that is no suffix array the answers are unspecified, but
+ * nothing is read outside T or the tables and nothing is written outside the outputs.
+ * The LCP array is built inside (sa_amd_lcp_device's stages): sa_amd_last_lcp_stats is filled by that build, as after
+ * sa_amd_lcp; sa_amd_last_lz_stats, sa_amd_last_repeat_stats and the other features' statistics are not touched.
+ */
+#define SA_AMD_SUBSTR_ALL 0
+#define SA_AMD_SUBSTR_BY_COUNT 1
+#define SA_AMD_SUBSTR_BY_LENGTH 2
+#define SA_AMD_SUBSTR_BY_COVER 3
+typedef struct sa_amd_substr_query {
+    int32_t min_len;                 /* >= 1 */
+    int32_t max_len;                 /* 0: no upper limit; otherwise >= min_len */
+    int32_t min_count;               /* >= 2 */
+    int32_t order;                   /* SA_AMD_SUBSTR_* */
+    int64_t k;                       /* ranked orders: >= 1; ignored by SA_AMD_SUBSTR_ALL */
+} sa_amd_substr_query;
+/* bytes of device scratch the device call needs: sa_amd_lcp_work_bytes(n) plus five n-entry buffers, about 41 (n + 1); -1 when n < 0 */
+int64_t sa_amd_substrings_work_bytes(int32_t n);
+/* the most rows any query can have: max(n - 1, 0); -1 when n < 0 */
+int64_t sa_amd_substrings_bound(int32_t n);
+/* device pointers: dT n bytes (any byte address), dSA n + 1 entries, dRows 4 * capacity entries and dPos capacity entries (dRows
+ * may be NULL when capacity is 0, dPos whenever it is not wanted), dWork sa_amd_substrings_work_bytes(n) bytes 256-byte aligned;
+ * total a HOST pointer; stream a hipStream_t (NULL = default stream).  Blocks until done. */
+int32_t sa_amd_substrings_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, const sa_amd_substr_query *query, uint32_t *dRows,
+                                 uint32_t *dPos, int64_t capacity, int64_t *total, void *dWork, int64_t work_bytes, void *stream);
+/* host pointers.  SA == NULL: the array is built on the device, used there and never downloaded: n bytes go up, 16 (+ 4) bytes
+ * per row come back.  SA != NULL (n + 1 entries): the caller's array goes up. */
+int32_t sa_amd_substrings(const uint8_t *T, int32_t n, const uint32_t *SA, const sa_amd_substr_query *query, uint32_t *rows,
+                          uint32_t *pos, int64_t capacity, int64_t *total);
+/* from the index's resident text and suffix array (with or without sa_amd_index_enable_lcp: its table is not the LCP array) */
+int32_t sa_amd_index_substrings(const sa_amd_index *ix, const sa_amd_substr_query *query, uint32_t *rows, uint32_t *pos,
+                                int64_t capacity, int64_t *total);
+
+typedef struct sa_amd_substr_stats { /* of the calling thread's most recent substrings call */
+    int64_t nodes;                   /* all nodes, whatever the query */
+    int64_t selected;                /* nodes the filter keeps, whatever k and capacity */
+    int64_t distinct_all;            /* sum of depth - parent over all nodes: the distinct substrings that occur at least twice */
+    int64_t distinct_selected;       /* sum of len - max(parent, min_len - 1) over the selected nodes: the distinct substrings
+                                        with a length in the window and at least min_count occurrences */
+    int64_t unresolved;              /* slots whose neighbour, on either side, was not inside their tile of 1024 slots */
+    int64_t far_steps;               /* words of the block minima (and of LCP) those slots loaded, all of them together */
+    int64_t far_max;                 /* the most one side of one slot loaded: at most 31 (K - 1) + 32 K, K the number of levels (347) */
+    int64_t sorted;                  /* pairs the final sort of a ranked order ran on: min(k, selected); 0 for SA_AMD_SUBSTR_ALL */
+    int32_t select_passes;           /* digit histograms of the radix select: at most 8; 0 when k >= selected */
+    int32_t readbacks;               /* blocking device -> host read-backs of counters, the LCP build's included */
+} sa_amd_substr_stats;
+void sa_amd_last_substr_stats(sa_amd_substr_stats *out);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

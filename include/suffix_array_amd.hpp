@@ -10,6 +10,9 @@
 //                                           inverse_bw_transform of the C engine the reference binds)
 //   SuffixArray::repeat_lengths / repeat_spans, repeat_lengths(), repeat_spans()
 //                                           EXTENSION: the longest-repeat array and the byte ranges that are copies
+//   SuffixArray::repeated_substrings, repeated_substrings()
+//                                           EXTENSION: the substrings that occur at least twice, as suffix-tree nodes: all of
+//                                           them or the k most frequent, longest or most covering
 //   DocumentIndex                           EXTENSION: a device-resident index over a collection of documents: which document a
 //                                           position lies in, in how many documents a pattern occurs and in which ones,
 //                                           (term_frequencies, top_k) how often in each and the k documents with the most
@@ -85,6 +88,38 @@ inline std::vector<std::pair<std::uint32_t, std::uint32_t>> repeat_spans(const s
     if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
     std::vector<std::pair<std::uint32_t, std::uint32_t>> out(static_cast<std::size_t>(count < cap ? count : cap));
     for (std::size_t i = 0; i < out.size(); ++i) out[i] = { flat[2 * i], flat[2 * i + 1] };
+    return out;
+}
+
+// EXTENSION: the substrings of s that occur at least twice (suffix_array_amd.h, "Repeated substrings"): one row per internal node
+// of the suffix tree -- the substring s[pos .. pos + depth) occurs exactly `count` times, at sa[lo .. lo + count), and so does
+// every prefix of it longer than `parent`.  order SA_AMD_SUBSTR_ALL: every selected node in suffix-array order; the ranked
+// orders: the best k by count, length or count * length (sa_amd_substrings).  Only the rows come back from the device.
+struct RepeatedSubstring {
+    std::uint32_t lo, count, depth, parent;
+    std::uint32_t pos;                                            // sa[lo]: where the substring can be read
+    bool operator==(const RepeatedSubstring &o) const
+    {
+        return lo == o.lo && count == o.count && depth == o.depth && parent == o.parent && pos == o.pos;
+    }
+    bool operator!=(const RepeatedSubstring &o) const { return !(*this == o); }
+};
+inline std::vector<RepeatedSubstring> repeated_substrings(const std::uint8_t *s, std::size_t n, std::int32_t min_len = 1, std::int32_t max_len = 0,
+                                                          std::int32_t min_count = 2, std::int32_t order = SA_AMD_SUBSTR_ALL, std::int64_t k = 0,
+                                                          const std::uint32_t *sa = nullptr)
+{
+    if (n > MAX_LENGTH) throw std::logic_error("assertion failed: s.len() <= MAX_LENGTH");
+    const sa_amd_substr_query q = { min_len, max_len, min_count, order, k };
+    std::int64_t cap = sa_amd_substrings_bound(static_cast<std::int32_t>(n));
+    if (order != SA_AMD_SUBSTR_ALL && k >= 1 && k < cap) cap = k;
+    std::vector<std::uint32_t> flat(static_cast<std::size_t>(cap) * 4), pos(static_cast<std::size_t>(cap));
+    std::int64_t total = 0;
+    const std::int32_t rc = sa_amd_substrings(s, static_cast<std::int32_t>(n), sa, &q, flat.data(), pos.data(), cap, &total);
+    if (rc == SA_AMD_ERANGE) throw std::out_of_range("suffix offset out of range");
+    if (rc == SA_AMD_EINVAL) throw std::invalid_argument("not a query of this feature / not a suffix array of this layout");
+    if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
+    std::vector<RepeatedSubstring> out(static_cast<std::size_t>(total < cap ? total : cap));
+    for (std::size_t i = 0; i < out.size(); ++i) out[i] = { flat[4 * i], flat[4 * i + 1], flat[4 * i + 2], flat[4 * i + 3], pos[i] };
     return out;
 }
 
@@ -172,6 +207,13 @@ public:
     {
         if (n_ + 1 != sa_.size()) throw std::logic_error("assertion failed: s.len() + 1 == sa.len()");
         return suffix_array::repeat_spans(s_, n_, min_len, keep_first, sa_.data());
+    }
+    // EXTENSION (not in the reference): the substrings that occur at least twice, from the text and this array
+    std::vector<RepeatedSubstring> repeated_substrings(std::int32_t min_len = 1, std::int32_t max_len = 0, std::int32_t min_count = 2,
+                                                       std::int32_t order = SA_AMD_SUBSTR_ALL, std::int64_t k = 0) const
+    {
+        if (n_ + 1 != sa_.size()) throw std::logic_error("assertion failed: s.len() + 1 == sa.len()");
+        return suffix_array::repeated_substrings(s_, n_, min_len, max_len, min_count, order, k, sa_.data());
     }
 
 private:

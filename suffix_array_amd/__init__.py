@@ -28,6 +28,8 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "repeat_lengths", "repeat_spans", "last_repeat_stats", "repeats_work_bytes", "repeat_spans_bound",
            "repeat_lengths_device_ptr", "repeat_spans_device_ptr", "RepeatStats", "REPEATS_ALL", "REPEATS_KEEP_FIRST",
            "lpf", "lz77", "lz77_decode", "lz77_literals", "last_lz_stats", "lz_work_bytes", "lpf_device_ptr", "lz77_device_ptr", "LzStats", "LZ_LITERAL",
+           "repeated_substrings", "last_substr_stats", "substrings_work_bytes", "substrings_bound", "substrings_device_ptr", "SubstrQuery", "SubstrStats",
+           "SUBSTR_ALL", "SUBSTR_BY_COUNT", "SUBSTR_BY_LENGTH", "SUBSTR_BY_COVER",
            "MatchStats", "last_match_stats", "match_work_bytes", "match_set_group_cap", "match_set_group_lanes", "match_stats_device_ptr", "match_spans_device_ptr",
            "MATCH_NONE", "MATCH_TILE",
            "DocRepeatStats", "last_doc_repeat_stats", "doc_repeats_work_bytes", "DOCREP_ANY", "DOCREP_OTHER",
@@ -112,6 +114,26 @@ class LzStats(ctypes.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class SubstrQuery(ctypes.Structure):
+    """sa_amd_substr_query of include/suffix_array_amd.h"""
+    _fields_ = [("min_len", ctypes.c_int32), ("max_len", ctypes.c_int32), ("min_count", ctypes.c_int32), ("order", ctypes.c_int32),
+                ("k", ctypes.c_int64)]
+
+
+class SubstrStats(ctypes.Structure):
+    """sa_amd_substr_stats of include/suffix_array_amd.h"""
+    _fields_ = [("nodes", ctypes.c_int64), ("selected", ctypes.c_int64), ("distinct_all", ctypes.c_int64),
+                ("distinct_selected", ctypes.c_int64), ("unresolved", ctypes.c_int64), ("far_steps", ctypes.c_int64),
+                ("far_max", ctypes.c_int64), ("sorted", ctypes.c_int64), ("select_passes", ctypes.c_int32), ("readbacks", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+#: orders of ``repeated_substrings`` (SA_AMD_SUBSTR_* of include/suffix_array_amd.h)
+SUBSTR_ALL, SUBSTR_BY_COUNT, SUBSTR_BY_LENGTH, SUBSTR_BY_COVER = 0, 1, 2, 3
 
 
 class MatchStats(ctypes.Structure):
@@ -331,6 +353,18 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_index_lz77.restype = ctypes.c_int32
         L.sa_amd_last_lz_stats.argtypes = [c_vp]
         L.sa_amd_last_lz_stats.restype = None
+        L.sa_amd_substrings_work_bytes.argtypes = [ctypes.c_int32]
+        L.sa_amd_substrings_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_substrings_bound.argtypes = [ctypes.c_int32]
+        L.sa_amd_substrings_bound.restype = ctypes.c_int64
+        L.sa_amd_substrings_device.argtypes = [c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_substrings_device.restype = ctypes.c_int32
+        L.sa_amd_substrings.argtypes = [c_vp, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_substrings.restype = ctypes.c_int32
+        L.sa_amd_index_substrings.argtypes = [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_substrings.restype = ctypes.c_int32
+        L.sa_amd_last_substr_stats.argtypes = [c_vp]
+        L.sa_amd_last_substr_stats.restype = None
         L.sa_amd_match_work_bytes.argtypes = [ctypes.c_int32]
         L.sa_amd_match_work_bytes.restype = ctypes.c_int64
         L.sa_amd_index_match_stats.argtypes = [c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]
@@ -884,6 +918,67 @@ def lz77_device_ptr(text_ptr: int, sa_ptr: int, n: int, phrases_ptr: int, capaci
     return int(count.value)
 
 
+def _substr_rows(n: int, query: SubstrQuery, positions: bool, call):
+    """the two-call protocol of the substrings routes: ``call(query, rows_ptr, pos_ptr, capacity, total)`` -> return code"""
+    bound = max(n - 1, 0)
+    cap = min(bound, int(query.k)) if query.order != SUBSTR_ALL and query.k >= 1 else min(bound, max(1 << 16, n // 8))
+    while True:
+        rows = np.empty((cap, 4), dtype=np.uint32)
+        pos = np.empty(cap, dtype=np.uint32) if positions else None
+        total = ctypes.c_int64(0)
+        _bwt_rc(call(ctypes.byref(query), rows.ctypes.data if cap else None, pos.ctypes.data if positions and cap else None, cap,
+                     ctypes.byref(total)))
+        if total.value <= cap:
+            r = rows[:int(total.value)].copy()
+            return (r, pos[:int(total.value)].copy()) if positions else r
+        cap = int(total.value)
+
+
+def repeated_substrings(s, min_len: int = 1, max_len: int = 0, min_count: int = 2, order: int = SUBSTR_ALL, k: int = 0,
+                        sa: Optional[np.ndarray] = None, positions: bool = False):
+    """The substrings of ``s`` that occur at least twice, as the internal nodes of its suffix tree, on the GPU: a ``(rows, 4)``
+    uint32 array of ``(lo, count, depth, parent)``.  The node's substring has ``depth`` bytes, occurs exactly ``count`` times,
+    at ``SA[lo : lo + count]``, and so does every prefix of it longer than ``parent``.  A node is selected when
+    ``depth >= min_len``, ``max_len == 0 or parent < max_len`` and ``count >= min_count``; its effective length is ``depth``,
+    cut to ``max_len`` when that is not 0.  ``SUBSTR_ALL`` returns every selected node in suffix-array order; ``SUBSTR_BY_COUNT``,
+    ``SUBSTR_BY_LENGTH`` and ``SUBSTR_BY_COVER`` (count times length) return the best ``k`` by that key, ties in suffix-array
+    order.  ``positions=True`` adds ``pos`` with ``pos[r] = SA[lo_r]``: ``s[pos[r] : pos[r] + depth_r]`` is row ``r``'s
+    substring.  ``sa`` as for ``repeat_lengths``; neither the suffix array nor the LCP array comes back from the device."""
+    t = _as_u8(s)
+    assert t.size <= MAX_LENGTH
+    a = _sa_arg(t, sa)
+    q = SubstrQuery(int(min_len), int(max_len), int(min_count), int(order), int(k))
+    return _substr_rows(t.size, q, positions, lambda qp, rp, pp, cap, tot: lib().sa_amd_substrings(
+        t.ctypes.data, t.size, None if a is None else a.ctypes.data, qp, rp, pp, cap, tot))
+
+
+def last_substr_stats() -> dict:
+    """nodes / selected / distinct_all / distinct_selected / unresolved / far_steps / far_max / sorted / select_passes / readbacks
+    of this thread's most recent ``repeated_substrings`` call; ``last_lcp_stats`` holds the LCP build inside it"""
+    st = SubstrStats()
+    lib().sa_amd_last_substr_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def substrings_work_bytes(n: int) -> int:
+    return int(lib().sa_amd_substrings_work_bytes(n))
+
+
+def substrings_bound(n: int) -> int:
+    """the most rows any ``repeated_substrings`` query of an ``n``-byte text can have: ``max(n - 1, 0)``"""
+    return int(lib().sa_amd_substrings_bound(n))
+
+
+def substrings_device_ptr(text_ptr: int, sa_ptr: int, n: int, query: SubstrQuery, rows_ptr: int, pos_ptr: int, capacity: int,
+                          work_ptr: int, work_bytes: int, stream: int = 0) -> int:
+    """Device-resident rows (raw device pointers; ``rows_ptr``: ``4 * capacity`` uint32, ``pos_ptr``: ``capacity`` uint32 or 0);
+    blocks until done and returns the number of all rows of the query, of which the first ``capacity`` have been written."""
+    total = ctypes.c_int64(0)
+    _bwt_rc(lib().sa_amd_substrings_device(text_ptr, sa_ptr, n, ctypes.byref(query), rows_ptr or None, pos_ptr or None, int(capacity),
+                                           ctypes.byref(total), work_ptr, work_bytes, stream))
+    return int(total.value)
+
+
 def last_match_stats() -> dict:
     """positions / matched / longest / longest_pos / ml_sum / long_positions / compared_bytes / steps / spans / covered_bytes /
     flagged / route_long / readbacks / group_lanes / group_cap / tile of this thread's most recent ``match_stats`` /
@@ -1076,6 +1171,13 @@ class DeviceIndex:
             if count.value <= cap:
                 return out[:int(count.value)].copy()
             cap = int(count.value)
+
+    def repeated_substrings(self, min_len: int = 1, max_len: int = 0, min_count: int = 2, order: int = SUBSTR_ALL, k: int = 0,
+                            positions: bool = False):
+        """EXTENSION (the reference lacks it): the repeated substrings from the resident text and suffix array, all of them or
+        the best ``k`` (see ``repeated_substrings``)"""
+        q = SubstrQuery(int(min_len), int(max_len), int(min_count), int(order), int(k))
+        return _substr_rows(self._s.size, q, positions, lambda qp, rp, pp, cap, tot: lib().sa_amd_index_substrings(self._h, qp, rp, pp, cap, tot))
 
     def match_stats(self, query, max_len: int):
         """-> ``(ml, pos)``, uint32 arrays over the positions of ``query``: ``ml[j]`` is the length, capped at ``max_len``, of the
@@ -1399,6 +1501,12 @@ class SuffixArray:
     def lz77(self) -> np.ndarray:
         """EXTENSION (the reference lacks it): the greedy LZ77 parse of the text, on the GPU (see ``lz77``)"""
         return lz77(self._s, self._sa)
+
+    def repeated_substrings(self, min_len: int = 1, max_len: int = 0, min_count: int = 2, order: int = SUBSTR_ALL, k: int = 0,
+                            positions: bool = False):
+        """EXTENSION (the reference lacks it): the substrings that occur at least twice, all of them or the best ``k``, on the GPU
+        (see ``repeated_substrings``)"""
+        return repeated_substrings(self._s, min_len, max_len, min_count, order, k, self._sa, positions)
 
     def match_stats(self, query, max_len: int):
         """EXTENSION (the reference lacks it): matching statistics of ``query`` against the text (see ``DeviceIndex.match_stats``)"""

@@ -47,18 +47,21 @@ static LzLevels lz_levels(int64_t n, uint32_t *base)
 
 // Stage 1 over A[0 .. n) (n > 0): psl, nsl n entries each, levels n / 31 + 8 words.  Pphi != nullptr: the two partner arrays
 // in text order (every A[i] < n is written through); else the finished neighbour slots stay in psl / nsl.
+// LEQ_LEFT (values below 2^31, the slots stay): the left neighbour is the nearest value <= A[i] (host/substrings.hpp).
+template <bool LEQ_LEFT = false>
 static int lz_nsv(const uint32_t *A, int64_t n, uint32_t *psl, uint32_t *nsl, uint32_t *levels, uint32_t *Pphi, uint32_t *Nphi,
                   unsigned long long *ctl, hipStream_t st)
 {
     const LzLevels lv = lz_levels(n, levels);
     const int64_t tiles = ceil_div(n, LZ_TILE);
-    PROF(KC_LCP_PHI, n, st, hipLaunchKernelGGL(k_lz_tile, dim3((unsigned)tiles), dim3(LZ_THREADS), 0, st, A, n, psl, nsl, levels + lv.off[1],
+    PROF(KC_LCP_PHI, n, st, hipLaunchKernelGGL((k_lz_tile<LEQ_LEFT>), dim3((unsigned)tiles), dim3(LZ_THREADS), 0, st, A, n, psl, nsl, levels + lv.off[1],
                                                levels + lv.off[2], ctl));
     for (int k = 3; k <= lv.top; ++k)
         PROF(KC_LCP_PHI, lv.cnt[k], st, hipLaunchKernelGGL(k_lz_level, dim3((unsigned)ceil_div(lv.cnt[k], LZ_THREADS)), dim3(LZ_THREADS), 0, st,
                                                            (const uint32_t *)(levels + lv.off[k - 1]), lv.cnt[k - 1], levels + lv.off[k], lv.cnt[k]));
     const unsigned g = (unsigned)ceil_div(n, LZ_THREADS);
-    if (Pphi) PROF(KC_LCP_PHI, n, st, hipLaunchKernelGGL((k_lz_far<true>), dim3(g), dim3(LZ_THREADS), 0, st, A, n, psl, nsl, lv, Pphi, Nphi, ctl));
+    if (LEQ_LEFT) PROF(KC_LCP_PHI, n, st, hipLaunchKernelGGL((k_lz_far<false, true>), dim3(g), dim3(LZ_THREADS), 0, st, A, n, psl, nsl, lv, Pphi, Nphi, ctl));
+    else if (Pphi) PROF(KC_LCP_PHI, n, st, hipLaunchKernelGGL((k_lz_far<true>), dim3(g), dim3(LZ_THREADS), 0, st, A, n, psl, nsl, lv, Pphi, Nphi, ctl));
     else PROF(KC_LCP_PHI, n, st, hipLaunchKernelGGL((k_lz_far<false>), dim3(g), dim3(LZ_THREADS), 0, st, A, n, psl, nsl, lv, Pphi, Nphi, ctl));
     return SA_AMD_OK;
 }

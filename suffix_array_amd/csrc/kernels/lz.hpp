@@ -58,6 +58,9 @@ struct LzLevels {
     int top;
 };
 
+// LEQ_LEFT (kernels/substrings.hpp, values below 2^31): the left side asks for the nearest value <= v, as "< v + 1"; the right
+// side and the minima are the same.  false: both sides ask for "< v", the arithmetic of the factorisation.
+template <bool LEQ_LEFT>
 __global__ __launch_bounds__(LZ_THREADS) void k_lz_tile(const uint32_t *__restrict__ A, int64_t n, uint32_t *__restrict__ psl,
                                                          uint32_t *__restrict__ nsl, uint32_t *__restrict__ lvl1, uint32_t *__restrict__ lvl2,
                                                          unsigned long long *__restrict__ ctl)
@@ -93,14 +96,15 @@ __global__ __launch_bounds__(LZ_THREADS) void k_lz_tile(const uint32_t *__restri
         const int idx = k * LZ_THREADS + t;
         if (base + idx >= n) continue;
         const uint32_t v = x[k];
+        const uint32_t vl = LEQ_LEFT ? v + 1u : v;
         const int g = idx >> LZ_FAN_LOG, g0 = g << LZ_FAN_LOG;
         // ---- left ----
         int found = -1;
-        for (int j = idx - 1; j >= g0; --j) if (s_a[j] < v) { found = j; break; }
+        for (int j = idx - 1; j >= g0; --j) if (s_a[j] < vl) { found = j; break; }
         if (found < 0) {
             int h = g - 1;
-            while (h >= 0 && !(s_m[h] < v)) --h;
-            if (h >= 0) { found = (h << LZ_FAN_LOG) + LZ_FAN - 1; while (!(s_a[found] < v)) --found; }
+            while (h >= 0 && !(s_m[h] < vl)) --h;
+            if (h >= 0) { found = (h << LZ_FAN_LOG) + LZ_FAN - 1; while (!(s_a[found] < vl)) --found; }
         }
         const uint32_t pl = found >= 0 ? (uint32_t)(base + found) : LZ_UNRES;
         // ---- right ----
@@ -164,8 +168,9 @@ __device__ __forceinline__ uint32_t lz_far_query(const uint32_t *__restrict__ A,
     return (uint32_t)hit;
 }
 
-// SCATTER: Pphi[A[i]] = A[psv(i)], Nphi[A[i]] = A[nsv(i)] (n: none); else (diagnostic) the finished slot arrays stay in psl / nsl.
-template <bool SCATTER>
+// SCATTER: Pphi[A[i]] = A[psv(i)], Nphi[A[i]] = A[nsv(i)] (n: none); else the finished slot arrays stay in psl / nsl.
+// LEQ_LEFT: as in k_lz_tile.
+template <bool SCATTER, bool LEQ_LEFT = false>
 __global__ __launch_bounds__(LZ_THREADS) void k_lz_far(const uint32_t *__restrict__ A, int64_t n, uint32_t *__restrict__ psl, uint32_t *__restrict__ nsl,
                                                         LzLevels lv, uint32_t *__restrict__ Pphi, uint32_t *__restrict__ Nphi,
                                                         unsigned long long *__restrict__ ctl)
@@ -176,7 +181,7 @@ __global__ __launch_bounds__(LZ_THREADS) void k_lz_far(const uint32_t *__restric
     if (i < n) {
         const uint32_t v = A[i];
         uint32_t pl = psl[i], nr = nsl[i];
-        if (pl == LZ_UNRES) { uint32_t s = 0; pl = lz_far_query<-1>(A, n, lv, i, v, s); total += s; worst = s; }
+        if (pl == LZ_UNRES) { uint32_t s = 0; pl = lz_far_query<-1>(A, n, lv, i, LEQ_LEFT ? v + 1u : v, s); total += s; worst = s; }
         if (nr == LZ_UNRES) { uint32_t s = 0; nr = lz_far_query<1>(A, n, lv, i, v, s); total += s; worst = worst > s ? worst : s; }
         if (SCATTER) {
             if ((int64_t)v < n) {

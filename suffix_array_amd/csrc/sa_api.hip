@@ -28,6 +28,7 @@
 #include "host/docs.hpp"
 #include "host/doc_repeats.hpp"
 #include "host/doc_tf.hpp"
+#include "host/substrings.hpp"
 
 extern "C" {
 
@@ -646,6 +647,51 @@ SA_EXPORT int32_t sa_amd_unbwt_set_splitter_spacing(int32_t spacing)
     while (s * 2 <= spacing && s < sa::UNBWT_SPACING_MAX) s *= 2;
     sa::g_unbwt_spacing = s;
     return prev;
+}
+
+// ---- repeated substrings (host/substrings.hpp, kernels/substrings.hpp) ----
+
+SA_EXPORT int64_t sa_amd_substrings_work_bytes(int32_t n)
+{
+    if (n < 0) return -1;
+    return (int64_t)sa::sub_layout(n).bytes;
+}
+
+SA_EXPORT int64_t sa_amd_substrings_bound(int32_t n)
+{
+    if (n < 0) return -1;
+    return sa::substrings_bound(n);
+}
+
+SA_EXPORT int32_t sa_amd_substrings_device(const uint8_t *dT, const uint32_t *dSA, int32_t n, const sa_amd_substr_query *query, uint32_t *dRows,
+                                           uint32_t *dPos, int64_t capacity, int64_t *total, void *dWork, int64_t work_bytes, void *stream)
+{
+    if (n < 0 || !dSA || !dWork || (n > 0 && !dT)) return SA_AMD_EINVAL;
+    SA_ABI_GUARD_BEGIN
+    return sa::substrings_device(dT, dSA, n, query, dRows, dPos, capacity, total, dWork, work_bytes, (hipStream_t)stream);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_substrings(const uint8_t *T, int32_t n, const uint32_t *SA, const sa_amd_substr_query *query, uint32_t *rows,
+                                    uint32_t *pos, int64_t capacity, int64_t *total)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::substrings_host(T, n, SA, query, rows, pos, capacity, total);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_substrings(const sa_amd_index *ix, const sa_amd_substr_query *query, uint32_t *rows, uint32_t *pos,
+                                          int64_t capacity, int64_t *total)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix) return SA_AMD_EINVAL;
+    return sa::substrings_index(*ix, query, rows, pos, capacity, total);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_substr_stats(sa_amd_substr_stats *out)
+{
+    if (out) *out = sa::g_last_substr_stats;
 }
 
 // ---- packed format (reference src/packed_sa.rs); byte layout: u32 magic "SA4x" LE, u32 length, u64 data length
