@@ -771,6 +771,74 @@ typedef struct sa_amd_substr_stats { /* of the calling thread's most recent subs
 } sa_amd_substr_stats;
 void sa_amd_last_substr_stats(sa_amd_substr_stats *out);
 
+/*
+ * Repeated substrings with their document frequency (an extension): in how many documents of the index's collection every
+ * repeated substring occurs, and the nodes filtered and ranked by that number, on the device.  A string
+ * that occurs 10 000 times inside one log file and a licence header that occurs once in each of 10 000 files have the same
+ * count; their document frequencies are 1 and 10 000.  The collection is doc_off[0 .. ndocs] as sa_amd_index_set_documents took
+ * it; slots, LCP and the nodes (lo, count, depth, parent) are exactly those of "Repeated substrings" above.
+ *   Document frequency: df(node) = the number of distinct doc(SA[i]) over lo <= i < lo + count.  An occurrence belongs to the
+ *     document it starts in, as for sa_amd_index_doc_search.  Nodes have lo >= 1, so slot 0 (the empty suffix, which belongs to
+ *     no document) is never inside one.  1 <= df <= min(count, the non-empty documents); with ndocs = 1 every df is 1.
+ *   A node's substring may cross a document boundary, as a pattern of sa_amd_index_doc_search may: "ab|cd" and "xab|cd" share
+ *     "abcd".  A caller who does not want that separates the documents by a byte that cannot repeat usefully (one separator
+ *     byte still forms nodes of depth 1 around it).  Nodes that respect the boundaries are not offered.
+ *   How it is computed: with P[i] the previous slot of the document of slot i (the index's per-slot word) and m(i) any slot of
+ *     (P[i], i] where LCP has its minimum over (P[i], i], G[m] = the number of i with m(i) = m and E the exclusive running sum
+ *     of G (n + 2 entries): df = count - (E[lo + count] - E[lo + 1]).  Any such m gives the same df.
+ * Query: min_len, max_len, min_count, order and k as in sa_amd_substr_query, with the same ranges; min_docs >= 1, where 1 means
+ *   no document filter.  A node is SELECTED when the filter of "Repeated substrings" holds and df >= min_docs.
+ * Orders: SA_AMD_SUBSTR_ALL, _BY_COUNT, _BY_LENGTH and _BY_COVER as above.  SA_AMD_SUBSTR_BY_DOCS: key = df, descending, equal
+ *   keys by representative slot ascending; k >= 1.  The order is strict, so the answer is unique.  The longest substring common
+ *   to at least m documents is SA_AMD_SUBSTR_BY_LENGTH with min_docs = m and k = 1.
+ * Outputs: rows of 4 uint32 as above; df and pos are parallel arrays of one uint32 a row, and either may be NULL.  capacity and
+ *   *total as for sa_amd_index_substrings: the first min(capacity, *total) rows are written and nothing behind them.
+ *   "abracadabra", doc_off = {0, 4, 4, 7, 11} ("abra", "", "cad", "abra"): the nodes are "a" (count 5, df 3), "abra" (2, 2),
+ *     "bra" (2, 2) and "ra" (2, 2).  "aaaa", doc_off = {0, 2, 4}: "a" (4, 2), "aa" (3, 2), "aaa" (2, 1).
+ *   With min_docs = 1 and the orders 0 .. 3 the rows, pos and *total are bit for bit those of sa_amd_index_substrings for the same
+ *     first five fields; df of a row is the df sa_amd_index_doc_search reports for the pattern T[pos .. pos + depth).
+ * Errors, each SA_AMD_EINVAL with nothing written and answered before a device is looked for: a NULL index, no collection set,
+ * a query outside its ranges or an order outside 0 .. 4, capacity < 0, a NULL total, NULL rows with capacity > 0.  The array's
+ * range errors are those of sa_amd_index_substrings.  With an array that is no suffix array the answers are unspecified, but
+ * nothing is read outside the tables and nothing is written outside the outputs.
+ * sa_amd_last_lcp_stats is filled as by sa_amd_index_substrings; sa_amd_last_substr_stats and every other feature's statistics
+ * are not touched.  The threading rule of sa_amd_index_set_documents applies.
+ * Cost: sa_amd_index_substrings plus one range-minimum query per slot over the minima its first stage has built -- at most
+ * 93 K + 32 loaded words a query, K the number of levels of minima (K = 6, 590 words, for n < 2^31) --, one atomic per slot or
+ * fewer, a scan of n + 2 words and two more loads per node.
+ */
+#define SA_AMD_SUBSTR_BY_DOCS 4
+typedef struct sa_amd_doc_substr_query {
+    int32_t min_len;                 /* >= 1 */
+    int32_t max_len;                 /* 0: no upper limit; otherwise >= min_len */
+    int32_t min_count;               /* >= 2 */
+    int32_t order;                   /* SA_AMD_SUBSTR_*, SA_AMD_SUBSTR_BY_DOCS included */
+    int64_t k;                       /* ranked orders: >= 1; ignored by SA_AMD_SUBSTR_ALL */
+    int64_t min_docs;                /* >= 1; 1: no document filter */
+} sa_amd_doc_substr_query;
+/* bytes of device scratch the call takes from the pool: sa_amd_substrings_work_bytes(n) plus one buffer of n + 2 entries;
+ * -1 when n < 0 */
+int64_t sa_amd_doc_substrings_work_bytes(int32_t n);
+/* host pointers: 16 (+ 4 + 4) bytes per row come back */
+int32_t sa_amd_index_doc_substrings(const sa_amd_index *ix, const sa_amd_doc_substr_query *query, uint32_t *rows, uint32_t *df,
+                                    uint32_t *pos, int64_t capacity, int64_t *total);
+
+typedef struct sa_amd_doc_substr_stats { /* of the calling thread's most recent sa_amd_index_doc_substrings */
+    int64_t nodes;                   /* all nodes, whatever the query */
+    int64_t selected;                /* nodes the filter keeps, df >= min_docs included, whatever k and capacity */
+    int64_t distinct_selected;       /* sum of len - max(parent, min_len - 1) over the selected nodes */
+    int64_t df_sum;                  /* sum of df over the selected nodes */
+    int64_t max_df;                  /* the largest df of a selected node; 0 when none is selected */
+    int64_t pairs;                   /* slots that have a previous slot of their document: n less the non-empty documents */
+    int64_t rmq_far;                 /* pairs whose range (previous slot, slot] does not lie inside one block of 32 slots */
+    int64_t rmq_steps;               /* words of LCP and of its minima the range-minimum queries loaded, all of them together */
+    int64_t rmq_max;                 /* the most one query loaded: at most 93 K + 32, K the number of levels of minima */
+    int64_t sorted;                  /* pairs the final sort of a ranked order ran on: min(k, selected); 0 for SA_AMD_SUBSTR_ALL */
+    int32_t select_passes;           /* digit histograms of the radix select: at most 8; 0 when k >= selected */
+    int32_t readbacks;               /* blocking device -> host read-backs of counters, the LCP build's included */
+} sa_amd_doc_substr_stats;
+void sa_amd_last_doc_substr_stats(sa_amd_doc_substr_stats *out);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

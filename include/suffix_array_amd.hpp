@@ -16,8 +16,9 @@
 //   DocumentIndex                           EXTENSION: a device-resident index over a collection of documents: which document a
 //                                           position lies in, in how many documents a pattern occurs and in which ones,
 //                                           (term_frequencies, top_k) how often in each and the k documents with the most
-//                                           occurrences, and (repeat_spans) the duplicate byte ranges that respect the
-//                                           document boundaries
+//                                           occurrences, (repeat_spans) the duplicate byte ranges that respect the
+//                                           document boundaries, and (repeated_substrings) the repeated substrings with the
+//                                           number of documents each occurs in
 // Rust panics (assert!, engine failure) are std::logic_error / std::runtime_error here.
 #pragma once
 #include "suffix_array_amd.h"
@@ -338,6 +339,32 @@ public:
         check(sa_amd_index_doc_repeat_spans(ix_, min_len, mode, scope, flat.data(), cap, &count, doc_bytes ? doc_bytes->data() : nullptr));
         std::vector<std::pair<std::uint32_t, std::uint32_t>> out(static_cast<std::size_t>(count < cap ? count : cap));
         for (std::size_t i = 0; i < out.size(); ++i) out[i] = { flat[2 * i], flat[2 * i + 1] };
+        return out;
+    }
+    // the repeated substrings with their document frequency (suffix_array_amd.h, "Repeated substrings with their document
+    // frequency"): the rows of suffix_array::repeated_substrings with df, the number of distinct documents an occurrence starts
+    // in.  A node is selected when that function's filter holds and df >= min_docs; order SA_AMD_SUBSTR_BY_DOCS ranks by df.
+    struct DocSubstring {
+        std::uint32_t lo, count, depth, parent;
+        std::uint32_t pos;                                        // sa[lo]: where the substring can be read
+        std::uint32_t df;
+        bool operator==(const DocSubstring &o) const
+        {
+            return lo == o.lo && count == o.count && depth == o.depth && parent == o.parent && pos == o.pos && df == o.df;
+        }
+        bool operator!=(const DocSubstring &o) const { return !(*this == o); }
+    };
+    std::vector<DocSubstring> repeated_substrings(std::int32_t min_len = 1, std::int32_t max_len = 0, std::int32_t min_count = 2,
+                                                  std::int64_t min_docs = 1, std::int32_t order = SA_AMD_SUBSTR_ALL, std::int64_t k = 0) const
+    {
+        const sa_amd_doc_substr_query q = { min_len, max_len, min_count, order, k, min_docs };
+        std::int64_t cap = sa_amd_substrings_bound(static_cast<std::int32_t>(n_));
+        if (order != SA_AMD_SUBSTR_ALL && k >= 1 && k < cap) cap = k;
+        std::vector<std::uint32_t> flat(static_cast<std::size_t>(cap) * 4 + 4), df(static_cast<std::size_t>(cap) + 1), pos(df.size());
+        std::int64_t total = 0;
+        check(sa_amd_index_doc_substrings(ix_, &q, flat.data(), df.data(), pos.data(), cap, &total));
+        std::vector<DocSubstring> out(static_cast<std::size_t>(total < cap ? total : cap));
+        for (std::size_t i = 0; i < out.size(); ++i) out[i] = { flat[4 * i], flat[4 * i + 1], flat[4 * i + 2], flat[4 * i + 3], pos[i], df[i] };
         return out;
     }
 

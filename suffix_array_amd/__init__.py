@@ -30,6 +30,7 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "lpf", "lz77", "lz77_decode", "lz77_literals", "last_lz_stats", "lz_work_bytes", "lpf_device_ptr", "lz77_device_ptr", "LzStats", "LZ_LITERAL",
            "repeated_substrings", "last_substr_stats", "substrings_work_bytes", "substrings_bound", "substrings_device_ptr", "SubstrQuery", "SubstrStats",
            "SUBSTR_ALL", "SUBSTR_BY_COUNT", "SUBSTR_BY_LENGTH", "SUBSTR_BY_COVER",
+           "DocSubstrQuery", "DocSubstrStats", "SUBSTR_BY_DOCS", "last_doc_substr_stats", "doc_substrings_work_bytes",
            "MatchStats", "last_match_stats", "match_work_bytes", "match_set_group_cap", "match_set_group_lanes", "match_stats_device_ptr", "match_spans_device_ptr",
            "MATCH_NONE", "MATCH_TILE",
            "DocRepeatStats", "last_doc_repeat_stats", "doc_repeats_work_bytes", "DOCREP_ANY", "DOCREP_OTHER",
@@ -134,6 +135,25 @@ class SubstrStats(ctypes.Structure):
 
 #: orders of ``repeated_substrings`` (SA_AMD_SUBSTR_* of include/suffix_array_amd.h)
 SUBSTR_ALL, SUBSTR_BY_COUNT, SUBSTR_BY_LENGTH, SUBSTR_BY_COVER = 0, 1, 2, 3
+#: the order ``DeviceIndex.doc_substrings`` adds: by document frequency (SA_AMD_SUBSTR_BY_DOCS)
+SUBSTR_BY_DOCS = 4
+
+
+class DocSubstrQuery(ctypes.Structure):
+    """sa_amd_doc_substr_query of include/suffix_array_amd.h"""
+    _fields_ = [("min_len", ctypes.c_int32), ("max_len", ctypes.c_int32), ("min_count", ctypes.c_int32), ("order", ctypes.c_int32),
+                ("k", ctypes.c_int64), ("min_docs", ctypes.c_int64)]
+
+
+class DocSubstrStats(ctypes.Structure):
+    """sa_amd_doc_substr_stats of include/suffix_array_amd.h"""
+    _fields_ = [("nodes", ctypes.c_int64), ("selected", ctypes.c_int64), ("distinct_selected", ctypes.c_int64),
+                ("df_sum", ctypes.c_int64), ("max_df", ctypes.c_int64), ("pairs", ctypes.c_int64), ("rmq_far", ctypes.c_int64),
+                ("rmq_steps", ctypes.c_int64), ("rmq_max", ctypes.c_int64), ("sorted", ctypes.c_int64),
+                ("select_passes", ctypes.c_int32), ("readbacks", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class MatchStats(ctypes.Structure):
@@ -365,6 +385,12 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_index_substrings.restype = ctypes.c_int32
         L.sa_amd_last_substr_stats.argtypes = [c_vp]
         L.sa_amd_last_substr_stats.restype = None
+        L.sa_amd_doc_substrings_work_bytes.argtypes = [ctypes.c_int32]
+        L.sa_amd_doc_substrings_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_index_doc_substrings.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_doc_substrings.restype = ctypes.c_int32
+        L.sa_amd_last_doc_substr_stats.argtypes = [c_vp]
+        L.sa_amd_last_doc_substr_stats.restype = None
         L.sa_amd_match_work_bytes.argtypes = [ctypes.c_int32]
         L.sa_amd_match_work_bytes.restype = ctypes.c_int64
         L.sa_amd_index_match_stats.argtypes = [c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]
@@ -969,6 +995,18 @@ def substrings_bound(n: int) -> int:
     return int(lib().sa_amd_substrings_bound(n))
 
 
+def last_doc_substr_stats() -> dict:
+    """nodes / selected / distinct_selected / df_sum / max_df / pairs / rmq_far / rmq_steps / rmq_max / sorted / select_passes /
+    readbacks of this thread's most recent ``doc_substrings`` call; ``last_lcp_stats`` holds the LCP build inside it"""
+    st = DocSubstrStats()
+    lib().sa_amd_last_doc_substr_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def doc_substrings_work_bytes(n: int) -> int:
+    return int(lib().sa_amd_doc_substrings_work_bytes(n))
+
+
 def substrings_device_ptr(text_ptr: int, sa_ptr: int, n: int, query: SubstrQuery, rows_ptr: int, pos_ptr: int, capacity: int,
                           work_ptr: int, work_bytes: int, stream: int = 0) -> int:
     """Device-resident rows (raw device pointers; ``rows_ptr``: ``4 * capacity`` uint32, ``pos_ptr``: ``capacity`` uint32 or 0);
@@ -1178,6 +1216,29 @@ class DeviceIndex:
         the best ``k`` (see ``repeated_substrings``)"""
         q = SubstrQuery(int(min_len), int(max_len), int(min_count), int(order), int(k))
         return _substr_rows(self._s.size, q, positions, lambda qp, rp, pp, cap, tot: lib().sa_amd_index_substrings(self._h, qp, rp, pp, cap, tot))
+
+    def doc_substrings(self, min_len: int = 1, max_len: int = 0, min_count: int = 2, min_docs: int = 1, order: int = SUBSTR_ALL, k: int = 0,
+                       positions: bool = False):
+        """EXTENSION: the repeated substrings with their document frequency -> ``(rows, df)`` or ``(rows, df, pos)``.  ``rows``
+        and ``pos`` as ``repeated_substrings`` returns them; ``df[r]`` is the number of distinct documents of the collection
+        (``set_documents``) that an occurrence of row ``r``'s substring starts in.  A node is selected when the filter of
+        ``repeated_substrings`` holds and ``df >= min_docs``; ``SUBSTR_BY_DOCS`` ranks by ``df``, ties in suffix-array order.  A
+        substring may cross a document boundary, as a pattern of ``doc_search`` may."""
+        q = DocSubstrQuery(int(min_len), int(max_len), int(min_count), int(order), int(k), int(min_docs))
+        n = self._s.size
+        bound = max(n - 1, 0)
+        cap = min(bound, int(q.k)) if q.order != SUBSTR_ALL and q.k >= 1 else min(bound, max(1 << 16, n // 8))
+        while True:
+            rows = np.empty((cap, 4), dtype=np.uint32)
+            df = np.empty(cap, dtype=np.uint32)
+            pos = np.empty(cap, dtype=np.uint32) if positions else None
+            total = ctypes.c_int64(0)
+            _bwt_rc(lib().sa_amd_index_doc_substrings(self._h, ctypes.byref(q), rows.ctypes.data if cap else None, df.ctypes.data if cap else None,
+                                                      pos.ctypes.data if positions and cap else None, cap, ctypes.byref(total)))
+            if total.value <= cap:
+                m = int(total.value)
+                return (rows[:m].copy(), df[:m].copy(), pos[:m].copy()) if positions else (rows[:m].copy(), df[:m].copy())
+            cap = int(total.value)
 
     def match_stats(self, query, max_len: int):
         """-> ``(ml, pos)``, uint32 arrays over the positions of ``query``: ``ml[j]`` is the length, capped at ``max_len``, of the
@@ -1507,6 +1568,12 @@ class SuffixArray:
         """EXTENSION (the reference lacks it): the substrings that occur at least twice, all of them or the best ``k``, on the GPU
         (see ``repeated_substrings``)"""
         return repeated_substrings(self._s, min_len, max_len, min_count, order, k, self._sa, positions)
+
+    def doc_substrings(self, min_len: int = 1, max_len: int = 0, min_count: int = 2, min_docs: int = 1, order: int = SUBSTR_ALL, k: int = 0,
+                       positions: bool = False):
+        """EXTENSION (the reference lacks it): the repeated substrings with their document frequency (see
+        ``DeviceIndex.doc_substrings``)"""
+        return self._index().doc_substrings(min_len, max_len, min_count, min_docs, order, k, positions)
 
     def match_stats(self, query, max_len: int):
         """EXTENSION (the reference lacks it): matching statistics of ``query`` against the text (see ``DeviceIndex.match_stats``)"""

@@ -14,6 +14,9 @@
 //                 and granules of the LCP block.
 // Read-backs, all through read_words and counted: the LCP build's; one behind the node pass (ORDER_ALL: the last one); ranked:
 // one per select pass and one at the end (the sort's error word and the cut's totals).
+//
+// substrings_run is the sequence, written once for this file's entry points (Docs = SubNoDocs: the kernels' DF = false, the
+// arithmetic of section 19) and for host/doc_substrings.hpp, whose Docs adds the document table between stage 1 and the node pass.
 #pragma once
 #include "lcp.hpp"
 #include "lz.hpp"
@@ -63,24 +66,27 @@ static int64_t sub_row_cap(int64_t n, const sa_amd_substr_query &q, int64_t capa
     return capacity < cap ? capacity : cap;
 }
 
-// dT, dSA (n + 1 entries, SA[0] = n): device memory on the current device; dWork: sub_layout(n).bytes, 256-byte aligned.  The
-// first `capacity` rows of the query to dRows (4 words a row) and dPos (may be null), the number of all of them to *total_out
-// (host).  Blocks until done.
-static int substrings_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, const sa_amd_substr_query *query, uint32_t *dRows, uint32_t *dPos,
-                             int64_t capacity, int64_t *total_out, void *dWork, int64_t work_bytes, hipStream_t st)
+// the Docs of a run without documents: no table, DF = false in the kernels
+struct SubNoDocs {
+    static constexpr bool on = false;
+    int table(const uint32_t *, int64_t, const LzLevels &, char *, hipStream_t) { return SA_AMD_OK; }
+    SubDf df() const { return SubDf{ nullptr, 0u, nullptr, nullptr }; }
+    void counters(const uint32_t *) {}
+};
+
+// dT, dSA (n + 1 entries, SA[0] = n): device memory on the current device; dWork: the block of layout S (checked by the caller,
+// as is the query Q), 256-byte aligned.  The first `capacity` rows of the query to dRows (4 words a row) and dPos (may be null),
+// the number of all of them to *total_out (host); the counters to ss, which the caller has cleared.  docs: see SubNoDocs; its
+// table is built while the levels of minima stand in A2, its counters are read from the node pass's read-back.  Blocks until done.
+template <class Docs>
+static int substrings_run(const uint8_t *dT, const uint32_t *dSA, int32_t n32, const sa_amd_substr_query &Q, uint32_t *dRows, uint32_t *dPos,
+                          int64_t capacity, int64_t *total_out, void *dWork, const SubLayout &S, hipStream_t st, sa_amd_substr_stats &ss, Docs &docs)
 {
     const int64_t n = n32;
-    sa_amd_substr_stats ss;
-    memset(&ss, 0, sizeof(ss));
-    g_last_substr_stats = ss;
     sa_amd_lcp_stats stats;
     memset(&stats, 0, sizeof(stats));
     g_last_lcp_stats = stats;
-    const SubLayout S = sub_layout(n32);
     const LcpLayout &L = S.lcp;
-    if (work_bytes < (int64_t)S.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
-    if (!sub_args_ok(query, dRows, capacity, total_out)) return SA_AMD_EINVAL;
-    const sa_amd_substr_query Q = *query;
     const bool ranked = Q.order != SA_AMD_SUBSTR_ALL;
     const Tuning tn = route_tuning();
     const int rb0 = g_readbacks;
@@ -92,7 +98,6 @@ static int substrings_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32
     if (n == 0) {
         *total_out = 0;
         ss.readbacks = g_readbacks - rb0;
-        g_last_substr_stats = ss;
         return SA_AMD_OK;
     }
     char *base = (char *)dWork;
@@ -112,6 +117,7 @@ static int substrings_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32
     // ---- stage 1 over LCP[0 .. n]: the nearest "<=" on the left, the nearest "<" on the right ----
     uint32_t *psl = alt, *nsl = alt + ae;
     { const int rcn = lz_nsv<true>(lcpv, N1, psl, nsl, alt + 2 * ae, nullptr, nullptr, ctl, st); if (rcn) return rcn; }
+    { const int rcd = docs.table(lcpv, N1, lz_levels(N1, alt + 2 * ae), base, st); if (rcd) return rcd; }
 
     // ---- node pass: counts per tile, their running sum, rows (ORDER_ALL) or candidates (ranked) in slot order ----
     SubQuery q;
@@ -120,11 +126,13 @@ static int substrings_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32
     unsigned long long *ckeys = (unsigned long long *)(alt + 2 * ae);
     uint32_t *cslots = phi;
     const int64_t tiles = ceil_div(N1, REP_TILE);
-    PROF(KC_REP_SPANS, N1, st, hipLaunchKernelGGL((k_sub_nodes<0>), dim3((unsigned)tiles), dim3(REP_THREADS), 0, st, (const uint32_t *)lcpv,
-                                                  (const uint32_t *)psl, (const uint32_t *)nsl, dSA, n, q, cnt, dRows, dPos, capacity, ckeys, cslots, ctl));
+    PROF(KC_REP_SPANS, N1, st, hipLaunchKernelGGL((k_sub_nodes<0, Docs::on>), dim3((unsigned)tiles), dim3(REP_THREADS), 0, st, (const uint32_t *)lcpv,
+                                                  (const uint32_t *)psl, (const uint32_t *)nsl, dSA, n, q, cnt, dRows, dPos, capacity, ckeys, cslots, ctl,
+                                                  docs.df()));
     PROF(KC_REP_SPANS, tiles, st, hipLaunchKernelGGL(k_rep_sum_spine, dim3(1), dim3(REP_SPINE_THREADS), 0, st, cnt, tiles, &ctl[SUB_C_TOTAL]));
-    PROF(KC_REP_SPANS, N1, st, hipLaunchKernelGGL((k_sub_nodes<1>), dim3((unsigned)tiles), dim3(REP_THREADS), 0, st, (const uint32_t *)lcpv,
-                                                  (const uint32_t *)psl, (const uint32_t *)nsl, dSA, n, q, cnt, dRows, dPos, capacity, ckeys, cslots, ctl));
+    PROF(KC_REP_SPANS, N1, st, hipLaunchKernelGGL((k_sub_nodes<1, Docs::on>), dim3((unsigned)tiles), dim3(REP_THREADS), 0, st, (const uint32_t *)lcpv,
+                                                  (const uint32_t *)psl, (const uint32_t *)nsl, dSA, n, q, cnt, dRows, dPos, capacity, ckeys, cslots, ctl,
+                                                  docs.df()));
     uint32_t head[256 / 4];
     { const int rcw = read_words(head, err, sizeof(head), st); if (rcw) return rcw; }
     unsigned long long cw[SUB_C_WORDS];
@@ -136,6 +144,7 @@ static int substrings_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32
     ss.selected = (int64_t)cw[SUB_C_SELECTED];
     ss.distinct_all = (int64_t)cw[SUB_C_DALL];
     ss.distinct_selected = (int64_t)cw[SUB_C_DSEL];
+    docs.counters(head);
     if ((int64_t)cw[SUB_C_TOTAL] != ss.selected || ss.selected > substrings_bound(n)) return SA_AMD_EINTERNAL;
     const int64_t m = ss.selected;
     const int64_t kept = ranked ? (Q.k < m ? Q.k : m) : m;
@@ -192,9 +201,9 @@ static int substrings_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32
         ss.sorted = kept;
         const int64_t wr = kept < capacity ? kept : capacity;
         if (wr > 0)
-            PROF(KC_REP_SPANS, wr, st, hipLaunchKernelGGL(k_sub_gather, dim3((unsigned)ceil_div(wr, SUB_HIST_THREADS)), dim3(SUB_HIST_THREADS), 0, st,
+            PROF(KC_REP_SPANS, wr, st, hipLaunchKernelGGL((k_sub_gather<Docs::on>), dim3((unsigned)ceil_div(wr, SUB_HIST_THREADS)), dim3(SUB_HIST_THREADS), 0, st,
                                                           (const uint32_t *)res.vals, wr, m, (const uint32_t *)cslots, (const uint32_t *)lcpv,
-                                                          (const uint32_t *)psl, (const uint32_t *)nsl, dSA, n, dRows, dPos));
+                                                          (const uint32_t *)psl, (const uint32_t *)nsl, dSA, n, dRows, dPos, docs.df()));
         { const int rcw = read_words(head, err, sizeof(head), st); if (rcw) return rcw; }
         memcpy(cw, (const char *)head + SUB_CTL_OFF, sizeof(cw));
         if (head[0]) return SA_AMD_EINTERNAL;               // a look-back of the sort gave up (never seen; never a silently wrong order)
@@ -205,8 +214,27 @@ static int substrings_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32
     g_prof.resolve();
     *total_out = kept;
     ss.readbacks = g_readbacks - rb0;
-    g_last_substr_stats = ss;
     return SA_AMD_OK;
+}
+
+// dWork: sub_layout(n).bytes, 256-byte aligned; the rest as substrings_run.  The calling thread's statistics are this call's,
+// all zero when it fails.
+static int substrings_device(const uint8_t *dT, const uint32_t *dSA, int32_t n32, const sa_amd_substr_query *query, uint32_t *dRows, uint32_t *dPos,
+                             int64_t capacity, int64_t *total_out, void *dWork, int64_t work_bytes, hipStream_t st)
+{
+    sa_amd_substr_stats ss;
+    memset(&ss, 0, sizeof(ss));
+    g_last_substr_stats = ss;
+    sa_amd_lcp_stats stats;
+    memset(&stats, 0, sizeof(stats));
+    g_last_lcp_stats = stats;
+    const SubLayout S = sub_layout(n32);
+    if (work_bytes < (int64_t)S.bytes || (((uintptr_t)dWork) & 255u)) return SA_AMD_EINVAL;
+    if (!sub_args_ok(query, dRows, capacity, total_out)) return SA_AMD_EINVAL;
+    SubNoDocs none;
+    const int rc = substrings_run(dT, dSA, n32, *query, dRows, dPos, capacity, total_out, dWork, S, st, ss, none);
+    if (rc == SA_AMD_OK) g_last_substr_stats = ss;
+    return rc;
 }
 
 // Over a resident text and array, the outputs in two slabs of the scope's block: the first min(capacity, total) rows and their

@@ -26,12 +26,16 @@
 //   sort_pairs       on exactly min(k, selected) pairs, key bits [0, width of the largest key): stable, so equal keys stay in
 //                    slot order
 //   k_sub_gather     row and pos of sorted pair r, r < capacity
+// DF = true (kernels/doc_substrings.hpp): the node pass and the gather also read the scanned table E of
+// the document pairs -- df = count - (E[hi] - E[lo + 1]) --, filter by df >= min_docs, rank by df under SUB_ORDER_DOCS and
+// write df beside the rows.  DF = false is the arithmetic of section 19, unchanged.
 #pragma once
 #include "lz.hpp"
 
 namespace sa {
 
 constexpr int SUB_ORDER_ALL = 0, SUB_ORDER_COUNT = 1, SUB_ORDER_LENGTH = 2, SUB_ORDER_COVER = 3;
+constexpr int SUB_ORDER_DOCS = 4;               // DF = true only: key = df
 constexpr int SUB_HIST_THREADS = 256;
 
 // control words (uint64) at byte 128 of the LCP control slab; the first three are stage 1's (LZ_C_UNRES, LZ_C_HSTEPS, LZ_C_HMAX)
@@ -41,6 +45,9 @@ static_assert(LZ_C_HMAX < SUB_C_NODES, "stage 1 counts into the same slab");
 
 struct SubQuery { uint32_t min_len, max_len, min_count; int order; };
 struct SubNode { uint32_t lo, count, depth, parent; };
+// DF = true: E (n + 2 entries), the filter, the df column (may be null) and the DSUB_C_* control words; unused when DF = false
+struct SubDf { const uint32_t *E; uint32_t min_docs; uint32_t *df; unsigned long long *ctl; };
+constexpr int DSUB_C_DFSUM = 0, DSUB_C_MAXDF = 1;       // the node pass's two of the DSUB_C_* words (kernels/doc_substrings.hpp)
 
 // the node of slot i when i is a representative (every index read is checked against the tables first)
 __device__ __forceinline__ bool sub_node(const uint32_t *__restrict__ LCP, const uint32_t *__restrict__ psl, const uint32_t *__restrict__ nsl,
@@ -75,27 +82,40 @@ __device__ __forceinline__ unsigned long long sub_key(const SubNode &nd, uint32_
          : order == SUB_ORDER_LENGTH ? (unsigned long long)len : (unsigned long long)nd.count * len;
 }
 
+// distinct documents among the node's slots: its count less the pairs counted strictly inside it.  sub_node has checked
+// lo + 1 <= hi = lo + count <= n + 1, and E has n + 2 entries.
+__device__ __forceinline__ uint32_t sub_df(const SubNode &nd, const uint32_t *__restrict__ E)
+{
+    return nd.count - (E[nd.lo + nd.count] - E[nd.lo + 1u]);
+}
+
 // WRITE = 0: cnt[tile] = selected nodes of the tile; nodes, selected, the two sums and the largest key to ctl.
 // WRITE = 1: cnt holds the selected nodes in front of every tile (k_rep_sum_spine); ORDER_ALL: the first `capacity` rows (and
 // pos, when not null); ranked: every candidate's key and slot.
-template <int WRITE>
+// DF: selected also needs df >= d.min_docs; the sum and the largest df of the selected nodes to d.ctl; df beside the rows.
+template <int WRITE, bool DF = false>
 __global__ __launch_bounds__(REP_THREADS) void k_sub_nodes(const uint32_t *__restrict__ LCP, const uint32_t *__restrict__ psl,
                                                             const uint32_t *__restrict__ nsl, const uint32_t *__restrict__ SA, int64_t n, SubQuery q,
                                                             uint32_t *__restrict__ cnt, uint32_t *__restrict__ rows, uint32_t *__restrict__ pos,
                                                             int64_t capacity, unsigned long long *__restrict__ ckeys, uint32_t *__restrict__ cslots,
-                                                            unsigned long long *__restrict__ ctl)
+                                                            unsigned long long *__restrict__ ctl, SubDf d)
 {
     __shared__ uint32_t lds[REP_WAVES + 1];
     const int t = threadIdx.x;
     const int64_t j0 = (int64_t)blockIdx.x * REP_TILE + (int64_t)t * REP_ITEMS;
     SubNode nd[REP_ITEMS];
-    uint32_t bits = 0;
-    unsigned long long nodes = 0, dall = 0, dsel = 0, best = 0;
+    uint32_t dfv[DF ? REP_ITEMS : 1];
+    uint32_t bits = 0, dmax = 0;
+    unsigned long long nodes = 0, dall = 0, dsel = 0, best = 0, dfs = 0;
 #pragma unroll
     for (int k = 0; k < REP_ITEMS; ++k) {
         if (!sub_node(LCP, psl, nsl, n, j0 + k, nd[k])) continue;
         uint32_t len;
-        const bool sel = sub_selected(nd[k], q, len);
+        bool sel = sub_selected(nd[k], q, len);
+        if (DF) {
+            dfv[k] = sub_df(nd[k], d.E);
+            sel = sel && dfv[k] >= d.min_docs;
+        }
         if (sel) bits |= 1u << k;
         if (WRITE == 0) {
             ++nodes;
@@ -103,8 +123,9 @@ __global__ __launch_bounds__(REP_THREADS) void k_sub_nodes(const uint32_t *__res
             if (sel) {
                 const uint32_t floor = nd[k].parent > q.min_len - 1u ? nd[k].parent : q.min_len - 1u;
                 dsel += len - floor;
-                const unsigned long long key = sub_key(nd[k], len, q.order);
+                const unsigned long long key = DF && q.order == SUB_ORDER_DOCS ? (unsigned long long)dfv[DF ? k : 0] : sub_key(nd[k], len, q.order);
                 best = best > key ? best : key;
+                if (DF) { dfs += dfv[k]; dmax = dmax > dfv[k] ? dmax : dfv[k]; }
             }
         }
     }
@@ -119,6 +140,12 @@ __global__ __launch_bounds__(REP_THREADS) void k_sub_nodes(const uint32_t *__res
         lcp_block_add((unsigned long long)__popc(bits), &ctl[SUB_C_SELECTED]);
         lcp_block_add(dall, &ctl[SUB_C_DALL]);
         lcp_block_add(dsel, &ctl[SUB_C_DSEL]);
+        if (DF) {
+#pragma unroll
+            for (int o = WAVE / 2; o > 0; o >>= 1) { const uint32_t m2 = __shfl_xor(dmax, o, WAVE); dmax = dmax > m2 ? dmax : m2; }
+            if (lane_id() == 0 && dmax) atomicMax(&d.ctl[DSUB_C_MAXDF], (unsigned long long)dmax);
+            lcp_block_add(dfs, &d.ctl[DSUB_C_DFSUM]);
+        }
     } else {
         int64_t c = (int64_t)cnt[blockIdx.x] + ex;
 #pragma unroll
@@ -127,7 +154,7 @@ __global__ __launch_bounds__(REP_THREADS) void k_sub_nodes(const uint32_t *__res
             if (q.order != SUB_ORDER_ALL) {
                 uint32_t len;
                 (void)sub_selected(nd[k], q, len);
-                ckeys[c] = sub_key(nd[k], len, q.order);
+                ckeys[c] = DF && q.order == SUB_ORDER_DOCS ? (unsigned long long)dfv[DF ? k : 0] : sub_key(nd[k], len, q.order);
                 cslots[c] = (uint32_t)(j0 + k);
             } else if (c < capacity) {
                 rows[4 * c] = nd[k].lo;
@@ -135,6 +162,7 @@ __global__ __launch_bounds__(REP_THREADS) void k_sub_nodes(const uint32_t *__res
                 rows[4 * c + 2] = nd[k].depth;
                 rows[4 * c + 3] = nd[k].parent;
                 if (pos) pos[c] = SA[nd[k].lo];
+                if (DF && d.df) d.df[c] = dfv[DF ? k : 0];
             }
             ++c;
         }
@@ -201,12 +229,14 @@ __global__ __launch_bounds__(REP_THREADS) void k_sub_cut(const unsigned long lon
     }
 }
 
-// rows[4 r ..] and pos[r] (when not null) of the sorted pair r, r < count: its value is a candidate index, cslots holds the slot
+// rows[4 r ..] and pos[r] (when not null) of the sorted pair r, r < count: its value is a candidate index, cslots holds the slot.
+// DF: and d.df[r] (when not null).
+template <bool DF = false>
 __global__ __launch_bounds__(SUB_HIST_THREADS) void k_sub_gather(const uint32_t *__restrict__ svals, int64_t count, int64_t m,
                                                                  const uint32_t *__restrict__ cslots, const uint32_t *__restrict__ LCP,
                                                                  const uint32_t *__restrict__ psl, const uint32_t *__restrict__ nsl,
                                                                  const uint32_t *__restrict__ SA, int64_t n, uint32_t *__restrict__ rows,
-                                                                 uint32_t *__restrict__ pos)
+                                                                 uint32_t *__restrict__ pos, SubDf d)
 {
     const int64_t r = (int64_t)blockIdx.x * SUB_HIST_THREADS + threadIdx.x;
     if (r >= count) return;
@@ -218,6 +248,7 @@ __global__ __launch_bounds__(SUB_HIST_THREADS) void k_sub_gather(const uint32_t 
     rows[4 * r + 2] = nd.depth;
     rows[4 * r + 3] = nd.parent;
     if (pos) pos[r] = ok ? SA[nd.lo] : 0u;
+    if (DF && d.df) d.df[r] = ok ? sub_df(nd, d.E) : 0u;
 }
 
 }  // namespace sa

@@ -29,6 +29,7 @@
 #include "host/doc_repeats.hpp"
 #include "host/doc_tf.hpp"
 #include "host/substrings.hpp"
+#include "host/doc_substrings.hpp"
 
 extern "C" {
 
@@ -692,6 +693,28 @@ SA_EXPORT int32_t sa_amd_index_substrings(const sa_amd_index *ix, const sa_amd_s
 SA_EXPORT void sa_amd_last_substr_stats(sa_amd_substr_stats *out)
 {
     if (out) *out = sa::g_last_substr_stats;
+}
+
+// ---- repeated substrings with their document frequency (host/doc_substrings.hpp, kernels/doc_substrings.hpp) ----
+
+SA_EXPORT int64_t sa_amd_doc_substrings_work_bytes(int32_t n)
+{
+    if (n < 0) return -1;
+    return (int64_t)sa::dsub_layout(n).bytes;
+}
+
+SA_EXPORT int32_t sa_amd_index_doc_substrings(const sa_amd_index *ix, const sa_amd_doc_substr_query *query, uint32_t *rows, uint32_t *df,
+                                              uint32_t *pos, int64_t capacity, int64_t *total)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix) return SA_AMD_EINVAL;
+    return sa::doc_substrings_index(*ix, query, rows, df, pos, capacity, total);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_doc_substr_stats(sa_amd_doc_substr_stats *out)
+{
+    if (out) *out = sa::g_last_doc_substr_stats;
 }
 
 // ---- packed format (reference src/packed_sa.rs); byte layout: u32 magic "SA4x" LE, u32 length, u64 data length

@@ -26,6 +26,9 @@ int32_t sa_amd_debug_head_flags(int32_t mode);
 /* the second bound of the term-frequency kernel (process-wide; returns the previous mode): 0 galloping from the first bound (what
  * the product library always does), 1 a plain binary search of the document's part.  Both give the same answers. */
 int32_t sa_amd_debug_doc_tf_bounds(int32_t mode);
+/* the pair pass of sa_amd_index_doc_substrings (process-wide; returns the previous mode): 0 equal targets inside a wave are
+ * combined into one atomic (what the product library always does), 1 one atomic per pair.  Both give the same table. */
+int32_t sa_amd_debug_dsub_plain_atomics(int32_t mode);
 int32_t sa_amd_debug_sort_variant_count(void);
 const char *sa_amd_debug_sort_variant_name(int32_t index);
 /* stable LSD radix sort of (u64 key, u32 value) pairs on bits [begin_bit, end_bit); host buffers */

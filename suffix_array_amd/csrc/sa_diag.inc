@@ -29,6 +29,11 @@ SA_EXPORT int32_t sa_amd_debug_doc_tf_bounds(int32_t mode)
     return sa::g_doc_tf_plain_bounds.exchange(mode ? 1 : 0);
 }
 
+SA_EXPORT int32_t sa_amd_debug_dsub_plain_atomics(int32_t mode)
+{
+    return sa::g_dsub_plain_atomics.exchange(mode ? 1 : 0);
+}
+
 SA_EXPORT int32_t sa_amd_debug_head_flags(int32_t mode)
 {
     return sa::g_head_flags_mode.exchange(mode < 0 ? 0 : (mode > 2 ? 2 : mode));
