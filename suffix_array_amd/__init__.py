@@ -465,6 +465,8 @@ def diag_lib() -> ctypes.CDLL:
         L.sa_amd_test_sort_pairs_flags.restype = ctypes.c_int32
         L.sa_amd_debug_head_flags.argtypes = [ctypes.c_int32]
         L.sa_amd_debug_head_flags.restype = ctypes.c_int32
+        L.sa_amd_debug_round_flags.argtypes = [ctypes.c_int32]
+        L.sa_amd_debug_round_flags.restype = ctypes.c_int32
         L.sa_amd_last_stats.argtypes = [c_vp]
         L.sa_amd_test_sample_sort64.argtypes = [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, c_vp]
         L.sa_amd_test_sample_sort64.restype = ctypes.c_int32

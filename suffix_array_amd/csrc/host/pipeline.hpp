@@ -202,7 +202,11 @@ static int scatter_binned(const SortScratch &ss, uint32_t *isa, uint32_t *pk, ui
     return SA_AMD_OK;
 }
 
-struct Refined { const uint64_t *keys; const uint32_t *vals; uint32_t *vnext; int64_t m_global; };   // m_global: members ordered by the global sort
+struct Refined {
+    const uint64_t *keys; const uint32_t *vals; uint32_t *vnext;
+    int64_t m_global;                      // members ordered by the global sort
+    const uint8_t *status = nullptr;       // != nullptr: the round's status bytes (RS_*, kernels/common.hpp) -- the re-rank reads the group starts from them, `keys` holds true keys at RS_KEYED places only
+};
 
 // Read-backs of a refinement round (DeviceBuild::finish_round).  A round used to block twice: once in the middle for the number
 // of members the local pass could not order (they go through the global sort before the re-rank) and once at its end for the
@@ -248,6 +252,7 @@ struct RrApply {
     uint64_t *pair_k = nullptr;
     const uint32_t *tile_next = nullptr, *gate = nullptr;
     int g_shift = 0, key_shift = 0, parent_tail = 0, sa_final = 0;
+    const uint8_t *status = nullptr;                         // a round behind a local pass that wrote status bytes (Refined::status)
 };
 
 // Gram keys: how many of the sigma^g possible g-grams occur?  A word-structured text uses a small part of them, so a key of
@@ -443,13 +448,14 @@ struct DeviceBuild {
     // ---- the re-rank step: k_rr_count, k_rr_scan (a round: k_rr_scan_round, finish_round), k_rr_apply (kernels/rerank.hpp) ----
     // One launcher each, over the RR_TILE-element tiles of m elements; tile_cnt / tile_head / total == nullptr: the workspace's.
     // FLAGS: the groups come from head_flags, not from the keys (the first re-rank behind a flags pass of the initial sort)
+    // (a round: its status bytes, `status`)
     template <bool FIRST, typename KeyT = uint64_t, bool PARENTS = false, bool FLAGS = false>
     int rr_count(const KeyT *keys, const uint32_t *U, int64_t m, uint32_t *tile_first = nullptr, int g_shift = 0, const uint32_t *gate = nullptr,
-                 uint32_t *tile_cnt = nullptr, uint32_t *tile_head = nullptr)
+                 uint32_t *tile_cnt = nullptr, uint32_t *tile_head = nullptr, const uint8_t *status = nullptr)
     {
         PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_rr_count<FIRST, KeyT, PARENTS, FLAGS>), dim3((unsigned)ceil_div(m, RR_TILE)), dim3(RR_THREADS), 0, st, keys, U, m,
                                                     tile_cnt ? tile_cnt : w.tcnt, tile_head ? tile_head : w.thead, 0, tile_first, g_shift, gate,
-                                                    FLAGS ? (const uint8_t *)head_flags : (const uint8_t *)nullptr));
+                                                    FLAGS ? (status ? status : (const uint8_t *)head_flags) : (const uint8_t *)nullptr));
         return SA_AMD_OK;
     }
     int rr_scan(int64_t m, uint32_t *tile_cnt = nullptr, uint32_t *tile_head = nullptr, uint32_t *total = nullptr)
@@ -466,7 +472,7 @@ struct DeviceBuild {
                                                       a.tile_head ? a.tile_head : (const uint32_t *)w.thead, a.SA, a.ISA, a.Uo, a.Go, a.Vo, a.n_text, a.has_isa, a.g_shift,
                                                       a.pair_k, a.pair_v, a.tile_total ? a.tile_total : (const uint32_t *)w.total, a.key_shift, a.tile_next,
                                                       a.parent_tail, a.changed_cnt, a.gate, a.sa_final,
-                                                      FLAGS ? (const uint8_t *)head_flags : (const uint8_t *)nullptr));
+                                                      FLAGS ? (a.status ? a.status : (const uint8_t *)head_flags) : (const uint8_t *)nullptr));
         return SA_AMD_OK;
     }
     // the rank set-up of the dense route (ISA_MODE 0: direct ISA stores, 2: ranks for the binned scatter): tail or head ranks,
@@ -598,6 +604,19 @@ struct DeviceBuild {
         return SA_AMD_OK;
     }
 
+    // Where a dense doubling round keeps its status bytes (RS_*, kernels/common.hpp; nullptr: the round takes the key route).
+    // They cannot share L.Gn with the key form's flags: k_rr_apply writes the next list's group heads there while it reads them.
+    // On the route that starts rank doubling straight from the initial order the rounds' key buffers are w.keysA / w.keysB and
+    // w.keysC is dead -- the initial sort's group-start flags in it are consumed by the rank set-up, the early download takes it
+    // only when the rounds are over (early_finish).  Behind text rounds w.keysC is a key buffer of the rounds (keys_beside),
+    // and on the reduced-memory route it may be pinned host memory (flags_slab_ok): keys then.  One byte per member, m <= n.
+    uint8_t *round_status_slab(const KeySrc &K) const
+    {
+        if (tn.round_flags == 0 || (K.mode != KS_RANK && K.mode != KS_CHASE)) return nullptr;
+        if (!flags_slab_ok || L.rkA == w.keysC || L.rkB == w.keysC) return nullptr;
+        return (uint8_t *)w.keysC;
+    }
+
     // One refinement round of the tied list with a secondary key taken from the text (KeySrc): afterwards every
     // group is ordered by (group head << kb) | key2.  Small groups: gather fused with the in-LDS group sort
     // (k_group_sort); groups no tile owns, or everything when *use_local is off: plain gather + global radix sort.
@@ -630,7 +649,7 @@ struct DeviceBuild {
         uint32_t groups = 0;
         if (!*use_local && retry_local && !tn.no_local_sort && m < tn.dense_rekey_min) *use_local = true;     // (small lists do not count their groups)
         if (!*use_local && retry_local && !tn.no_local_sort && m >= tn.dense_rekey_min) {
-            PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_flag_count), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
+            PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_flag_count<false>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
                                                         (const uint8_t *)nullptr, L.U, L.G, m, w.tcnt, w.ft_cnt));
             PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.ft_cnt, w.thead, tiles, w.total + 8));
             { const int rcw = read_words(&groups, w.total + 8, 4, st); if (rcw) return rcw; }
@@ -638,8 +657,10 @@ struct DeviceBuild {
             if ((int64_t)groups * 2 * tn.group_cap >= m) *use_local = true;
         }
         const bool had_local_pass = *use_local;            // (then the keys are in L.rkA already when the whole list goes through the global sort after all)
+        uint8_t *const status = round_status_slab(K);      // != nullptr: the local pass writes status bytes there and no keys for the members it orders
+        out->status = nullptr;
         if (*use_local) {
-            uint8_t *flags = (uint8_t *)L.Gn;
+            uint8_t *flags = status ? status : (uint8_t *)L.Gn;
             const unsigned gs_blocks = (unsigned)ceil_div(m, GS_TILE);
             const int cap = tn.group_cap;                    // largest group ordered in LDS (C3: 1024 beats 512 by 1%)
             // groups of up to GB_CAP (8 192) members whose keys fit 32 bits: one workgroup each, in LDS (k_group_sort_big), on the list of
@@ -650,14 +671,19 @@ struct DeviceBuild {
             if (!(ctl && ctl->counters_clear))
                 HIP_TRY(hipMemsetAsync(w.total + RC_BIG_LISTED, 0, 8, st));           // [12] listed first members, [13] members ordered by k_group_sort_big
             if (K.mode == KS_SPARSE && (rc = gather_sparse())) return rc;      // (then the sort on those keys: KS_PRE)
-#define GS_LAUNCH(M) PROF(KC_LOCAL, m, st, hipLaunchKernelGGL((k_group_sort<M>), dim3(gs_blocks), dim3(GS_THREADS), 0, st, (const uint32_t *)L.V, L.G, L.U, dT, Pk, m, n, K, \
+            if (status && tn.round_flags == 2) {
+                // (diag library: what the round does not write must not be read -- a poisoned entry that is read changes the result)
+                HIP_TRY(hipMemsetAsync(L.rkA, 0xEE, (size_t)m * 8, st));
+                HIP_TRY(hipMemsetAsync(status, 0xFF, (((size_t)m + 7) & ~(size_t)7) + 8, st));
+            }
+#define GS_LAUNCH(M, S) PROF(KC_LOCAL, m, st, hipLaunchKernelGGL((k_group_sort<M, S>), dim3(gs_blocks), dim3(GS_THREADS), 0, st, (const uint32_t *)L.V, L.G, L.U, dT, Pk, m, n, K, \
                                                             L.rkA, L.V, flags, cap, bheads, bcount))
             switch (K.mode) {
-            case KS_TEXT: GS_LAUNCH(KS_TEXT); break;
-            case KS_LOWKEY: GS_LAUNCH(KS_LOWKEY); break;
-            case KS_RANK: GS_LAUNCH(KS_RANK); break;
-            case KS_CHASE: GS_LAUNCH(KS_CHASE); break;
-            default: GS_LAUNCH(KS_PRE); break;      // (KS_SPARSE: the keys have just been gathered)
+            case KS_TEXT: GS_LAUNCH(KS_TEXT, false); break;
+            case KS_LOWKEY: GS_LAUNCH(KS_LOWKEY, false); break;
+            case KS_RANK: if (status) GS_LAUNCH(KS_RANK, true); else GS_LAUNCH(KS_RANK, false); break;
+            case KS_CHASE: if (status) GS_LAUNCH(KS_CHASE, true); else GS_LAUNCH(KS_CHASE, false); break;
+            default: GS_LAUNCH(KS_PRE, false); break;      // (KS_SPARSE: the keys have just been gathered)
             }
 #undef GS_LAUNCH
             if (gs_blocks > 1)
@@ -670,7 +696,7 @@ struct DeviceBuild {
                 PROF(KC_LOCAL, 0, st, hipLaunchKernelGGL((k_group_sort_big<512>), dim3((unsigned)(4 * cu_count())), dim3(512), 0, st, L.rkA, L.V, L.G, m, kb,
                                                          lo > GB_CAP_SMALL ? lo : GB_CAP_SMALL, (const uint32_t *)bheads, (const uint32_t *)bcount, flags, w.total + 13));
             }
-            PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_flag_count), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
+            PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((status ? k_flag_count<true> : k_flag_count<false>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
                                                         (const uint8_t *)flags, L.U, L.G, m, w.tcnt, w.ft_cnt));
             // (flagged members -> w.total[RC_FLAGGED], flagged groups -> w.total[RC_GROUPS]; one launch)
             PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan_pair), dim3(2), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, w.total + RC_FLAGGED,
@@ -679,7 +705,7 @@ struct DeviceBuild {
             if (ctl && ctl->defer && !resume) {
                 // the counts stay on the device: the caller launches the re-rank kernels gated on w.total[RC_FLAGGED] and reads everything at once
                 ctl->deferred = true;
-                out->keys = L.rkA; out->vals = L.V; out->vnext = Valt; out->m_global = 0;
+                out->keys = L.rkA; out->vals = L.V; out->vnext = Valt; out->m_global = 0; out->status = status;
                 return SA_AMD_OK;
             }
             uint32_t tot9[RC_WORDS] = { 0 };                      // [RC_FLAGGED] flagged members, [RC_GROUPS] flagged groups, [RC_BIG_ORDERED] members k_group_sort_big ordered
@@ -697,7 +723,7 @@ struct DeviceBuild {
                     // groups no tile owns: global sort of (index of the group among them, key2), then back to their list positions
                     // (a text that is one long run has ONE such group: no index bits at all, four passes instead of eight)
                     const int idx_bits = bit_length((uint64_t)(tot9[RC_GROUPS] > 0 ? tot9[RC_GROUPS] - 1 : 0));
-                    PROF(KC_RR_APPLY, m, st, hipLaunchKernelGGL((k_flag_gather), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
+                    PROF(KC_RR_APPLY, m, st, hipLaunchKernelGGL((status ? k_flag_gather<true> : k_flag_gather<false>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
                                                                 (const uint8_t *)flags, (const uint64_t *)L.rkA, (const uint32_t *)L.V, L.U, L.G, m,
                                                                 (const uint32_t *)w.tcnt, (const uint32_t *)w.ft_cnt, kb, L.rkB, Valt, L.Un));
                     SortJob<uint64_t> big{ L.rkB, Valt, L.rkB + half, Valt + half, m_big, 0, kb + idx_bits };
@@ -709,11 +735,24 @@ struct DeviceBuild {
                                                                    (const uint32_t *)L.Un, L.G, kb, m_big, L.rkA, L.V));
                 }
                 out->keys = L.rkA; out->vals = L.V; out->vnext = Valt; out->m_global = m_big + m_big_local;      // (neither kind has been chased)
+                out->status = status;
                 local.locally_sorted += m - m_big;
                 if (m_big * 2 > m) *use_local = false;           // mostly large groups: not worth another local pass
                 return SA_AMD_OK;
             }
             if (m_big * 10 >= m * 9) *use_local = false;     // (nearly) the whole list sits in groups no tile can own (runs, periodic texts): the next rounds skip the local pass
+            if (status) {
+                // The global sort below wants a key for EVERY member and the places the local pass owned have none: the pass runs again
+                // in its key form for those places alone (k_group_sort REFILL), on the order it left.  It changes nothing in that
+                // order and writes the keys it would have written the first time -- after a chase the places of the final
+                // subgroups, so no subgroups merge and the round's tied count is what the key route's is.  The keys of every
+                // other place are where the first launch, k_group_sort_straddle and k_group_sort_big left them.  A tile without an
+                // owned place -- all of them on a run or a periodic text, which is what comes here -- returns behind 2 KiB of bytes.
+#define GS_REFILL(M) PROF(KC_LOCAL, m, st, hipLaunchKernelGGL((k_group_sort<M, false, true>), dim3(gs_blocks), dim3(GS_THREADS), 0, st, (const uint32_t *)L.V, L.G, L.U, dT, Pk, m, n, K, \
+                                                            L.rkA, L.V, status, cap, (uint32_t *)nullptr, (uint32_t *)nullptr))
+                if (K.mode == KS_CHASE) GS_REFILL(KS_CHASE); else GS_REFILL(KS_RANK);
+#undef GS_REFILL
+            }
         }
         // the whole list through the global sort.  Large lists are keyed by (index of the group in the list, key2) instead of
         // (28-bit slot of the group head, key2) when that saves radix passes: count the group heads first, then gather the keys in
@@ -723,7 +762,7 @@ struct DeviceBuild {
         bool rekeyed = false;
         if (m >= tn.dense_rekey_min) {
             if (!counted || had_local_pass) {              // (the local pass has used the count arrays for its own compaction)
-                PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_flag_count), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
+                PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_flag_count<false>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
                                                             (const uint8_t *)nullptr, L.U, L.G, m, w.tcnt, w.ft_cnt));
                 PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.ft_cnt, w.thead, tiles, w.total + 8));
                 { const int rcw = read_words(&groups, w.total + 8, 4, st); if (rcw) return rcw; }
@@ -794,13 +833,25 @@ struct DeviceBuild {
             const uint32_t *gate = ctl.deferred ? (const uint32_t *)(w.total + RC_FLAGGED) : (const uint32_t *)nullptr;
             // dense rounds: a group's rank is its last slot + 1 and a parent's last subgroup keeps it (k_rr_apply, TAIL); the tiles
             // then also need the first group start BEHIND them (k_rr_scan_next, second block of k_rr_scan_round)
-            if ((rc = rr_count<false, uint64_t, PARENTS>(rf.keys, L.U, L.m, PARENTS ? w.tnext : (uint32_t *)nullptr, PARENTS ? key2_bits : 0, gate))) return rc;
+            // (rf.status: the local pass wrote status bytes, the group starts are read from them -- dense rounds only)
+            bool by_status = false;
+            if constexpr (PARENTS) by_status = rf.status != nullptr;
+            if constexpr (PARENTS) {
+                if (by_status) rc = rr_count<false, uint64_t, true, true>(rf.keys, L.U, L.m, w.tnext, key2_bits, gate, nullptr, nullptr, rf.status);
+            }
+            if (!by_status) rc = rr_count<false, uint64_t, PARENTS>(rf.keys, L.U, L.m, PARENTS ? w.tnext : (uint32_t *)nullptr, PARENTS ? key2_bits : 0, gate);
+            if (rc) return rc;
             // (second block: the tiles' next group starts and the changed-rank counters of a dense round, the big-group counters saved and zeroed)
             PROF(KC_RR_SCAN, tiles_m, st, hipLaunchKernelGGL((k_rr_scan_round), dim3(2), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles_m, w.total,
                                                              PARENTS ? w.tnext : (uint32_t *)nullptr, PARENTS ? w.chg : (uint32_t *)nullptr, w.total + RC_BIG_LISTED, gate));
             RrApply a = round_args(rf, extra);
             a.gate = gate;
-            if ((rc = rr_apply<false, true, ISA_MODE>(rf.keys, a))) return rc;
+            a.status = rf.status;
+            if constexpr (PARENTS) {
+                if (by_status) rc = rr_apply<false, true, ISA_MODE, uint64_t, false, true>(rf.keys, a);
+            }
+            if (!by_status) rc = rr_apply<false, true, ISA_MODE>(rf.keys, a);
+            if (rc) return rc;
             // the one read-back of the round: w.total and, where asked for, the changed-rank counters behind it (w.chg)
             { const int rcw = read_words(words, w.total, words_bytes, st); if (rcw) return rcw; }
             if constexpr (ISA_MODE == 2) {
@@ -1509,6 +1560,7 @@ struct DeviceBuild {
                 }
             }
             if (trace) fprintf(stderr, "suffix_array_amd: doubling round %d h %lld (%s, %d look-ups, %lld through the global sort): tied %lld -> %u, %lld ranks written\n", local.rounds + 1, (long long)h, sparse ? "sparse" : "dense", K.iters, (long long)rf.m_global, (long long)L.m, m32, sparse ? -1ll : (long long)changed_prev), fprintf(stderr, "    (%.2f ms)\n", lap());
+            if (trace && !sparse) fprintf(stderr, "    (group starts read from %s)\n", rf.status ? "status bytes" : "keys");
             L.m = m32;
             L.advance(rf);
             // every group that is still tied went through K.iters look-ups -- unless some went through the global sort (one look-up)

@@ -49,6 +49,8 @@ inline int env_small_max() { return (int)env_int("SA_AMD_SMALL_MAX", 8192, 0, 81
 inline std::atomic<int> g_rerank_routes{0};
 // when the last pass of the 64-bit initial sort writes group-start flags (Tuning::head_flags), set by sa_amd_debug_head_flags
 inline std::atomic<int> g_head_flags_mode{1};
+// whether the dense doubling rounds hand status bytes instead of keys to their re-rank (Tuning::round_flags), set by sa_amd_debug_round_flags
+inline std::atomic<int> g_round_flags_mode{1};
 #endif
 
 struct Tuning {
@@ -74,6 +76,10 @@ struct Tuning {
     int head_flags = 1;              // the last pass of the 64-bit initial sort writes group-start flags instead of the sorted keys: 0 never, 1 when the dense
                                      //   route is expected (its first re-rank is then the keys' only reader), 2 always (the keys are rebuilt where needed).
                                      //   The product library has no switch (always 1); diag library: sa_amd_debug_head_flags, for A/B and the route tests
+    int round_flags = 1;             // a dense doubling round's local pass writes one status byte per member and no keys for the members it orders, where a
+                                     //   dead device slab exists for the bytes (DeviceBuild::round_status_slab): 0 never (keys), 1 by that rule, 2 the rule with
+                                     //   the round's key buffer and status slab filled with a poison pattern first.  The product library has no switch
+                                     //   (always 1); diag library: sa_amd_debug_round_flags, for A/B and the route tests
     bool no_first_tail = false;      // SA_AMD_NO_FIRST_TAIL: the dense route's first ranks are head ranks (the first doubling round then rewrites every rank)
     // the re-rank writes of round 4 (diag library only, sa_amd_debug_rerank_routes: A/B and route tests; the product library has no switch)
     bool sa_every_round = false;     // bit 0: the dense rounds write SA for every listed element each round, not only when it leaves the list
@@ -210,6 +216,8 @@ struct Tuning {
             t.setup_key_copy = (r & 2) != 0;
             const int hf = g_head_flags_mode.load(std::memory_order_relaxed);
             t.head_flags = hf < 0 ? 0 : (hf > 2 ? 2 : hf);
+            const int rf = g_round_flags_mode.load(std::memory_order_relaxed);
+            t.round_flags = rf < 0 ? 0 : (rf > 2 ? 2 : rf);
         }
 #endif
         return t;

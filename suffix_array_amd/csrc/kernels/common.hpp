@@ -51,6 +51,16 @@ constexpr uint8_t OS_HF_START = 1;  // p starts a group (always so at p = 0)
 constexpr uint8_t OS_HF_SEAM = 2;   // p is the first element of a tile's digit run: the pass could not see p - 1, but it stored the true
                                     // keys of p and p - 1 in its key buffer -- p starts a group iff they differ
 
+// Status byte of a member of the tied list in a dense doubling round: written by the round's local pass (k_group_sort with STATUS,
+// kernels/refine.hpp) per list PLACE, read by the round's re-rank (rr_wave_classify_status, kernels/rerank.hpp) in place of the
+// 8-byte keys.  A group starts at place i iff  PHEAD(i) || (KEYED(i) ? keys[i] != keys[i - 1] : HEAD(i)).  A KEYED place that is no
+// parent head has a KEYED place of the same parent group before it (ownership is per parent group), so both keys are true keys;
+// no other entry of the key buffer is read, and the owned places have none.
+constexpr uint8_t RS_PENDING = 1;   // member of a group no tile owned that is not ordered yet (k_flag_count / k_flag_gather; cleared by the kernels that order it)
+constexpr uint8_t RS_KEYED = 2;     // the place was not owned by a tile of k_group_sort: keys[i] is its true key
+constexpr uint8_t RS_HEAD = 4;      // owned places only: a group starts here in this round's order
+constexpr uint8_t RS_PHEAD = 8;     // first place of its parent group (every place, owned or not)
+
 // Exclusive block sum over THREADS threads; *total receives the block sum. lds: THREADS/64 + 1 words.
 template <int THREADS>
 __device__ __forceinline__ uint32_t block_excl_sum(uint32_t v, uint32_t *lds, uint32_t *total)

@@ -157,7 +157,7 @@ __global__ __launch_bounds__(GK_THREADS) void k_gather_textkey(const uint32_t *_
 //      broadcast read per step, wave cost = its largest group -- which is its place in the group;
 //   3. (key, suffix) pairs are permuted through LDS and stored coalesced.  Members of groups that
 //      are not owned keep their place and are flagged; they go through the global radix sort.
-// Algorithmic traffic per element: 12 B read + the text gather, 13 B written.
+// Algorithmic traffic per element: 12 B read + the text gather, 13 B written (STATUS, below: 5 B for an owned element).
 // ------------------------------------------------------------------------------------------
 constexpr int GS_THREADS = 256;
 constexpr int GS_ITEMS = 8;
@@ -166,7 +166,16 @@ constexpr int GS_WORDS = GS_TILE / 64;
 constexpr int GS_CAP = 1024;        // upper bound of the run-time group-size cap
 constexpr int GB_LIST_MIN = 256;    // k_group_sort_big: a group that runs on beyond its tile is listed when it has this many members inside it
 
-template <int MODE>
+// STATUS (KS_RANK / KS_CHASE, the dense doubling rounds): `bigflag` takes the RS_* status byte of every place (kernels/common.hpp)
+// and the owned places write NO key: the round's re-rank reads where their groups start from the byte (RS_HEAD: the sorted key2 in
+// LDS differs from the place before / chasing: the place is the first of its final subgroup).  Places that are not owned are
+// RS_PENDING | RS_KEYED and get their key as before.  Without STATUS the byte is 1 for such a place and 0 otherwise.
+// REFILL (KS_RANK / KS_CHASE, key form): the launch BEHIND a STATUS launch of the same round whose whole list goes through the global
+// sort after all, which wants a key for every member: only the keys of the owned places are written, on the order the first launch
+// left (ties are broken by list position, so an ordered group stays as it is and gets the keys it would have got the first time --
+// chasing: the places of the same final subgroups).  Everything else of the list stands: suffixes, bytes (`bigflag` is read: a tile
+// without an owned place returns at once) and the keys of the places that are not owned, which other kernels may have rewritten.
+template <int MODE, bool STATUS = false, bool REFILL = false>
 __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, const uint32_t *__restrict__ G,
                                                             const uint32_t *__restrict__ U, const uint8_t *__restrict__ T, KeyParams P,
                                                             int64_t m, int64_t n, KeySrc K, uint64_t *keys,
@@ -179,11 +188,22 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, 
     __shared__ uint64_t s_head[GS_WORDS + 1];
     __shared__ int s_nextH[GS_WORDS + 2];          // first group start in words >= w (-1: none): a group's end is one look-up
     __shared__ uint8_t lcode[256];
+    static_assert(!STATUS || MODE == KS_RANK || MODE == KS_CHASE, "status bytes are the dense doubling rounds'");
+    static_assert(!REFILL || (!STATUS && (MODE == KS_RANK || MODE == KS_CHASE)), "the key form behind a status launch");
     lcode[threadIdx.x] = P.code[threadIdx.x];
     __syncthreads();
     const bool aligned8 = (((uintptr_t)T) & 7) == 0;
     const int64_t base = (int64_t)blockIdx.x * GS_TILE;
     const int t = threadIdx.x;
+    if constexpr (REFILL) {
+        bool mine = false;
+#pragma unroll
+        for (int r = 0; r < GS_ITEMS; ++r) {
+            const int64_t j = base + r * GS_THREADS + t;
+            mine |= j < m && (bigflag[j] & RS_KEYED) == 0;
+        }
+        if (!__syncthreads_or(mine)) return;                     // (uniform)
+    }
 #ifdef SA_AMD_DIAG
     const bool stamping = g_gs_stamp_on != 0 && t == 0;
     unsigned long long t_prev = stamping ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -263,7 +283,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, 
     __shared__ uint32_t s_val2[CHASE ? GS_TILE : 1];              // second value buffer + subgroup extents (first << 16 | size)
     __shared__ uint32_t s_rng[CHASE ? 2 : 1][CHASE ? GS_TILE : 1];
     int start_[GS_ITEMS];
-    uint32_t owned_mask = 0;
+    uint32_t owned_mask = 0, phead_mask = 0;                      // phead_mask (STATUS): the place is the first one of its parent group
     // end of the group of tile position jl = next group start after jl (GS_TILE: the tile ends with the group; -1: it goes on)
     auto group_end = [&](int jl) -> int {
         const int wi = jl >> 6;
@@ -346,6 +366,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, 
             }
         }
         if (owned) owned_mask |= 1u << r;
+        if (STATUS && u[r] == g[r]) phead_mask |= 1u << r;
         dest[r] = owned ? start + rank : jl;
         big[r] = valid && !owned;
         // first member of a group of more than GS_CAP members, or of one that runs on beyond the tile (its size is not known here:
@@ -372,10 +393,16 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, 
             if (j < m) {
                 // place jl belongs to the group the member loaded from jl belongs to (a group keeps its places); members of
                 // one final subgroup share its first place, every other member of the group has another one
+                if constexpr (STATUS) {
+                    if (big[r]) keys[j] = ((uint64_t)g[r] << K.kb) | key[r];
+                    Vout[j] = val_cur[jl];
+                    bigflag[j] = (uint8_t)((big[r] ? RS_PENDING | RS_KEYED : ((int)(s_rng[cur][jl] >> 16) == jl ? RS_HEAD : 0)) |
+                                           (((phead_mask >> r) & 1u) ? RS_PHEAD : 0));
+                } else {
                 const uint64_t low = ((owned_mask >> r) & 1u) ? (uint64_t)((int)(s_rng[cur][jl] >> 16) - start_[r]) : key[r];
-                keys[j] = ((uint64_t)g[r] << K.kb) | low;
-                Vout[j] = val_cur[jl];
-                bigflag[j] = big[r] ? 1 : 0;
+                if (!REFILL || !big[r]) keys[j] = ((uint64_t)g[r] << K.kb) | low;
+                if (!REFILL) { Vout[j] = val_cur[jl]; bigflag[j] = big[r] ? 1 : 0; }
+                }
             }
         }
         stamp(5);
@@ -393,7 +420,19 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, 
     for (int r = 0; r < GS_ITEMS; ++r) {
         const int jl = r * GS_THREADS + t;
         const int64_t j = base + jl;
-        if (j < m) { keys[j] = s_key[jl]; Vout[j] = s_val[jl]; bigflag[j] = big[r] ? 1 : 0; }
+        if constexpr (STATUS) {
+            if (j < m) {
+                // (an owned place behind its group's first has the group's place before it; at the first one RS_PHEAD decides)
+                const uint64_t k = s_key[jl];
+                if (big[r]) keys[j] = k;
+                Vout[j] = s_val[jl];
+                bigflag[j] = (uint8_t)((big[r] ? RS_PENDING | RS_KEYED : ((jl == 0 || s_key[jl - 1] != k) ? RS_HEAD : 0)) |
+                                       (((phead_mask >> r) & 1u) ? RS_PHEAD : 0));
+            }
+        } else if (j < m) {
+            if (!REFILL || !big[r]) keys[j] = s_key[jl];
+            if (!REFILL) { Vout[j] = s_val[jl]; bigflag[j] = big[r] ? 1 : 0; }
+        }
     }
     stamp(5);      // stores issued
 }
@@ -401,6 +440,9 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sort(const uint32_t *Vin, 
 // The groups k_group_sort could not own only because they straddle a tile boundary: one workgroup per
 // boundary sorts the (at most one) group of up to GS_CAP members that contains it, the same way, on
 // the keys the first kernel stored, and clears its flags.  What stays flagged are groups > GS_CAP.
+// The byte of place i of a group that k_group_sort left RS_PENDING | RS_KEYED, once the group is ordered: RS_PENDING goes, the rest
+// stands (the group's first place is its parent's first).  The key form of a round only asks whether RS_PENDING is set.
+__device__ __forceinline__ uint8_t rs_ordered(int i) { return (uint8_t)(RS_KEYED | (i == 0 ? RS_PHEAD : 0)); }
 constexpr int GX_THREADS = 256;
 constexpr int GX_ITEMS = GS_CAP / GX_THREADS;
 constexpr int GX_BITONIC_MIN = 96;          // groups of more members than this are ordered by a bitonic network, not by counting
@@ -473,7 +515,7 @@ __global__ __launch_bounds__(GX_THREADS) void k_group_sort_straddle(uint64_t *__
                 const uint64_t c = s_key[i];
                 keys[start + i] = s_ghead | (c >> 10);
                 V[start + i] = s_v[0][(int)(c & 1023u)];
-                bigflag[start + i] = 0;
+                bigflag[start + i] = rs_ordered(i);
             }
         }
         return;
@@ -490,7 +532,7 @@ __global__ __launch_bounds__(GX_THREADS) void k_group_sort_straddle(uint64_t *__
                 }
                 keys[start + rank] = key[r];
                 V[start + rank] = v[r];
-                bigflag[start + i] = 0;
+                bigflag[start + i] = rs_ordered(i);
             }
         }
         return;
@@ -515,7 +557,7 @@ __global__ __launch_bounds__(GX_THREADS) void k_group_sort_straddle(uint64_t *__
         if (i < size) {
             keys[start + i] = ghead | (uint64_t)(s_rg[cur][i] >> 16);
             V[start + i] = s_v[cur][i];
-            bigflag[start + i] = 0;
+            bigflag[start + i] = rs_ordered(i);
         }
     }
 }
@@ -632,7 +674,7 @@ __global__ __launch_bounds__(GB_THREADS) void k_group_sort_big(uint64_t *__restr
             if (idx < size) {
                 keys[j0 + idx] = ghead | (uint64_t)lds_k[idx];
                 V[j0 + idx] = lds_v[idx];
-                bigflag[j0 + idx] = 0;
+                bigflag[j0 + idx] = rs_ordered(idx);
             }
         }
         if (tid == 0) atomicAdd(sorted_members, (uint32_t)size);
@@ -1007,6 +1049,9 @@ __global__ __launch_bounds__(256) void k_surv_compact(const uint32_t *__restrict
 // Every flagged group is flagged as a whole, head included.  Besides the flagged members per tile, the flagged group HEADS
 // are counted: the global sort then keys the members by (index of their group among the flagged groups, secondary key)
 // instead of (28-bit slot of the group head, secondary key) -- about 47 instead of 58 key bits on C3: two radix passes less.
+// STATUS: `flag` holds RS_* status bytes (kernels/common.hpp), which say both things (RS_PENDING, RS_PHEAD): U and G are not read.
+// A lane counts eight bytes of one 8-byte load (the slab is 8-byte aligned and reaches beyond the list's last byte).
+template <bool STATUS = false>
 __global__ __launch_bounds__(RR_THREADS) void k_flag_count(const uint8_t *__restrict__ flag, const uint32_t *__restrict__ U,
                                                             const uint32_t *__restrict__ G, int64_t m, uint32_t *__restrict__ tile_cnt,
                                                             uint32_t *__restrict__ tile_heads)
@@ -1016,13 +1061,30 @@ __global__ __launch_bounds__(RR_THREADS) void k_flag_count(const uint8_t *__rest
     const int l = lane_id(), w = wave_id();
     const int64_t wbase = (int64_t)blockIdx.x * RR_TILE + (int64_t)w * RR_WAVE_ELEMS;     // wave-striped: 64 consecutive elements per load
     uint32_t c = 0, h = 0;
+    if constexpr (STATUS) {
+        const int64_t i0 = wbase + 8 * l;
+        uint32_t both = 0;                                     // pending members | pending parent heads << 16
+        if (i0 < m) {
+            uint2 x = *(const uint2 *)(flag + i0);
+            if (i0 + 8 > m) {                                  // (bytes behind the end are nothing)
+                const uint64_t keep = (1ull << (8 * (int)(m - i0))) - 1ull;
+                x.x &= (uint32_t)keep; x.y &= (uint32_t)(keep >> 32);
+            }
+            const uint32_t px = x.x & 0x01010101u * RS_PENDING, py = x.y & 0x01010101u * RS_PENDING;
+            both = (uint32_t)(__popc(px) + __popc(py)) | ((uint32_t)(__popc(px & (x.x >> 3)) + __popc(py & (x.y >> 3))) << 16);
+        }
+        static_assert(RS_PENDING == 1 && RS_PHEAD == 8, "bit 3 beside bit 0");
+        both = (uint32_t)__shfl((int)wave_incl_sum(both), WAVE - 1, WAVE);      // (at most 512 of either: no carry between the halves)
+        c = both & 0xffffu; h = both >> 16;
+    } else {
 #pragma unroll
     for (int r = 0; r < RR_ITEMS; ++r) {
         const int64_t i = wbase + 64 * r + l;
-        const bool f = i < m && (!flag || flag[i] != 0);       // flag == nullptr: every member (the whole list goes through the global sort)
+        const bool f = i < m && (!flag || (flag[i] & RS_PENDING) != 0);       // flag == nullptr: every member (the whole list goes through the global sort)
         const bool hd = f && U[i] == G[i];
         c += (uint32_t)__popcll(__ballot(f));
         h += (uint32_t)__popcll(__ballot(hd));
+    }
     }
     if (l == 0) { wc[w] = c; wh[w] = h; }
     __syncthreads();
@@ -1034,6 +1096,8 @@ __global__ __launch_bounds__(RR_THREADS) void k_flag_count(const uint8_t *__rest
 }
 
 // bk = (group index among the flagged groups << kb) | secondary key
+// STATUS: as in k_flag_count (the keys of RS_PENDING places are true keys: they are RS_KEYED)
+template <bool STATUS = false>
 __global__ __launch_bounds__(RR_THREADS) void k_flag_gather(const uint8_t *__restrict__ flag, const uint64_t *__restrict__ keys,
                                                              const uint32_t *__restrict__ V, const uint32_t *__restrict__ U,
                                                              const uint32_t *__restrict__ G, int64_t m, const uint32_t *__restrict__ tile_cnt,
@@ -1049,8 +1113,9 @@ __global__ __launch_bounds__(RR_THREADS) void k_flag_gather(const uint8_t *__res
 #pragma unroll
     for (int r = 0; r < RR_ITEMS; ++r) {
         const int64_t i = wbase + 64 * r + l;
-        const bool f = i < m && flag[i] != 0;
-        const bool hd = f && U[i] == G[i];
+        const uint8_t fb = i < m ? flag[i] : (uint8_t)0;
+        const bool f = (fb & RS_PENDING) != 0;
+        const bool hd = f && (STATUS ? (fb & RS_PHEAD) != 0 : U[i] == G[i]);
         fm[r] = __ballot(f); hm[r] = __ballot(hd);
         c += (uint32_t)__popcll(fm[r]); h += (uint32_t)__popcll(hm[r]);
     }

@@ -134,6 +134,89 @@ __device__ __forceinline__ WaveGroups rr_wave_classify_flags(const uint8_t *__re
     return g;
 }
 
+// The same masks from the status bytes of a dense doubling round (RS_*, kernels/common.hpp): one byte per place of the tied list
+// instead of its 8-byte key, loaded and transposed as above (one 8-byte load per lane, v_readlane).  `keys` is the round's key
+// buffer and holds true keys only at RS_KEYED places -- the members the local pass did not own, which on a text with long repeats
+// are tens of millions in long runs: a lane that has such a place among its eight reads its eight keys as one contiguous 64
+// bytes (and the key before them when its first place needs it) and compares neighbours without a branch per element; the keys
+// of the places that are not KEYED are read with them and masked out.  phead: RS_PHEAD.
+template <bool PARENTS = false>
+__device__ __forceinline__ WaveGroups rr_wave_classify_status(const uint8_t *__restrict__ status, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase_in)
+{
+    const int l = lane_id();
+    WaveGroups g;
+    // (the wave's base is the same in every lane, which the compiler cannot see from threadIdx.x >> 6: said here, the masks below
+    // are scalar values -- left to itself it keeps all 32 of them in vector register pairs and spills)
+    const int64_t wbase = ((int64_t)__builtin_amdgcn_readfirstlane((int)(wbase_in >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wbase_in);
+    const int64_t i0 = wbase + 8 * l;                           // this lane's eight places
+    const int64_t a = wbase + RR_WAVE_ELEMS;                    // (uniform) the place behind the wave
+    const uint8_t fa = a < m ? status[a] : RS_PHEAD;
+    uint32_t hb = 0, pb = 0;                                    // bit k: place i0 + k starts a group / a parent group
+    if (i0 < m) {
+        const uint2 w = *(const uint2 *)(status + i0);
+        // bit `b` of every byte -> eight bits
+        auto plane = [&](int b) -> uint32_t {
+            return ((((w.x >> b) & 0x01010101u) * 0x01020408u) >> 24 & 15u) | (((((w.y >> b) & 0x01010101u) * 0x01020408u) >> 24 & 15u) << 4);
+        };
+        const uint32_t here = i0 + 8 > m ? (1u << (int)(m - i0)) - 1u : 255u;       // (places behind the end are nothing)
+        pb = plane(3) & here;
+        const uint32_t kd = plane(1) & here;
+        hb = pb | (plane(2) & ~kd & here);
+        const uint32_t need = kd & ~pb;                         // KEYED and no parent head: compared with the place before
+        if (need) {
+            uint64_t k[8];
+            if (i0 + 8 <= m) {
+                const uint4 *src = (const uint4 *)(keys + i0);  // (i0 is a multiple of 8: 64-byte aligned)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const uint4 x = src[q];
+                    k[2 * q] = ((uint64_t)x.y << 32) | x.x;
+                    k[2 * q + 1] = ((uint64_t)x.w << 32) | x.z;
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) k[q] = i0 + q < m ? keys[i0 + q] : 0ull;
+            }
+            const uint64_t before = ((need & 1u) && i0 > 0) ? keys[i0 - 1] : ~k[0];     // (place 0 of the list is a parent head)
+            uint32_t ne = before != k[0] ? 1u : 0u;
+#pragma unroll
+            for (int q = 1; q < 8; ++q) ne |= (k[q] != k[q - 1] ? 1u : 0u) << q;
+            hb |= need & ne;
+        }
+    }
+    // lane 4 q: the bytes of lanes 4 q .. 4 q + 3 as one word (shuffles executed by every lane)
+    const uint32_t h1 = (uint32_t)__shfl_down((int)hb, 1, WAVE), h2 = (uint32_t)__shfl_down((int)hb, 2, WAVE), h3 = (uint32_t)__shfl_down((int)hb, 3, WAVE);
+    const uint32_t quad = hb | (h1 << 8) | (h2 << 16) | (h3 << 24);
+    uint32_t pquad = 0;
+    if (PARENTS) {
+        const uint32_t p1 = (uint32_t)__shfl_down((int)pb, 1, WAVE), p2 = (uint32_t)__shfl_down((int)pb, 2, WAVE), p3 = (uint32_t)__shfl_down((int)pb, 3, WAVE);
+        pquad = pb | (p1 << 8) | (p2 << 16) | (p3 << 24);
+    }
+    const int64_t left = m - wbase;                             // (uniform) places of the wave that exist
+#pragma unroll
+    for (int r = 0; r < RR_ITEMS; ++r) {
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)quad, 8 * r), hi = (uint32_t)__builtin_amdgcn_readlane((int)quad, 8 * r + 4);
+        const int64_t here = left - 64 * r;
+        g.valid[r] = here >= 64 ? ~0ull : (here <= 0 ? 0ull : ((1ull << here) - 1ull));
+        g.head[r] = (((uint64_t)hi << 32) | lo) & g.valid[r];
+        g.phead[r] = 0ull;
+        if (PARENTS) {
+            const uint32_t plo = (uint32_t)__builtin_amdgcn_readlane((int)pquad, 8 * r), phi = (uint32_t)__builtin_amdgcn_readlane((int)pquad, 8 * r + 4);
+            g.phead[r] = (((uint64_t)phi << 32) | plo) & g.valid[r];
+        }
+    }
+    const bool boundary_after = (fa & RS_PHEAD) != 0 || ((fa & RS_KEYED) ? keys[a] != keys[a - 1] : (fa & RS_HEAD) != 0);
+#pragma unroll
+    for (int r = 0; r < RR_ITEMS; ++r) {
+        const uint64_t bnd = g.head[r] | ~g.valid[r];
+        const uint64_t bnd_next0 = (r + 1 < RR_ITEMS) ? ((g.head[(r + 1) % RR_ITEMS] | ~g.valid[(r + 1) % RR_ITEMS]) & 1ull)
+                                                      : (boundary_after ? 1ull : 0ull);
+        const uint64_t next = (bnd >> 1) | (bnd_next0 << 63);
+        g.tied[r] = g.valid[r] & ~(g.head[r] & next);
+    }
+    return g;
+}
+
 // "head code" of the dense doubling rounds: (list index of a group start << 1) | (it also starts a parent group);
 // RR_NO_HEAD: there is none (list indices are below 2^31, so the code of index m with the parent bit set is the same word)
 constexpr uint32_t RR_NO_HEAD = 0xffffffffu;
@@ -154,7 +237,8 @@ __device__ __forceinline__ uint32_t rr_first_head_code(const WaveGroups &g, int6
 
 // PARENTS (dense doubling rounds): also tile_first, the head code of the tile's first group start (g_shift: the parent
 // group is the key above that bit)
-// FLAGS (FIRST only): the groups come from head_flags (rr_wave_classify_flags), `keys` is the flag pass's sparsely written key buffer
+// FLAGS: FIRST: the groups come from head_flags (rr_wave_classify_flags), `keys` is the flag pass's sparsely written key buffer;
+// a round (PARENTS): head_flags = the round's status bytes (rr_wave_classify_status), `keys` holds true keys at RS_KEYED places only
 template <bool FIRST, typename KeyT = uint64_t, bool PARENTS = false, bool FLAGS = false>
 __global__ __launch_bounds__(RR_THREADS) void k_rr_count(const KeyT *__restrict__ keys,
                                                           const uint32_t *__restrict__ U, int64_t m,
@@ -164,13 +248,14 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_count(const KeyT *__restrict_
                                                           const uint32_t *__restrict__ gate = nullptr,      // != nullptr: the launch does nothing when *gate != 0 (see RoundCtl, host/pipeline.hpp)
                                                           const uint8_t *__restrict__ head_flags = nullptr)
 {
-    static_assert(!FLAGS || (FIRST && sizeof(KeyT) == 8), "group-start flags come from the 64-bit initial sort");
+    static_assert(!FLAGS || (sizeof(KeyT) == 8 && (FIRST || PARENTS)), "group-start flags come from the 64-bit initial sort, status bytes from a dense round");
     __shared__ uint32_t wcnt[RR_THREADS / WAVE], whead[RR_THREADS / WAVE], wfirst[RR_THREADS / WAVE];
     if (gate && *gate) return;
     const int64_t wbase = (int64_t)blockIdx.x * RR_TILE + (int64_t)wave_id() * RR_WAVE_ELEMS;
     uint64_t kk[RR_ITEMS + 1];
     WaveGroups g;
-    if constexpr (FLAGS) g = rr_wave_classify_flags<false>(head_flags, (const uint64_t *)keys, m, wbase);
+    if constexpr (FLAGS && FIRST) g = rr_wave_classify_flags<false>(head_flags, (const uint64_t *)keys, m, wbase);
+    else if constexpr (FLAGS) g = rr_wave_classify_status<true>(head_flags, (const uint64_t *)keys, m, wbase);
     else g = rr_wave_classify<KeyT, false>(keys, m, wbase, key_shift, 0, PARENTS ? kk : nullptr);
     uint32_t cnt = 0, lasthead = 0;
 #pragma unroll
@@ -184,7 +269,8 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_count(const KeyT *__restrict_
     // the wave's first group start, and whether its parent group starts there too: only that one element's key and its left
     // neighbour's are compared (wave-uniform item and lane: two shuffles, not a ballot per item)
     uint32_t first_code = RR_NO_HEAD;
-    if (PARENTS) {
+    if constexpr (PARENTS && FLAGS && !FIRST) first_code = rr_first_head_code(g, wbase, 0);
+    else if (PARENTS) {
         bool found = false;
 #pragma unroll
         for (int r = 0; r < RR_ITEMS; ++r) {
@@ -333,7 +419,7 @@ __global__ __launch_bounds__(SPINE_THREADS) void k_rr_scan_round(uint32_t *__res
 // (ISA = group heads, has_isa = bitmap, pair_v = counts per tile) instead of being listed, 2 = write (suffix, rank) pairs in slot order; the host bins them by suffix position
 // with one radix pass and k_scatter_pairs then writes the ISA window by window (a random 4-byte
 // store costs a whole 64-byte memory transaction, a binned one is merged in the caches).
-// FLAGS (FIRST only): as in k_rr_count
+// FLAGS: as in k_rr_count (a round: ISA_MODE 0 or 2, the dense rounds)
 template <bool FIRST, bool WRITE_SA, int ISA_MODE, typename KeyT = uint64_t, bool FTAIL = false, bool FLAGS = false>
 __global__ __launch_bounds__(RR_THREADS) void k_rr_apply(
     const KeyT *__restrict__ keys, const uint32_t *__restrict__ V, const uint32_t *__restrict__ U, int64_t m,
@@ -346,7 +432,7 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_apply(
     int sa_final = 0,                                 // 1: SA[slot] = suffix only for the elements that leave the tied list (see below)
     const uint8_t *__restrict__ head_flags = nullptr)
 {
-    static_assert(!FLAGS || (FIRST && sizeof(KeyT) == 8), "group-start flags come from the 64-bit initial sort");
+    static_assert(!FLAGS || (sizeof(KeyT) == 8 && (FIRST || ISA_MODE == 0 || ISA_MODE == 2)), "group-start flags come from the 64-bit initial sort, status bytes from a dense round");
     constexpr bool SPARSE = ISA_MODE == 1;
     if (gate && *gate) return;
     // Dense doubling rounds (TAIL): the rank of a group is its LAST slot + 1 (Larsson-Sadakane's group number).  When a
@@ -375,7 +461,8 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_apply(
     const int l = lane_id(), w = wave_id();
     const int64_t wbase = (int64_t)blockIdx.x * RR_TILE + (int64_t)w * RR_WAVE_ELEMS;
     WaveGroups g;
-    if constexpr (FLAGS) g = rr_wave_classify_flags<TAIL>(head_flags, (const uint64_t *)keys, m, wbase);
+    if constexpr (FLAGS && FIRST) g = rr_wave_classify_flags<TAIL>(head_flags, (const uint64_t *)keys, m, wbase);
+    else if constexpr (FLAGS) g = rr_wave_classify_status<TAIL>(head_flags, (const uint64_t *)keys, m, wbase);
     else g = rr_wave_classify<KeyT, TAIL>(keys, m, wbase, key_shift, g_shift);
     uint32_t slot[RR_ITEMS], v[RR_ITEMS];
 #pragma unroll

@@ -23,6 +23,11 @@ int32_t sa_amd_debug_rerank_routes(int32_t flags);
  * previous mode): 0 never (the key route), 1 when the dense route is expected (what the product library always does), 2 whenever
  * that sort runs -- the routes that read the sorted keys then rebuild them.  Every mode gives the same array and statistics. */
 int32_t sa_amd_debug_head_flags(int32_t mode);
+/* whether a dense doubling round hands its re-rank one status byte per list member instead of the 8-byte keys (process-wide;
+ * returns the previous mode): 0 never (the key route), 1 where a dead device-resident slab exists for the bytes (what the product
+ * library always does), 2 the same with the round's key buffer and status slab filled with a poison pattern before the local
+ * pass, so that a read of an entry the round never wrote changes the result.  Every mode gives the same array and statistics. */
+int32_t sa_amd_debug_round_flags(int32_t mode);
 /* the second bound of the term-frequency kernel (process-wide; returns the previous mode): 0 galloping from the first bound (what
  * the product library always does), 1 a plain binary search of the document's part.  Both give the same answers. */
 int32_t sa_amd_debug_doc_tf_bounds(int32_t mode);

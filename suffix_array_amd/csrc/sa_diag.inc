@@ -39,6 +39,11 @@ SA_EXPORT int32_t sa_amd_debug_head_flags(int32_t mode)
     return sa::g_head_flags_mode.exchange(mode < 0 ? 0 : (mode > 2 ? 2 : mode));
 }
 
+SA_EXPORT int32_t sa_amd_debug_round_flags(int32_t mode)
+{
+    return sa::g_round_flags_mode.exchange(mode < 0 ? 0 : (mode > 2 ? 2 : mode));
+}
+
 SA_EXPORT int32_t sa_amd_debug_sort_variant_count(void) { return sa::N_SORT_VARIANTS; }
 SA_EXPORT const char *sa_amd_debug_sort_variant_name(int32_t i)
 {
