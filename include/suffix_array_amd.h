@@ -839,6 +839,83 @@ typedef struct sa_amd_doc_substr_stats { /* of the calling thread's most recent 
 } sa_amd_doc_substr_stats;
 void sa_amd_last_doc_substr_stats(sa_amd_doc_substr_stats *out);
 
+/*
+ * n-gram and infinity-gram queries (an extension): what follows a context in the text and how often, and the longest suffix
+ * of a prompt that occurs often enough, on the device.  T has n bytes, SA has n + 1 slots in the layout
+ * of sa_amd_saca_u8; a context c of p bytes has the match range [lo, hi) that sa_amd_index_search reports.
+ *   at_end is 1 iff some slot of the range has SA[i] + p == n: the context is a suffix of the text.  It can only be slot lo
+ *     (the suffix that is the context itself is the smallest one that starts with it).  Otherwise at_end is 0.
+ *   next[b] = the number of slots i in [lo, hi) with SA[i] + p < n and T[SA[i] + p] == b.
+ *   sum(next) + at_end == hi - lo.
+ *   Inside the range the slots are ordered by the byte behind the context: those with continuation b are the contiguous
+ *     sub-range that starts at lo + at_end + sum(next[b'] for b' < b) and has next[b] slots.  It is the range of c + b: a caller
+ *     descends from a context to a longer one without another search.
+ *   The LISTING of a context is its non-zero (b, next[b]) pairs in ascending b: at most 256 entries.
+ *   The empty context has the range [0, n + 1) and at_end = 1; its listing is the byte histogram of T.
+ *   A context that does not occur has lo == hi, at_end = 0 and an empty listing.
+ * Back-off (sa_amd_index_infgram), for a prompt P of L bytes, min_count >= 1 and max_len:
+ *   max_len <= 0 means no cap: cap = L, otherwise cap = min(L, max_len).
+ *   s = the largest value in 0 .. cap such that P[L - s .. L) has at least min_count occurrences (hi - lo >= min_count).
+ *   s = 0 always qualifies, also when min_count > n + 1: the fallback is the unigram distribution.
+ *   The count never grows with s, so s is well defined and found by bisection: at most 2 ceil(log2(cap + 1)) + 2 range
+ *     searches per prompt (this implementation runs at most ceil(log2(cap + 1))).
+ *   The outputs are s, the range of that suffix, its at_end and its listing.
+ *   T = "abracadabra", SA = {11,10,7,0,3,5,8,1,4,6,9,2}:
+ *     context   range     at_end  listing
+ *     "a"       [1, 6)    1       {b:2, c:1, d:1}
+ *     "abra"    [2, 4)    1       {c:1}
+ *     ""        [0, 12)   1       {a:5, b:2, c:1, d:1, r:2}
+ *     "x"       empty     0       empty
+ *     prompt    min_count max_len  s   range
+ *     "xcabra"  1         none     4   [2, 4)
+ *     "xcabra"  2         none     4   [2, 4)
+ *     "xcabra"  3         none     1   [1, 6)   ("a")
+ *     "xcabra"  1         2        2   [10, 12) ("ra")
+ * Patterns are passed as for sa_amd_index_search.  The listing follows sa_amd_index_doc_tf: list_off has count + 1 entries, the
+ * listing of pattern q is (bytes, counts)[list_off[q] .. list_off[q + 1]); more entries than `capacity` is no error: the first
+ * `capacity` are written, *total_out (= list_off[count]) and list_off describe all of them.  EVERY output pointer may be NULL;
+ * bytes and counts may each be NULL, and with both NULL `capacity` is ignored (nothing is emitted).  count == 0 succeeds with
+ * list_off[0] = 0.
+ * Errors, each with nothing written: a NULL index, a negative count or capacity, pat_off as sa_amd_index_search rejects it,
+ * min_count < 1: SA_AMD_EINVAL.  If the resident array is not the suffix array of the text the answers are unspecified, but
+ * nothing is read outside the text, the patterns and the tables: every slot read lies in [0, n + 1), every SA entry is checked
+ * against n before T is read through it (an entry with SA[i] + p >= n counts as "at end"), and nothing is written outside the
+ * outputs.  The answers are the same with or without the bucket table and the LCP table.
+ * Cost: per context the range search; then hi - lo slots streamed (each 4 bytes of SA and one byte of text) when the range
+ * has at most `stream cap` slots, else at most 64 + 256 (ceil(log2(cnt + 1)) + 1) slots probed, cnt = hi - lo - at_end.  With
+ * bytes or counts asked for, the continuations are computed twice (counted, then emitted in order); the probe counters below
+ * are those of the counting pass.
+ */
+int32_t sa_amd_index_next_bytes(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count,
+                                uint32_t *range_lo, uint32_t *range_hi, uint8_t *at_end,
+                                int64_t *list_off, uint8_t *bytes, uint32_t *counts, int64_t capacity, int64_t *total_out);
+int32_t sa_amd_index_infgram(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count,
+                             int32_t min_count, int32_t max_len, uint32_t *suffix_len,
+                             uint32_t *range_lo, uint32_t *range_hi, uint8_t *at_end,
+                             int64_t *list_off, uint8_t *bytes, uint32_t *counts, int64_t capacity, int64_t *total_out);
+
+typedef struct sa_amd_ngram_stats {  /* of the calling thread's most recent next_bytes / infgram call (no other feature's statistics are touched) */
+    int64_t patterns;
+    int64_t range_searches;          /* infgram: the probes of the bisection, all prompts; next_bytes: one per pattern */
+    int64_t compared_bytes;          /* infgram: text bytes the range searches compared; -1 after next_bytes (the search kernels do not count) */
+    int64_t stream_slots;            /* slots probed by the streaming route: the sum of cnt over its queries, exactly */
+    int64_t search_slots;            /* slots probed by the boundary-search route */
+    int64_t stream_queries;          /* queries by route: 0 < cnt <= stream_cap */
+    int64_t search_queries;          /*                   cnt > stream_cap */
+    int64_t empty_queries;           /*                   cnt == 0: nothing is probed */
+    int64_t entries;                 /* entries of the whole listing (= *total_out) */
+    int32_t stream_cap;              /* the stream cap in effect */
+    int32_t readbacks;               /* blocking device -> host read-backs of counters: 1 */
+    int32_t backoff;                 /* 1 after infgram, 0 after next_bytes */
+    int32_t passes;                  /* runs of the continuation kernel: 1 (counted only: bytes and counts NULL, or capacity 0), else 2 */
+} sa_amd_ngram_stats;
+void sa_amd_last_ngram_stats(sa_amd_ngram_stats *out);
+/* route switch of the calling thread's later next_bytes / infgram calls (never changes a result): ranges of at most `slots`
+ * slots (after the at-end slot is stripped) are streamed, longer ones are searched.  0 makes every non-empty range search, a
+ * huge value (clamped to 2^31 - 1) makes every range stream; a negative value restores the default (1024).  Returns the
+ * previous value. */
+int32_t sa_amd_ngram_set_stream_cap(int32_t slots);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

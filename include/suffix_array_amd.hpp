@@ -367,8 +367,64 @@ public:
         for (std::size_t i = 0; i < out.size(); ++i) out[i] = { flat[4 * i], flat[4 * i + 1], flat[4 * i + 2], flat[4 * i + 3], pos[i], df[i] };
         return out;
     }
+    // what follows a context in the text and how often (suffix_array_amd.h, "n-gram and infinity-gram queries"): [lo, hi) is the
+    // context's match range, at_end says that the context is a suffix of the text, next holds the (byte, count) pairs with a
+    // non-zero count in ascending byte order.  The counts and at_end sum to hi - lo.
+    struct NextBytes {
+        std::uint32_t lo = 0, hi = 0;
+        bool at_end = false;
+        std::vector<std::pair<std::uint8_t, std::uint32_t>> next;
+    };
+    // the same for the longest suffix of a prompt that occurs at least min_count times: suffix_len is its length
+    struct Infgram : NextBytes {
+        std::uint32_t suffix_len = 0;
+    };
+    std::vector<NextBytes> next_bytes(const std::vector<std::string> &patterns) const
+    {
+        std::vector<NextBytes> out(patterns.size());
+        ngram(patterns, false, 1, 0, out, nullptr);
+        return out;
+    }
+    // max_len <= 0: no cap on the suffix length.  A suffix of length 0 (the byte histogram of the text) always qualifies.
+    std::vector<Infgram> infgram(const std::vector<std::string> &prompts, std::int32_t min_count = 1, std::int32_t max_len = 0) const
+    {
+        if (min_count < 1) throw std::invalid_argument("min_count must be at least 1");
+        std::vector<Infgram> out(prompts.size());
+        std::vector<std::uint32_t> slen(prompts.size() + 1);
+        ngram(prompts, true, min_count, max_len, out, slen.data());
+        for (std::size_t q = 0; q < out.size(); ++q) out[q].suffix_len = slen[q];
+        return out;
+    }
 
 private:
+    template <class Row>
+    void ngram(const std::vector<std::string> &patterns, bool backoff, std::int32_t min_count, std::int32_t max_len, std::vector<Row> &out,
+               std::uint32_t *slen) const
+    {
+        const Batch b(patterns);
+        const std::size_t c = patterns.size();
+        std::vector<std::uint32_t> lo(c + 1), hi(c + 1), counts(1 << 12);
+        std::vector<std::uint8_t> ae(c + 1), bytes(1 << 12);
+        std::vector<std::int64_t> loff(c + 1);
+        std::int64_t total = 0;
+        for (;;) {
+            const std::int64_t cap = static_cast<std::int64_t>(bytes.size());
+            if (backoff)
+                check(sa_amd_index_infgram(ix_, b.data(), b.off.data(), b.count(), min_count, max_len, slen, lo.data(), hi.data(), ae.data(),
+                                           loff.data(), bytes.data(), counts.data(), cap, &total));
+            else
+                check(sa_amd_index_next_bytes(ix_, b.data(), b.off.data(), b.count(), lo.data(), hi.data(), ae.data(), loff.data(), bytes.data(),
+                                              counts.data(), cap, &total));
+            if (total <= cap) break;
+            bytes.resize(static_cast<std::size_t>(total));
+            counts.resize(static_cast<std::size_t>(total));
+        }
+        for (std::size_t q = 0; q < c; ++q) {
+            out[q].lo = lo[q]; out[q].hi = hi[q]; out[q].at_end = ae[q] != 0;
+            for (std::int64_t e = loff[q]; e < loff[q + 1]; ++e)
+                out[q].next.emplace_back(bytes[static_cast<std::size_t>(e)], counts[static_cast<std::size_t>(e)]);
+        }
+    }
     struct Batch {
         std::string bytes;
         std::vector<std::int64_t> off;

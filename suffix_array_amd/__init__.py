@@ -37,7 +37,8 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "DocsStats", "last_docs_stats", "docs_set_chunk", "docs_work_bytes", "doc_of_device_ptr", "DOC_NONE", "DOC_SAMPLES",
            "DOC_CHUNK_MIN", "DOC_CHUNK_MAX", "DOC_CHUNK_DEFAULT",
            "DocTfStats", "last_doc_tf_stats", "docs_set_topk_piece", "DOC_TOPK_MAX", "DOC_TOPK_PIECE_MIN", "DOC_TOPK_PIECE_MAX",
-           "DOC_TOPK_PIECE_DEFAULT"]
+           "DOC_TOPK_PIECE_DEFAULT",
+           "NgramStats", "last_ngram_stats", "ngram_set_stream_cap", "NGRAM_STREAM_CAP_DEFAULT"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
@@ -187,6 +188,21 @@ class DocTfStats(ctypes.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+class NgramStats(ctypes.Structure):
+    """sa_amd_ngram_stats of include/suffix_array_amd.h"""
+    _fields_ = [("patterns", ctypes.c_int64), ("range_searches", ctypes.c_int64), ("compared_bytes", ctypes.c_int64),
+                ("stream_slots", ctypes.c_int64), ("search_slots", ctypes.c_int64), ("stream_queries", ctypes.c_int64),
+                ("search_queries", ctypes.c_int64), ("empty_queries", ctypes.c_int64), ("entries", ctypes.c_int64),
+                ("stream_cap", ctypes.c_int32), ("readbacks", ctypes.c_int32), ("backoff", ctypes.c_int32), ("passes", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+#: slots up to which ``next_bytes`` / ``infgram`` stream a range instead of searching its run starts (kernels/ngram.hpp)
+NGRAM_STREAM_CAP_DEFAULT = 1024
 
 
 class DocRepeatStats(ctypes.Structure):
@@ -438,6 +454,15 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_index_doc_topk.restype = ctypes.c_int32
         L.sa_amd_last_doc_tf_stats.argtypes = [c_vp]
         L.sa_amd_last_doc_tf_stats.restype = None
+        L.sa_amd_index_next_bytes.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_next_bytes.restype = ctypes.c_int32
+        L.sa_amd_index_infgram.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_infgram.restype = ctypes.c_int32
+        L.sa_amd_last_ngram_stats.argtypes = [c_vp]
+        L.sa_amd_last_ngram_stats.restype = None
+        L.sa_amd_ngram_set_stream_cap.argtypes = [ctypes.c_int32]
+        L.sa_amd_ngram_set_stream_cap.restype = ctypes.c_int32
         L.sa_amd_docs_set_topk_piece.argtypes = [ctypes.c_int32]
         L.sa_amd_docs_set_topk_piece.restype = ctypes.c_int32
         _lib = L
@@ -1114,6 +1139,21 @@ def docs_set_topk_piece(entries: int) -> int:
     return int(lib().sa_amd_docs_set_topk_piece(int(entries)))
 
 
+def last_ngram_stats() -> dict:
+    """patterns / range_searches / compared_bytes / stream_slots / search_slots / stream_queries / search_queries / empty_queries /
+    entries / stream_cap / readbacks / backoff / passes of this thread's most recent ``next_bytes`` / ``infgram`` call"""
+    st = NgramStats()
+    lib().sa_amd_last_ngram_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def ngram_set_stream_cap(slots: int) -> int:
+    """Route switch of this thread's later ``next_bytes`` / ``infgram`` calls (never changes a result): match ranges of at most
+    ``slots`` slots are streamed, longer ones have their run starts searched; 0 searches every range, a huge value streams every
+    range, negative restores ``NGRAM_STREAM_CAP_DEFAULT``.  Returns the previous value."""
+    return int(lib().sa_amd_ngram_set_stream_cap(max(-1, min(int(slots), 2**31 - 1))))
+
+
 def doc_of_device_ptr(index, pos_ptr: int, count: int, doc_ptr: int, stream: int = 0) -> None:
     """Device-resident ``doc_of``: ``count`` uint32 positions at ``pos_ptr`` -> their documents at ``doc_ptr`` (raw device pointers
     on the index's device, 4-byte aligned); needs no scratch; blocks until done."""
@@ -1360,6 +1400,51 @@ class DeviceIndex:
         _check(lib().sa_amd_index_doc_topk(self._h, data.ctypes.data, off.ctypes.data, cnt, k, toff.ctypes.data, out[0].ctypes.data,
                                            out[1].ctypes.data))
         return [(out[0, toff[q]:toff[q + 1]].copy(), out[1, toff[q]:toff[q + 1]].copy()) for q in range(cnt)]
+
+    def _ngram(self, patterns, backoff: bool, min_count: int, max_len: int):
+        data, off, cnt = _pattern_batch(patterns)
+        slen, lo, hi = (np.zeros(cnt, dtype=np.uint32) for _ in range(3))
+        ae = np.zeros(cnt, dtype=np.uint8)
+        loff = np.zeros(cnt + 1, dtype=np.int64)
+        total = ctypes.c_int64(0)
+        cap = min(256 * cnt, max(1 << 16, 8 * cnt))
+        while True:
+            b = np.empty(max(cap, 1), dtype=np.uint8)
+            c = np.empty(max(cap, 1), dtype=np.uint32)
+            if backoff:
+                _check(lib().sa_amd_index_infgram(self._h, data.ctypes.data, off.ctypes.data, cnt, int(min_count), int(max_len), slen.ctypes.data,
+                                                  lo.ctypes.data, hi.ctypes.data, ae.ctypes.data, loff.ctypes.data, b.ctypes.data, c.ctypes.data,
+                                                  cap, ctypes.byref(total)))
+            else:
+                _check(lib().sa_amd_index_next_bytes(self._h, data.ctypes.data, off.ctypes.data, cnt, lo.ctypes.data, hi.ctypes.data,
+                                                     ae.ctypes.data, loff.ctypes.data, b.ctypes.data, c.ctypes.data, cap, ctypes.byref(total)))
+            if total.value <= cap:
+                m = int(total.value)
+                return slen, lo, hi, ae, loff, b[:m].copy(), c[:m].copy()
+            cap = int(total.value)
+
+    def next_bytes(self, patterns, dense: bool = False):
+        """EXTENSION: what follows each context in the text, and how often -> ``(lo, hi, at_end, list_off, bytes, counts)``.
+        ``[lo, hi)`` is the context's match range (``search``), ``at_end`` is 1 where the context is a suffix of the text, and the
+        listing of context ``q`` is ``bytes[list_off[q]:list_off[q + 1]]`` (ascending) with ``counts`` next to it: the number of
+        occurrences followed by that byte.  ``sum(counts) + at_end == hi - lo``, and the occurrences followed by ``b`` are the
+        sub-range that starts at ``lo + at_end`` plus the counts of the smaller bytes.  ``dense=True`` -> ``(lo, hi, at_end, next)``
+        with ``next`` a ``(count, 256)`` uint32 array, filled on the host from the sparse result."""
+        _, lo, hi, ae, loff, b, c = self._ngram(patterns, False, 1, 0)
+        if not dense:
+            return lo, hi, ae, loff, b, c
+        nxt = np.zeros((lo.size, 256), dtype=np.uint32)
+        nxt[np.repeat(np.arange(lo.size), np.diff(loff)), b] = c
+        return lo, hi, ae, nxt
+
+    def infgram(self, prompts, min_count: int = 1, max_len: int = 0):
+        """EXTENSION: the infinity-gram query -> ``(suffix_len, lo, hi, at_end, list_off, bytes, counts)``.  ``suffix_len[q]`` is the
+        length ``s`` of the longest suffix of prompt ``q`` -- of at most ``max_len`` bytes where ``max_len > 0`` -- that occurs at
+        least ``min_count`` times; ``s = 0`` (the unigram distribution) always qualifies.  The other outputs are those of
+        ``next_bytes`` for that suffix."""
+        if int(min_count) < 1:
+            raise SuffixArrayError(-1, "infgram: min_count >= 1")
+        return self._ngram(prompts, True, min(int(min_count), 2**31 - 1), max(0, min(int(max_len), 2**31 - 1)))
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): build and keep the LCP table of the
@@ -1618,6 +1703,16 @@ class SuffixArray:
         """EXTENSION (the reference lacks it): the ``k`` documents with the most occurrences per pattern (see
         ``DeviceIndex.doc_topk``)"""
         return self._index().doc_topk(patterns, k)
+
+    def next_bytes(self, patterns, dense: bool = False):
+        """EXTENSION (the reference lacks it): the bytes that follow each context and their counts (see
+        ``DeviceIndex.next_bytes``)"""
+        return self._index().next_bytes(patterns, dense)
+
+    def infgram(self, prompts, min_count: int = 1, max_len: int = 0):
+        """EXTENSION (the reference lacks it): the longest suffix of each prompt that occurs ``min_count`` times, and what
+        follows it (see ``DeviceIndex.infgram``)"""
+        return self._index().infgram(prompts, min_count, max_len)
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): contains / search_all / search_lcp

@@ -30,6 +30,7 @@
 #include "host/doc_tf.hpp"
 #include "host/substrings.hpp"
 #include "host/doc_substrings.hpp"
+#include "host/ngram.hpp"
 
 extern "C" {
 
@@ -715,6 +716,41 @@ SA_EXPORT int32_t sa_amd_index_doc_substrings(const sa_amd_index *ix, const sa_a
 SA_EXPORT void sa_amd_last_doc_substr_stats(sa_amd_doc_substr_stats *out)
 {
     if (out) *out = sa::g_last_doc_substr_stats;
+}
+
+// ---- n-gram / infinity-gram queries (host/ngram.hpp, kernels/ngram.hpp) ----
+
+SA_EXPORT int32_t sa_amd_index_next_bytes(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, uint32_t *range_lo,
+                                          uint32_t *range_hi, uint8_t *at_end, int64_t *list_off, uint8_t *bytes, uint32_t *counts, int64_t capacity,
+                                          int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::search_patterns_valid(pat_data, pat_off, count) || capacity < 0) return SA_AMD_EINVAL;
+    return sa::ngram_query(*ix, pat_data, pat_off, count, false, 1, 0, nullptr, range_lo, range_hi, at_end, list_off, bytes, counts, capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_infgram(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, int32_t min_count,
+                                       int32_t max_len, uint32_t *suffix_len, uint32_t *range_lo, uint32_t *range_hi, uint8_t *at_end, int64_t *list_off,
+                                       uint8_t *bytes, uint32_t *counts, int64_t capacity, int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::search_patterns_valid(pat_data, pat_off, count) || capacity < 0 || min_count < 1) return SA_AMD_EINVAL;
+    return sa::ngram_query(*ix, pat_data, pat_off, count, true, min_count, max_len, suffix_len, range_lo, range_hi, at_end, list_off, bytes, counts,
+                           capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_ngram_stats(sa_amd_ngram_stats *out)
+{
+    if (out) *out = sa::g_last_ngram_stats;
+}
+
+SA_EXPORT int32_t sa_amd_ngram_set_stream_cap(int32_t slots)
+{
+    const int32_t prev = sa::g_ngram_stream_cap < 0 ? sa::NG_STREAM_CAP_DEFAULT : sa::g_ngram_stream_cap;
+    sa::g_ngram_stream_cap = slots < 0 ? -1 : (slots > sa::NG_STREAM_CAP_MAX ? sa::NG_STREAM_CAP_MAX : slots);
+    return prev;
 }
 
 // ---- packed format (reference src/packed_sa.rs); byte layout: u32 magic "SA4x" LE, u32 length, u64 data length
