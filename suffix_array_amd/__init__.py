@@ -505,6 +505,8 @@ def diag_lib() -> ctypes.CDLL:
         L.sa_amd_debug_phase_cycles.restype = ctypes.c_int32
         L.sa_amd_debug_group_sort_stamps.argtypes = [ctypes.c_int32]
         L.sa_amd_debug_group_sort_stamps.restype = ctypes.c_int32
+        L.sa_amd_debug_rr_count_stamps.argtypes = [ctypes.c_int32]
+        L.sa_amd_debug_rr_count_stamps.restype = ctypes.c_int32
         L.sa_amd_debug_sort_variant_count.restype = ctypes.c_int32
         L.sa_amd_debug_sort_variant_name.argtypes = [ctypes.c_int32]
         L.sa_amd_debug_sort_variant_name.restype = ctypes.c_char_p

@@ -453,7 +453,7 @@ struct DeviceBuild {
     int rr_count(const KeyT *keys, const uint32_t *U, int64_t m, uint32_t *tile_first = nullptr, int g_shift = 0, const uint32_t *gate = nullptr,
                  uint32_t *tile_cnt = nullptr, uint32_t *tile_head = nullptr, const uint8_t *status = nullptr)
     {
-        PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_rr_count<FIRST, KeyT, PARENTS, FLAGS>), dim3((unsigned)ceil_div(m, RR_TILE)), dim3(RR_THREADS), 0, st, keys, U, m,
+        PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_rr_count<FIRST, KeyT, PARENTS, FLAGS>), dim3(rr_count_grid<FLAGS>(m)), dim3(RR_THREADS), 0, st, keys, U, m,
                                                     tile_cnt ? tile_cnt : w.tcnt, tile_head ? tile_head : w.thead, 0, tile_first, g_shift, gate,
                                                     FLAGS ? (status ? status : (const uint8_t *)head_flags) : (const uint8_t *)nullptr));
         return SA_AMD_OK;
@@ -649,7 +649,7 @@ struct DeviceBuild {
         uint32_t groups = 0;
         if (!*use_local && retry_local && !tn.no_local_sort && m < tn.dense_rekey_min) *use_local = true;     // (small lists do not count their groups)
         if (!*use_local && retry_local && !tn.no_local_sort && m >= tn.dense_rekey_min) {
-            PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_flag_count<false>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
+            PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_flag_count<false>), dim3(rr_count_grid<false>(m)), dim3(RR_THREADS), 0, st,
                                                         (const uint8_t *)nullptr, L.U, L.G, m, w.tcnt, w.ft_cnt));
             PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.ft_cnt, w.thead, tiles, w.total + 8));
             { const int rcw = read_words(&groups, w.total + 8, 4, st); if (rcw) return rcw; }
@@ -696,7 +696,7 @@ struct DeviceBuild {
                 PROF(KC_LOCAL, 0, st, hipLaunchKernelGGL((k_group_sort_big<512>), dim3((unsigned)(4 * cu_count())), dim3(512), 0, st, L.rkA, L.V, L.G, m, kb,
                                                          lo > GB_CAP_SMALL ? lo : GB_CAP_SMALL, (const uint32_t *)bheads, (const uint32_t *)bcount, flags, w.total + 13));
             }
-            PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((status ? k_flag_count<true> : k_flag_count<false>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
+            PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((status ? k_flag_count<true> : k_flag_count<false>), dim3(status ? rr_count_grid<true>(m) : rr_count_grid<false>(m)), dim3(RR_THREADS), 0, st,
                                                         (const uint8_t *)flags, L.U, L.G, m, w.tcnt, w.ft_cnt));
             // (flagged members -> w.total[RC_FLAGGED], flagged groups -> w.total[RC_GROUPS]; one launch)
             PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan_pair), dim3(2), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, w.total + RC_FLAGGED,
@@ -762,7 +762,7 @@ struct DeviceBuild {
         bool rekeyed = false;
         if (m >= tn.dense_rekey_min) {
             if (!counted || had_local_pass) {              // (the local pass has used the count arrays for its own compaction)
-                PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_flag_count<false>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
+                PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_flag_count<false>), dim3(rr_count_grid<false>(m)), dim3(RR_THREADS), 0, st,
                                                             (const uint8_t *)nullptr, L.U, L.G, m, w.tcnt, w.ft_cnt));
                 PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.ft_cnt, w.thead, tiles, w.total + 8));
                 { const int rcw = read_words(&groups, w.total + 8, 4, st); if (rcw) return rcw; }

@@ -129,6 +129,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_radix_upsweep32(const uint32_t
 // over tiles and workgroups
 __device__ unsigned long long g_phase_cycles[16];
 __device__ int g_gs_stamp_on;          // k_group_sort adds its per-phase cycles (wave 0) to g_phase_cycles[8..15]
+__device__ int g_rr_stamp_on;          // k_rr_count adds its per-phase cycles (wave 0) to g_phase_cycles[0..7] (tools/rr_count_stamps.py)
 #endif
 
 }  // namespace sa

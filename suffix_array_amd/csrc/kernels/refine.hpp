@@ -1057,15 +1057,28 @@ __global__ __launch_bounds__(RR_THREADS) void k_flag_count(const uint8_t *__rest
                                                             uint32_t *__restrict__ tile_heads)
 {
     constexpr int NW = RR_THREADS / WAVE;
-    __shared__ uint32_t wc[NW], wh[NW];
+    constexpr int SPAN = rr_count_span<STATUS>();              // STATUS: a workgroup covers a span of tiles, all loads first (RR_COUNT_SPAN, kernels/rerank.hpp)
+    __shared__ uint32_t wc[SPAN][NW], wh[SPAN][NW];
     const int l = lane_id(), w = wave_id();
-    const int64_t wbase = (int64_t)blockIdx.x * RR_TILE + (int64_t)w * RR_WAVE_ELEMS;     // wave-striped: 64 consecutive elements per load
+    const int64_t tiles = (m + RR_TILE - 1) / RR_TILE;
+    const int64_t tile0 = (int64_t)blockIdx.x * SPAN;
+    uint2 raw[SPAN];
+    if constexpr (STATUS) {
+#pragma unroll
+        for (int s = 0; s < SPAN; ++s) {
+            const int64_t i0 = (tile0 + s) * RR_TILE + (int64_t)w * RR_WAVE_ELEMS + 8 * l;
+            raw[s] = i0 < m ? *(const uint2 *)(flag + i0) : make_uint2(0u, 0u);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < SPAN; ++s) {
+    const int64_t wbase = (tile0 + s) * RR_TILE + (int64_t)w * RR_WAVE_ELEMS;     // wave-striped: 64 consecutive elements per load
     uint32_t c = 0, h = 0;
     if constexpr (STATUS) {
         const int64_t i0 = wbase + 8 * l;
         uint32_t both = 0;                                     // pending members | pending parent heads << 16
         if (i0 < m) {
-            uint2 x = *(const uint2 *)(flag + i0);
+            uint2 x = raw[s];
             if (i0 + 8 > m) {                                  // (bytes behind the end are nothing)
                 const uint64_t keep = (1ull << (8 * (int)(m - i0))) - 1ull;
                 x.x &= (uint32_t)keep; x.y &= (uint32_t)(keep >> 32);
@@ -1086,12 +1099,16 @@ __global__ __launch_bounds__(RR_THREADS) void k_flag_count(const uint8_t *__rest
         h += (uint32_t)__popcll(__ballot(hd));
     }
     }
-    if (l == 0) { wc[w] = c; wh[w] = h; }
+    if (l == 0) { wc[s][w] = c; wh[s][w] = h; }
+    }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t tc = 0, th = 0;
-        for (int i = 0; i < NW; ++i) { tc += wc[i]; th += wh[i]; }
-        tile_cnt[blockIdx.x] = tc; tile_heads[blockIdx.x] = th;
+    // wave s: the totals of tile s, one lane per wave of the tile
+    if (w < SPAN && tile0 + w < tiles) {
+        static_assert(NW == 16, "xor steps 8 .. 1");
+        uint32_t tc = l < NW ? wc[w][l] : 0u, th = l < NW ? wh[w][l] : 0u;
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) { tc += (uint32_t)__shfl_xor((int)tc, o, WAVE); th += (uint32_t)__shfl_xor((int)th, o, WAVE); }
+        if (l == 0) { tile_cnt[tile0 + w] = tc; tile_heads[tile0 + w] = th; }
     }
 }
 

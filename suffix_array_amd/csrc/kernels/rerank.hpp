@@ -11,6 +11,7 @@ namespace sa {
 // doubling rounds (slot of its LAST element) + 1, see TAIL in k_rr_apply.
 //   k_rr_count : per tile, how many elements stay tied with a neighbour, and the last group
 //                head slot (+1) inside the tile; dense rounds: also the tile's first group start
+//                (the byte forms: one workgroup per RR_COUNT_SPAN tiles, still one entry per tile)
 //   k_rr_scan  : exclusive sum / exclusive max over the tiles (one workgroup)
 //   k_rr_scan_next : dense rounds: for every tile the first group start behind it (one workgroup)
 //   k_rr_apply : SA[U[j]] = V[j] (dense rounds: only for the elements that leave the list); ISA[V[j]] = rank;
@@ -85,19 +86,33 @@ __device__ __forceinline__ WaveGroups rr_wave_classify(const KeyT *__restrict__ 
 // its bytes into 8 head bits, and the wave's 64 such bytes ARE head[0 .. 7] in order: four lanes' bytes are joined into a word
 // and sixteen v_readlane fetch them.  (Measured on C3, 2^28 slots: byte loads in the wave-striped layout of the keys -- eight
 // 64-byte loads per wave -- left k_rr_count at 427 us, 0.63 TB/s: bound by load instructions, not bytes.)
+// The bytes one wave classifies: lane l holds those of elements 8 l .. 8 l + 7 of the wave, every lane the byte of the element
+// behind the wave (`none` when the list ends there).  Loading is a step of its own so that a workgroup of k_rr_count can issue
+// the loads of all the tiles of its span before it classifies the first.
+struct WaveBytes { uint2 w; uint32_t fa; };
+__device__ __forceinline__ WaveBytes rr_wave_load_bytes(const uint8_t *__restrict__ bytes, int64_t m, int64_t wbase, uint8_t none)
+{
+    const int64_t i0 = wbase + 8 * lane_id();
+    const int64_t a = wbase + RR_WAVE_ELEMS;                    // (uniform) the element behind the wave
+    WaveBytes b;
+    b.w = i0 < m ? *(const uint2 *)(bytes + i0) : make_uint2(0u, 0u);
+    // (loaded here, next to the wave's own: the kernels that call this do so little per tile that the memory round trips in a
+    // row, not the bytes, are their time)
+    b.fa = a < m ? (uint32_t)bytes[a] : (uint32_t)none;
+    return b;
+}
+
 template <bool PARENTS = false>
-__device__ __forceinline__ WaveGroups rr_wave_classify_flags(const uint8_t *__restrict__ flags, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase)
+__device__ __forceinline__ WaveGroups rr_wave_classify_flags(const WaveBytes &raw, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase)
 {
     const int l = lane_id();
     WaveGroups g;
     const int64_t i0 = wbase + 8 * l;                           // this lane's eight elements
     const int64_t a = wbase + RR_WAVE_ELEMS;                    // (uniform) the element behind the wave
-    // (its flag is loaded here, next to the wave's own: the kernels that call this do so little per tile that the memory round
-    // trips in a row, not the bytes, are their time)
-    const uint8_t fa = a < m ? flags[a] : OS_HF_START;
+    const uint32_t fa = raw.fa;
     uint32_t hb = 0;                                            // bit k: element i0 + k starts a group
     if (i0 < m) {
-        const uint2 w = *(const uint2 *)(flags + i0);
+        const uint2 w = raw.w;
         // bit 0 of every byte (OS_HF_START) -> four bits per word
         hb = (((w.x & 0x01010101u) * 0x01020408u) >> 24 & 15u) | ((((w.y & 0x01010101u) * 0x01020408u) >> 24 & 15u) << 4);
         if ((w.x | w.y) & 0x02020202u) {                        // (rare: the first element of a digit run of a tile of the sort)
@@ -134,14 +149,22 @@ __device__ __forceinline__ WaveGroups rr_wave_classify_flags(const uint8_t *__re
     return g;
 }
 
+template <bool PARENTS = false>
+__device__ __forceinline__ WaveGroups rr_wave_classify_flags(const uint8_t *__restrict__ flags, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase)
+{
+    return rr_wave_classify_flags<PARENTS>(rr_wave_load_bytes(flags, m, wbase, OS_HF_START), keys, m, wbase);
+}
+
 // The same masks from the status bytes of a dense doubling round (RS_*, kernels/common.hpp): one byte per place of the tied list
 // instead of its 8-byte key, loaded and transposed as above (one 8-byte load per lane, v_readlane).  `keys` is the round's key
 // buffer and holds true keys only at RS_KEYED places -- the members the local pass did not own, which on a text with long repeats
 // are tens of millions in long runs: a lane that has such a place among its eight reads its eight keys as one contiguous 64
 // bytes (and the key before them when its first place needs it) and compares neighbours without a branch per element; the keys
 // of the places that are not KEYED are read with them and masked out.  phead: RS_PHEAD.
+// (Measured on C3: a wave-striped read of the wave's 512 keys where most lanes need them, neighbours from shuffles, chosen per
+// wave from a ballot -- thresholds of 8, 16, 32 and 48 lanes -- was no faster than this read in k_rr_count or k_rr_apply: CHANGELOG.)
 template <bool PARENTS = false>
-__device__ __forceinline__ WaveGroups rr_wave_classify_status(const uint8_t *__restrict__ status, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase_in)
+__device__ __forceinline__ WaveGroups rr_wave_classify_status(const WaveBytes &raw, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase_in)
 {
     const int l = lane_id();
     WaveGroups g;
@@ -150,10 +173,10 @@ __device__ __forceinline__ WaveGroups rr_wave_classify_status(const uint8_t *__r
     const int64_t wbase = ((int64_t)__builtin_amdgcn_readfirstlane((int)(wbase_in >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wbase_in);
     const int64_t i0 = wbase + 8 * l;                           // this lane's eight places
     const int64_t a = wbase + RR_WAVE_ELEMS;                    // (uniform) the place behind the wave
-    const uint8_t fa = a < m ? status[a] : RS_PHEAD;
+    const uint32_t fa = raw.fa;
     uint32_t hb = 0, pb = 0;                                    // bit k: place i0 + k starts a group / a parent group
     if (i0 < m) {
-        const uint2 w = *(const uint2 *)(status + i0);
+        const uint2 w = raw.w;
         // bit `b` of every byte -> eight bits
         auto plane = [&](int b) -> uint32_t {
             return ((((w.x >> b) & 0x01010101u) * 0x01020408u) >> 24 & 15u) | (((((w.y >> b) & 0x01010101u) * 0x01020408u) >> 24 & 15u) << 4);
@@ -217,6 +240,12 @@ __device__ __forceinline__ WaveGroups rr_wave_classify_status(const uint8_t *__r
     return g;
 }
 
+template <bool PARENTS = false>
+__device__ __forceinline__ WaveGroups rr_wave_classify_status(const uint8_t *__restrict__ status, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase)
+{
+    return rr_wave_classify_status<PARENTS>(rr_wave_load_bytes(status, m, wbase, RS_PHEAD), keys, m, wbase);
+}
+
 // "head code" of the dense doubling rounds: (list index of a group start << 1) | (it also starts a parent group);
 // RR_NO_HEAD: there is none (list indices are below 2^31, so the code of index m with the parent bit set is the same word)
 constexpr uint32_t RR_NO_HEAD = 0xffffffffu;
@@ -235,12 +264,35 @@ __device__ __forceinline__ uint32_t rr_first_head_code(const WaveGroups &g, int6
     return code;
 }
 
+// Tiles one workgroup of the counting kernels covers when a member is one byte (k_rr_count<.., FLAGS>, k_flag_count<STATUS>,
+// kernels/refine.hpp): at one 8-byte load per lane a workgroup that covers a single tile has 8 KiB in flight and lives for one
+// memory round trip after the other -- a CU holds two such workgroups and waits.  The loads of the whole span are issued before
+// the first tile is classified, and the span ends in ONE barrier.  Every tile still gets its own tile_cnt / tile_head /
+// tile_first entry: the scans and k_rr_apply see RR_TILE tiles as before.
+constexpr int RR_COUNT_SPAN = 4;
+static_assert(RR_COUNT_SPAN <= RR_THREADS / WAVE, "wave s of the workgroup reduces tile s of the span");
+template <bool BYTES> constexpr int rr_count_span() { return BYTES ? RR_COUNT_SPAN : 1; }
+
+// sum / maximum / minimum of a, b, c over each aligned group of 16 lanes (the 16 waves of a tile), in every lane of the group
+__device__ __forceinline__ void rr_reduce16(uint32_t &a, uint32_t &b, uint32_t &c)
+{
+    static_assert(RR_THREADS / WAVE == 16, "one lane per wave of the tile");
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+        const uint32_t ta = (uint32_t)__shfl_xor((int)a, o, WAVE), tb = (uint32_t)__shfl_xor((int)b, o, WAVE), tc = (uint32_t)__shfl_xor((int)c, o, WAVE);
+        a += ta; b = b > tb ? b : tb; c = c < tc ? c : tc;
+    }
+}
+
 // PARENTS (dense doubling rounds): also tile_first, the head code of the tile's first group start (g_shift: the parent
 // group is the key above that bit)
 // FLAGS: FIRST: the groups come from head_flags (rr_wave_classify_flags), `keys` is the flag pass's sparsely written key buffer;
 // a round (PARENTS): head_flags = the round's status bytes (rr_wave_classify_status), `keys` holds true keys at RS_KEYED places only
+// A workgroup covers rr_count_span<FLAGS>() consecutive tiles (grid: rr_count_grid).  Its waves carry the LIST INDEX of their last
+// group start, not its slot: slots grow with the index, so the tile's last group start is the largest index, and U is read once
+// per tile, by the lane that writes tile_head, instead of once per wave in the middle of every wave's chain.
 template <bool FIRST, typename KeyT = uint64_t, bool PARENTS = false, bool FLAGS = false>
-__global__ __launch_bounds__(RR_THREADS) void k_rr_count(const KeyT *__restrict__ keys,
+__global__ __launch_bounds__(RR_THREADS) __attribute__((amdgpu_waves_per_eu(8))) void k_rr_count(const KeyT *__restrict__ keys,
                                                           const uint32_t *__restrict__ U, int64_t m,
                                                           uint32_t *__restrict__ tile_cnt,
                                                           uint32_t *__restrict__ tile_head, int key_shift,
@@ -249,22 +301,54 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_count(const KeyT *__restrict_
                                                           const uint8_t *__restrict__ head_flags = nullptr)
 {
     static_assert(!FLAGS || (sizeof(KeyT) == 8 && (FIRST || PARENTS)), "group-start flags come from the 64-bit initial sort, status bytes from a dense round");
-    __shared__ uint32_t wcnt[RR_THREADS / WAVE], whead[RR_THREADS / WAVE], wfirst[RR_THREADS / WAVE];
+    constexpr int SPAN = rr_count_span<FLAGS>();
+    constexpr int NW = RR_THREADS / WAVE;
+    __shared__ uint32_t wcnt[SPAN][NW], whead[SPAN][NW], wfirst[SPAN][NW];
     if (gate && *gate) return;
-    const int64_t wbase = (int64_t)blockIdx.x * RR_TILE + (int64_t)wave_id() * RR_WAVE_ELEMS;
+#ifdef SA_AMD_DIAG
+    // diagnostic library only (sa_amd_debug_rr_count_stamps): cycles of wave 0 per phase, summed over the workgroups
+    // (tools/rr_count_stamps.py); a stamp with `wait` first waits for everything the wave has outstanding.  The cycles are
+    // added to the counters behind the last stamp: an atomic per stamp would be waited for by the next one.
+    const bool stamping = g_rr_stamp_on != 0 && threadIdx.x == 0;
+    unsigned long long t_prev = stamping ? __builtin_amdgcn_s_memtime() : 0ull, t_phase[4] = { 0ull, 0ull, 0ull, 0ull };
+    auto stamp = [&](int phase, bool wait) {
+        if (stamping) {
+            if (wait) __builtin_amdgcn_s_waitcnt(0);
+            const unsigned long long now = __builtin_amdgcn_s_memtime();
+            t_phase[phase] = now - t_prev;
+            t_prev = now;
+            if (phase == 3)
+                for (int p = 0; p < 4; ++p) atomicAdd(&g_phase_cycles[p], t_phase[p]);
+        }
+    };
+#else
+    auto stamp = [](int, bool) {};
+#endif
+    // (the wave's number is the same in every lane, which the compiler cannot see from threadIdx.x >> 6: said here, the masks
+    // of the span's tiles are scalar values)
+    const int w = __builtin_amdgcn_readfirstlane(wave_id());
+    const int64_t tiles = (m + RR_TILE - 1) / RR_TILE;
+    const int64_t tile0 = (int64_t)blockIdx.x * SPAN;
+    WaveBytes raw[SPAN];
+    if constexpr (FLAGS) {
+#pragma unroll
+        for (int s = 0; s < SPAN; ++s)      // (a tile behind the last one: nothing is loaded, nothing is valid, nothing is written)
+            raw[s] = rr_wave_load_bytes(head_flags, m, (tile0 + s) * RR_TILE + (int64_t)w * RR_WAVE_ELEMS, FIRST ? OS_HF_START : RS_PHEAD);
+    }
+    stamp(0, false);      // byte loads of the span issued
+#pragma unroll
+    for (int s = 0; s < SPAN; ++s) {
+    const int64_t wbase = (tile0 + s) * RR_TILE + (int64_t)w * RR_WAVE_ELEMS;
     uint64_t kk[RR_ITEMS + 1];
     WaveGroups g;
-    if constexpr (FLAGS && FIRST) g = rr_wave_classify_flags<false>(head_flags, (const uint64_t *)keys, m, wbase);
-    else if constexpr (FLAGS) g = rr_wave_classify_status<true>(head_flags, (const uint64_t *)keys, m, wbase);
+    if constexpr (FLAGS && FIRST) g = rr_wave_classify_flags<false>(raw[s], (const uint64_t *)keys, m, wbase);
+    else if constexpr (FLAGS) g = rr_wave_classify_status<true>(raw[s], (const uint64_t *)keys, m, wbase);
     else g = rr_wave_classify<KeyT, false>(keys, m, wbase, key_shift, 0, PARENTS ? kk : nullptr);
-    uint32_t cnt = 0, lasthead = 0;
+    uint32_t cnt = 0, lasthead = 0;                             // lasthead: list index of the wave's last group start, + 1
 #pragma unroll
     for (int r = 0; r < RR_ITEMS; ++r) {
         cnt += (uint32_t)__popcll(g.tied[r]);
-        if (g.head[r]) {
-            const int64_t i = wbase + 64 * r + (63 - __builtin_clzll(g.head[r]));
-            lasthead = (FIRST ? (uint32_t)i : U[i]) + 1u;       // slots grow with the index: the last head wins
-        }
+        if (g.head[r]) lasthead = (uint32_t)(wbase + 64 * r + (63 - __builtin_clzll(g.head[r]))) + 1u;
     }
     // the wave's first group start, and whether its parent group starts there too: only that one element's key and its left
     // neighbour's are compared (wave-uniform item and lane: two shuffles, not a ballot per item)
@@ -288,16 +372,26 @@ __global__ __launch_bounds__(RR_THREADS) void k_rr_count(const KeyT *__restrict_
             }
         }
     }
-    if (lane_id() == 0) { wcnt[wave_id()] = cnt; whead[wave_id()] = lasthead; wfirst[wave_id()] = first_code; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t tot = 0, mx = 0, fc = RR_NO_HEAD;
-        for (int w = 0; w < RR_THREADS / WAVE; ++w) { tot += wcnt[w]; mx = mx > whead[w] ? mx : whead[w]; fc = fc < wfirst[w] ? fc : wfirst[w]; }
-        tile_cnt[blockIdx.x] = tot;
-        tile_head[blockIdx.x] = mx;
-        if (PARENTS) tile_first[blockIdx.x] = fc;
+    if (lane_id() == 0) { wcnt[s][w] = cnt; whead[s][w] = lasthead; wfirst[s][w] = first_code; }
     }
+    stamp(1, true);       // the span classified (waits for the bytes; a round: and for the keys of the KEYED places)
+    __syncthreads();
+    stamp(2, true);       // barrier: the slowest wave of the workgroup
+    // wave s: the totals of tile s, one lane per wave of the tile
+    if (w < SPAN && tile0 + w < tiles) {
+        const int l = lane_id();
+        uint32_t tot = l < NW ? wcnt[w][l] : 0u, mx = l < NW ? whead[w][l] : 0u, fc = l < NW ? wfirst[w][l] : RR_NO_HEAD;
+        rr_reduce16(tot, mx, fc);
+        if (l == 0) {
+            tile_cnt[tile0 + w] = tot;
+            tile_head[tile0 + w] = (FIRST || mx == 0u) ? mx : U[mx - 1u] + 1u;     // slot of the tile's last group start, + 1
+            if (PARENTS) tile_first[tile0 + w] = fc;
+        }
+    }
+    stamp(3, true);       // wave reduction, the tile's one look-up in U, stores
 }
+// workgroups of a counting launch over the tiles of m members
+template <bool BYTES> inline unsigned rr_count_grid(int64_t m) { return (unsigned)(((m + RR_TILE - 1) / RR_TILE + rr_count_span<BYTES>() - 1) / rr_count_span<BYTES>()); }
 
 // one workgroup: tile_first (head code of every tile's first group start) -> for every tile the smallest code of the tiles
 // BEHIND it (RR_NO_HEAD: no group starts behind this tile); also clears the round's changed-rank counter

@@ -15,6 +15,8 @@ extern "C" {
 int32_t sa_amd_debug_phase_cycles(uint64_t *out, int32_t count);
 /* k_group_sort: switch its per-phase stamps on / off (entries 8..13 of the same array) */
 int32_t sa_amd_debug_group_sort_stamps(int32_t on);
+/* k_rr_count: switch its per-phase stamps on / off (entries 0..7 of the same array; tools/rr_count_stamps.py) */
+int32_t sa_amd_debug_rr_count_stamps(int32_t on);
 /* the old forms of the dense route's re-rank writes, for A/B and the route tests (process-wide; returns the previous flags):
  * bit 0: dense rounds write SA for every listed suffix each round (not only in the round it leaves the list),
  * bit 1: the binned rank set-up copies SA into its pair keys (instead of binning straight from the suffix array) */

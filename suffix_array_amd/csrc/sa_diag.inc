@@ -19,6 +19,12 @@ SA_EXPORT int32_t sa_amd_debug_group_sort_stamps(int32_t on)
     return hipMemcpyToSymbol(HIP_SYMBOL(sa::g_gs_stamp_on), &v, sizeof(v)) == hipSuccess ? SA_AMD_OK : SA_AMD_EHIP;
 }
 
+SA_EXPORT int32_t sa_amd_debug_rr_count_stamps(int32_t on)
+{
+    const int v = on ? 1 : 0;
+    return hipMemcpyToSymbol(HIP_SYMBOL(sa::g_rr_stamp_on), &v, sizeof(v)) == hipSuccess ? SA_AMD_OK : SA_AMD_EHIP;
+}
+
 SA_EXPORT int32_t sa_amd_debug_rerank_routes(int32_t flags)
 {
     return sa::g_rerank_routes.exchange(flags & 3);
