@@ -916,6 +916,74 @@ void sa_amd_last_ngram_stats(sa_amd_ngram_stats *out);
  * previous value. */
 int32_t sa_amd_ngram_set_stream_cap(int32_t slots);
 
+/*
+ * Scoring a text under the infinity-gram model (an extension): for every position of a query the back-off of
+ * sa_amd_index_infgram and the count of the byte that is really there, on the device.  T has n bytes,
+ * SA has n + 1 slots; "range of a string" is the [lo, hi) that sa_amd_index_search reports; at_end and next[b] are those of
+ * sa_amd_index_next_bytes.
+ *   Q has m bytes.  q_off has ndocs + 1 entries, q_off[0] = 0, non-decreasing, q_off[ndocs] = m: document d is
+ *   Q[q_off[d] .. q_off[d + 1]), empty documents are allowed.  q_off == NULL means one document [0, m) (ndocs is ignored).
+ * For position j of the document that starts at `start`:
+ *   cap_j  = min(j - start, max_len): a context never crosses a document start.
+ *   S[j]   = the largest s in 0 .. cap_j such that Q[j - s .. j) has hi - lo >= min_count.  s = 0 always qualifies, with the
+ *            range [0, n + 1) and at_end = 1.  It is what sa_amd_index_infgram returns as suffix_len for the prompt
+ *            Q[start .. j) with the same min_count and max_len.
+ *   LO[j], HI[j], AT_END[j] = that suffix's range and at-end flag, again sa_amd_index_infgram's.
+ *   NLO[j] = LO + AT_END + sum(next[b'] for b' < Q[j]),  NHI[j] = NLO + next[Q[j]].
+ *   Where NHI > NLO, [NLO, NHI) is the range of Q[j - s .. j]; where the continuation does not occur, NHI == NLO is its
+ *   insertion point inside the context's range.
+ * The model's probability of Q[j] is (NHI - NLO) / (HI - LO - AT_END); the denominator is 0 when the context occurs only as
+ * the text's last bytes.
+ *   T = "abracadabra", Q = "xcabra", one document, min_count = 1, max_len = 4:
+ *     j  byte  S  [LO, HI)  AT_END  [NLO, NHI)
+ *     0  x     0  [0, 12)   1       [12, 12)
+ *     1  c     0  [0, 12)   1       [8, 9)
+ *     2  a     1  [8, 9)    0       [8, 9)
+ *     3  b     2  [8, 9)    0       [8, 8)
+ *     4  r     2  [2, 4)    0       [2, 4)
+ *     5  a     3  [2, 4)    0       [2, 4)
+ *   With min_count = 3, position 5 has S = 0: its context ends in "r", which occurs twice.
+ * The length is found by galloping (s = 1, 2, 4, ... clamped to cap_j) and a bisection between the last good and the first
+ * bad length: at most 2 ceil(log2(S[j] + 2)) + 2 range searches for position j, whatever the group cap below.
+ * EVERY output pointer may be NULL.  m == 0 succeeds.  Errors, each with nothing written: a NULL index, m < 0, min_count < 1,
+ * max_len outside 1 .. SA_AMD_SCORE_MAX_CONTEXT, with q_off: ndocs < 0 or offsets that break the rules above: SA_AMD_EINVAL.
+ * If the resident array is not the suffix array of the text the answers are unspecified, but the reads obey the rules of
+ * sa_amd_index_next_bytes: every slot read lies in [0, n + 1), every SA entry is checked against n in 64 bits before T is
+ * read through it, Q is read inside [0, m) only and nothing is written outside the outputs.  The answers are the same with or
+ * without the bucket table and the LCP table, and for every group cap.
+ */
+#define SA_AMD_SCORE_MAX_CONTEXT 4096
+int32_t sa_amd_index_infgram_score(const sa_amd_index *ix, const uint8_t *Q, int64_t m, const int64_t *q_off, int64_t ndocs,
+                                   int32_t min_count, int32_t max_len, uint32_t *S, uint32_t *LO, uint32_t *HI, uint8_t *AT_END,
+                                   uint32_t *NLO, uint32_t *NHI);
+/* bytes of work space for the device form below; -1 when m or ndocs is negative */
+int64_t sa_amd_score_work_bytes(int64_t m, int64_t ndocs);
+/* the same code path on device-resident data: dQ and the outputs live on the index's device (any of the outputs NULL), q_off
+ * stays a HOST pointer (it is checked, then copied into the work space), dWork is 256-byte aligned with at least
+ * sa_amd_score_work_bytes(m, ndocs) bytes (ndocs = 1 where q_off is NULL).  Blocks until done. */
+int32_t sa_amd_index_infgram_score_device(const sa_amd_index *ix, const uint8_t *dQ, int64_t m, const int64_t *q_off, int64_t ndocs,
+                                          int32_t min_count, int32_t max_len, uint32_t *dS, uint32_t *dLO, uint32_t *dHI,
+                                          uint8_t *dAT_END, uint32_t *dNLO, uint32_t *dNHI, void *dWork, int64_t work_bytes,
+                                          void *stream);
+
+typedef struct sa_amd_score_stats {  /* of the calling thread's most recent infgram_score call (no other feature's statistics are touched) */
+    int64_t positions;               /* m */
+    int64_t documents;               /* ndocs; 1 where q_off is NULL */
+    int64_t group_searches;          /* range searches of the group path (8 lanes a position, the context in LDS) */
+    int64_t long_searches;           /* range searches of the long path (one wave a position) */
+    int64_t next_lookups;            /* slots probed by the two lower bounds on the byte behind the context, all positions */
+    int64_t compared_bytes;          /* text bytes the range searches compared, chunks charged whole (32 on the group path, up to 64 on the long path) */
+    int64_t long_positions;          /* positions finished by the long path */
+    int64_t zero_positions;          /* positions with NHI == NLO */
+    int32_t group_cap;               /* the cap in effect: min(group cap, max_len, 4096) */
+    int32_t readbacks;               /* blocking device -> host read-backs of counters: 1, or 2 with long positions */
+} sa_amd_score_stats;
+void sa_amd_last_score_stats(sa_amd_score_stats *out);
+/* route switch of the calling thread's later infgram_score calls (never changes a result): context bytes a lane group probes
+ * before the position goes to the one-wave-per-position path, 0 .. 1 048 576 (0: every position with a context; above 4096
+ * acts as 4096); a negative value restores the default (64).  Returns the previous value. */
+int32_t sa_amd_score_set_group_cap(int32_t bytes);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

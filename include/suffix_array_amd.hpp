@@ -395,6 +395,33 @@ public:
         for (std::size_t q = 0; q < out.size(); ++q) out[q].suffix_len = slen[q];
         return out;
     }
+    // a text scored under the infinity-gram model (suffix_array_amd.h, "Scoring a text under the infinity-gram model"): per
+    // position of the query the back-off length s, the context's range [lo, hi) and at_end, and [nlo, nhi), the part of that
+    // range which the query's byte follows.  count() / total() are the numerator and the denominator of its probability.
+    struct Score {
+        std::vector<std::uint32_t> s, lo, hi, nlo, nhi;
+        std::vector<std::uint8_t> at_end;
+        std::size_t size() const { return s.size(); }
+        std::uint32_t count(std::size_t j) const { return nhi[j] - nlo[j]; }
+        std::uint32_t total(std::size_t j) const { return hi[j] - lo[j] - at_end[j]; }
+    };
+    // doc_offsets: ndocs + 1 non-decreasing values from 0 to query.size(), or empty for one document; a context never reaches
+    // back over the start of its position's document.  1 <= max_len <= SA_AMD_SCORE_MAX_CONTEXT.
+    Score infgram_score(const std::string &query, std::int32_t min_count = 1, std::int32_t max_len = SA_AMD_SCORE_MAX_CONTEXT,
+                        const std::vector<std::int64_t> &doc_offsets = {}) const
+    {
+        if (min_count < 1) throw std::invalid_argument("min_count must be at least 1");
+        if (max_len < 1 || max_len > SA_AMD_SCORE_MAX_CONTEXT) throw std::invalid_argument("max_len must be 1 .. SA_AMD_SCORE_MAX_CONTEXT");
+        const std::size_t m = query.size();
+        Score r;
+        r.s.resize(m + 1); r.lo.resize(m + 1); r.hi.resize(m + 1); r.nlo.resize(m + 1); r.nhi.resize(m + 1); r.at_end.resize(m + 1);
+        check(sa_amd_index_infgram_score(ix_, reinterpret_cast<const std::uint8_t *>(query.data()), static_cast<std::int64_t>(m),
+                                         doc_offsets.empty() ? nullptr : doc_offsets.data(),
+                                         doc_offsets.empty() ? 0 : static_cast<std::int64_t>(doc_offsets.size()) - 1, min_count, max_len, r.s.data(),
+                                         r.lo.data(), r.hi.data(), r.at_end.data(), r.nlo.data(), r.nhi.data()));
+        r.s.resize(m); r.lo.resize(m); r.hi.resize(m); r.nlo.resize(m); r.nhi.resize(m); r.at_end.resize(m);
+        return r;
+    }
 
 private:
     template <class Row>

@@ -38,7 +38,9 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "DOC_CHUNK_MIN", "DOC_CHUNK_MAX", "DOC_CHUNK_DEFAULT",
            "DocTfStats", "last_doc_tf_stats", "docs_set_topk_piece", "DOC_TOPK_MAX", "DOC_TOPK_PIECE_MIN", "DOC_TOPK_PIECE_MAX",
            "DOC_TOPK_PIECE_DEFAULT",
-           "NgramStats", "last_ngram_stats", "ngram_set_stream_cap", "NGRAM_STREAM_CAP_DEFAULT"]
+           "NgramStats", "last_ngram_stats", "ngram_set_stream_cap", "NGRAM_STREAM_CAP_DEFAULT",
+           "ScoreStats", "ScoreResult", "last_score_stats", "score_set_group_cap", "score_work_bytes", "infgram_score_device_ptr",
+           "SCORE_MAX_CONTEXT", "SCORE_GROUP_CAP_DEFAULT", "SCORE_TILE"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
@@ -199,6 +201,66 @@ class NgramStats(ctypes.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class ScoreStats(ctypes.Structure):
+    """sa_amd_score_stats of include/suffix_array_amd.h"""
+    _fields_ = [("positions", ctypes.c_int64), ("documents", ctypes.c_int64), ("group_searches", ctypes.c_int64),
+                ("long_searches", ctypes.c_int64), ("next_lookups", ctypes.c_int64), ("compared_bytes", ctypes.c_int64),
+                ("long_positions", ctypes.c_int64), ("zero_positions", ctypes.c_int64), ("group_cap", ctypes.c_int32),
+                ("readbacks", ctypes.c_int32)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["range_searches"] = d["group_searches"] + d["long_searches"]
+        return d
+
+
+#: the longest context ``infgram_score`` takes (SA_AMD_SCORE_MAX_CONTEXT: what a tile stages)
+SCORE_MAX_CONTEXT = 4096
+#: context bytes the lane groups of ``infgram_score`` probe before a position goes to the one-wave path (kernels/score.hpp)
+SCORE_GROUP_CAP_DEFAULT = 64
+#: query positions per workgroup of ``infgram_score``
+SCORE_TILE = 256
+
+
+class ScoreResult:
+    """What ``infgram_score`` returns, arrays over the positions of the query: ``s`` (the back-off length), ``lo`` / ``hi`` /
+    ``at_end`` (the context's range and at-end flag) and ``nlo`` / ``nhi`` (the sub-range of the context followed by the byte
+    that is there)."""
+
+    def __init__(self, s, lo, hi, at_end, nlo, nhi):
+        self.s, self.lo, self.hi, self.at_end, self.nlo, self.nhi = s, lo, hi, at_end, nlo, nhi
+
+    def __iter__(self):
+        return iter((self.s, self.lo, self.hi, self.at_end, self.nlo, self.nhi))
+
+    def __len__(self):
+        return int(self.s.size)
+
+    def counts(self):
+        """-> ``(count, total)`` int64: occurrences of the context followed by the byte, and followed by any byte"""
+        cnt = self.nhi.astype(np.int64) - self.nlo.astype(np.int64)
+        den = self.hi.astype(np.int64) - self.lo.astype(np.int64) - self.at_end.astype(np.int64)
+        return cnt, den
+
+    def log2_prob(self) -> np.ndarray:
+        """float64 ``log2`` of the model's probability of every byte; ``-inf`` where the count or the denominator is 0"""
+        cnt, den = self.counts()
+        out = np.full(cnt.size, -np.inf, dtype=np.float64)
+        ok = (cnt > 0) & (den > 0)
+        out[ok] = np.log2(cnt[ok].astype(np.float64)) - np.log2(den[ok].astype(np.float64))
+        return out
+
+    def doc_bits(self, doc_offsets=None):
+        """-> ``(bits, zeros)`` per document of ``doc_offsets`` (``None``: one document): the sum of ``-log2 p`` over the
+        positions with ``p > 0`` and the number of positions with ``p = 0`` -- how those are smoothed is the caller's policy"""
+        lp = self.log2_prob()
+        off = np.array([0, lp.size], dtype=np.int64) if doc_offsets is None else np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        fin = np.isfinite(lp)
+        cb = np.concatenate(([0.0], np.cumsum(np.where(fin, -lp, 0.0))))
+        cz = np.concatenate(([0], np.cumsum(~fin))).astype(np.int64)
+        return cb[off[1:]] - cb[off[:-1]], cz[off[1:]] - cz[off[:-1]]
 
 
 #: slots up to which ``next_bytes`` / ``infgram`` stream a range instead of searching its run starts (kernels/ngram.hpp)
@@ -463,6 +525,18 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_last_ngram_stats.restype = None
         L.sa_amd_ngram_set_stream_cap.argtypes = [ctypes.c_int32]
         L.sa_amd_ngram_set_stream_cap.restype = ctypes.c_int32
+        L.sa_amd_index_infgram_score.argtypes = [c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp,
+                                                 c_vp, c_vp, c_vp]
+        L.sa_amd_index_infgram_score.restype = ctypes.c_int32
+        L.sa_amd_index_infgram_score_device.argtypes = [c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp,
+                                                        c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_index_infgram_score_device.restype = ctypes.c_int32
+        L.sa_amd_score_work_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
+        L.sa_amd_score_work_bytes.restype = ctypes.c_int64
+        L.sa_amd_last_score_stats.argtypes = [c_vp]
+        L.sa_amd_last_score_stats.restype = None
+        L.sa_amd_score_set_group_cap.argtypes = [ctypes.c_int32]
+        L.sa_amd_score_set_group_cap.restype = ctypes.c_int32
         L.sa_amd_docs_set_topk_piece.argtypes = [ctypes.c_int32]
         L.sa_amd_docs_set_topk_piece.restype = ctypes.c_int32
         _lib = L
@@ -1156,6 +1230,46 @@ def ngram_set_stream_cap(slots: int) -> int:
     return int(lib().sa_amd_ngram_set_stream_cap(max(-1, min(int(slots), 2**31 - 1))))
 
 
+def last_score_stats() -> dict:
+    """positions / documents / group_searches / long_searches / range_searches (their sum) / next_lookups / compared_bytes /
+    long_positions / zero_positions / group_cap / readbacks of this thread's most recent ``infgram_score`` call"""
+    st = ScoreStats()
+    lib().sa_amd_last_score_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def score_set_group_cap(nbytes: int) -> int:
+    """Route switch of this thread's later ``infgram_score`` calls (never changes a result): context bytes a lane group probes
+    before the position goes to the one-wave-per-position path, 0 .. 1 048 576 (0: every position with a context; above 4096
+    acts as 4096); negative restores ``SCORE_GROUP_CAP_DEFAULT``.  Returns the previous value."""
+    return int(lib().sa_amd_score_set_group_cap(max(-1, min(int(nbytes), 2**31 - 1))))
+
+
+def score_work_bytes(m: int, ndocs: int = 1) -> int:
+    return int(lib().sa_amd_score_work_bytes(int(m), int(ndocs)))
+
+
+def _score_offsets(doc_offsets):
+    if doc_offsets is None:
+        return None, 0
+    off = np.ascontiguousarray(doc_offsets)
+    if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu":
+        raise SuffixArrayError(-1, "infgram_score: doc_offsets are ndocs + 1 integers")
+    off = off.astype(np.int64)
+    return off, int(off.size - 1)
+
+
+def infgram_score_device_ptr(index, query_ptr: int, m: int, min_count: int, max_len: int, s_ptr: int, lo_ptr: int, hi_ptr: int,
+                             at_end_ptr: int, nlo_ptr: int, nhi_ptr: int, work_ptr: int, work_bytes: int, doc_offsets=None,
+                             stream: int = 0) -> None:
+    """Device-resident ``infgram_score`` of ``m`` query bytes against ``index`` (a ``DeviceIndex``; raw device pointers on its
+    device, any output may be 0; ``doc_offsets`` stays a host array); blocks until done."""
+    off, ndocs = _score_offsets(doc_offsets)
+    _check(lib().sa_amd_index_infgram_score_device(_index_handle(index), query_ptr or None, int(m), off.ctypes.data if off is not None else None,
+                                                   ndocs, int(min_count), int(max_len), s_ptr or None, lo_ptr or None, hi_ptr or None,
+                                                   at_end_ptr or None, nlo_ptr or None, nhi_ptr or None, work_ptr or None, int(work_bytes), stream))
+
+
 def doc_of_device_ptr(index, pos_ptr: int, count: int, doc_ptr: int, stream: int = 0) -> None:
     """Device-resident ``doc_of``: ``count`` uint32 positions at ``pos_ptr`` -> their documents at ``doc_ptr`` (raw device pointers
     on the index's device, 4-byte aligned); needs no scratch; blocks until done."""
@@ -1448,6 +1562,25 @@ class DeviceIndex:
             raise SuffixArrayError(-1, "infgram: min_count >= 1")
         return self._ngram(prompts, True, min(int(min_count), 2**31 - 1), max(0, min(int(max_len), 2**31 - 1)))
 
+    def infgram_score(self, query, min_count: int = 1, max_len: int = SCORE_MAX_CONTEXT, doc_offsets=None) -> ScoreResult:
+        """EXTENSION: score ``query`` under the infinity-gram model -> ``ScoreResult``.  For every position ``j`` the context is
+        the longest ``query[j - s:j]`` -- of at most ``max_len`` bytes (1 .. ``SCORE_MAX_CONTEXT``), never reaching back over the
+        start of ``j``'s document -- that occurs at least ``min_count`` times: exactly ``infgram`` of the prompt
+        ``query[start:j]``.  ``s``, ``lo`` / ``hi`` / ``at_end`` describe it, ``[nlo, nhi)`` is the part of its range that
+        ``query[j]`` follows (empty, at its insertion point, where it never does).  ``doc_offsets``: ``ndocs + 1`` non-decreasing
+        values from 0 to ``len(query)``; ``None`` is one document.  The query is read once on the device."""
+        q = _as_u8(query)
+        if int(min_count) < 1:
+            raise SuffixArrayError(-1, "infgram_score: min_count >= 1")
+        off, ndocs = _score_offsets(doc_offsets)
+        m = int(q.size)
+        s, lo, hi, nlo, nhi = (np.zeros(m, dtype=np.uint32) for _ in range(5))
+        ae = np.zeros(m, dtype=np.uint8)
+        _check(lib().sa_amd_index_infgram_score(self._h, q.ctypes.data if m else None, m, off.ctypes.data if off is not None else None, ndocs,
+                                                min(int(min_count), 2**31 - 1), max(-1, min(int(max_len), 2**31 - 1)), s.ctypes.data, lo.ctypes.data,
+                                                hi.ctypes.data, ae.ctypes.data, nlo.ctypes.data, nhi.ctypes.data))
+        return ScoreResult(s, lo, hi, ae, nlo, nhi)
+
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): build and keep the LCP table of the
         search tree (8 (n + 1) bytes); later searches take the LCP route with the same answers.  A no-op when it exists."""
@@ -1715,6 +1848,11 @@ class SuffixArray:
         """EXTENSION (the reference lacks it): the longest suffix of each prompt that occurs ``min_count`` times, and what
         follows it (see ``DeviceIndex.infgram``)"""
         return self._index().infgram(prompts, min_count, max_len)
+
+    def infgram_score(self, query, min_count: int = 1, max_len: int = SCORE_MAX_CONTEXT, doc_offsets=None) -> ScoreResult:
+        """EXTENSION (the reference lacks it): per-position back-off and next-byte counts of ``query`` under the infinity-gram
+        model of the text (see ``DeviceIndex.infgram_score``)"""
+        return self._index().infgram_score(query, min_count, max_len, doc_offsets)
 
     def enable_lcp(self) -> None:
         """EXTENSION (the reference's README TODO "speed up searching by LCP array"): contains / search_all / search_lcp

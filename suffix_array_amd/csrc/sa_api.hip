@@ -31,6 +31,7 @@
 #include "host/substrings.hpp"
 #include "host/doc_substrings.hpp"
 #include "host/ngram.hpp"
+#include "host/score.hpp"
 
 extern "C" {
 
@@ -750,6 +751,49 @@ SA_EXPORT int32_t sa_amd_ngram_set_stream_cap(int32_t slots)
 {
     const int32_t prev = sa::g_ngram_stream_cap < 0 ? sa::NG_STREAM_CAP_DEFAULT : sa::g_ngram_stream_cap;
     sa::g_ngram_stream_cap = slots < 0 ? -1 : (slots > sa::NG_STREAM_CAP_MAX ? sa::NG_STREAM_CAP_MAX : slots);
+    return prev;
+}
+
+// ---- scoring a text under the infinity-gram model (host/score.hpp, kernels/score.hpp) ----
+
+SA_EXPORT int64_t sa_amd_score_work_bytes(int64_t m, int64_t ndocs)
+{
+    if (m < 0 || ndocs < 0 || m > (int64_t)SA_AMD_MAX_LENGTH || ndocs > (int64_t)SA_AMD_MAX_LENGTH) return -1;
+    return (int64_t)sa::score_layout(m, ndocs).bytes;
+}
+
+SA_EXPORT int32_t sa_amd_index_infgram_score(const sa_amd_index *ix, const uint8_t *Q, int64_t m, const int64_t *q_off, int64_t ndocs, int32_t min_count,
+                                             int32_t max_len, uint32_t *S, uint32_t *LO, uint32_t *HI, uint8_t *AT_END, uint32_t *NLO, uint32_t *NHI)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::score_args_valid(m, q_off, ndocs, min_count, max_len) || (m > 0 && !Q)) return SA_AMD_EINVAL;
+    return sa::score_host(*ix, Q, m, q_off, ndocs, min_count, max_len, S, LO, HI, AT_END, NLO, NHI);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_infgram_score_device(const sa_amd_index *ix, const uint8_t *dQ, int64_t m, const int64_t *q_off, int64_t ndocs,
+                                                    int32_t min_count, int32_t max_len, uint32_t *dS, uint32_t *dLO, uint32_t *dHI, uint8_t *dAT_END,
+                                                    uint32_t *dNLO, uint32_t *dNHI, void *dWork, int64_t work_bytes, void *stream)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::score_args_valid(m, q_off, ndocs, min_count, max_len) || (m > 0 && !dQ)) return SA_AMD_EINVAL;
+    sa::DeviceGuard guard(ix->device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    sa::ScoreOut out;
+    out.S = dS; out.LO = dLO; out.HI = dHI; out.AT_END = dAT_END; out.NLO = dNLO; out.NHI = dNHI;
+    return sa::score_device(*ix, dQ, m, q_off, ndocs, min_count, max_len, out, dWork, work_bytes, (hipStream_t)stream);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_score_stats(sa_amd_score_stats *out)
+{
+    if (out) *out = sa::g_last_score_stats;
+}
+
+SA_EXPORT int32_t sa_amd_score_set_group_cap(int32_t bytes)
+{
+    const int32_t prev = sa::g_score_cap < 0 ? sa::SCORE_CAP_DEFAULT : sa::g_score_cap;
+    sa::g_score_cap = bytes < 0 ? -1 : (bytes > sa::SCORE_CAP_MAX ? sa::SCORE_CAP_MAX : bytes);
     return prev;
 }
 
