@@ -66,7 +66,18 @@ int32_t sa_amd_saca_u8(const uint8_t *T, uint32_t *SA, int32_t n);
 int32_t sa_amd_saca_batch(const uint8_t *const *T, uint32_t *const *SA, const int32_t *n,
                           const int32_t *device, int32_t count, int32_t *status);
 
-/* ---- device-resident entry points (text already in HBM; used by bench.py) ---- */
+/* ---- device-resident entry points (text already in HBM; used by bench.py) ----
+ *
+ * The `stream` of every `_device` form, here and below: any hipStream_t of the current device (of the index's device for the
+ * sa_amd_index_* forms) -- NULL = the default stream, a blocking stream or a non-blocking one (hipStreamNonBlocking).
+ *   Everything the call does on the device (kernels, clears of its control words, read-backs, sort passes, the copy of host
+ *     arguments such as q_off) is queued on `stream` and on no other stream.
+ *   So the call orders itself behind the work already queued on `stream`: inputs and a work block that are still being produced
+ *     there need no synchronisation before the call.  Work on OTHER streams is not waited for; that is the caller's job.
+ *   "Blocks until done": the call has waited for `stream` when it returns.  The outputs in device memory are complete and can be
+ *     read from any stream without a further wait on `stream`; the host words (*count_out, *total, *primary_out, the return
+ *     value, the statistics getters) are final.  Because the calls block they cannot be captured into a graph.
+ */
 
 typedef struct sa_amd_stats {
     int32_t sigma;            /* distinct byte values in T */
