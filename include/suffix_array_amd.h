@@ -995,6 +995,96 @@ void sa_amd_last_score_stats(sa_amd_score_stats *out);
  * acts as 4096); a negative value restores the default (64).  Returns the previous value. */
 int32_t sa_amd_score_set_group_cap(int32_t bytes);
 
+/*
+ * Texts over a 16-bit token alphabet (an extension): the suffix array of a text of tokeniser ids, a device-resident token index
+ * and the n-gram / infinity-gram queries on it.  T has n tokens, compared as unsigned 16-bit values; a
+ * suffix that is a proper prefix of another sorts first.  SA has n + 1 entries in TOKEN positions, SA[0] = n (the layout of
+ * sa_amd_saca_u8 with "byte" replaced by "token").  The raw little-endian bytes of T are NOT a substitute: 0x0100 would sort
+ * before 0x0001, matches could start in the middle of a token, and the counts would be next-byte counts.
+ * Construction: the big-endian byte image of T (2 n bytes) goes through the byte builder, and an order-preserving compaction
+ * keeps the even entries of its array, halved.  Peak device memory of sa_amd_saca_u16: 2 n (T) + 2 n (image) + 4 (2 n + 1) +
+ * sa_amd_workspace_bytes(2 n), one pooled block; a block that does not fit is SA_AMD_ENOMEM (no reduced-memory route).
+ * sa_amd_last_stats is that of the byte build.
+ * n == 0 gives SA = {0}.  n < 0, n > sa_amd_max_tokens_u16(), a NULL SA, or a NULL T with n > 0: SA_AMD_EINVAL.
+ */
+int32_t sa_amd_max_tokens_u16(void);                                              /* 1073741823 = (2^31 - 1) / 2 */
+int32_t sa_amd_saca_u16(const uint16_t *T, uint32_t *SA, int32_t n);              /* host pointers */
+
+/*
+ * The token index keeps T (2 n bytes) and the token suffix array (4 (n + 1) bytes) in HBM; the byte image and the byte-level
+ * array are scratch of the build.  SA == NULL: the array is built on the device and never downloaded.  A supplied SA (n + 1
+ * entries) is range-checked before anything reads through it: an entry above n is SA_AMD_ERANGE, SA[0] != n is SA_AMD_EINVAL;
+ * with a wrong but in-range array the answers are unspecified, and nothing is read outside T, the patterns and the array.
+ * The queries follow sa_amd_index_search, sa_amd_index_next_bytes and sa_amd_index_infgram (above) with "byte" replaced by
+ * "token": lengths, pat_off, suffix_len and max_len are in tokens, pat_data holds the patterns' tokens back to back.
+ *   at_end is 1 iff some slot of the range has SA[i] + p == n; it can only be slot lo.
+ *   next[t] = the number of slots i in [lo, hi) with SA[i] + p < n and T[SA[i] + p] == t;  sum(next) + at_end == hi - lo.
+ *   The slots with continuation t are the contiguous sub-range that starts at lo + at_end + sum(next[t'] for t' < t) and has
+ *     next[t] slots.  It is the range of c + t.
+ *   The LISTING of a context is its non-zero (t, next[t]) pairs in ascending t: at most min(65 536, hi - lo) entries.
+ *   The empty context has the range [0, n + 1) and at_end = 1; its listing is the token histogram of T.
+ *   A context that does not occur has lo == hi, at_end = 0 and an empty listing.
+ *   Back-off: s = the largest value in 0 .. cap (cap = L, or min(L, max_len) where max_len > 0) such that the last s tokens of
+ *     the prompt occur at least min_count times; at most ceil(log2(cap + 1)) range searches per prompt.
+ *   T = {256, 1, 256, 1, 2}, SA = {5, 3, 1, 4, 2, 0} (the little-endian byte image gives another order):
+ *     context     range     at_end  listing
+ *     {256, 1}    [4, 6)    0       {2:1, 256:1}
+ *     {1}         [1, 3)    0       {2:1, 256:1}
+ *     {2}         [3, 4)    1       empty
+ *     {}          [0, 6)    1       {1:2, 2:1, 256:2}
+ *     {9}         empty     0       empty
+ *     prompt       min_count max_len  s   range
+ *     {7, 256, 1}  1         none     2   [4, 6)
+ *     {7, 256, 1}  3         none     0   [0, 6)
+ *     {7, 256, 1}  2         1        1   [1, 3)
+ * list_off has count + 1 entries, the listing of pattern q is (tokens, counts)[list_off[q] .. list_off[q + 1]); more entries
+ * than `capacity` is no error: the first `capacity` are written, *total_out (= list_off[count]) and list_off describe all of
+ * them.  EVERY output pointer may be NULL; tokens and counts may each be NULL, and with both NULL `capacity` is ignored.
+ * count == 0 succeeds with list_off[0] = 0.
+ * Errors, each with nothing written: a NULL index, a negative count or capacity, pat_off as sa_amd_index_search rejects it,
+ * min_count < 1: SA_AMD_EINVAL.
+ * Cost: a search is a plain binary search that compares 64 tokens a wave step (no bucket table, no LCP table).  A range of at
+ * most `stream cap` slots (sa_amd_ngram_set_stream_cap of the calling thread) is streamed once; a longer one is sampled at 64
+ * slots and every run start between two differing samples is found by one binary search: at most
+ * 64 + D (ceil(log2(cnt + 1)) + 1) slots probed for D distinct continuations, cnt = hi - lo - at_end.  With tokens or counts
+ * asked for, the continuations are computed twice (counted, then emitted in order).
+ */
+typedef struct sa_amd_tok_index sa_amd_tok_index;
+int32_t sa_amd_tok_index_create(const uint16_t *T, int32_t n, const uint32_t *SA, sa_amd_tok_index **out);
+void sa_amd_tok_index_destroy(sa_amd_tok_index *ix);
+int32_t sa_amd_tok_index_sa(const sa_amd_tok_index *ix, uint32_t *SA_out);        /* n + 1 entries */
+int32_t sa_amd_tok_index_search(const sa_amd_tok_index *ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t count,
+                                uint8_t *contains, uint32_t *range_lo, uint32_t *range_hi);
+int32_t sa_amd_tok_index_next_tokens(const sa_amd_tok_index *ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t count,
+                                     uint32_t *range_lo, uint32_t *range_hi, uint8_t *at_end,
+                                     int64_t *list_off, uint16_t *tokens, uint32_t *counts, int64_t capacity, int64_t *total_out);
+int32_t sa_amd_tok_index_infgram(const sa_amd_tok_index *ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t count,
+                                 int32_t min_count, int32_t max_len, uint32_t *suffix_len,
+                                 uint32_t *range_lo, uint32_t *range_hi, uint8_t *at_end,
+                                 int64_t *list_off, uint16_t *tokens, uint32_t *counts, int64_t capacity, int64_t *total_out);
+
+typedef struct sa_amd_tok_stats {    /* of the calling thread: the query fields of its most recent next_tokens / infgram call on a token
+                                        index, the three times of its most recent token build (no other feature's statistics are touched) */
+    int64_t patterns;
+    int64_t range_searches;          /* infgram: the probes of the bisection, all prompts; next_tokens: one per pattern */
+    int64_t compared_tokens;         /* infgram: text tokens the range searches compared; -1 after next_tokens */
+    int64_t stream_slots;            /* slots probed by the streaming route: the sum of cnt over its queries, exactly */
+    int64_t search_slots;            /* slots probed by the boundary-search route */
+    int64_t stream_queries;          /* queries by route: 0 < cnt <= stream_cap */
+    int64_t search_queries;          /*                   cnt > stream_cap */
+    int64_t empty_queries;           /*                   cnt == 0: nothing is probed */
+    int64_t entries;                 /* entries of the whole listing (= *total_out) */
+    int32_t stream_cap;              /* the stream cap in effect */
+    int32_t readbacks;               /* blocking device -> host read-backs of counters: 1 */
+    int32_t backoff;                 /* 1 after infgram, 0 after next_tokens */
+    int32_t passes;                  /* runs of the continuation kernel: 1 (counted only), else 2 */
+    double image_ms;                 /* the most recent token build (sa_amd_saca_u16, or sa_amd_tok_index_create with SA == NULL), host
+                                        time around a drained stream: the byte image, */
+    double build_ms;                 /*   the byte builder on the image, */
+    double compact_ms;               /*   counts, scan and scatter of the compaction */
+} sa_amd_tok_stats;
+void sa_amd_last_tok_stats(sa_amd_tok_stats *out);
+
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and
  * copies up to `capacity` classes out (ms = summed event time, launches, units = elements or bytes

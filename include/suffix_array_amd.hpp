@@ -479,4 +479,134 @@ private:
     std::size_t n_ = 0, ndocs_ = 0;
 };
 
+// EXTENSION (not in the reference): a text of 16-bit tokens and its suffix array resident on the device (sa_amd_tok_index;
+// suffix_array_amd.h, "Texts over a 16-bit token alphabet").  Tokens compare as unsigned 16-bit values; every length, position
+// and offset is in tokens.
+class TokenIndex {
+public:
+    using Tokens = std::vector<std::uint16_t>;
+    // sa == nullptr: the suffix array is built on the device and never downloaded; a supplied one (n + 1 entries) is range-checked
+    TokenIndex(const std::uint16_t *t, std::size_t n, const std::uint32_t *sa = nullptr)
+    {
+        if (n > static_cast<std::size_t>(MAX_LENGTH / 2)) throw std::logic_error("assertion failed: t.len() <= MAX_LENGTH / 2");
+        check(sa_amd_tok_index_create(t, static_cast<std::int32_t>(n), sa, &ix_));
+        n_ = n;
+    }
+    TokenIndex(const TokenIndex &) = delete;
+    TokenIndex &operator=(const TokenIndex &) = delete;
+    ~TokenIndex() { sa_amd_tok_index_destroy(ix_); }
+
+    std::size_t len() const { return n_; }
+    // the token suffix array: n + 1 entries, entry 0 is n
+    std::vector<std::uint32_t> sa() const
+    {
+        std::vector<std::uint32_t> out(n_ + 1);
+        check(sa_amd_tok_index_sa(ix_, out.data()));
+        return out;
+    }
+    // per pattern its match range [lo, hi) in the token suffix array; lo == hi where it does not occur
+    std::vector<std::pair<std::uint32_t, std::uint32_t>> search(const std::vector<Tokens> &patterns) const
+    {
+        const Batch b(patterns);
+        std::vector<std::uint32_t> lo(patterns.size() + 1), hi(patterns.size() + 1);
+        check(sa_amd_tok_index_search(ix_, b.toks.data(), b.off.data(), b.count(), nullptr, lo.data(), hi.data()));
+        std::vector<std::pair<std::uint32_t, std::uint32_t>> out(patterns.size());
+        for (std::size_t q = 0; q < out.size(); ++q) out[q] = { lo[q], hi[q] };
+        return out;
+    }
+    // occurrences of every pattern (the empty pattern has n + 1), and whether it occurs at all
+    std::vector<std::uint32_t> count(const std::vector<Tokens> &patterns) const
+    {
+        const auto r = search(patterns);
+        std::vector<std::uint32_t> out(r.size());
+        for (std::size_t q = 0; q < out.size(); ++q) out[q] = r[q].second - r[q].first;
+        return out;
+    }
+    std::vector<bool> contains(const std::vector<Tokens> &patterns) const
+    {
+        const auto r = search(patterns);
+        std::vector<bool> out(r.size());
+        for (std::size_t q = 0; q < out.size(); ++q) out[q] = r[q].second > r[q].first;
+        return out;
+    }
+    // what follows a context and how often: next holds the (token, count) pairs with a non-zero count in ascending token order;
+    // the counts and at_end sum to hi - lo
+    struct NextTokens {
+        std::uint32_t lo = 0, hi = 0;
+        bool at_end = false;
+        std::vector<std::pair<std::uint16_t, std::uint32_t>> next;
+    };
+    // the same for the longest suffix of a prompt that occurs at least min_count times: suffix_len is its length in tokens
+    struct Infgram : NextTokens {
+        std::uint32_t suffix_len = 0;
+    };
+    std::vector<NextTokens> next_tokens(const std::vector<Tokens> &patterns) const
+    {
+        std::vector<NextTokens> out(patterns.size());
+        ngram(patterns, false, 1, 0, out, nullptr);
+        return out;
+    }
+    // max_len <= 0: no cap on the suffix length.  A suffix of length 0 (the token histogram of the text) always qualifies.
+    std::vector<Infgram> infgram(const std::vector<Tokens> &prompts, std::int32_t min_count = 1, std::int32_t max_len = 0) const
+    {
+        if (min_count < 1) throw std::invalid_argument("min_count must be at least 1");
+        std::vector<Infgram> out(prompts.size());
+        std::vector<std::uint32_t> slen(prompts.size() + 1);
+        ngram(prompts, true, min_count, max_len, out, slen.data());
+        for (std::size_t q = 0; q < out.size(); ++q) out[q].suffix_len = slen[q];
+        return out;
+    }
+
+private:
+    struct Batch {
+        Tokens toks;
+        std::vector<std::int64_t> off;
+        explicit Batch(const std::vector<Tokens> &patterns) : off(patterns.size() + 1, 0)
+        {
+            for (std::size_t q = 0; q < patterns.size(); ++q) {
+                toks.insert(toks.end(), patterns[q].begin(), patterns[q].end());
+                off[q + 1] = static_cast<std::int64_t>(toks.size());
+            }
+            if (toks.empty()) toks.push_back(0);       // (never a NULL pattern pointer)
+        }
+        std::int32_t count() const { return static_cast<std::int32_t>(off.size() - 1); }
+    };
+    template <class Row>
+    void ngram(const std::vector<Tokens> &patterns, bool backoff, std::int32_t min_count, std::int32_t max_len, std::vector<Row> &out,
+               std::uint32_t *slen) const
+    {
+        const Batch b(patterns);
+        const std::size_t c = patterns.size();
+        std::vector<std::uint32_t> lo(c + 1), hi(c + 1), counts(1 << 12);
+        std::vector<std::uint8_t> ae(c + 1);
+        Tokens toks(1 << 12);
+        std::vector<std::int64_t> loff(c + 1);
+        std::int64_t total = 0;
+        for (;;) {
+            const std::int64_t cap = static_cast<std::int64_t>(toks.size());
+            if (backoff)
+                check(sa_amd_tok_index_infgram(ix_, b.toks.data(), b.off.data(), b.count(), min_count, max_len, slen, lo.data(), hi.data(), ae.data(),
+                                               loff.data(), toks.data(), counts.data(), cap, &total));
+            else
+                check(sa_amd_tok_index_next_tokens(ix_, b.toks.data(), b.off.data(), b.count(), lo.data(), hi.data(), ae.data(), loff.data(),
+                                                   toks.data(), counts.data(), cap, &total));
+            if (total <= cap) break;
+            toks.resize(static_cast<std::size_t>(total));
+            counts.resize(static_cast<std::size_t>(total));
+        }
+        for (std::size_t q = 0; q < c; ++q) {
+            out[q].lo = lo[q]; out[q].hi = hi[q]; out[q].at_end = ae[q] != 0;
+            for (std::int64_t e = loff[q]; e < loff[q + 1]; ++e)
+                out[q].next.emplace_back(toks[static_cast<std::size_t>(e)], counts[static_cast<std::size_t>(e)]);
+        }
+    }
+    static void check(std::int32_t rc)
+    {
+        if (rc == SA_AMD_EINVAL) throw std::invalid_argument("suffix_array_amd: invalid argument");
+        if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
+    }
+    sa_amd_tok_index *ix_ = nullptr;
+    std::size_t n_ = 0;
+};
+
 }  // namespace suffix_array

@@ -40,10 +40,13 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "DOC_TOPK_PIECE_DEFAULT",
            "NgramStats", "last_ngram_stats", "ngram_set_stream_cap", "NGRAM_STREAM_CAP_DEFAULT",
            "ScoreStats", "ScoreResult", "last_score_stats", "score_set_group_cap", "score_work_bytes", "infgram_score_device_ptr",
-           "SCORE_MAX_CONTEXT", "SCORE_GROUP_CAP_DEFAULT", "SCORE_TILE"]
+           "SCORE_MAX_CONTEXT", "SCORE_GROUP_CAP_DEFAULT", "SCORE_TILE",
+           "saca_u16", "MAX_TOKENS_U16", "TokenIndex", "TokStats", "last_tok_stats"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
+#: the longest 16-bit token text (sa_amd_max_tokens_u16): its byte image has at most MAX_LENGTH bytes
+MAX_TOKENS_U16 = MAX_LENGTH // 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libsuffix_array_amd.so"
@@ -198,6 +201,18 @@ class NgramStats(ctypes.Structure):
                 ("stream_slots", ctypes.c_int64), ("search_slots", ctypes.c_int64), ("stream_queries", ctypes.c_int64),
                 ("search_queries", ctypes.c_int64), ("empty_queries", ctypes.c_int64), ("entries", ctypes.c_int64),
                 ("stream_cap", ctypes.c_int32), ("readbacks", ctypes.c_int32), ("backoff", ctypes.c_int32), ("passes", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class TokStats(ctypes.Structure):
+    """sa_amd_tok_stats of include/suffix_array_amd.h"""
+    _fields_ = [("patterns", ctypes.c_int64), ("range_searches", ctypes.c_int64), ("compared_tokens", ctypes.c_int64),
+                ("stream_slots", ctypes.c_int64), ("search_slots", ctypes.c_int64), ("stream_queries", ctypes.c_int64),
+                ("search_queries", ctypes.c_int64), ("empty_queries", ctypes.c_int64), ("entries", ctypes.c_int64),
+                ("stream_cap", ctypes.c_int32), ("readbacks", ctypes.c_int32), ("backoff", ctypes.c_int32), ("passes", ctypes.c_int32),
+                ("image_ms", ctypes.c_double), ("build_ms", ctypes.c_double), ("compact_ms", ctypes.c_double)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -539,6 +554,25 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_score_set_group_cap.restype = ctypes.c_int32
         L.sa_amd_docs_set_topk_piece.argtypes = [ctypes.c_int32]
         L.sa_amd_docs_set_topk_piece.restype = ctypes.c_int32
+        L.sa_amd_max_tokens_u16.argtypes = []
+        L.sa_amd_max_tokens_u16.restype = ctypes.c_int32
+        L.sa_amd_saca_u16.argtypes = [c_vp, c_vp, ctypes.c_int32]
+        L.sa_amd_saca_u16.restype = ctypes.c_int32
+        L.sa_amd_tok_index_create.argtypes = [c_vp, ctypes.c_int32, c_vp, c_vp]
+        L.sa_amd_tok_index_create.restype = ctypes.c_int32
+        L.sa_amd_tok_index_destroy.argtypes = [c_vp]
+        L.sa_amd_tok_index_destroy.restype = None
+        L.sa_amd_tok_index_sa.argtypes = [c_vp, c_vp]
+        L.sa_amd_tok_index_sa.restype = ctypes.c_int32
+        L.sa_amd_tok_index_search.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, c_vp]
+        L.sa_amd_tok_index_search.restype = ctypes.c_int32
+        L.sa_amd_tok_index_next_tokens.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_tok_index_next_tokens.restype = ctypes.c_int32
+        L.sa_amd_tok_index_infgram.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                               c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_tok_index_infgram.restype = ctypes.c_int32
+        L.sa_amd_last_tok_stats.argtypes = [c_vp]
+        L.sa_amd_last_tok_stats.restype = None
         _lib = L
     return _lib
 
@@ -1599,6 +1633,146 @@ class DeviceIndex:
         _check(lib().sa_amd_index_search(self._h, data.ctypes.data, off.ctypes.data, cnt, c.ctypes.data, lo.ctypes.data,
                                          hi.ctypes.data, ls.ctypes.data, ll.ctypes.data))
         return {"contains": c.astype(bool), "lo": lo, "hi": hi, "lcp_start": ls, "lcp_len": ll}
+
+
+def _as_u16(tokens, what: str = "tokens") -> np.ndarray:
+    """a uint16 array as it is, or a sequence of ints in 0 .. 65 535 -> contiguous 1-D uint16; anything else raises before the
+    library is called"""
+    if isinstance(tokens, np.ndarray):
+        if tokens.dtype != np.uint16 or tokens.ndim != 1:
+            raise TypeError(f"{what}: a 1-D uint16 array or a sequence of ints in 0 .. 65535")
+        return np.ascontiguousarray(tokens)
+    if isinstance(tokens, (bytes, bytearray, str)):
+        raise TypeError(f"{what}: a 1-D uint16 array or a sequence of ints in 0 .. 65535, not {type(tokens).__name__}")
+    vals = list(tokens)
+    for v in vals:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{what}: {v!r} is not an int")
+        if not 0 <= int(v) <= 65535:
+            raise ValueError(f"{what}: token {int(v)} is outside 0 .. 65535")
+    return np.array(vals, dtype=np.uint16).reshape(-1)
+
+
+def _token_batch(patterns):
+    pats = [_as_u16(p, "pattern") for p in patterns]
+    off = np.zeros(len(pats) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([p.size for p in pats])
+    data = np.concatenate(pats) if off[-1] else np.zeros(1, dtype=np.uint16)
+    return np.ascontiguousarray(data, dtype=np.uint16), off, len(pats)
+
+
+def saca_u16(tokens) -> np.ndarray:
+    """EXTENSION: the suffix array of a text of 16-bit tokens (``sa_amd_saca_u16``) -> uint32 array of ``n + 1`` entries in
+    token positions, entry 0 is ``n``.  Tokens compare as unsigned 16-bit values; a suffix that is a prefix of another sorts
+    first.  Built on the GPU from the big-endian byte image of the tokens; only the final array comes down."""
+    t = _as_u16(tokens)
+    if t.size > MAX_TOKENS_U16:
+        raise ValueError(f"saca_u16: at most {MAX_TOKENS_U16} tokens")
+    out = np.empty(t.size + 1, dtype=np.uint32)
+    _check(lib().sa_amd_saca_u16(t.ctypes.data if t.size else None, out.ctypes.data, t.size))
+    return out
+
+
+def last_tok_stats() -> dict:
+    """the query counters of this thread's most recent ``TokenIndex.next_tokens`` / ``.infgram`` call (the fields of
+    ``last_ngram_stats``, ``compared_tokens`` in place of ``compared_bytes``) and image_ms / build_ms / compact_ms of its most
+    recent token build"""
+    st = TokStats()
+    lib().sa_amd_last_tok_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+class TokenIndex:
+    """EXTENSION: a text of 16-bit tokens and its suffix array resident in HBM (sa_amd_tok_index of
+    include/suffix_array_amd.h): batched range search, next-token counts and the infinity-gram back-off.  ``sa=None`` builds the
+    array on the device without downloading it; a supplied array is range-checked.  Patterns are sequences of uint16 arrays
+    or of sequences of ints in 0 .. 65 535; every length and offset is in tokens."""
+
+    def __init__(self, tokens, sa: Optional[np.ndarray] = None):
+        self._t = _as_u16(tokens)
+        if self._t.size > MAX_TOKENS_U16:
+            raise ValueError(f"TokenIndex: at most {MAX_TOKENS_U16} tokens")
+        a = None if sa is None else np.ascontiguousarray(sa, dtype=np.uint32)
+        if a is not None and a.size != self._t.size + 1:
+            raise ValueError("TokenIndex: sa has len(tokens) + 1 entries")
+        h = ctypes.c_void_p()
+        _check(lib().sa_amd_tok_index_create(self._t.ctypes.data if self._t.size else None, self._t.size,
+                                             None if a is None else a.ctypes.data, ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sa_amd_tok_index_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __len__(self):
+        return int(self._t.size)
+
+    def sa(self) -> np.ndarray:
+        out = np.empty(self._t.size + 1, dtype=np.uint32)
+        _check(lib().sa_amd_tok_index_sa(self._h, out.ctypes.data))
+        return out
+
+    def _search(self, patterns, contains: bool):
+        data, off, cnt = _token_batch(patterns)
+        lo, hi = np.zeros(cnt, dtype=np.uint32), np.zeros(cnt, dtype=np.uint32)
+        has = np.zeros(cnt, dtype=np.uint8)
+        _check(lib().sa_amd_tok_index_search(self._h, data.ctypes.data, off.ctypes.data, cnt, has.ctypes.data if contains else None,
+                                             lo.ctypes.data, hi.ctypes.data))
+        return has, lo, hi
+
+    def search(self, patterns):
+        """-> ``(lo, hi)``: the match range of every pattern in the token suffix array; ``lo == hi`` where it does not occur"""
+        _, lo, hi = self._search(patterns, False)
+        return lo, hi
+
+    def count(self, patterns) -> np.ndarray:
+        """occurrences of every pattern (``hi - lo``; the empty pattern has ``n + 1``)"""
+        lo, hi = self.search(patterns)
+        return hi.astype(np.int64) - lo.astype(np.int64)
+
+    def contains(self, patterns) -> np.ndarray:
+        return self._search(patterns, True)[0].astype(bool)
+
+    def _ngram(self, patterns, backoff: bool, min_count: int, max_len: int):
+        data, off, cnt = _token_batch(patterns)
+        slen, lo, hi = (np.zeros(cnt, dtype=np.uint32) for _ in range(3))
+        ae = np.zeros(cnt, dtype=np.uint8)
+        loff = np.zeros(cnt + 1, dtype=np.int64)
+        total = ctypes.c_int64(0)
+        cap = max(1 << 16, 8 * cnt)
+        while True:
+            t = np.empty(max(cap, 1), dtype=np.uint16)
+            c = np.empty(max(cap, 1), dtype=np.uint32)
+            if backoff:
+                _check(lib().sa_amd_tok_index_infgram(self._h, data.ctypes.data, off.ctypes.data, cnt, int(min_count), int(max_len),
+                                                      slen.ctypes.data, lo.ctypes.data, hi.ctypes.data, ae.ctypes.data, loff.ctypes.data,
+                                                      t.ctypes.data, c.ctypes.data, cap, ctypes.byref(total)))
+            else:
+                _check(lib().sa_amd_tok_index_next_tokens(self._h, data.ctypes.data, off.ctypes.data, cnt, lo.ctypes.data, hi.ctypes.data,
+                                                          ae.ctypes.data, loff.ctypes.data, t.ctypes.data, c.ctypes.data, cap,
+                                                          ctypes.byref(total)))
+            if total.value <= cap:
+                m = int(total.value)
+                return slen, lo, hi, ae, loff, t[:m].copy(), c[:m].copy()
+            cap = int(total.value)
+
+    def next_tokens(self, patterns):
+        """what follows each context in the text, and how often -> ``(lo, hi, at_end, list_off, tokens, counts)``, the result
+        shape of ``DeviceIndex.next_bytes`` with tokens in place of bytes: the listing of context ``q`` is
+        ``tokens[list_off[q]:list_off[q + 1]]`` (ascending) with ``counts`` next to it, ``sum(counts) + at_end == hi - lo``, and the
+        occurrences followed by ``t`` are the sub-range that starts at ``lo + at_end`` plus the counts of the smaller tokens."""
+        return self._ngram(patterns, False, 1, 0)[1:]
+
+    def infgram(self, prompts, min_count: int = 1, max_len: int = 0):
+        """the infinity-gram query -> ``(suffix_len, lo, hi, at_end, list_off, tokens, counts)``: ``suffix_len[q]`` is the length in
+        tokens of the longest suffix of prompt ``q`` -- of at most ``max_len`` tokens where ``max_len > 0`` -- that occurs at least
+        ``min_count`` times; the other outputs are those of ``next_tokens`` for that suffix."""
+        if int(min_count) < 1:
+            raise SuffixArrayError(-1, "infgram: min_count >= 1")
+        return self._ngram(prompts, True, min(int(min_count), 2**31 - 1), max(0, min(int(max_len), 2**31 - 1)))
 
 
 def workspace_bytes(n: int) -> int:

@@ -81,6 +81,28 @@ def english_corpus(n: int, seed: int, vocab: int = 50000, dup_fraction: float = 
     return out
 
 
+def token_corpus(n: int, vocab: int = 50000, seed: int = 0) -> np.ndarray:
+    """n tokeniser-like ids (uint16) for the 16-bit token texts: Zipf-distributed ranks (weight 1 / rank) over `vocab` <= 65 536
+    words, the rank -> id map a seeded permutation (frequent words get ids with any high byte), and one block of n / 16 tokens
+    repeated further on (a copied passage: long common prefixes).  numpy only; the same array for the same arguments."""
+    if not 1 <= vocab <= 65536:
+        raise ValueError("token_corpus: 1 <= vocab <= 65536")
+    rng = np.random.default_rng([int(seed), int(vocab), 0x746F6B])
+    cdf = np.cumsum(1.0 / np.arange(1, vocab + 1, dtype=np.float64))
+    ids = rng.permutation(vocab).astype(np.uint16)
+    out = np.empty(n, dtype=np.uint16)
+    step = 1 << 22
+    for a in range(0, n, step):                                   # in pieces: the float64 draws of 128 Mi tokens would be 1 GiB
+        b = min(n, a + step)
+        out[a:b] = ids[np.minimum(np.searchsorted(cdf, rng.random(b - a) * cdf[-1]), vocab - 1)]
+    blk = n // 16
+    if blk:
+        src = int(rng.integers(0, n - 2 * blk + 1))
+        dst = int(rng.integers(src + blk, n - blk + 1))
+        out[dst:dst + blk] = out[src:src + blk]
+    return out
+
+
 #: BASELINE.md section 2 workloads: name -> (generator, n, seed)
 WORKLOADS = {
     "c1_uniform_1k": (uniform, 1 << 10, 1),

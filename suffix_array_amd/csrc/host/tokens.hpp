@@ -1,0 +1,303 @@
+// host/tokens.hpp -- texts over a 16-bit token alphabet (kernels/tokens.hpp): the type behind the ABI's
+// `sa_amd_tok_index *` (the owner of the token text and its suffix array, as host/index.hpp is for the byte index), the token
+// build -- byte image, the byte builder on it, compaction -- behind sa_amd_saca_u16 and sa_amd_tok_index_create, and the
+// queries: sa_amd_tok_index_search, sa_amd_tok_index_next_tokens and sa_amd_tok_index_infgram.
+#pragma once
+#include "ngram.hpp"
+#include "../kernels/tokens.hpp"
+
+// Token text (n tokens, 16 bytes of slack behind them) and token suffix array (n + 1 entries) kept in HBM.  Both are DevBufs of
+// the index's own: deleting the index frees them, in no call that can throw and without a change of device.
+extern "C++" {
+
+struct sa_amd_tok_index {
+    int device = 0;
+    int32_t n = 0;
+    sa::DevBuf dT, dSA;
+    const uint16_t *text() const { return dT.as<const uint16_t>(); }
+    const uint32_t *sa() const { return dSA.as<const uint32_t>(); }
+};
+
+}  // extern "C++"
+
+namespace sa {
+
+constexpr int32_t TOK_MAX_TOKENS_U16 = SA_AMD_MAX_LENGTH / 2;      // the byte image has 2 n <= 2^31 - 2 bytes
+
+static thread_local sa_amd_tok_stats g_last_tok_stats;
+
+static unsigned tok_stream_grid(int64_t items, int per_block)
+{
+    int64_t g = ceil_div(items, per_block);
+    const int64_t most = (int64_t)cu_count() * 8;
+    if (g > most) g = most;
+    return (unsigned)(g < 1 ? 1 : g);
+}
+
+// The scratch of one token build, carved from the scope's block in this order: the byte builder's work block, the byte image,
+// the byte-level array.  Once the builder is done its work block holds the compaction's output (where the caller has no
+// buffer of its own for it) and, behind that, the tile counts and the scan's tile sums.
+struct TokBuild {
+    size_t wb = 0, b_out = 0, b_cnt = 0, b_img = 0, b_sa2 = 0;
+    int64_t tiles = 0;
+    size_t bytes() const { return wb + b_img + b_sa2; }
+};
+
+static TokBuild tok_build_layout(int32_t n)
+{
+    TokBuild L;
+    const int64_t len = 2 * (int64_t)n + 1;
+    L.tiles = ceil_div(len, TK_TILE);
+    L.b_out = align_up(((size_t)n + 1) * 4, 256);
+    L.b_cnt = align_up((size_t)(L.tiles + 1) * 8, 256);
+    const size_t after = L.b_out + L.b_cnt + align_up(docs_scan_words(L.tiles + 1) * 8, 256);
+    L.wb = align_up((size_t)carve(nullptr, 2 * (int64_t)n).bytes, 256);
+    if (L.wb < after) L.wb = after;
+    L.b_img = align_up(2 * (size_t)n + 16, 256);
+    L.b_sa2 = align_up((size_t)len * 4, 256);
+    return L;
+}
+
+// The token suffix array (n + 1 entries) of dT[0 .. n), n > 0 (device pointers, dT 16-byte aligned with 16 bytes of slack
+// behind the tokens) -> dOut, or, dOut == nullptr, the start of the work block; *out_ptr: where it is.  The scope has acquired
+// at least L.bytes() more than has been taken.  Blocks until done; the three times go to the calling thread's statistics.
+static int32_t tok_build_device(PooledScope &sc, const TokBuild &L, const uint16_t *dT, int32_t n32, uint32_t *dOut, const uint32_t **out_ptr)
+{
+    const int64_t n = n32, len = 2 * n + 1;
+    char *dW = (char *)sc.take(L.wb);
+    uint8_t *dB = (uint8_t *)sc.take(L.b_img);
+    uint32_t *dSA2 = (uint32_t *)sc.take(L.b_sa2);
+    if (sc.rc) return sc.rc;
+    hipStream_t st = sc.st;
+    double t0 = now_ms();
+    PROF(KC_MISC, n, st, hipLaunchKernelGGL(k_tok_be_image, dim3(tok_stream_grid(ceil_div(n, TK_IMAGE_ITEMS), TK_THREADS)), dim3(TK_THREADS), 0, st,
+                                            dT, dB, n));
+    HIP_TRY(hipStreamSynchronize(st));
+    double t1 = now_ms();
+    g_last_tok_stats.image_ms = t1 - t0;
+    { const int rcb = build_device(dB, dSA2, (int32_t)(2 * n), dW, (int64_t)L.wb, st, nullptr); if (rcb) return rcb; }
+    t0 = now_ms();
+    g_last_tok_stats.build_ms = t0 - t1;
+    // ---- the even entries, halved, in their order: tile counts, one scan, scatter ----
+    if (!dOut) dOut = (uint32_t *)dW;
+    unsigned long long *cnt = (unsigned long long *)(dW + L.b_out), *tsum = (unsigned long long *)(dW + L.b_out + L.b_cnt);
+    const unsigned grid = tok_stream_grid(ceil_div(L.tiles, TK_SPAN), 1);
+    PROF(KC_MISC, len, st, hipLaunchKernelGGL(k_tok_compact_count, dim3(grid), dim3(TK_THREADS), 0, st, (const uint32_t *)dSA2, len, L.tiles, cnt));
+    { const int rcs = docs_scan(cnt, L.tiles + 1, tsum, nullptr, st); if (rcs) return rcs; }
+    PROF(KC_MISC, len, st, hipLaunchKernelGGL(k_tok_compact_scatter, dim3(grid), dim3(TK_THREADS), 0, st, (const uint32_t *)dSA2, len, L.tiles,
+                                              (const unsigned long long *)cnt, dOut, n + 1));
+    HIP_TRY(hipStreamSynchronize(st));
+    g_last_tok_stats.compact_ms = now_ms() - t0;
+    g_prof.resolve();
+    if (out_ptr) *out_ptr = dOut;
+    return SA_AMD_OK;
+}
+
+// sa_amd_saca_u16 behind its argument checks, n > 0: one pooled block -- T | the build's scratch --, only the final array
+// comes down
+static int32_t tok_saca_host(const uint16_t *T, uint32_t *SA, int32_t n)
+{
+    PooledScope sc(pick_device(), false);
+    const TokBuild L = tok_build_layout(n);
+    const size_t b_t = align_up(2 * (size_t)n + 16, 256);
+    sc.acquire(b_t + L.bytes());
+    uint16_t *dT = (uint16_t *)sc.take(b_t);
+    if (sc.rc) return sc.rc;
+    HIP_TRY(hipMemcpyAsync(dT, T, 2 * (size_t)n, hipMemcpyHostToDevice, sc.st));
+    const uint32_t *dOut = nullptr;
+    sc.rc = tok_build_device(sc, L, dT, n, nullptr, &dOut);
+    sc.down(SA, dOut, ((size_t)n + 1) * 4);
+    return sc.finish();
+}
+
+// sa_amd_tok_index_create behind its argument checks: the tokens go up, and the caller's array (range-checked before anything
+// reads through it) or, SA == nullptr, the one built on the device; *out owns both
+static int32_t tok_index_create(const uint16_t *T, int32_t n, const uint32_t *SA, sa_amd_tok_index **out)
+{
+    DeviceGuard guard(pick_device());
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    DevBuf dT, dSA;
+    const size_t N = (size_t)n;
+    if (index_table_alloc(dT, 2 * N + 16) != SA_AMD_OK || index_table_alloc(dSA, (N + 1) * 4) != SA_AMD_OK) return SA_AMD_ENOMEM;
+    if (N) HIP_TRY(hipMemcpy(dT.p, T, 2 * N, hipMemcpyHostToDevice));
+    if (SA) {
+        PooledScope sc(-1, false);
+        sc.acquire(256);
+        uint32_t *flags = (uint32_t *)sc.take(256);
+        if (sc.rc) return sc.rc;
+        HIP_TRY(hipMemcpyAsync(dSA.p, SA, (N + 1) * 4, hipMemcpyHostToDevice, sc.st));
+        HIP_TRY(hipMemsetAsync(flags, 0, 4, sc.st));
+        PROF(KC_MISC, n, sc.st, hipLaunchKernelGGL(k_tok_sa_range, dim3(tok_stream_grid((int64_t)n + 1, TK_THREADS)), dim3(TK_THREADS), 0, sc.st,
+                                                   dSA.as<const uint32_t>(), (int64_t)n, flags));
+        uint32_t f = 0;
+        { const int rcw = read_words(&f, flags, 4, sc.st); if (rcw) return rcw; }
+        if (sc.finish() != SA_AMD_OK) return sc.rc;
+        if (f & 1u) return SA_AMD_ERANGE;
+        if (SA[0] != (uint32_t)n) return SA_AMD_EINVAL;
+    } else if (n == 0) {
+        HIP_TRY(hipMemset(dSA.p, 0, 4));
+    } else {
+        PooledScope sc(-1, false);
+        const TokBuild L = tok_build_layout(n);
+        sc.acquire(L.bytes());
+        sc.rc = sc.rc ? sc.rc : tok_build_device(sc, L, dT.as<const uint16_t>(), n, dSA.as<uint32_t>(), nullptr);
+        if (sc.finish() != SA_AMD_OK) return sc.rc;
+    }
+    sa_amd_tok_index *ix = new (std::nothrow) sa_amd_tok_index();
+    if (!ix) return SA_AMD_ENOMEM;
+    ix->n = n;
+    (void)hipGetDevice(&ix->device);
+    ix->dT = std::move(dT);
+    ix->dSA = std::move(dSA);
+    *out = ix;
+    return SA_AMD_OK;
+}
+
+static int32_t tok_index_sa(const sa_amd_tok_index &ix, uint32_t *SA_out)
+{
+    DeviceGuard guard(ix.device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    return hipMemcpy(SA_out, ix.sa(), ((size_t)ix.n + 1) * 4, hipMemcpyDeviceToHost) == hipSuccess ? SA_AMD_OK : SA_AMD_EHIP;
+}
+
+// the pattern arguments of the token queries: as search_patterns_valid, offsets in tokens
+static bool tok_patterns_valid(const uint16_t *pat_data, const int64_t *pat_off, int32_t count)
+{
+    return search_patterns_valid((const uint8_t *)pat_data, pat_off, count);
+}
+
+// sa_amd_tok_index_search: host pointers, every output may be nullptr, arguments checked by the caller
+static int32_t tok_search(const sa_amd_tok_index &ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t count, uint8_t *contains,
+                          uint32_t *range_lo, uint32_t *range_hi)
+{
+    if (count == 0) return SA_AMD_OK;
+    const size_t C = (size_t)count, total = (size_t)pat_off[count];
+    PooledScope sc(ix.device, false);
+    const size_t b_pat = align_up(2 * total + 16, 256), b_off = align_up((C + 1) * 8, 256), b_w = align_up(C * 4 + 4, 256), b_b = align_up(C + 4, 256);
+    sc.acquire(b_pat + b_off + 2 * b_w + b_b);
+    uint16_t *dP = (uint16_t *)sc.take(b_pat);
+    int64_t *dO = (int64_t *)sc.take(b_off);
+    uint32_t *dLo = (uint32_t *)sc.take(b_w), *dHi = (uint32_t *)sc.take(b_w);
+    uint8_t *dC = (uint8_t *)sc.take(b_b);
+    if (sc.rc) return sc.rc;
+    hipStream_t st = sc.st;
+    if (total) HIP_TRY(hipMemcpyAsync(dP, pat_data, 2 * total, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dO, pat_off, (C + 1) * 8, hipMemcpyHostToDevice, st));
+    PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_tok_search, dim3(ngram_grid(count)), dim3(NG_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n,
+                                                (const uint16_t *)dP, (const int64_t *)dO, count, dC, dLo, dHi));
+    if (contains) sc.down(contains, dC, C);
+    if (range_lo) sc.down(range_lo, dLo, C * 4);
+    if (range_hi) sc.down(range_hi, dHi, C * 4);
+    if (sc.finish() != SA_AMD_OK) return sc.rc;
+    g_prof.resolve();
+    return SA_AMD_OK;
+}
+
+// backoff == false: sa_amd_tok_index_next_tokens (suffix_len is nullptr).  backoff == true: sa_amd_tok_index_infgram.  Host
+// pointers, every output may be nullptr, arguments checked by the caller.  The ranges and the counting pass run in one pooled
+// block (8 bytes per query for the listing); a listing has up to 65 536 entries per query, so its device side -- min(capacity,
+// the counted total) entries -- is a second block taken once the total is known.  One blocking read-back: the total and the
+// counters, all of which the counting pass has written.
+static int tok_query(const sa_amd_tok_index &ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t count, bool backoff, int32_t min_count,
+                     int32_t max_len, uint32_t *suffix_len, uint32_t *range_lo, uint32_t *range_hi, uint8_t *at_end, int64_t *list_off,
+                     uint16_t *tokens, uint32_t *counts, int64_t capacity, int64_t *total_out)
+{
+    sa_amd_tok_stats ts = g_last_tok_stats;                     // (the times of the last build stay)
+    ts.patterns = count;
+    ts.range_searches = ts.stream_slots = ts.search_slots = ts.stream_queries = ts.search_queries = ts.empty_queries = ts.entries = 0;
+    ts.stream_cap = g_ngram_stream_cap < 0 ? NG_STREAM_CAP_DEFAULT : g_ngram_stream_cap;
+    ts.readbacks = 0;
+    ts.backoff = backoff ? 1 : 0;
+    ts.passes = 0;
+    ts.compared_tokens = backoff ? 0 : -1;
+    g_last_tok_stats = ts;
+    if (count == 0) {
+        if (list_off) list_off[0] = 0;
+        if (total_out) *total_out = 0;
+        return SA_AMD_OK;
+    }
+    route_tuning();                                             // (the posted read-backs' switch; nothing else of the tuning is used here)
+    const int rb0 = g_readbacks;
+    const size_t C = (size_t)count, total = (size_t)pat_off[count];
+    const bool want = tokens || counts;
+
+    PooledScope sc(ix.device, false);
+    const size_t b_pat = align_up(2 * total + 16, 256), b_off = align_up((C + 1) * 8, 256), b_w = align_up(C * 4 + 4, 256), b_b = align_up(C + 4, 256);
+    const size_t b_ts = align_up(docs_scan_words((int64_t)C + 1) * 8, 256);
+    sc.acquire(256 + b_pat + 2 * b_off + 3 * b_w + b_b + b_ts);
+    unsigned long long *ctl = (unsigned long long *)sc.take(256);
+    uint16_t *dP = (uint16_t *)sc.take(b_pat);
+    int64_t *dO = (int64_t *)sc.take(b_off);
+    unsigned long long *nnz = (unsigned long long *)sc.take(b_off), *tsum = (unsigned long long *)sc.take(b_ts);
+    uint32_t *dLo = (uint32_t *)sc.take(b_w), *dHi = (uint32_t *)sc.take(b_w), *dLen = (uint32_t *)sc.take(b_w);
+    uint8_t *dEnd = (uint8_t *)sc.take(b_b);
+    if (sc.rc) return sc.rc;
+    hipStream_t st = sc.st;
+    HIP_TRY(hipMemsetAsync(ctl, 0, 256, st));
+    HIP_TRY(hipMemsetAsync(nnz + C, 0, 8, st));
+    if (total) HIP_TRY(hipMemcpyAsync(dP, pat_data, 2 * total, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dO, pat_off, (C + 1) * 8, hipMemcpyHostToDevice, st));
+
+    // ---- the ranges: the plain search, or the back-off ----
+    const unsigned grid = ngram_grid(count);
+    if (backoff)
+        PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_tok_infgram_suffix, dim3(grid), dim3(NG_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n,
+                                                    (const uint16_t *)dP, (const int64_t *)dO, count, (uint32_t)min_count, (int64_t)max_len, dLen, dLo, dHi,
+                                                    ctl));
+    else
+        PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_tok_search, dim3(grid), dim3(NG_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n,
+                                                    (const uint16_t *)dP, (const int64_t *)dO, count, (uint8_t *)nullptr, dLo, dHi));
+    // ---- the continuations: counted, scanned ... ----
+    const uint32_t *depth = backoff ? dLen : nullptr;
+    PROF(KC_MISC, count, st, hipLaunchKernelGGL((k_tok_next<false>), dim3(grid), dim3(NG_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n,
+                                                (const uint32_t *)dLo, (const uint32_t *)dHi, depth, (const int64_t *)dO, count, (uint32_t)ts.stream_cap, dEnd,
+                                                nnz, (uint16_t *)nullptr, (uint32_t *)nullptr, 0ull, ctl));
+    { const int rcn = docs_scan(nnz, (int64_t)count + 1, tsum, &ctl[NG_W_TOTAL], st); if (rcn) return rcn; }
+    unsigned long long cw[NG_W_COUNT];
+    { const int rcw = read_words(cw, ctl, sizeof(cw), st); if (rcw) return rcw; }
+    const int64_t listed = (int64_t)cw[NG_W_TOTAL];
+    if (listed < 0 || listed > (int64_t)TK_END * (int64_t)count) return SA_AMD_EINTERNAL;
+    const size_t cap = want ? (size_t)(capacity < listed ? capacity : listed) : 0;
+
+    // ---- ... and emitted in order, into a block of the listing's size ----
+    PooledScope lsc(-1, false);
+    const size_t b_lt = align_up(cap * 2 + 8, 256), b_lc = align_up(cap * 4 + 8, 256);
+    uint16_t *dToks = nullptr;
+    uint32_t *dCounts = nullptr;
+    if (cap > 0) {
+        lsc.acquire(b_lt + b_lc);
+        dToks = (uint16_t *)lsc.take(b_lt);
+        dCounts = (uint32_t *)lsc.take(b_lc);
+        if (lsc.rc) return lsc.rc;
+        PROF(KC_MISC, count, st, hipLaunchKernelGGL((k_tok_next<true>), dim3(grid), dim3(NG_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n,
+                                                    (const uint32_t *)dLo, (const uint32_t *)dHi, depth, (const int64_t *)dO, count, (uint32_t)ts.stream_cap,
+                                                    (uint8_t *)nullptr, nnz, tokens ? dToks : (uint16_t *)nullptr, counts ? dCounts : (uint32_t *)nullptr,
+                                                    (unsigned long long)cap, ctl));
+    }
+
+    // ---- down: straight into the caller's arrays ----
+    if (suffix_len) sc.down(suffix_len, dLen, C * 4);
+    if (range_lo) sc.down(range_lo, dLo, C * 4);
+    if (range_hi) sc.down(range_hi, dHi, C * 4);
+    if (at_end) sc.down(at_end, dEnd, C);
+    if (tokens && cap > 0) sc.down(tokens, dToks, cap * 2);
+    if (counts && cap > 0) sc.down(counts, dCounts, cap * 4);
+    if (list_off) sc.down(list_off, nnz, (C + 1) * 8);
+    if (sc.finish() != SA_AMD_OK) return sc.rc;
+    if (total_out) *total_out = listed;
+    g_prof.resolve();
+    ts.range_searches = backoff ? (int64_t)cw[NG_W_SEARCHES] : (int64_t)count;
+    if (backoff) ts.compared_tokens = (int64_t)cw[NG_W_BYTES];
+    ts.stream_slots = (int64_t)cw[NG_W_STREAM_SLOTS];
+    ts.search_slots = (int64_t)cw[NG_W_SEARCH_SLOTS];
+    ts.stream_queries = (int64_t)cw[NG_W_STREAM_Q];
+    ts.search_queries = (int64_t)cw[NG_W_SEARCH_Q];
+    ts.empty_queries = (int64_t)cw[NG_W_EMPTY_Q];
+    ts.entries = listed;
+    ts.passes = cap > 0 ? 2 : 1;
+    ts.readbacks = g_readbacks - rb0;
+    g_last_tok_stats = ts;
+    return SA_AMD_OK;
+}
+
+}  // namespace sa

@@ -32,6 +32,7 @@
 #include "host/doc_substrings.hpp"
 #include "host/ngram.hpp"
 #include "host/score.hpp"
+#include "host/tokens.hpp"
 
 extern "C" {
 
@@ -795,6 +796,77 @@ SA_EXPORT int32_t sa_amd_score_set_group_cap(int32_t bytes)
     const int32_t prev = sa::g_score_cap < 0 ? sa::SCORE_CAP_DEFAULT : sa::g_score_cap;
     sa::g_score_cap = bytes < 0 ? -1 : (bytes > sa::SCORE_CAP_MAX ? sa::SCORE_CAP_MAX : bytes);
     return prev;
+}
+
+// ---- 16-bit token texts: construction, the token index and its queries (host/tokens.hpp, kernels/tokens.hpp) ----
+
+SA_EXPORT int32_t sa_amd_max_tokens_u16(void) { return sa::TOK_MAX_TOKENS_U16; }
+
+SA_EXPORT int32_t sa_amd_saca_u16(const uint16_t *T, uint32_t *SA, int32_t n)
+{
+    if (n < 0 || n > sa::TOK_MAX_TOKENS_U16 || !SA || (n > 0 && !T)) return SA_AMD_EINVAL;
+    if (n == 0) { SA[0] = 0; return SA_AMD_OK; }
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
+    SA_ABI_GUARD_BEGIN
+    return sa::tok_saca_host(T, SA, n);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_create(const uint16_t *T, int32_t n, const uint32_t *SA, sa_amd_tok_index **out)
+{
+    if (!out || n < 0 || n > sa::TOK_MAX_TOKENS_U16 || (n > 0 && !T)) return SA_AMD_EINVAL;
+    *out = nullptr;
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
+    SA_ABI_GUARD_BEGIN
+    return sa::tok_index_create(T, n, SA, out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_tok_index_destroy(sa_amd_tok_index *ix)      // (frees and deletes: nothing that throws, no change of device)
+{
+    delete ix;
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_sa(const sa_amd_tok_index *ix, uint32_t *SA_out)
+{
+    if (!ix || !SA_out) return SA_AMD_EINVAL;
+    return sa::tok_index_sa(*ix, SA_out);
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_search(const sa_amd_tok_index *ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t count,
+                                          uint8_t *contains, uint32_t *range_lo, uint32_t *range_hi)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::tok_patterns_valid(pat_data, pat_off, count)) return SA_AMD_EINVAL;
+    return sa::tok_search(*ix, pat_data, pat_off, count, contains, range_lo, range_hi);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_next_tokens(const sa_amd_tok_index *ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t count,
+                                               uint32_t *range_lo, uint32_t *range_hi, uint8_t *at_end, int64_t *list_off, uint16_t *tokens,
+                                               uint32_t *counts, int64_t capacity, int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::tok_patterns_valid(pat_data, pat_off, count) || capacity < 0) return SA_AMD_EINVAL;
+    return sa::tok_query(*ix, pat_data, pat_off, count, false, 1, 0, nullptr, range_lo, range_hi, at_end, list_off, tokens, counts, capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_infgram(const sa_amd_tok_index *ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t count,
+                                           int32_t min_count, int32_t max_len, uint32_t *suffix_len, uint32_t *range_lo, uint32_t *range_hi,
+                                           uint8_t *at_end, int64_t *list_off, uint16_t *tokens, uint32_t *counts, int64_t capacity,
+                                           int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::tok_patterns_valid(pat_data, pat_off, count) || capacity < 0 || min_count < 1) return SA_AMD_EINVAL;
+    return sa::tok_query(*ix, pat_data, pat_off, count, true, min_count, max_len, suffix_len, range_lo, range_hi, at_end, list_off, tokens, counts,
+                         capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_tok_stats(sa_amd_tok_stats *out)
+{
+    if (out) *out = sa::g_last_tok_stats;
 }
 
 // ---- packed format (reference src/packed_sa.rs); byte layout: u32 magic "SA4x" LE, u32 length, u64 data length
