@@ -1318,6 +1318,29 @@ def _pattern_batch(patterns):
     return data, off, len(pats)
 
 
+def _ngram_query(next_fn, infgram_fn, handle, batch, sym_dtype, cap: int, backoff: bool, min_count: int, max_len: int):
+    """the continuation query of either index (``next_fn`` / ``infgram_fn`` of its ABI) over an uploaded ``batch`` of patterns ->
+    ``(suffix_len, lo, hi, at_end, list_off, symbols, counts)``; a listing longer than ``cap`` entries is asked for again with
+    the capacity the first call reported"""
+    data, off, cnt = batch
+    slen, lo, hi = (np.zeros(cnt, dtype=np.uint32) for _ in range(3))
+    ae = np.zeros(cnt, dtype=np.uint8)
+    loff = np.zeros(cnt + 1, dtype=np.int64)
+    total = ctypes.c_int64(0)
+    while True:
+        syms = np.empty(max(cap, 1), dtype=sym_dtype)
+        c = np.empty(max(cap, 1), dtype=np.uint32)
+        out = (lo.ctypes.data, hi.ctypes.data, ae.ctypes.data, loff.ctypes.data, syms.ctypes.data, c.ctypes.data, cap, ctypes.byref(total))
+        if backoff:
+            _check(infgram_fn(handle, data.ctypes.data, off.ctypes.data, cnt, int(min_count), int(max_len), slen.ctypes.data, *out))
+        else:
+            _check(next_fn(handle, data.ctypes.data, off.ctypes.data, cnt, *out))
+        if total.value <= cap:
+            m = int(total.value)
+            return slen, lo, hi, ae, loff, syms[:m].copy(), c[:m].copy()
+        cap = int(total.value)
+
+
 class DeviceIndex:
     """Text + suffix array resident in HBM (sa_amd_index of include/suffix_array_amd.h): batched
     `contains` / `search_all` / `search_lcp` (reference src/sa.rs:164-253), bucket table, integrity check.
@@ -1552,26 +1575,9 @@ class DeviceIndex:
         return [(out[0, toff[q]:toff[q + 1]].copy(), out[1, toff[q]:toff[q + 1]].copy()) for q in range(cnt)]
 
     def _ngram(self, patterns, backoff: bool, min_count: int, max_len: int):
-        data, off, cnt = _pattern_batch(patterns)
-        slen, lo, hi = (np.zeros(cnt, dtype=np.uint32) for _ in range(3))
-        ae = np.zeros(cnt, dtype=np.uint8)
-        loff = np.zeros(cnt + 1, dtype=np.int64)
-        total = ctypes.c_int64(0)
-        cap = min(256 * cnt, max(1 << 16, 8 * cnt))
-        while True:
-            b = np.empty(max(cap, 1), dtype=np.uint8)
-            c = np.empty(max(cap, 1), dtype=np.uint32)
-            if backoff:
-                _check(lib().sa_amd_index_infgram(self._h, data.ctypes.data, off.ctypes.data, cnt, int(min_count), int(max_len), slen.ctypes.data,
-                                                  lo.ctypes.data, hi.ctypes.data, ae.ctypes.data, loff.ctypes.data, b.ctypes.data, c.ctypes.data,
-                                                  cap, ctypes.byref(total)))
-            else:
-                _check(lib().sa_amd_index_next_bytes(self._h, data.ctypes.data, off.ctypes.data, cnt, lo.ctypes.data, hi.ctypes.data,
-                                                     ae.ctypes.data, loff.ctypes.data, b.ctypes.data, c.ctypes.data, cap, ctypes.byref(total)))
-            if total.value <= cap:
-                m = int(total.value)
-                return slen, lo, hi, ae, loff, b[:m].copy(), c[:m].copy()
-            cap = int(total.value)
+        batch = _pattern_batch(patterns)
+        return _ngram_query(lib().sa_amd_index_next_bytes, lib().sa_amd_index_infgram, self._h, batch, np.uint8,
+                            min(256 * batch[2], max(1 << 16, 8 * batch[2])), backoff, min_count, max_len)
 
     def next_bytes(self, patterns, dense: bool = False):
         """EXTENSION: what follows each context in the text, and how often -> ``(lo, hi, at_end, list_off, bytes, counts)``.
@@ -1737,27 +1743,9 @@ class TokenIndex:
         return self._search(patterns, True)[0].astype(bool)
 
     def _ngram(self, patterns, backoff: bool, min_count: int, max_len: int):
-        data, off, cnt = _token_batch(patterns)
-        slen, lo, hi = (np.zeros(cnt, dtype=np.uint32) for _ in range(3))
-        ae = np.zeros(cnt, dtype=np.uint8)
-        loff = np.zeros(cnt + 1, dtype=np.int64)
-        total = ctypes.c_int64(0)
-        cap = max(1 << 16, 8 * cnt)
-        while True:
-            t = np.empty(max(cap, 1), dtype=np.uint16)
-            c = np.empty(max(cap, 1), dtype=np.uint32)
-            if backoff:
-                _check(lib().sa_amd_tok_index_infgram(self._h, data.ctypes.data, off.ctypes.data, cnt, int(min_count), int(max_len),
-                                                      slen.ctypes.data, lo.ctypes.data, hi.ctypes.data, ae.ctypes.data, loff.ctypes.data,
-                                                      t.ctypes.data, c.ctypes.data, cap, ctypes.byref(total)))
-            else:
-                _check(lib().sa_amd_tok_index_next_tokens(self._h, data.ctypes.data, off.ctypes.data, cnt, lo.ctypes.data, hi.ctypes.data,
-                                                          ae.ctypes.data, loff.ctypes.data, t.ctypes.data, c.ctypes.data, cap,
-                                                          ctypes.byref(total)))
-            if total.value <= cap:
-                m = int(total.value)
-                return slen, lo, hi, ae, loff, t[:m].copy(), c[:m].copy()
-            cap = int(total.value)
+        batch = _token_batch(patterns)
+        return _ngram_query(lib().sa_amd_tok_index_next_tokens, lib().sa_amd_tok_index_infgram, self._h, batch, np.uint16,
+                            max(1 << 16, 8 * batch[2]), backoff, min_count, max_len)
 
     def next_tokens(self, patterns):
         """what follows each context in the text, and how often -> ``(lo, hi, at_end, list_off, tokens, counts)``, the result

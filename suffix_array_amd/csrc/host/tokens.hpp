@@ -194,8 +194,8 @@ static int32_t tok_search(const sa_amd_tok_index &ix, const uint16_t *pat_data, 
 }
 
 // backoff == false: sa_amd_tok_index_next_tokens (suffix_len is nullptr).  backoff == true: sa_amd_tok_index_infgram.  Host
-// pointers, every output may be nullptr, arguments checked by the caller.  The ranges and the counting pass run in one pooled
-// block (8 bytes per query for the listing); a listing has up to 65 536 entries per query, so its device side -- min(capacity,
+// pointers, every output may be nullptr, arguments checked by the caller.  The steps are those of host/ngram.hpp, in another
+// order: the ranges and the counting pass run in one pooled block (8 bytes per query for the listing); a listing has up to 65 536 entries per query, so its device side -- min(capacity,
 // the counted total) entries -- is a second block taken once the total is known.  One blocking read-back: the total and the
 // counters, all of which the counting pass has written.
 static int tok_query(const sa_amd_tok_index &ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t count, bool backoff, int32_t min_count,
@@ -203,13 +203,7 @@ static int tok_query(const sa_amd_tok_index &ix, const uint16_t *pat_data, const
                      uint16_t *tokens, uint32_t *counts, int64_t capacity, int64_t *total_out)
 {
     sa_amd_tok_stats ts = g_last_tok_stats;                     // (the times of the last build stay)
-    ts.patterns = count;
-    ts.range_searches = ts.stream_slots = ts.search_slots = ts.stream_queries = ts.search_queries = ts.empty_queries = ts.entries = 0;
-    ts.stream_cap = g_ngram_stream_cap < 0 ? NG_STREAM_CAP_DEFAULT : g_ngram_stream_cap;
-    ts.readbacks = 0;
-    ts.backoff = backoff ? 1 : 0;
-    ts.passes = 0;
-    ts.compared_tokens = backoff ? 0 : -1;
+    ngram_stats_fill(ts, ts.compared_tokens, count, backoff, nullptr, 0, 0);
     g_last_tok_stats = ts;
     if (count == 0) {
         if (list_off) list_off[0] = 0;
@@ -218,46 +212,28 @@ static int tok_query(const sa_amd_tok_index &ix, const uint16_t *pat_data, const
     }
     route_tuning();                                             // (the posted read-backs' switch; nothing else of the tuning is used here)
     const int rb0 = g_readbacks;
-    const size_t C = (size_t)count, total = (size_t)pat_off[count];
-    const bool want = tokens || counts;
 
     PooledScope sc(ix.device, false);
-    const size_t b_pat = align_up(2 * total + 16, 256), b_off = align_up((C + 1) * 8, 256), b_w = align_up(C * 4 + 4, 256), b_b = align_up(C + 4, 256);
-    const size_t b_ts = align_up(docs_scan_words((int64_t)C + 1) * 8, 256);
-    sc.acquire(256 + b_pat + 2 * b_off + 3 * b_w + b_b + b_ts);
-    unsigned long long *ctl = (unsigned long long *)sc.take(256);
-    uint16_t *dP = (uint16_t *)sc.take(b_pat);
-    int64_t *dO = (int64_t *)sc.take(b_off);
-    unsigned long long *nnz = (unsigned long long *)sc.take(b_off), *tsum = (unsigned long long *)sc.take(b_ts);
-    uint32_t *dLo = (uint32_t *)sc.take(b_w), *dHi = (uint32_t *)sc.take(b_w), *dLen = (uint32_t *)sc.take(b_w);
-    uint8_t *dEnd = (uint8_t *)sc.take(b_b);
-    if (sc.rc) return sc.rc;
+    NgScratch s;
+    { const int rcb = ngram_begin(sc, s, pat_data, pat_off, count, 2, 0); if (rcb) return rcb; }
     hipStream_t st = sc.st;
-    HIP_TRY(hipMemsetAsync(ctl, 0, 256, st));
-    HIP_TRY(hipMemsetAsync(nnz + C, 0, 8, st));
-    if (total) HIP_TRY(hipMemcpyAsync(dP, pat_data, 2 * total, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dO, pat_off, (C + 1) * 8, hipMemcpyHostToDevice, st));
 
     // ---- the ranges: the plain search, or the back-off ----
     const unsigned grid = ngram_grid(count);
     if (backoff)
-        PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_tok_infgram_suffix, dim3(grid), dim3(NG_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n,
-                                                    (const uint16_t *)dP, (const int64_t *)dO, count, (uint32_t)min_count, (int64_t)max_len, dLen, dLo, dHi,
-                                                    ctl));
+        PROF(KC_MISC, count, st, hipLaunchKernelGGL((k_infgram_suffix<uint16_t>), dim3(grid), dim3(NG_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n,
+                                                    (const uint32_t *)nullptr, (const uint64_t *)nullptr, 0, (const uint16_t *)s.pat, (const int64_t *)s.off,
+                                                    count, (uint32_t)min_count, (int64_t)max_len, s.len, s.lo, s.hi, s.ctl));
     else
         PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_tok_search, dim3(grid), dim3(NG_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n,
-                                                    (const uint16_t *)dP, (const int64_t *)dO, count, (uint8_t *)nullptr, dLo, dHi));
+                                                    (const uint16_t *)s.pat, (const int64_t *)s.off, count, (uint8_t *)nullptr, s.lo, s.hi));
     // ---- the continuations: counted, scanned ... ----
-    const uint32_t *depth = backoff ? dLen : nullptr;
-    PROF(KC_MISC, count, st, hipLaunchKernelGGL((k_tok_next<false>), dim3(grid), dim3(NG_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n,
-                                                (const uint32_t *)dLo, (const uint32_t *)dHi, depth, (const int64_t *)dO, count, (uint32_t)ts.stream_cap, dEnd,
-                                                nnz, (uint16_t *)nullptr, (uint32_t *)nullptr, 0ull, ctl));
-    { const int rcn = docs_scan(nnz, (int64_t)count + 1, tsum, &ctl[NG_W_TOTAL], st); if (rcn) return rcn; }
+    { const int rcn = ngram_count(k_tok_next<false>, ix.text(), ix.sa(), ix.n, s, backoff, count, st); if (rcn) return rcn; }
     unsigned long long cw[NG_W_COUNT];
-    { const int rcw = read_words(cw, ctl, sizeof(cw), st); if (rcw) return rcw; }
+    { const int rcw = read_words(cw, s.ctl, sizeof(cw), st); if (rcw) return rcw; }
     const int64_t listed = (int64_t)cw[NG_W_TOTAL];
     if (listed < 0 || listed > (int64_t)TK_END * (int64_t)count) return SA_AMD_EINTERNAL;
-    const size_t cap = want ? (size_t)(capacity < listed ? capacity : listed) : 0;
+    const size_t cap = tokens || counts ? (size_t)(capacity < listed ? capacity : listed) : 0;
 
     // ---- ... and emitted in order, into a block of the listing's size ----
     PooledScope lsc(-1, false);
@@ -269,33 +245,19 @@ static int tok_query(const sa_amd_tok_index &ix, const uint16_t *pat_data, const
         dToks = (uint16_t *)lsc.take(b_lt);
         dCounts = (uint32_t *)lsc.take(b_lc);
         if (lsc.rc) return lsc.rc;
-        PROF(KC_MISC, count, st, hipLaunchKernelGGL((k_tok_next<true>), dim3(grid), dim3(NG_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n,
-                                                    (const uint32_t *)dLo, (const uint32_t *)dHi, depth, (const int64_t *)dO, count, (uint32_t)ts.stream_cap,
-                                                    (uint8_t *)nullptr, nnz, tokens ? dToks : (uint16_t *)nullptr, counts ? dCounts : (uint32_t *)nullptr,
-                                                    (unsigned long long)cap, ctl));
+        const int rce = ngram_pass(k_tok_next<true>, ix.text(), ix.sa(), ix.n, s, backoff, count, nullptr, tokens ? dToks : nullptr,
+                                   counts ? dCounts : nullptr, cap, st);
+        if (rce) return rce;
     }
 
     // ---- down: straight into the caller's arrays ----
-    if (suffix_len) sc.down(suffix_len, dLen, C * 4);
-    if (range_lo) sc.down(range_lo, dLo, C * 4);
-    if (range_hi) sc.down(range_hi, dHi, C * 4);
-    if (at_end) sc.down(at_end, dEnd, C);
     if (tokens && cap > 0) sc.down(tokens, dToks, cap * 2);
     if (counts && cap > 0) sc.down(counts, dCounts, cap * 4);
-    if (list_off) sc.down(list_off, nnz, (C + 1) * 8);
+    ngram_down(sc, s, count, suffix_len, range_lo, range_hi, at_end, list_off);
     if (sc.finish() != SA_AMD_OK) return sc.rc;
     if (total_out) *total_out = listed;
     g_prof.resolve();
-    ts.range_searches = backoff ? (int64_t)cw[NG_W_SEARCHES] : (int64_t)count;
-    if (backoff) ts.compared_tokens = (int64_t)cw[NG_W_BYTES];
-    ts.stream_slots = (int64_t)cw[NG_W_STREAM_SLOTS];
-    ts.search_slots = (int64_t)cw[NG_W_SEARCH_SLOTS];
-    ts.stream_queries = (int64_t)cw[NG_W_STREAM_Q];
-    ts.search_queries = (int64_t)cw[NG_W_SEARCH_Q];
-    ts.empty_queries = (int64_t)cw[NG_W_EMPTY_Q];
-    ts.entries = listed;
-    ts.passes = cap > 0 ? 2 : 1;
-    ts.readbacks = g_readbacks - rb0;
+    ngram_stats_fill(ts, ts.compared_tokens, count, backoff, cw, cap > 0 ? 2 : 1, g_readbacks - rb0);
     g_last_tok_stats = ts;
     return SA_AMD_OK;
 }

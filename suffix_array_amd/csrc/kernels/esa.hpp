@@ -11,6 +11,7 @@
 #pragma once
 #include "common.hpp"
 #include "extras.hpp"
+#include "sym.hpp"
 
 namespace sa {
 
@@ -46,33 +47,6 @@ __global__ __launch_bounds__(ESA_THREADS) void k_esa_tree(const uint32_t *__rest
         if (y > 0 && x <= N) pair[x - 1] = pr[y];
     }
     if (threadIdx.x == 0 && tile_min) tile_min[blockIdx.x] = a[0];
-}
-
-// wave_compare from byte c0 on: the caller knows that s[p..] and pat agree on their first c0 bytes.  *bytes grows by the
-// bytes of every 64-byte chunk loaded.  Reads only T[p + c0 .. min(n, p + plen)) and pat[c0 .. plen).
-__device__ __forceinline__ SuffixCmp wave_compare_from(const uint8_t *__restrict__ T, int64_t n, int64_t p,
-                                                       const uint8_t *__restrict__ pat, int64_t plen, int64_t c0, int64_t *bytes)
-{
-    const int l = lane_id();
-    const int64_t slen = n - p;
-    int64_t common = slen < plen ? slen : plen;
-    if (common < 0) common = 0;                              // (an entry > n: only when the array is not a suffix array)
-    for (int64_t c = c0; c < common; c += WAVE) {
-        const int64_t i = c + l;
-        const bool in = i < common;
-        const uint8_t x = in ? T[p + i] : 0, y = in ? pat[i] : 0;
-        *bytes += common - c < WAVE ? common - c : WAVE;
-        const uint64_t diff = __ballot(in && x != y);
-        if (diff) {
-            const int first = __ffsll((unsigned long long)diff) - 1;
-            const int xv = __shfl((int)x, first, WAVE), yv = __shfl((int)y, first, WAVE);
-            SuffixCmp r; r.ord = xv < yv ? -1 : 1; r.lcp = (uint32_t)(c + first);
-            return r;
-        }
-    }
-    SuffixCmp r; r.lcp = (uint32_t)common;
-    r.ord = slen < plen ? -1 : (slen > plen ? 1 : 0);
-    return r;
 }
 
 struct EsaState { uint64_t L; int64_t l, r; };       // the final left end and lcp(pat, suf(L)), lcp(pat, suf(R)) (R = L + 1)

@@ -6,6 +6,7 @@
 //   k_ci_*             reference src/sa.rs:72-84 (check_integrity) in its linear-time form
 #pragma once
 #include "common.hpp"
+#include "sym.hpp"
 
 namespace sa {
 
@@ -281,36 +282,10 @@ __global__ __launch_bounds__(CI_THREADS) void k_ci_check_shared(const uint32_t *
 // Batched search: contains / search_all / search_lcp of reference
 // src/sa.rs:164-253 for MANY patterns at once, one wave per pattern.  The reference's API is one
 // pattern per call (latency-bound binary search, CPU-appropriate); the batched form is what a GPU
-// can help with.  Comparisons are done 64 bytes at a time: lane l compares byte c + l of the
-// pattern with byte c + l of the suffix, a ballot finds the first difference.
+// can help with.  Comparisons are done 64 bytes at a time (wave_compare_from, kernels/sym.hpp),
+// the two lower bounds of search_all are plain_range of the same header.
 // ------------------------------------------------------------------------------------------
 namespace sa {
-
-struct SuffixCmp { int ord; uint32_t lcp; };   // ord: -1 suffix < pattern, 0 equal, +1 suffix > pattern
-
-// Rust slice ordering of s[p..] against pat (lexicographic, a proper prefix is smaller) and their lcp
-__device__ __forceinline__ SuffixCmp wave_compare(const uint8_t *__restrict__ T, int64_t n, int64_t p,
-                                                  const uint8_t *__restrict__ pat, int64_t plen)
-{
-    const int l = lane_id();
-    const int64_t slen = n - p;
-    const int64_t common = slen < plen ? slen : plen;
-    for (int64_t c = 0; c < common; c += WAVE) {
-        const int64_t i = c + l;
-        const bool in = i < common;
-        const uint8_t a = in ? T[p + i] : 0, b = in ? pat[i] : 0;
-        const uint64_t diff = __ballot(in && a != b);
-        if (diff) {
-            const int first = __ffsll((unsigned long long)diff) - 1;
-            const int av = __shfl((int)a, first, WAVE), bv = __shfl((int)b, first, WAVE);
-            SuffixCmp r; r.ord = av < bv ? -1 : 1; r.lcp = (uint32_t)(c + first);
-            return r;
-        }
-    }
-    SuffixCmp r; r.lcp = (uint32_t)common;
-    r.ord = slen < plen ? -1 : (slen > plen ? 1 : 0);
-    return r;
-}
 
 constexpr int SEARCH_THREADS = 256;
 
@@ -335,21 +310,10 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_batch(
     } else if (bkt && plen == 1) {
         lo = bkt[(int)pat[0] * 257]; hi = bkt[(int)pat[0] * 257 + 257];
     }
-    const int64_t bucket_hi = hi;
     const bool empty_bucket = bkt != nullptr && plen > 0 && lo == hi;      // (search_lcp below: reference src/sa.rs:211-222)
-    // search_all, first loop (reference src/sa.rs:182-190): first i with !(pat > s[sa[i]..])
-    while (lo < hi) {
-        const int64_t m = lo + (hi - lo) / 2;
-        if (wave_compare(T, n, (int64_t)SA[m], pat, plen).ord < 0) lo = m + 1; else hi = m;
-    }
-    const int64_t i = lo;
-    // second loop (src/sa.rs:192-201): first j >= i whose suffix does not start with pat
-    int64_t lo2 = i, hi2 = bucket_hi;
-    while (lo2 < hi2) {
-        const int64_t m = lo2 + (hi2 - lo2) / 2;
-        if ((int64_t)wave_compare(T, n, (int64_t)SA[m], pat, plen).lcp == plen) lo2 = m + 1; else hi2 = m;
-    }
-    const int64_t j = lo2;
+    int64_t symbols = 0;                                      // (nobody reads the count here)
+    const NgRange r = plain_range(T, SA, n, lo, hi, pat, plen, &symbols);      // search_all (reference src/sa.rs:182-201)
+    const int64_t i = r.lo, j = r.hi;
     // search_lcp without buckets (src/sa.rs:207-253): i is also the insertion point of pat
     uint32_t ls = (uint32_t)n, ll = 0;
     if (empty_bucket) {
@@ -360,13 +324,13 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_batch(
         if (thi > tlo) { ls = SA[tlo]; ll = 1; }
     } else {
         SuffixCmp cb; cb.ord = 1; cb.lcp = 0;
-        if (i < len) cb = wave_compare(T, n, (int64_t)SA[i], pat, plen);
+        if (i < len) cb = wave_compare_from(T, n, (int64_t)SA[i], pat, plen, 0, &symbols);
         if (i < len && cb.ord == 0) { ls = SA[i]; ll = (uint32_t)(n - (int64_t)SA[i]); }            // Ok(i): start..s.len()
         else if (i > 0 && i < len) {
-            const SuffixCmp ca = wave_compare(T, n, (int64_t)SA[i - 1], pat, plen);
+            const SuffixCmp ca = wave_compare_from(T, n, (int64_t)SA[i - 1], pat, plen, 0, &symbols);
             if (ca.lcp > cb.lcp) { ls = SA[i - 1]; ll = ca.lcp; } else { ls = SA[i]; ll = cb.lcp; }
         } else if (i == 0) { ls = SA[0]; ll = cb.lcp; }
-        else { const SuffixCmp ca = wave_compare(T, n, (int64_t)SA[i - 1], pat, plen); ls = SA[i - 1]; ll = ca.lcp; }
+        else { const SuffixCmp ca = wave_compare_from(T, n, (int64_t)SA[i - 1], pat, plen, 0, &symbols); ls = SA[i - 1]; ll = ca.lcp; }
     }
     if (lane_id() == 0) {
         if (contains) contains[q] = (uint8_t)(j > i);         // src/sa.rs:164-170: some suffix starts with pat

@@ -17,6 +17,7 @@
 // A wrong permutation gives unspecified answers; every entry of SA is checked against n before it is used, every slot taken from
 // the bucket table is clamped to 1 .. n + 1 and every load of T or Q is guarded by the array's ends.
 #pragma once
+#include "sym.hpp"
 #include "esa.hpp"
 #include "lcp.hpp"
 

@@ -17,6 +17,7 @@
 // A wrong permutation gives unspecified answers; every slot read lies in [0, n + 1), every SA entry is checked against n
 // before T is read through it, and Q is read inside [0, m) only.
 #pragma once
+#include "sym.hpp"
 #include "match.hpp"
 #include "ngram.hpp"
 
@@ -108,7 +109,7 @@ __device__ __forceinline__ uint32_t score_byte_bound(const uint8_t *__restrict__
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2;
         ++*probes;
-        if (ngram_byte(T, SA, n, depth, mid) < target) lo = mid + 1; else hi = mid;
+        if (next_symbol(T, SA, n, depth, mid) < target) lo = mid + 1; else hi = mid;
     }
     return lo;
 }

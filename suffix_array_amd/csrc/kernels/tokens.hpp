@@ -2,7 +2,7 @@
 // of the token text (k_tok_be_image), the byte builder on B, then an order-preserving compaction that keeps the even entries of
 // B's suffix array, halved (k_tok_compact_count, one scan, k_tok_compact_scatter) -- big-endian bytes compare like the tokens and
 // two even-offset suffixes of B have even lengths, so their byte order is the token order.  Queries over a resident token index:
-// range search (k_tok_search), back-off (k_tok_infgram_suffix) and the counts of the token that follows a context (k_tok_next),
+// range search (k_tok_search), back-off (k_infgram_suffix<uint16_t>) and the counts of the token that follows a context (k_tok_next),
 // the token forms of kernels/ngram.hpp.  One wave per query, no atomics on the answers.  gfx950, wave64.  Every slot read lies
 // in [0, n + 1) and every SA entry is checked against n before T is read through it, whatever the arrays hold.
 #pragma once
@@ -18,7 +18,7 @@ constexpr int TK_WAVE_ITEMS = TK_LOADS * TK_CHUNK;          // consecutive entri
 constexpr int TK_TILE = TK_WAVES * TK_WAVE_ITEMS;           // 2048 entries of the byte-level array: one count
 constexpr int TK_SPAN = 4;                                  // consecutive tiles a workgroup takes in one trip
 constexpr int TK_IMAGE_ITEMS = 8;                           // tokens per work-item of the image pass: one 16-byte load and store
-constexpr int TK_END = 65536;                               // the "token" of a slot whose suffix ends at the context: sorts behind every token
+constexpr int TK_END = 65536;                               // the "token" of a slot whose suffix ends at the context: sym_end<uint16_t>()
 
 // B[2 i] = T[i] >> 8, B[2 i + 1] = T[i] & 255 for i < n: the two bytes of every token swapped.  T and B are 16-byte aligned and
 // their slabs end at or behind the 16-byte group of the last token; the bytes of B behind 2 n are written as zeros.
@@ -149,56 +149,8 @@ __global__ __launch_bounds__(TK_THREADS) void k_tok_sa_range(const uint32_t *__r
     if (__ballot(bad) && lane_id() == 0) atomicOr(flags, 1u);
 }
 
-// wave_compare_from (kernels/esa.hpp) over tokens: the order of the token suffix at p against pat[0 .. plen) and their common
-// prefix, 64 tokens (128 bytes) a step.  *tokens grows by the tokens of every chunk loaded.  Reads only
-// T[p .. min(n, p + plen)) and pat[0 .. plen).
-__device__ __forceinline__ SuffixCmp tok_wave_compare(const uint16_t *__restrict__ T, int64_t n, int64_t p,
-                                                      const uint16_t *__restrict__ pat, int64_t plen, int64_t *tokens)
-{
-    const int l = lane_id();
-    const int64_t slen = n - p;
-    int64_t common = slen < plen ? slen : plen;
-    if (common < 0) common = 0;                              // (an entry > n: only when the array is not a suffix array)
-    for (int64_t c = 0; c < common; c += WAVE) {
-        const int64_t i = c + l;
-        const bool in = i < common;
-        const uint16_t x = in ? T[p + i] : 0, y = in ? pat[i] : 0;
-        *tokens += common - c < WAVE ? common - c : WAVE;
-        const uint64_t diff = __ballot(in && x != y);
-        if (diff) {
-            const int first = __ffsll((unsigned long long)diff) - 1;
-            const int xv = __shfl((int)x, first, WAVE), yv = __shfl((int)y, first, WAVE);
-            SuffixCmp r; r.ord = xv < yv ? -1 : 1; r.lcp = (uint32_t)(c + first);
-            return r;
-        }
-    }
-    SuffixCmp r; r.lcp = (uint32_t)common;
-    r.ord = slen < plen ? -1 : (slen > plen ? 1 : 0);
-    return r;
-}
-
-// The match range of pat[0 .. plen): two lower bounds over the n + 1 slots, as k_search_batch finds them (no bucket table and no
-// LCP table).  Executed by a whole wave.
-__device__ __forceinline__ NgRange tok_range(const uint16_t *__restrict__ T, const uint32_t *__restrict__ SA, int64_t n,
-                                             const uint16_t *__restrict__ pat, int64_t plen, int64_t *tokens)
-{
-    int64_t lo = 0, hi = n + 1;
-    while (lo < hi) {                                         // first i whose suffix is not smaller than pat
-        const int64_t m = lo + (hi - lo) / 2;
-        if (tok_wave_compare(T, n, (int64_t)SA[m], pat, plen, tokens).ord < 0) lo = m + 1; else hi = m;
-    }
-    int64_t lo2 = lo, hi2 = n + 1;
-    while (lo2 < hi2) {                                       // first j >= i whose suffix does not start with pat
-        const int64_t m = lo2 + (hi2 - lo2) / 2;
-        if ((int64_t)tok_wave_compare(T, n, (int64_t)SA[m], pat, plen, tokens).lcp == plen) lo2 = m + 1; else hi2 = m;
-    }
-    NgRange r;
-    r.lo = (uint32_t)lo; r.hi = (uint32_t)lo2;
-    return r;
-}
-
-// Range search of `count` patterns, one wave each (a wave takes every waves-th pattern); pat_off in tokens.  Every output may
-// be nullptr.
+// Range search of `count` patterns, one wave each (a wave takes every waves-th pattern): plain_range (kernels/sym.hpp) over the
+// n + 1 slots, no bucket table and no LCP table; pat_off in tokens.  Every output may be nullptr.
 __global__ __launch_bounds__(NG_THREADS) void k_tok_search(
     const uint16_t *__restrict__ T, const uint32_t *__restrict__ SA, int64_t n, const uint16_t *__restrict__ pat_data,
     const int64_t *__restrict__ pat_off, int32_t count, uint8_t *__restrict__ contains, uint32_t *__restrict__ range_lo,
@@ -207,50 +159,13 @@ __global__ __launch_bounds__(NG_THREADS) void k_tok_search(
     const int64_t waves = (int64_t)gridDim.x * NG_WAVES;
     int64_t tokens = 0;
     for (int64_t q = (int64_t)blockIdx.x * NG_WAVES + wave_id(); q < count; q += waves) {
-        const NgRange r = tok_range(T, SA, n, pat_data + pat_off[q], pat_off[q + 1] - pat_off[q], &tokens);
+        const NgRange r = plain_range(T, SA, n, 0, n + 1, pat_data + pat_off[q], pat_off[q + 1] - pat_off[q], &tokens);
         if (lane_id() == 0) {
             if (contains) contains[q] = r.hi > r.lo ? 1 : 0;
             if (range_lo) range_lo[q] = r.lo;
             if (range_hi) range_hi[q] = r.hi;
         }
     }
-}
-
-// Back-off, as k_infgram_suffix: the bisection on the suffix length of prompt q (L tokens, cap = L or min(L, max_len)), every
-// probe one range search, at most ceil(log2(cap + 1)) of them.  ctl[NG_W_SEARCHES] += probes, ctl[NG_W_BYTES] += tokens
-// compared (one atomic per wave each).
-__global__ __launch_bounds__(NG_THREADS) void k_tok_infgram_suffix(
-    const uint16_t *__restrict__ T, const uint32_t *__restrict__ SA, int64_t n, const uint16_t *__restrict__ pat_data,
-    const int64_t *__restrict__ pat_off, int32_t count, uint32_t min_count, int64_t max_len, uint32_t *__restrict__ suffix_len,
-    uint32_t *__restrict__ range_lo, uint32_t *__restrict__ range_hi, unsigned long long *__restrict__ ctl)
-{
-    const int64_t waves = (int64_t)gridDim.x * NG_WAVES;
-    int64_t tokens = 0, searches = 0;
-    for (int64_t q = (int64_t)blockIdx.x * NG_WAVES + wave_id(); q < count; q += waves) {
-        const uint16_t *pat = pat_data + pat_off[q];
-        const int64_t L = pat_off[q + 1] - pat_off[q];
-        const int64_t cap = max_len > 0 && max_len < L ? max_len : L;
-        int64_t good = 0, bad = cap + 1;
-        uint32_t lo = 0, hi = (uint32_t)n + 1u;
-        while (bad - good > 1) {
-            const int64_t s = good + (bad - good) / 2;
-            const NgRange r = tok_range(T, SA, n, pat + (L - s), s, &tokens);
-            ++searches;
-            if (r.hi > r.lo && r.hi - r.lo >= min_count) { good = s; lo = r.lo; hi = r.hi; } else bad = s;
-        }
-        if (lane_id() == 0) { suffix_len[q] = (uint32_t)good; range_lo[q] = lo; range_hi[q] = hi; }
-    }
-    if (lane_id() == 0) {
-        if (searches) atomicAdd(&ctl[NG_W_SEARCHES], (unsigned long long)searches);
-        if (tokens) atomicAdd(&ctl[NG_W_BYTES], (unsigned long long)tokens);
-    }
-}
-
-// the token behind the context of slot i < n + 1, TK_END where the suffix ends at or before it
-__device__ __forceinline__ int tok_next_token(const uint16_t *__restrict__ T, const uint32_t *__restrict__ SA, int64_t n, int64_t p, uint32_t i)
-{
-    const int64_t s = (int64_t)SA[i] + p;
-    return s < n ? (int)T[s] : TK_END;
 }
 
 // one entry of a listing: the token and count of the run with rank `r` behind the listing's offset `o`
@@ -263,21 +178,19 @@ __device__ __forceinline__ void tok_emit_count(uint32_t *__restrict__ counts, un
     if (counts && o + r < capacity) counts[o + r] = c;
 }
 
-// Continuations of query q with the range [lo, hi) (clamped to the n + 1 slots) and depth p (depth[q], or the pattern's length
-// where depth is nullptr).  at_end = the range's first slot ends at the context; it is stripped: s0 = lo + at_end,
-// cnt = hi - s0.  Inside the range the slots are sorted by the token behind the context, so the listing is the list of the runs
-// of equal tokens: a run STARTS at place i (relative to s0) where the token differs from the one at i - 1, and its count is the
-// next start (or cnt) less its own.  A run of TK_END (only an array that is no suffix array has one behind s0) ends the run
-// before it and is not listed.  There is no table per query: a run's rank in the listing is the number of listed starts before it.
+// Continuations of query q over its window (ng_window of kernels/ngram.hpp: s0, cnt, p, at_end).  Inside the range the slots
+// are sorted by the token behind the context, so the listing is the list of the runs of equal tokens: a run STARTS at place i
+// (relative to s0) where the token differs from the one at i - 1, and its count is the next start (or cnt) less its own.  A run
+// of TK_END (only an array that is no suffix array has one behind s0) ends the run before it and is not listed.  There is no
+// table per query: a run's rank in the listing is the number of listed starts before it.
 //   cnt <= stream_cap: the range is read once, NG_LOADS * 64 slots a trip; a lane compares its token with its left neighbour's
 //     (a shuffle; the last token of a trip is carried into the next).  The ranks come from the ballot of the listed starts, the
 //     count of a start from the next set bit of the ballot of all starts; the last start of a ballot waits (wave-uniform
 //     registers) for the first start of a later one.  cnt slots probed.
-//   else: lane l probes the sample slot l (cnt - 1) / 63; where a sample's token is below the next one's, run starts lie between
-//     them, and the lane finds each by a binary search for the first slot with a token above the last one found -- the upper end
-//     of the search is always a probed slot, so the token of the start is known without another probe.  At most
-//     64 + D (ceil(log2(cnt + 1)) + 1) slots probed for D distinct continuations.  A lane's ranks start at the exclusive sum of
-//     the starts the lanes before it found; the count of a lane's last run ends at the first start of a later lane.
+//   else: the 64 samples and the walk between them (ng_sample, ng_walk of kernels/ngram.hpp), walked once to count and, EMIT,
+//     once more to emit; only the first walk's probes are counted.  At most 64 + D (ceil(log2(cnt + 1)) + 1) slots probed for D
+//     distinct continuations.  A lane's ranks start at the exclusive sum of the starts the lanes before it found; the count of a
+//     lane's last run ends at the first start of a later lane.
 // EMIT = false: nnz[q] = the number of listed runs (nnz[count] is the host's), at_end[q], and the counters -- one atomic per
 // wave each behind all of its queries.  EMIT = true: nnz holds the scanned offsets; the (token, count) pairs go to toks /
 // counts (either may be nullptr) in ascending token order from nnz[q] on, while the offset is below `capacity`.
@@ -291,39 +204,23 @@ __global__ __launch_bounds__(NG_THREADS) void k_tok_next(
     const int l = lane_id();
     const uint64_t below = (1ull << l) - 1ull;
     const int64_t waves = (int64_t)gridDim.x * NG_WAVES;
-    const uint32_t N1 = (uint32_t)n + 1u;
-    unsigned long long stream_slots = 0, search_slots = 0;
-    uint32_t stream_q = 0, search_q = 0, empty_q = 0;
+    NgCounters ctr;
     for (int64_t q = (int64_t)blockIdx.x * NG_WAVES + wave_id(); q < count; q += waves) {
-        uint32_t hi = range_hi[q], lo = range_lo[q];
-        if (hi > N1) hi = N1;
-        if (lo > hi) lo = hi;
-        const int64_t p = depth ? (int64_t)depth[q] : pat_off[q + 1] - pat_off[q];
-        const uint32_t ae = hi > lo && (int64_t)SA[lo] + p >= n ? 1u : 0u;
-        const uint32_t s0 = lo + ae, cnt = hi - s0;
+        const NgWindow w = ng_window(SA, n, range_lo, range_hi, depth, pat_off, q);
+        const uint32_t cnt = w.cnt;
         const unsigned long long o = EMIT ? nnz[q] : 0ull;
         uint32_t listed = 0;                                              // listed runs so far (the same in every lane)
         if (cnt == 0) {
-            ++empty_q;
+            ++ctr.empty_q;
         } else if (cnt <= stream_cap) {
-            ++stream_q;
-            stream_slots += cnt;
+            ++ctr.stream_q;
+            ctr.stream_slots += cnt;
             int carry = -1;
             bool pend = false;                                            // a listed start whose count waits for the next start
             uint32_t pend_rank = 0, pend_at = 0;
             for (uint32_t r = 0; r < cnt; r += NG_LOADS * WAVE) {
-                uint32_t s[NG_LOADS];
                 int b[NG_LOADS];
-#pragma unroll
-                for (int t = 0; t < NG_LOADS; ++t) {
-                    const uint32_t i = r + (uint32_t)t * WAVE + l;
-                    s[t] = i < cnt ? SA[s0 + i] : 0xffffffffu;
-                }
-#pragma unroll
-                for (int t = 0; t < NG_LOADS; ++t) {
-                    const int64_t at = (int64_t)s[t] + p;                 // (an unread slot: 2^32 - 1 + p >= n)
-                    b[t] = at < n ? (int)T[at] : TK_END;
-                }
+                ng_stream_trip(T, SA, n, w, r, b);
 #pragma unroll
                 for (int t = 0; t < NG_LOADS; ++t) {
                     const uint32_t first = r + (uint32_t)t * WAVE, i = first + l;
@@ -351,76 +248,42 @@ __global__ __launch_bounds__(NG_THREADS) void k_tok_next(
             }
             if (EMIT && pend && l == 0) tok_emit_count(counts, o, pend_rank, capacity, cnt - pend_at);
         } else {
-            ++search_q;
-            const uint32_t pos = (uint32_t)(((uint64_t)l * (cnt - 1)) / (WAVE - 1));
-            const int b = tok_next_token(T, SA, n, p, s0 + pos);
-            const int bn = __shfl_down(b, 1, WAVE);
-            const uint32_t posn = (uint32_t)__shfl_down((int)pos, 1, WAVE);
-            uint32_t probes = 1;
-            // pass 0 counts the lane's listed starts and finds its first start; pass 1 (EMIT) walks them again with the ranks known
-            uint32_t mine = 0, first_at = 0xffffffffu, base = 0, next_first = cnt;
-            for (int pass = 0; pass < (EMIT ? 2 : 1); ++pass) {
-                uint32_t rank = base;
-                bool pend = false;
-                uint32_t pend_rank = 0, pend_at = 0;
-                if (l == 0) {                                             // the run that starts the range
-                    if (pass == 0) { first_at = 0; mine += b < TK_END ? 1u : 0u; }
-                    else if (b < TK_END) { tok_emit_token(toks, o, rank, capacity, b); pend = true; pend_rank = rank; pend_at = 0; ++rank; }
-                }
-                if (l < WAVE - 1) {
-                    int x = b;
-                    uint32_t a = pos;
-                    while (x < bn) {                                      // a run starts in (a, posn]: token(posn) = bn > x
-                        uint32_t u = a + 1, v = posn;
-                        int bv = bn;                                      // the token of slot v, always a probed one
-                        while (u < v) {
-                            const uint32_t m = u + (v - u) / 2;
-                            const int bm = tok_next_token(T, SA, n, p, s0 + m);
-                            if (pass == 0) ++probes;
-                            if (bm > x) { v = m; bv = bm; } else u = m + 1;
-                        }
-                        if (pass == 0) {
-                            if (first_at == 0xffffffffu) first_at = u;
-                            mine += bv < TK_END ? 1u : 0u;
-                        } else {
-                            if (pend) tok_emit_count(counts, o, pend_rank, capacity, u - pend_at);
-                            pend = bv < TK_END;
-                            if (pend) { tok_emit_token(toks, o, rank, capacity, bv); pend_rank = rank; pend_at = u; ++rank; }
-                        }
-                        x = bv; a = u;
-                    }
-                }
-                if (pass == 0) {
-                    const uint32_t incl = wave_incl_sum(mine);
-                    base = incl - mine;
-                    listed = (uint32_t)__shfl((int)incl, WAVE - 1, WAVE);
-                    if (EMIT) {                                           // the first start of a later lane, else cnt
-                        uint32_t sm = first_at;
+            ++ctr.search_q;
+            const NgSample smp = ng_sample(T, SA, n, w);
+            // the first walk counts the lane's listed starts and finds its first start (lane 0: the run that starts the range) ...
+            uint32_t mine = l == 0 && smp.b < TK_END ? 1u : 0u, first_at = l == 0 ? 0u : 0xffffffffu;
+            const uint32_t probes = 1 + ng_walk(T, SA, n, w, smp, [&](uint32_t u, int bv) {
+                if (first_at == 0xffffffffu) first_at = u;
+                mine += bv < TK_END ? 1u : 0u;
+            });
+            ctr.search_slots += wave_incl_sum(probes);                    // (lane 63 holds the wave's sum)
+            const uint32_t incl = wave_incl_sum(mine);
+            listed = (uint32_t)__shfl((int)incl, WAVE - 1, WAVE);
+            if (EMIT) {                                                   // ... the second walks them again with the ranks known
+                uint32_t nf = first_at;                                   // the first start of a later lane, else cnt
 #pragma unroll
-                        for (int d = 1; d < WAVE; d <<= 1) {              // inclusive suffix minimum over the lanes
-                            const uint32_t t = (uint32_t)__shfl_down((int)sm, d, WAVE);
-                            if (l + d < WAVE && t < sm) sm = t;
-                        }
-                        const uint32_t nx = (uint32_t)__shfl_down((int)sm, 1, WAVE);
-                        next_first = l == WAVE - 1 || nx > cnt ? cnt : nx;
-                    }
-                } else if (pend) {
-                    tok_emit_count(counts, o, pend_rank, capacity, next_first - pend_at);
+                for (int d = 1; d < WAVE; d <<= 1) {                      // inclusive suffix minimum over the lanes
+                    const uint32_t t = (uint32_t)__shfl_down((int)nf, d, WAVE);
+                    if (l + d < WAVE && t < nf) nf = t;
                 }
+                const uint32_t nx = (uint32_t)__shfl_down((int)nf, 1, WAVE);
+                const uint32_t next_first = l == WAVE - 1 || nx > cnt ? cnt : nx;
+                uint32_t rank = incl - mine, pend_rank = 0, pend_at = 0;
+                bool pend = false;                                        // a listed start whose count waits for the next start
+                if (l == 0 && smp.b < TK_END) { tok_emit_token(toks, o, rank, capacity, smp.b); pend = true; pend_rank = rank; ++rank; }
+                ng_walk(T, SA, n, w, smp, [&](uint32_t u, int bv) {
+                    if (pend) tok_emit_count(counts, o, pend_rank, capacity, u - pend_at);
+                    pend = bv < TK_END;
+                    if (pend) { tok_emit_token(toks, o, rank, capacity, bv); pend_rank = rank; pend_at = u; ++rank; }
+                });
+                if (pend) tok_emit_count(counts, o, pend_rank, capacity, next_first - pend_at);
             }
-            search_slots += wave_incl_sum(probes);                        // (lane 63 holds the wave's sum)
         }
-        if (!EMIT && l == 0) { nnz[q] = listed; at_end[q] = (uint8_t)ae; }
+        if (!EMIT && l == 0) { nnz[q] = listed; at_end[q] = (uint8_t)w.ae; }
     }
-    if (!EMIT) {
-        if (l == WAVE - 1 && search_slots) atomicAdd(&ctl[NG_W_SEARCH_SLOTS], search_slots);
-        if (l == 0) {
-            if (stream_slots) atomicAdd(&ctl[NG_W_STREAM_SLOTS], stream_slots);
-            if (stream_q) atomicAdd(&ctl[NG_W_STREAM_Q], (unsigned long long)stream_q);
-            if (search_q) atomicAdd(&ctl[NG_W_SEARCH_Q], (unsigned long long)search_q);
-            if (empty_q) atomicAdd(&ctl[NG_W_EMPTY_Q], (unsigned long long)empty_q);
-        }
-    }
+    if (!EMIT) ng_flush(ctr, ctl);
 }
+
+static_assert(TK_END == sym_end<uint16_t>(), "TK_END is the token alphabet's sentinel");
 
 }  // namespace sa

@@ -1736,7 +1736,7 @@ def _exact_search_patterns(rng, s, arr):
     for k in (1, 2, 3, n // 2, n - 1, n - 64, n - 65):             # equal to a suffix, and a suffix with one byte more
         if 0 <= k < n:
             pats += [s[k:], s[k:] + b"\x00", s[k:] + b"\xff"]
-    for ln in (63, 64, 65, 127, 128, 129, 4096, 4097, 6000):        # one, two and many 64-byte chunks of wave_compare
+    for ln in (63, 64, 65, 127, 128, 129, 4096, 4097, 6000):        # one, two and many 64-byte chunks of wave_compare_from
         for _ in range(3):
             i = int(rng.integers(0, max(1, n - ln + 1)))
             p = s[i:i + ln]
@@ -1783,7 +1783,7 @@ def test_search_equals_the_reference_exactly(oracle, name):
     """all five outputs of the batched search equal oracle/search_model.py's restatement of src/sa.rs:123-253, on a fresh
     DeviceIndex (no bucket table: the whole array), again after buckets() (get_bucket ranges, the empty-bucket branch of
     search_lcp), and through the SuffixArray one-pattern wrappers without and with enable_buckets; patterns of 63-129 and
-    4096+ bytes (wave_compare over many chunks), longer than / equal to the text or a suffix, with 0x00 / 0xff, empty (c0, c1)
+    4096+ bytes (wave_compare_from over many chunks), longer than / equal to the text or a suffix, with 0x00 / 0xff, empty (c0, c1)
     buckets, the empty pattern, and ties between the two neighbours of the insertion point"""
     s = _search_texts_for_parity()[name]
     text = np.frombuffer(s, dtype=np.uint8) if s else np.zeros(0, dtype=np.uint8)
