@@ -992,7 +992,8 @@ typedef struct sa_amd_score_stats {  /* of the calling thread's most recent infg
 void sa_amd_last_score_stats(sa_amd_score_stats *out);
 /* route switch of the calling thread's later infgram_score calls (never changes a result): context bytes a lane group probes
  * before the position goes to the one-wave-per-position path, 0 .. 1 048 576 (0: every position with a context; above 4096
- * acts as 4096); a negative value restores the default (64).  Returns the previous value. */
+ * acts as 4096); a negative value restores the default (64).  Returns the previous value.  The same switch applies to the
+ * calling thread's sa_amd_tok_index_infgram_score calls (below), where it counts context TOKENS. */
 int32_t sa_amd_score_set_group_cap(int32_t bytes);
 
 /*
@@ -1084,6 +1085,62 @@ typedef struct sa_amd_tok_stats {    /* of the calling thread: the query fields 
     double compact_ms;               /*   counts, scan and scatter of the compaction */
 } sa_amd_tok_stats;
 void sa_amd_last_tok_stats(sa_amd_tok_stats *out);
+
+/*
+ * Scoring a token text under the infinity-gram model on the token index (an extension): for every
+ * position of a query the back-off of sa_amd_tok_index_infgram and the count of the token that is really there, on the device.
+ * The contract is that of sa_amd_index_infgram_score (above) with "byte" replaced by "token": T has n tokens, SA has n + 1
+ * slots of the token array; "range of a string" is the [lo, hi) that sa_amd_tok_index_search reports; at_end and next[t] are
+ * those of sa_amd_tok_index_next_tokens; m, q_off, S and max_len (1 .. SA_AMD_SCORE_MAX_CONTEXT) are in tokens.
+ *   Q has m tokens (2 m bytes, 2-byte aligned).  q_off has ndocs + 1 entries, q_off[0] = 0, non-decreasing, q_off[ndocs] = m:
+ *   document d is Q[q_off[d] .. q_off[d + 1]), empty documents are allowed.  q_off == NULL means one document [0, m) (ndocs is
+ *   ignored).
+ * For position j of the document that starts at `start`:
+ *   cap_j  = min(j - start, max_len): a context never crosses a document start.
+ *   S[j]   = the largest s in 0 .. cap_j such that Q[j - s .. j) has hi - lo >= min_count.  s = 0 always qualifies, with the
+ *            range [0, n + 1) and at_end = 1.
+ *   S[j], LO[j], HI[j], AT_END[j] = what sa_amd_tok_index_infgram returns as suffix_len, range and at_end for the prompt
+ *            Q[start .. j) with the same min_count and max_len.
+ *   NLO[j] = LO + AT_END + sum(next[t'] for t' < Q[j]),  NHI[j] = NLO + next[Q[j]].
+ *   Where NHI > NLO, [NLO, NHI) is the range of Q[j - s .. j]; where the continuation does not occur, NHI == NLO is its
+ *   insertion point inside the context's range.
+ * The model's probability of Q[j] is (NHI - NLO) / (HI - LO - AT_END); the denominator is 0 when the context occurs only as
+ * the text's last tokens.
+ *   T = {256, 1, 256, 1, 2}, SA = {5, 3, 1, 4, 2, 0}, Q = {7, 256, 1, 256}, one document, min_count = 1, max_len = 4:
+ *     j  token  S  [LO, HI)  AT_END  [NLO, NHI)
+ *     0  7      0  [0, 6)    1       [4, 4)
+ *     1  256    0  [0, 6)    1       [4, 6)
+ *     2  1      1  [4, 6)    0       [4, 6)
+ *     3  256    2  [4, 6)    0       [5, 6)
+ *   With min_count = 3, positions 2 and 3 have S = 0: {256} occurs twice.
+ * The same gallop and bisection: at most 2 ceil(log2(S[j] + 2)) + 2 range searches for position j, whatever the group cap
+ * (sa_amd_score_set_group_cap of the calling thread, here counted in tokens).  A range search is a plain binary search: the
+ * token index has no bucket table and no LCP table.
+ * EVERY output pointer may be NULL.  m == 0 succeeds.  Errors, each with nothing written: a NULL index, m < 0, a Q that is not
+ * 2-byte aligned, min_count < 1, max_len outside 1 .. SA_AMD_SCORE_MAX_CONTEXT, with q_off: ndocs < 0 or offsets that break the
+ * rules above: SA_AMD_EINVAL.  If the resident array is not the suffix array of the text the answers are unspecified, but every
+ * slot read lies in [0, n + 1), every SA entry is checked against n in 64 bits before T is read through it, Q is read inside
+ * [0, m) only and nothing is written outside the outputs.  The answers are the same for every group cap.
+ * Host pointers only: there is no device form of a token entry point.
+ */
+int32_t sa_amd_tok_index_infgram_score(const sa_amd_tok_index *ix, const uint16_t *Q, int64_t m, const int64_t *q_off, int64_t ndocs,
+                                       int32_t min_count, int32_t max_len, uint32_t *S, uint32_t *LO, uint32_t *HI, uint8_t *AT_END,
+                                       uint32_t *NLO, uint32_t *NHI);
+
+typedef struct sa_amd_tok_score_stats {  /* of the calling thread's most recent sa_amd_tok_index_infgram_score call: the fields of
+                                            sa_amd_score_stats (no other feature's statistics are touched, and no other call touches these) */
+    int64_t positions;               /* m */
+    int64_t documents;               /* ndocs; 1 where q_off is NULL */
+    int64_t group_searches;          /* range searches of the group path (8 lanes a position, the context in LDS) */
+    int64_t long_searches;           /* range searches of the long path (one wave a position) */
+    int64_t next_lookups;            /* slots probed by the two lower bounds on the token behind the context, all positions */
+    int64_t compared_tokens;         /* text tokens the range searches compared, chunks charged whole (16 on the group path, up to 64 on the long path) */
+    int64_t long_positions;          /* positions finished by the long path */
+    int64_t zero_positions;          /* positions with NHI == NLO */
+    int32_t group_cap;               /* the cap in effect, in tokens: min(group cap, max_len, 4096) */
+    int32_t readbacks;               /* blocking device -> host read-backs of counters: 1, or 2 with long positions */
+} sa_amd_tok_score_stats;
+void sa_amd_last_tok_score_stats(sa_amd_tok_score_stats *out);
 
 /* ---- per-kernel timing (HIP events on the launch stream), per calling thread ----
  * begin() zeroes and enables the counters for builds issued by this thread; end() disables them and

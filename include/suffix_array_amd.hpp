@@ -556,6 +556,25 @@ public:
         for (std::size_t q = 0; q < out.size(); ++q) out[q].suffix_len = slen[q];
         return out;
     }
+    // a token text scored under the infinity-gram model (suffix_array_amd.h, "Scoring a token text under the infinity-gram
+    // model"): DocumentIndex::infgram_score with tokens in place of bytes -- s, max_len and doc_offsets are in tokens, the ranges
+    // are slots of the token suffix array, [nlo, nhi) is the part of the context's range which the query's token follows.
+    using Score = DocumentIndex::Score;
+    Score infgram_score(const Tokens &query, std::int32_t min_count = 1, std::int32_t max_len = SA_AMD_SCORE_MAX_CONTEXT,
+                        const std::vector<std::int64_t> &doc_offsets = {}) const
+    {
+        if (min_count < 1) throw std::invalid_argument("min_count must be at least 1");
+        if (max_len < 1 || max_len > SA_AMD_SCORE_MAX_CONTEXT) throw std::invalid_argument("max_len must be 1 .. SA_AMD_SCORE_MAX_CONTEXT");
+        const std::size_t m = query.size();
+        Score r;
+        r.s.resize(m + 1); r.lo.resize(m + 1); r.hi.resize(m + 1); r.nlo.resize(m + 1); r.nhi.resize(m + 1); r.at_end.resize(m + 1);
+        check(sa_amd_tok_index_infgram_score(ix_, m ? query.data() : nullptr, static_cast<std::int64_t>(m),
+                                             doc_offsets.empty() ? nullptr : doc_offsets.data(),
+                                             doc_offsets.empty() ? 0 : static_cast<std::int64_t>(doc_offsets.size()) - 1, min_count, max_len,
+                                             r.s.data(), r.lo.data(), r.hi.data(), r.at_end.data(), r.nlo.data(), r.nhi.data()));
+        r.s.resize(m); r.lo.resize(m); r.hi.resize(m); r.nlo.resize(m); r.nhi.resize(m); r.at_end.resize(m);
+        return r;
+    }
 
 private:
     struct Batch {

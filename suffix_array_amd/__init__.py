@@ -41,7 +41,7 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "NgramStats", "last_ngram_stats", "ngram_set_stream_cap", "NGRAM_STREAM_CAP_DEFAULT",
            "ScoreStats", "ScoreResult", "last_score_stats", "score_set_group_cap", "score_work_bytes", "infgram_score_device_ptr",
            "SCORE_MAX_CONTEXT", "SCORE_GROUP_CAP_DEFAULT", "SCORE_TILE",
-           "saca_u16", "MAX_TOKENS_U16", "TokenIndex", "TokStats", "last_tok_stats"]
+           "saca_u16", "MAX_TOKENS_U16", "TokenIndex", "TokStats", "last_tok_stats", "TokScoreStats", "last_tok_score_stats"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
@@ -224,6 +224,16 @@ class ScoreStats(ctypes.Structure):
                 ("long_searches", ctypes.c_int64), ("next_lookups", ctypes.c_int64), ("compared_bytes", ctypes.c_int64),
                 ("long_positions", ctypes.c_int64), ("zero_positions", ctypes.c_int64), ("group_cap", ctypes.c_int32),
                 ("readbacks", ctypes.c_int32)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["range_searches"] = d["group_searches"] + d["long_searches"]
+        return d
+
+
+class TokScoreStats(ctypes.Structure):
+    """sa_amd_tok_score_stats of include/suffix_array_amd.h: the fields of ``ScoreStats``, ``compared_tokens`` for ``compared_bytes``"""
+    _fields_ = [(("compared_tokens" if name == "compared_bytes" else name), ctype) for name, ctype in ScoreStats._fields_]
 
     def as_dict(self):
         d = {name: getattr(self, name) for name, _ in self._fields_}
@@ -573,6 +583,11 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_tok_index_infgram.restype = ctypes.c_int32
         L.sa_amd_last_tok_stats.argtypes = [c_vp]
         L.sa_amd_last_tok_stats.restype = None
+        L.sa_amd_tok_index_infgram_score.argtypes = [c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp,
+                                                     c_vp, c_vp, c_vp, c_vp]
+        L.sa_amd_tok_index_infgram_score.restype = ctypes.c_int32
+        L.sa_amd_last_tok_score_stats.argtypes = [c_vp]
+        L.sa_amd_last_tok_score_stats.restype = None
         _lib = L
     return _lib
 
@@ -1275,7 +1290,8 @@ def last_score_stats() -> dict:
 def score_set_group_cap(nbytes: int) -> int:
     """Route switch of this thread's later ``infgram_score`` calls (never changes a result): context bytes a lane group probes
     before the position goes to the one-wave-per-position path, 0 .. 1 048 576 (0: every position with a context; above 4096
-    acts as 4096); negative restores ``SCORE_GROUP_CAP_DEFAULT``.  Returns the previous value."""
+    acts as 4096); negative restores ``SCORE_GROUP_CAP_DEFAULT``.  Returns the previous value.  The same switch applies to
+    ``TokenIndex.infgram_score``, where it counts context tokens."""
     return int(lib().sa_amd_score_set_group_cap(max(-1, min(int(nbytes), 2**31 - 1))))
 
 
@@ -1688,6 +1704,14 @@ def last_tok_stats() -> dict:
     return st.as_dict()
 
 
+def last_tok_score_stats() -> dict:
+    """the counters of this thread's most recent ``TokenIndex.infgram_score`` call: the keys of ``last_score_stats`` with
+    ``compared_tokens`` in place of ``compared_bytes``; no other call writes them"""
+    st = TokScoreStats()
+    lib().sa_amd_last_tok_score_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
 class TokenIndex:
     """EXTENSION: a text of 16-bit tokens and its suffix array resident in HBM (sa_amd_tok_index of
     include/suffix_array_amd.h): batched range search, next-token counts and the infinity-gram back-off.  ``sa=None`` builds the
@@ -1761,6 +1785,26 @@ class TokenIndex:
         if int(min_count) < 1:
             raise SuffixArrayError(-1, "infgram: min_count >= 1")
         return self._ngram(prompts, True, min(int(min_count), 2**31 - 1), max(0, min(int(max_len), 2**31 - 1)))
+
+    def infgram_score(self, query, min_count: int = 1, max_len: int = SCORE_MAX_CONTEXT, doc_offsets=None) -> ScoreResult:
+        """score a token ``query`` under the infinity-gram model -> ``ScoreResult`` (``DeviceIndex.infgram_score`` with tokens in
+        place of bytes).  For every position ``j`` the context is the longest ``query[j - s:j]`` -- of at most ``max_len`` tokens
+        (1 .. ``SCORE_MAX_CONTEXT``), never reaching back over the start of ``j``'s document -- that occurs at least
+        ``min_count`` times: exactly ``infgram`` of the prompt ``query[start:j]``.  ``s``, ``lo`` / ``hi`` / ``at_end`` describe
+        it, ``[nlo, nhi)`` is the part of its range that ``query[j]`` follows (empty, at its insertion point, where it never
+        does).  ``doc_offsets``: ``ndocs + 1`` non-decreasing values from 0 to ``len(query)``, in tokens; ``None`` is one
+        document.  The query (2 bytes a token) is read once on the device; ``score_set_group_cap`` applies, counted in tokens."""
+        q = _as_u16(query, "query")
+        if int(min_count) < 1:
+            raise SuffixArrayError(-1, "infgram_score: min_count >= 1")
+        off, ndocs = _score_offsets(doc_offsets)
+        m = int(q.size)
+        s, lo, hi, nlo, nhi = (np.zeros(m, dtype=np.uint32) for _ in range(5))
+        ae = np.zeros(m, dtype=np.uint8)
+        _check(lib().sa_amd_tok_index_infgram_score(self._h, q.ctypes.data if m else None, m, off.ctypes.data if off is not None else None, ndocs,
+                                                    min(int(min_count), 2**31 - 1), max(-1, min(int(max_len), 2**31 - 1)), s.ctypes.data,
+                                                    lo.ctypes.data, hi.ctypes.data, ae.ctypes.data, nlo.ctypes.data, nhi.ctypes.data))
+        return ScoreResult(s, lo, hi, ae, nlo, nhi)
 
 
 def workspace_bytes(n: int) -> int:

@@ -1,5 +1,7 @@
 // host/score.hpp -- scoring a query text under the infinity-gram model against a device-resident index (kernels/score.hpp,
-// DESIGN.md section 22): argument checks, work-block layout, the two passes, the host-pointer route.
+// DESIGN.md sections 22 and 24): argument checks, work-block layout, the two passes, the host-pointer route.  Written once over
+// the index type: the byte index (sa_amd_index, Sym = uint8_t) and the token index (sa_amd_tok_index, Sym = uint16_t) differ in
+// the symbol type of text(), in the tables (the token index has none) and in the statistics block they write.
 #pragma once
 #include "match.hpp"
 #include "ngram.hpp"
@@ -8,6 +10,7 @@
 namespace sa {
 
 static thread_local sa_amd_score_stats g_last_score_stats;
+static thread_local sa_amd_tok_score_stats g_last_tok_score_stats;     // of the token route: neither the one above nor sa_amd_tok_stats is touched
 static thread_local int32_t g_score_cap = -1;          // sa_amd_score_set_group_cap of the calling thread (-1: SCORE_CAP_DEFAULT)
 
 // layout of the work block: control words | the document offsets (ndocs + 1) | the long list: position, range lo, range hi (m each)
@@ -38,15 +41,19 @@ static bool score_args_valid(int64_t m, const int64_t *q_off, int64_t ndocs, int
     return true;
 }
 
-// dQ: m bytes on the index's device (any byte address); the outputs: m entries each on that device, any of them nullptr;
-// q_off: HOST offsets, checked by the caller; dWork: score_layout(m, ndocs).bytes, 256-byte aligned.  Blocks until done.
-static int score_device(const sa_amd_index &ix, const uint8_t *dQ, int64_t m, const int64_t *q_off, int64_t ndocs, int32_t min_count, int32_t max_len,
-                        const ScoreOut &out, void *dWork, int64_t work_bytes, hipStream_t st)
+// dQ: m symbols on the index's device (any address aligned to Sym); the outputs: m entries each on that device, any of them
+// nullptr; q_off: HOST offsets, checked by the caller; dWork: score_layout(m, ndocs).bytes, 256-byte aligned.  Blocks until
+// done.  last / compared: the calling thread's statistics block of this index type and its compared-symbols field.
+template <typename Index, typename Sym, typename Stats>
+static int score_device(const Index &ix, const Sym *dQ, int64_t m, const int64_t *q_off, int64_t ndocs, int32_t min_count, int32_t max_len,
+                        const ScoreOut &out, void *dWork, int64_t work_bytes, hipStream_t st, Stats &last, int64_t Stats::*compared)
 {
+    static_assert(std::is_same<decltype(ix.text()), const Sym *>::value, "the query has the text's symbol type");
     if (!q_off) ndocs = 1;
     const ScoreLayout L = score_layout(m, ndocs);
-    if (m > 0 && (!dQ || !dWork || work_bytes < (int64_t)L.bytes || (((uintptr_t)dWork) & 255u))) return SA_AMD_EINVAL;
-    sa_amd_score_stats ss;
+    if (m > 0 && (!dQ || !dWork || work_bytes < (int64_t)L.bytes || (((uintptr_t)dWork) & 255u) || (((uintptr_t)dQ) & (sizeof(Sym) - 1))))
+        return SA_AMD_EINVAL;
+    Stats ss;
     memset(&ss, 0, sizeof(ss));
     const int cap = g_score_cap < 0 ? SCORE_CAP_DEFAULT : g_score_cap;
     int ge = cap < SCORE_STAGE_MAX ? cap : SCORE_STAGE_MAX;
@@ -54,7 +61,7 @@ static int score_device(const sa_amd_index &ix, const uint8_t *dQ, int64_t m, co
     ss.positions = m;
     ss.documents = ndocs;
     ss.group_cap = ge;
-    g_last_score_stats = ss;
+    last = ss;
     if (m == 0) return SA_AMD_OK;
     route_tuning();                                             // (the posted read-backs' switch; nothing else of the tuning is used here)
     const int rb0 = g_readbacks;
@@ -66,8 +73,8 @@ static int score_device(const sa_amd_index &ix, const uint8_t *dQ, int64_t m, co
     if (q_off) HIP_TRY(hipMemcpyAsync(dOff, q_off, ((size_t)ndocs + 1) * 8, hipMemcpyHostToDevice, st));
 
     // ---- pass 1: the group path ----
-    PROF(KC_MISC, m, st, hipLaunchKernelGGL((k_score_tile<SCORE_G>), dim3((unsigned)ceil_div(m, SCORE_TILE)), dim3(SCORE_THREADS),
-                                            (size_t)score_stage_words(ge) * 4, st, ix.text(), ix.sa(), (int64_t)ix.n, ix.bkt(), dQ, m, (const int64_t *)dOff,
+    PROF(KC_MISC, m, st, hipLaunchKernelGGL((k_score_tile<SCORE_G, Sym>), dim3((unsigned)ceil_div(m, SCORE_TILE)), dim3(SCORE_THREADS),
+                                            (size_t)score_stage_words<Sym>(ge) * 4, st, ix.text(), ix.sa(), (int64_t)ix.n, ix.bkt(), dQ, m, (const int64_t *)dOff,
                                             ndocs, (uint32_t)min_count, (int64_t)max_len, ge, out, list, llo, lhi, ctl));
     unsigned long long cw[SC_W_COUNT];
     { const int rcw = read_words(cw, ctl, sizeof(cw), st); if (rcw) return rcw; }
@@ -76,7 +83,7 @@ static int score_device(const sa_amd_index &ix, const uint8_t *dQ, int64_t m, co
 
     // ---- pass 2: one wave per listed position ----
     if (longs > 0) {
-        PROF(KC_MISC, longs, st, hipLaunchKernelGGL(k_score_long, dim3((unsigned)ceil_div(longs * WAVE, SCORE_THREADS)), dim3(SCORE_THREADS), 0, st, ix.text(),
+        PROF(KC_MISC, longs, st, hipLaunchKernelGGL(k_score_long<Sym>, dim3((unsigned)ceil_div(longs * WAVE, SCORE_THREADS)), dim3(SCORE_THREADS), 0, st, ix.text(),
                                                     ix.sa(), (int64_t)ix.n, ix.bkt(), ix.pair(), esa_log_p(ix.n), dQ, m, (const int64_t *)dOff, ndocs,
                                                     (uint32_t)min_count, (int64_t)max_len, ge, (const uint32_t *)list, (const uint32_t *)llo,
                                                     (const uint32_t *)lhi, longs, out, ctl));
@@ -89,34 +96,37 @@ static int score_device(const sa_amd_index &ix, const uint8_t *dQ, int64_t m, co
     ss.group_searches = (int64_t)cw[SC_W_GROUP_SEARCHES];
     ss.long_searches = (int64_t)cw[SC_W_LONG_SEARCHES];
     ss.next_lookups = (int64_t)cw[SC_W_LOOKUPS];
-    ss.compared_bytes = (int64_t)cw[SC_W_BYTES];
+    ss.*compared = (int64_t)cw[SC_W_BYTES];
     ss.zero_positions = (int64_t)cw[SC_W_ZERO];
     ss.readbacks = g_readbacks - rb0;
-    g_last_score_stats = ss;
+    last = ss;
     return SA_AMD_OK;
 }
 
-// host buffers: the query goes up, the outputs asked for come back (4 m bytes each, AT_END m).  One pooled block.
-static int score_host(const sa_amd_index &ix, const uint8_t *Q, int64_t m, const int64_t *q_off, int64_t ndocs, int32_t min_count, int32_t max_len,
-                      uint32_t *S, uint32_t *LO, uint32_t *HI, uint8_t *AT_END, uint32_t *NLO, uint32_t *NHI)
+// host buffers: the query goes up (sizeof(Sym) m bytes), the outputs asked for come back (4 m bytes each, AT_END m).  One pooled
+// block.
+template <typename Index, typename Sym, typename Stats>
+static int score_host(const Index &ix, const Sym *Q, int64_t m, const int64_t *q_off, int64_t ndocs, int32_t min_count, int32_t max_len,
+                      uint32_t *S, uint32_t *LO, uint32_t *HI, uint8_t *AT_END, uint32_t *NLO, uint32_t *NHI, Stats &last, int64_t Stats::*compared)
 {
-    const size_t wb = score_layout(m, q_off ? ndocs : 1).bytes, qb = align_up((size_t)m + 16, 256), ab = align_up(((size_t)m + 1) * 4, 256);
+    const size_t wb = score_layout(m, q_off ? ndocs : 1).bytes, eb = align_up((size_t)m + 16, 256), qb = align_up(sizeof(Sym) * (size_t)m + 16, 256),
+                 ab = align_up(((size_t)m + 1) * 4, 256);
     uint32_t *const host4[5] = { S, LO, HI, NLO, NHI };
     uint32_t *dev4[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    size_t outs = AT_END ? qb : 0;
+    size_t outs = AT_END ? eb : 0;
     for (int k = 0; k < 5; ++k) outs += host4[k] ? ab : 0;
     PooledScope sc(ix.device, true);
     sc.acquire(wb + qb + outs);
     void *dW = sc.take(wb);
-    uint8_t *dQ = (uint8_t *)sc.take(qb);
+    Sym *dQ = (Sym *)sc.take(qb);
     for (int k = 0; k < 5; ++k)
         if (host4[k]) dev4[k] = (uint32_t *)sc.take(ab);
-    uint8_t *dEnd = AT_END ? (uint8_t *)sc.take(qb) : nullptr;
-    if (sc.rc == SA_AMD_OK && m > 0) sc.rc = hip_status(hipMemcpyAsync(dQ, Q, (size_t)m, hipMemcpyHostToDevice, sc.st));
+    uint8_t *dEnd = AT_END ? (uint8_t *)sc.take(eb) : nullptr;
+    if (sc.rc == SA_AMD_OK && m > 0) sc.rc = hip_status(hipMemcpyAsync(dQ, Q, sizeof(Sym) * (size_t)m, hipMemcpyHostToDevice, sc.st));
     if (sc.rc == SA_AMD_OK) {
         ScoreOut out;
         out.S = dev4[0]; out.LO = dev4[1]; out.HI = dev4[2]; out.AT_END = dEnd; out.NLO = dev4[3]; out.NHI = dev4[4];
-        sc.rc = score_device(ix, dQ, m, q_off, ndocs, min_count, max_len, out, dW, (int64_t)wb, sc.st);
+        sc.rc = score_device(ix, dQ, m, q_off, ndocs, min_count, max_len, out, dW, (int64_t)wb, sc.st, last, compared);
     }
     for (int k = 0; k < 5; ++k)
         if (m > 0 && host4[k]) sc.down(host4[k], dev4[k], (size_t)m * 4);

@@ -1,7 +1,8 @@
 // host/tokens.hpp -- texts over a 16-bit token alphabet (kernels/tokens.hpp): the type behind the ABI's
 // `sa_amd_tok_index *` (the owner of the token text and its suffix array, as host/index.hpp is for the byte index), the token
 // build -- byte image, the byte builder on it, compaction -- behind sa_amd_saca_u16 and sa_amd_tok_index_create, and the
-// queries: sa_amd_tok_index_search, sa_amd_tok_index_next_tokens and sa_amd_tok_index_infgram.
+// queries: sa_amd_tok_index_search, sa_amd_tok_index_next_tokens and sa_amd_tok_index_infgram.  sa_amd_tok_index_infgram_score
+// is host/score.hpp's route on this index type.
 #pragma once
 #include "ngram.hpp"
 #include "../kernels/tokens.hpp"
@@ -16,6 +17,9 @@ struct sa_amd_tok_index {
     sa::DevBuf dT, dSA;
     const uint16_t *text() const { return dT.as<const uint16_t>(); }
     const uint32_t *sa() const { return dSA.as<const uint32_t>(); }
+    // no bucket table and no LCP table: what the index-generic routes (host/score.hpp) pass to the kernels
+    const uint32_t *bkt() const { return nullptr; }
+    const uint64_t *pair() const { return nullptr; }
 };
 
 }  // extern "C++"

@@ -64,31 +64,44 @@ __device__ __forceinline__ uint32_t match_lds_word(const uint32_t *s_w, uint32_t
     return (uint32_t)((((uint64_t)w1 << 32) | w0) >> ((b & 3u) * 8u));
 }
 
-// lcp of T[p ..] and the window at byte offset wb of the staged words, both known to agree on [0, from) and compared on
-// [from, limit): the G lanes of a group take four bytes each, 4 G bytes a round.  limit <= n - p.  Returns limit when nothing
-// differs, else the offset of the first difference and *less = the text's byte is the smaller one.  *bytes grows by 4 G a round.
-template <int G>
-__device__ __forceinline__ int64_t match_group_lcp(const uint8_t *__restrict__ T, int64_t n, int64_t p, const uint32_t *s_w, uint32_t wb,
-                                                   int64_t from, int64_t limit, int gl, int gshift, unsigned long long *bytes, bool *less)
+// The compare of two little-endian 32-bit words that hold 4 / sizeof(Sym) symbols each and differ in the bits d != 0: the index
+// of the first differing SYMBOL of the word and *less = the text's symbol there is the smaller VALUE.  With 16-bit tokens the
+// lowest differing byte does not decide: 0x0102 against 0x0201 differs first in a byte that says "greater".
+template <typename Sym>
+__device__ __forceinline__ int match_word_diff(uint32_t d, uint32_t tw, uint32_t qw, bool *less)
 {
+    constexpr uint32_t BITS = 8u * sizeof(Sym), MASK = (1u << BITS) - 1u;
+    const int si = (__ffs(d) - 1) >> (sizeof(Sym) == 1 ? 3 : 4);
+    *less = ((tw >> (BITS * si)) & MASK) < ((qw >> (BITS * si)) & MASK);
+    return si;
+}
+
+// lcp of T[p ..] and the window at BYTE offset wb of the staged words, both known to agree on [0, from) and compared on
+// [from, limit) -- offsets and lengths in symbols: the G lanes of a group take one 32-bit word each, W = 4 / sizeof(Sym) symbols,
+// W G symbols a round.  limit <= n - p.  Returns limit when nothing differs, else the offset of the first difference and *less =
+// the text's symbol is the smaller one.  *symbols grows by W G a round.
+template <int G, typename Sym>
+__device__ __forceinline__ int64_t match_group_lcp(const Sym *__restrict__ T, int64_t n, int64_t p, const uint32_t *s_w, uint32_t wb,
+                                                   int64_t from, int64_t limit, int gl, int gshift, unsigned long long *symbols, bool *less)
+{
+    constexpr int W = 4 / (int)sizeof(Sym);
+    static_assert(sizeof(Sym) == 1 || sizeof(Sym) == 2, "a word holds whole symbols");
     const uintptr_t beg = (uintptr_t)T, end = (uintptr_t)(T + n);
-    for (int64_t off = from; off < limit; off += 4 * G) {
-        const int64_t o = off + 4 * gl;
+    for (int64_t off = from; off < limit; off += W * G) {
+        const int64_t o = off + W * gl;
         uint32_t d = 0, tw = 0, qw = 0;
         if (o < limit) {
             tw = match_word((uintptr_t)(T + p + o), beg, end);
-            qw = match_lds_word(s_w, wb + (uint32_t)o);
-            const int64_t v = limit - o;
-            d = (tw ^ qw) & (v >= 4 ? 0xffffffffu : ((1u << (8u * (uint32_t)v)) - 1u));
+            qw = match_lds_word(s_w, wb + (uint32_t)sizeof(Sym) * (uint32_t)o);
+            const int64_t v = limit - o;                           // symbols left: the tail of a word is masked in symbols
+            d = (tw ^ qw) & (v >= W ? 0xffffffffu : ((1u << (8u * (uint32_t)sizeof(Sym) * (uint32_t)v)) - 1u));
         }
-        *bytes += 4 * G;
+        *symbols += W * G;
         const uint32_t gm = (uint32_t)(__ballot(d != 0) >> gshift) & ((1u << G) - 1u);
         if (gm) {
             const int f = __ffs(gm) - 1;
             const uint32_t df = __shfl(d, gshift + f, WAVE), tf = __shfl(tw, gshift + f, WAVE), qf = __shfl(qw, gshift + f, WAVE);
-            const int bi = (__ffs(df) - 1) >> 3;
-            *less = ((tf >> (8 * bi)) & 255u) < ((qf >> (8 * bi)) & 255u);
-            return off + 4 * f + bi;
+            return off + W * f + match_word_diff<Sym>(df, tf, qf, less);
         }
     }
     return limit;

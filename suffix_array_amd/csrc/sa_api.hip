@@ -768,7 +768,8 @@ SA_EXPORT int32_t sa_amd_index_infgram_score(const sa_amd_index *ix, const uint8
 {
     SA_ABI_GUARD_BEGIN
     if (!ix || !sa::score_args_valid(m, q_off, ndocs, min_count, max_len) || (m > 0 && !Q)) return SA_AMD_EINVAL;
-    return sa::score_host(*ix, Q, m, q_off, ndocs, min_count, max_len, S, LO, HI, AT_END, NLO, NHI);
+    return sa::score_host(*ix, Q, m, q_off, ndocs, min_count, max_len, S, LO, HI, AT_END, NLO, NHI, sa::g_last_score_stats,
+                          &sa_amd_score_stats::compared_bytes);
     SA_ABI_GUARD_END(0)
 }
 
@@ -782,7 +783,8 @@ SA_EXPORT int32_t sa_amd_index_infgram_score_device(const sa_amd_index *ix, cons
     if (guard.rc != SA_AMD_OK) return guard.rc;
     sa::ScoreOut out;
     out.S = dS; out.LO = dLO; out.HI = dHI; out.AT_END = dAT_END; out.NLO = dNLO; out.NHI = dNHI;
-    return sa::score_device(*ix, dQ, m, q_off, ndocs, min_count, max_len, out, dWork, work_bytes, (hipStream_t)stream);
+    return sa::score_device(*ix, dQ, m, q_off, ndocs, min_count, max_len, out, dWork, work_bytes, (hipStream_t)stream, sa::g_last_score_stats,
+                            &sa_amd_score_stats::compared_bytes);
     SA_ABI_GUARD_END(0)
 }
 
@@ -867,6 +869,22 @@ SA_EXPORT int32_t sa_amd_tok_index_infgram(const sa_amd_tok_index *ix, const uin
 SA_EXPORT void sa_amd_last_tok_stats(sa_amd_tok_stats *out)
 {
     if (out) *out = sa::g_last_tok_stats;
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_infgram_score(const sa_amd_tok_index *ix, const uint16_t *Q, int64_t m, const int64_t *q_off, int64_t ndocs,
+                                                 int32_t min_count, int32_t max_len, uint32_t *S, uint32_t *LO, uint32_t *HI, uint8_t *AT_END,
+                                                 uint32_t *NLO, uint32_t *NHI)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::score_args_valid(m, q_off, ndocs, min_count, max_len) || (m > 0 && (!Q || ((uintptr_t)Q & 1u)))) return SA_AMD_EINVAL;
+    return sa::score_host(*ix, Q, m, q_off, ndocs, min_count, max_len, S, LO, HI, AT_END, NLO, NHI, sa::g_last_tok_score_stats,
+                          &sa_amd_tok_score_stats::compared_tokens);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_tok_score_stats(sa_amd_tok_score_stats *out)
+{
+    if (out) *out = sa::g_last_tok_score_stats;
 }
 
 // ---- packed format (reference src/packed_sa.rs); byte layout: u32 magic "SA4x" LE, u32 length, u64 data length
