@@ -218,6 +218,8 @@ struct Refined {
 // re-rank kernels ungated.
 constexpr int RC_FLAGGED = 16, RC_GROUPS = 8, RC_BIG_LISTED = 12, RC_BIG_ORDERED = 13, RC_WORDS = 17;      // words of w.total
 constexpr int RC_BIG_LISTED_SAVED = 14, RC_BIG_ORDERED_SAVED = 15;     // ... where k_rr_scan_round puts the two big-group counters before it zeroes them for the next round
+constexpr int RC_BIG_CLASS = 17;       // ... and [17], [18]: the lengths of the two lists k_big_classify sorts the listed heads into; zeroed with the two counters
+static_assert(RC_BIG_CLASS == RC_BIG_LISTED + RR_CLEAR_CLASS && RC_BIG_CLASS + 2 <= 64, "k_rr_scan_round zeroes them relative to the big-group counters; w.total has 64 words");
 struct RoundCtl {
     bool defer = false;                    // in: do not read the local pass's counts back, return right behind its launches
     const uint32_t *resume_tot = nullptr;  // in: the counts (RC_WORDS words of w.total) of a deferred call that did have flagged members
@@ -668,8 +670,10 @@ struct DeviceBuild {
             const bool big_local = !tn.no_big_group_sort && kb <= 32 && m > GS_CAP && !(ctl && ctl->skip_big);
             uint32_t *bheads = big_local ? L.Un : (uint32_t *)nullptr, *bcount = big_local ? w.total + RC_BIG_LISTED : (uint32_t *)nullptr;
             if (!resume) {
-            if (!(ctl && ctl->counters_clear))
+            if (!(ctl && ctl->counters_clear)) {
                 HIP_TRY(hipMemsetAsync(w.total + RC_BIG_LISTED, 0, 8, st));           // [12] listed first members, [13] members ordered by k_group_sort_big
+                HIP_TRY(hipMemsetAsync(w.total + RC_BIG_CLASS, 0, 8, st));            // [17], [18] listed groups of either k_group_sort_big instance
+            }
             if (K.mode == KS_SPARSE && (rc = gather_sparse())) return rc;      // (then the sort on those keys: KS_PRE)
             if (status && tn.round_flags == 2) {
                 // (diag library: what the round does not write must not be read -- a poisoned entry that is read changes the result)
@@ -691,10 +695,19 @@ struct DeviceBuild {
                                                          L.U, m, flags, cap, K, n));
             if (big_local) {
                 const int lo = cap > GS_CAP ? cap : GS_CAP;
+                // The listed heads are classified once (k_big_classify) into one list per instance, behind the heads in L.Un.  A tile
+                // lists at most two heads -- the group that runs on beyond it and one of more than GS_CAP members inside it --, so
+                // the heads end before hcap and neither list can outgrow it (3 * hcap <= m <= n: m > GS_CAP).
+                const uint32_t hcap = (2u * gs_blocks + 63u) & ~63u;
+                uint32_t *const bsmall = bheads + hcap, *const blarge = bheads + 2 * (size_t)hcap, *const bclass = w.total + RC_BIG_CLASS;
+                if (3 * (int64_t)hcap > n) return SA_AMD_EINTERNAL;
+                PROF(KC_LOCAL, 0, st, hipLaunchKernelGGL((k_big_classify), dim3((unsigned)ceil_div((int64_t)hcap, GC_THREADS)), dim3(GC_THREADS), 0, st, (const uint32_t *)L.G, m, lo,
+                                                         (const uint32_t *)bheads, (const uint32_t *)bcount, bsmall, blarge, hcap, bclass));
                 PROF(KC_LOCAL, 0, st, hipLaunchKernelGGL((k_group_sort_big<256>), dim3((unsigned)(8 * cu_count())), dim3(256), 0, st, L.rkA, L.V, L.G, m, kb, lo,
-                                                         (const uint32_t *)bheads, (const uint32_t *)bcount, flags, w.total + 13));
+                                                         (const uint32_t *)bsmall, (const uint32_t *)bclass, hcap, flags, w.total + RC_BIG_ORDERED));
                 PROF(KC_LOCAL, 0, st, hipLaunchKernelGGL((k_group_sort_big<512>), dim3((unsigned)(4 * cu_count())), dim3(512), 0, st, L.rkA, L.V, L.G, m, kb,
-                                                         lo > GB_CAP_SMALL ? lo : GB_CAP_SMALL, (const uint32_t *)bheads, (const uint32_t *)bcount, flags, w.total + 13));
+                                                         lo > GB_CAP_SMALL ? lo : GB_CAP_SMALL, (const uint32_t *)blarge, (const uint32_t *)(bclass + 1), hcap, flags,
+                                                         w.total + RC_BIG_ORDERED));
             }
             PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((status ? k_flag_count<true> : k_flag_count<false>), dim3(status ? rr_count_grid<true>(m) : rr_count_grid<false>(m)), dim3(RR_THREADS), 0, st,
                                                         (const uint8_t *)flags, L.U, L.G, m, w.tcnt, w.ft_cnt));

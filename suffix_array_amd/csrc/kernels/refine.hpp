@@ -579,12 +579,38 @@ constexpr int GB_CAP_SMALL = 256 * GB_ITEMS;       // 4 096 members: 256 threads
 constexpr int GB_CAP = 512 * GB_ITEMS;             // 8 192 members: 512 threads, 70 KiB of LDS, two workgroups per CU (a 1 024-thread instance
                                                    // for 16 384 took 60 ps per member, more than the global sort's share)
 constexpr int GB_ABITS = 10, GB_BBITS = 6;
-// size_lo < members <= GB_THREADS * GB_ITEMS: the groups this instance orders (two launches over the same list: 256 threads
-// for the groups of up to 4 096 members -- a larger workgroup spends its time in barriers on them --, 512 for the rest)
+// k_big_classify: which of the listed heads are k_group_sort_big's, and which instance's?  One lane per entry of the list
+// k_group_sort wrote; the three size probes of an entry -- is the member at lo, at GB_CAP_SMALL, at GB_CAP still the group's? --
+// are issued together.  A group of lo + 1 .. GB_CAP_SMALL members goes to list_small, one of GB_CAP_SMALL + 1 .. GB_CAP to
+// list_large (n_class[0], n_class[1]: their lengths, zero at the launch); every other entry goes nowhere -- a shorter group is
+// k_group_sort_straddle's, a longer one the global sort's.  Before, every workgroup of both k_group_sort_big launches walked the
+// whole list and paid three dependent round trips per entry (heads[ent], G[j0], the two probes) to find the few that are its own.
+// list_cap: entries either list holds (an entry beyond it would be dropped: its group stays flagged for the global sort).
+constexpr int GC_THREADS = 256;
+__global__ __launch_bounds__(GC_THREADS) void k_big_classify(const uint32_t *__restrict__ G, int64_t m, int lo, const uint32_t *__restrict__ heads,
+                                                             const uint32_t *__restrict__ n_heads, uint32_t *__restrict__ list_small,
+                                                             uint32_t *__restrict__ list_large, uint32_t list_cap, uint32_t *__restrict__ n_class)
+{
+    const uint32_t count = *n_heads;
+    const int mid = lo > GB_CAP_SMALL ? lo : GB_CAP_SMALL;         // (the large instance's lower bound, as the host passes it)
+    for (uint32_t ent = blockIdx.x * GC_THREADS + threadIdx.x; ent < count; ent += gridDim.x * GC_THREADS) {
+        const int64_t j0 = (int64_t)heads[ent];
+        const int64_t ja = j0 + lo, jb = j0 + mid, jc = j0 + GB_CAP;
+        const uint32_t g0 = G[j0];
+        const uint32_t ga = G[ja < m ? ja : j0], gb = G[jb < m ? jb : j0], gc = G[jc < m ? jc : j0];
+        const bool in_a = ja < m && ga == g0, in_b = jb < m && gb == g0, in_c = jc < m && gc == g0;     // more than lo / mid / GB_CAP members
+        if (in_a && !in_b) { const uint32_t s = atomicAdd(n_class, 1u); if (s < list_cap) list_small[s] = (uint32_t)j0; }
+        else if (in_b && !in_c) { const uint32_t s = atomicAdd(n_class + 1, 1u); if (s < list_cap) list_large[s] = (uint32_t)j0; }
+    }
+}
+
+// size_lo < members <= GB_THREADS * GB_ITEMS: the groups this instance orders (two launches, 256 threads for the groups of up
+// to 4 096 members -- a larger workgroup spends its time in barriers on them --, 512 for the rest), each over its own list
+// from k_big_classify: every entry of `heads` is a group of this instance, list_cap the entries the list holds
 template <int GB_THREADS>
 __global__ __launch_bounds__(GB_THREADS) void k_group_sort_big(uint64_t *__restrict__ keys, uint32_t *__restrict__ V, const uint32_t *__restrict__ G,
                                                                int64_t m, int kb, int size_lo, const uint32_t *__restrict__ heads,
-                                                               const uint32_t *__restrict__ n_heads, uint8_t *__restrict__ bigflag,
+                                                               const uint32_t *__restrict__ n_heads, uint32_t list_cap, uint8_t *__restrict__ bigflag,
                                                                uint32_t *__restrict__ sorted_members)
 {
     constexpr int GB_CAP = GB_THREADS * GB_ITEMS;  // (shadows the constant of the large instance)
@@ -600,7 +626,7 @@ __global__ __launch_bounds__(GB_THREADS) void k_group_sort_big(uint64_t *__restr
     __shared__ uint32_t scan_lds[NWAVES + 1];
     __shared__ int s_size;
     const int tid = threadIdx.x, l = lane_id(), w = wave_id();
-    const uint32_t count = *n_heads;
+    const uint32_t count = *n_heads < list_cap ? *n_heads : list_cap;
     const int lo_size = size_lo;                                   // smaller groups are not this instance's
     for (uint32_t ent = blockIdx.x; ent < count; ent += gridDim.x) {
         __syncthreads();                                           // (the previous group's LDS is free)
@@ -608,14 +634,8 @@ __global__ __launch_bounds__(GB_THREADS) void k_group_sort_big(uint64_t *__restr
         const uint32_t g0 = G[j0];
         if (tid == 0) s_size = GB_CAP + 1;
         __syncthreads();
-        // Mine?  Two look-ups say: the member at lo_size still belongs to the group (more than lo_size members) and the one at
-        // GB_CAP does not (at most GB_CAP).  Then the size: the first list position behind j0 whose group head differs -- all
-        // positions looked at in one go (a chunk at a time costs a memory round trip per chunk).
-        {
-            const bool more = j0 + lo_size < m && G[j0 + lo_size] == g0;
-            const bool fits = j0 + GB_CAP >= m || G[j0 + GB_CAP] != g0;
-            if (!(more && fits)) continue;                         // (uniform: every thread reads the same two words)
-        }
+        // Mine (k_big_classify: more than lo_size members, at most GB_CAP).  The size: the first list position behind j0 whose
+        // group head differs -- all positions looked at in one go (a chunk at a time costs a memory round trip per chunk).
         {
             int first = GB_CAP + 1;
 #pragma unroll

@@ -496,7 +496,8 @@ __global__ __launch_bounds__(SPINE_THREADS) void k_rr_scan_pair(uint32_t *__rest
 
 // the two single-workgroup steps between k_rr_count and k_rr_apply of a round in one launch (grid 2): block 0 = k_rr_scan,
 // block 1 = k_rr_scan_next (tile_first == nullptr: none) + the two counters the NEXT round's local pass starts from (clear2[0..1],
-// copied to clear2[2..3] first)
+// copied to clear2[2..3] first) and the two list lengths its k_big_classify counts up (clear2[RR_CLEAR_CLASS .. + 1])
+constexpr int RR_CLEAR_CLASS = 5;
 __global__ __launch_bounds__(SPINE_THREADS) void k_rr_scan_round(uint32_t *__restrict__ tile_cnt, uint32_t *__restrict__ tile_head, int64_t tiles,
                                                                   uint32_t *__restrict__ out_total, uint32_t *__restrict__ tile_first,
                                                                   uint32_t *__restrict__ changed_cnt, uint32_t *__restrict__ clear2,
@@ -506,6 +507,7 @@ __global__ __launch_bounds__(SPINE_THREADS) void k_rr_scan_round(uint32_t *__res
     if (blockIdx.x == 0) { rr_scan_body(tile_cnt, tile_head, tiles, out_total); return; }
     if (tile_first) rr_scan_next_body(tile_first, tiles, changed_cnt);
     if (threadIdx.x == 0 && clear2) { clear2[2] = clear2[0]; clear2[3] = clear2[1]; clear2[0] = 0u; clear2[1] = 0u; }      // (saved for the round's one read-back, then zeroed)
+    if (threadIdx.x == 0 && clear2) { clear2[RR_CLEAR_CLASS] = 0u; clear2[RR_CLEAR_CLASS + 1] = 0u; }
 }
 
 // ISA_MODE: 0 = scatter ISA[suffix] = rank directly, 1 = the same plus the has_isa bitmap (sparse
