@@ -615,6 +615,8 @@ def diag_lib() -> ctypes.CDLL:
         L.sa_amd_debug_head_flags.restype = ctypes.c_int32
         L.sa_amd_debug_round_flags.argtypes = [ctypes.c_int32]
         L.sa_amd_debug_round_flags.restype = ctypes.c_int32
+        L.sa_amd_debug_fill_blocks.argtypes = [ctypes.c_int32]
+        L.sa_amd_debug_fill_blocks.restype = ctypes.c_int32
         L.sa_amd_last_stats.argtypes = [c_vp]
         L.sa_amd_test_sample_sort64.argtypes = [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, c_vp]
         L.sa_amd_test_sample_sort64.restype = ctypes.c_int32
@@ -1368,13 +1370,14 @@ class DeviceIndex:
         a = None if sa is None else np.ascontiguousarray(sa, dtype=np.uint32)
         if a is not None:
             assert a.size == self._s.size + 1
-        _check(lib().sa_amd_index_create(self._s.ctypes.data, self._s.size, None if a is None else a.ctypes.data,
-                                         ctypes.byref(h)))
+        self._lib = lib()              # the library that made the handle destroys it, whichever one lib() answers by then
+        _check(self._lib.sa_amd_index_create(self._s.ctypes.data, self._s.size, None if a is None else a.ctypes.data,
+                                             ctypes.byref(h)))
         self._h = h
 
     def close(self):
         if getattr(self, "_h", None):
-            lib().sa_amd_index_destroy(self._h)
+            self._lib.sa_amd_index_destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -1726,13 +1729,14 @@ class TokenIndex:
         if a is not None and a.size != self._t.size + 1:
             raise ValueError("TokenIndex: sa has len(tokens) + 1 entries")
         h = ctypes.c_void_p()
-        _check(lib().sa_amd_tok_index_create(self._t.ctypes.data if self._t.size else None, self._t.size,
-                                             None if a is None else a.ctypes.data, ctypes.byref(h)))
+        self._lib = lib()              # (as DeviceIndex: destroyed through the library that made it)
+        _check(self._lib.sa_amd_tok_index_create(self._t.ctypes.data if self._t.size else None, self._t.size,
+                                                 None if a is None else a.ctypes.data, ctypes.byref(h)))
         self._h = h
 
     def close(self):
         if getattr(self, "_h", None):
-            lib().sa_amd_tok_index_destroy(self._h)
+            self._lib.sa_amd_tok_index_destroy(self._h)
             self._h = None
 
     __del__ = close

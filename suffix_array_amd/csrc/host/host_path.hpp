@@ -497,6 +497,9 @@ static int build_host_small(const uint8_t *T, uint32_t *SA_host, int32_t n, bool
     void *dbase = nullptr;
     rc = hip_status(hipHostGetDevicePointer(&dbase, pb.p, 0));
     if (rc == SA_AMD_OK) {
+#ifdef SA_AMD_DIAG
+        diag_fill_host(pb.p, need);
+#endif
         memcpy(pb.p, T, (size_t)n);
         if (n <= SM_LITE_SINGLE_N)
             hipLaunchKernelGGL((k_small_sa_lite), dim3(1), dim3(SM_LITE_THREADS), 0, st, (const uint8_t *)dbase, (uint32_t *)((char *)dbase + tb), (int)n,
@@ -562,6 +565,9 @@ static int acquire_build_block(int32_t n, int node, const HostTuning &ht, BuildB
     if (rc != SA_AMD_OK) return rc;
     b.st = st;
     rc = pool().acquire(b.device, b.tb + b.sb + wb, &b.blk);
+#ifdef SA_AMD_DIAG
+    if (rc == SA_AMD_OK) rc = diag_fill_device(b.blk.p, b.tb + b.sb + wb, st);      // (sa_amd_debug_fill_blocks: text | array | workspace, as asked for)
+#endif
     if (rc != SA_AMD_ENOMEM || !ht.reduced) return rc;
     // The device cannot give text + array + the whole workspace (another tenant, or a text near MAX_LENGTH next to other
     // blocks).  The reference's engine needs 257 KiB beside its output, so "out of memory" is not an answer a drop-in should
@@ -582,6 +588,12 @@ static int acquire_build_block(int32_t n, int node, const HostTuning &ht, BuildB
         if (rc != SA_AMD_OK) { pool().release(b.blk); b.blk = DevBlock(); }
     }
     if (rc == SA_AMD_OK) { b.ws_dev = align_up(dry.bytes, 256); b.ws_host = dry.bytes2; }
+#ifdef SA_AMD_DIAG
+    if (rc == SA_AMD_OK) {
+        rc = diag_fill_device(b.blk.p, b.tb + b.sb + b.ws_dev, st);
+        diag_fill_host(b.spill.p, b.ws_host);                                       // (the pinned spill: kernels reach it zero-copy)
+    }
+#endif
     return rc;
 }
 
@@ -699,6 +711,9 @@ static int build_host_small_batch(const uint8_t *const *T, uint32_t *const *SA, 
         void *dbase = nullptr;
         if (rcc == SA_AMD_OK) rcc = hip_status(hipHostGetDevicePointer(&dbase, pb.p, 0));
         if (rcc == SA_AMD_OK) {
+#ifdef SA_AMD_DIAG
+            diag_fill_host(pb.p, need);
+#endif
             uint4 *desc = (uint4 *)pb.p;
             char *tpart = (char *)pb.p + dbytes, *spart = tpart + align_up(tbytes, 256);
             // descriptors: the texts of up to SM_LITE_N bytes first (the light kernel's: eight workgroups per CU), then the others

@@ -42,6 +42,9 @@ struct PooledScope {
     int32_t acquire(size_t bytes)
     {
         if (rc == SA_AMD_OK) { need = bytes; rc = pool().acquire(device, bytes, &blk); }
+#ifdef SA_AMD_DIAG
+        if (rc == SA_AMD_OK) rc = diag_fill_device(blk.p, need, st);      // (sa_amd_debug_fill_blocks: the bytes asked for, before the first slab is used)
+#endif
         return rc;
     }
     // a smaller block where acquire() answered SA_AMD_ENOMEM (nothing is held then); any other state stays as it is

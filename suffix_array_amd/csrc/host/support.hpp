@@ -61,6 +61,69 @@ static bool debug_sync()
 
 inline int hip_status(hipError_t e) { return e == hipSuccess ? SA_AMD_OK : (e == hipErrorOutOfMemory ? SA_AMD_ENOMEM : SA_AMD_EHIP); }
 
+#ifdef SA_AMD_DIAG
+// The fill switch of the diagnostic library only (sa_amd_debug_fill_blocks, csrc/sa_diag.h): while it is on,
+// every pooled block, every zero-copy pinned block and every DevBuf is overwritten with the pattern before its first use, so
+// that a route which reads a word it never wrote gives a wrong answer there instead of depending on its predecessor.
+//   -1 off; 0 .. 255 that byte everywhere; 256 "small": word i = mix(i + seed) % 5; 257 "random": word i = mix(i + seed)
+constexpr int FILL_OFF = -1, FILL_SMALL = 256, FILL_RANDOM = 257;
+inline std::atomic<int> g_fill_pattern{FILL_OFF};
+inline std::atomic<uint32_t> g_fill_seed{0};       // moves on with every fill: two blocks of a call do not hold the same words
+
+__host__ __device__ static inline uint32_t fill_mix(uint32_t x)
+{
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+__host__ __device__ static inline uint32_t fill_word(uint32_t i, uint32_t seed, int pattern)
+{
+    const uint32_t m = fill_mix(i + seed);
+    return pattern == FILL_SMALL ? m % 5u : m;
+}
+
+__global__ void __launch_bounds__(256) k_diag_fill(uint32_t *p, size_t words, uint32_t seed, int pattern)
+{
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) p[i] = fill_word((uint32_t)i, seed, pattern);
+}
+
+// `bytes` of device memory at `p` (4-byte aligned) on `st`, and a wait for it: whatever stream the route goes on to use, the
+// fill is ordered before it.  The bytes behind the last whole word take the low byte of their word's pattern.
+static inline int diag_fill_device(void *p, size_t bytes, hipStream_t st)
+{
+    const int pattern = g_fill_pattern.load(std::memory_order_relaxed);
+    if (pattern == FILL_OFF || !p || bytes == 0) return SA_AMD_OK;
+    hipError_t e = hipSuccess;
+    if (pattern < FILL_SMALL) e = hipMemsetAsync(p, pattern, bytes, st);
+    else {
+        const uint32_t seed = g_fill_seed.fetch_add(0x9e3779b9u);
+        const size_t words = bytes / 4, tail = bytes % 4;
+        if (words > 0) {
+            const size_t blocks = (words + 255) / 256;
+            hipLaunchKernelGGL(k_diag_fill, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, (uint32_t *)p, words, seed, pattern);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && tail > 0) e = hipMemsetAsync((char *)p + words * 4, (int)(fill_word((uint32_t)words, seed, pattern) & 0xffu), tail, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return hip_status(e);
+}
+
+// the same for a pinned host block that kernels reach zero-copy, written by the host before anything is queued on it
+static inline void diag_fill_host(void *p, size_t bytes)
+{
+    const int pattern = g_fill_pattern.load(std::memory_order_relaxed);
+    if (pattern == FILL_OFF || !p || bytes == 0) return;
+    if (pattern < FILL_SMALL) { memset(p, pattern, bytes); return; }
+    const uint32_t seed = g_fill_seed.fetch_add(0x9e3779b9u);
+    const size_t words = bytes / 4;
+    uint32_t *w = (uint32_t *)p;
+    for (size_t i = 0; i < words; ++i) w[i] = fill_word((uint32_t)i, seed, pattern);
+    for (size_t i = words * 4; i < bytes; ++i) ((uint8_t *)p)[i] = (uint8_t)fill_word((uint32_t)words, seed, pattern);
+}
+#endif
+
 // device memory that is freed on every exit path (HIP_TRY returns early)
 struct DevBuf {
     void *p = nullptr;
@@ -73,7 +136,15 @@ struct DevBuf {
         return *this;
     }
     ~DevBuf() { reset(); }
-    int alloc(size_t bytes) { reset(); return hip_status(hipMalloc(&p, bytes ? bytes : 1)); }
+    int alloc(size_t bytes)
+    {
+        reset();
+        int rc = hip_status(hipMalloc(&p, bytes ? bytes : 1));
+#ifdef SA_AMD_DIAG
+        if (rc == SA_AMD_OK) rc = diag_fill_device(p, bytes ? bytes : 1, nullptr);      // (an index's tables, the slack behind its text included)
+#endif
+        return rc;
+    }
     void reset() { if (p) (void)hipFree(p); p = nullptr; }
     template <typename T> T *as() const { return (T *)p; }
 };

@@ -36,6 +36,15 @@ int32_t sa_amd_debug_doc_tf_bounds(int32_t mode);
 /* the pair pass of sa_amd_index_doc_substrings (process-wide; returns the previous mode): 0 equal targets inside a wave are
  * combined into one atomic (what the product library always does), 1 one atomic per pair.  Both give the same table. */
 int32_t sa_amd_debug_dsub_plain_atomics(int32_t mode);
+/* what recycled memory holds when a route gets it (process-wide; returns the previous pattern): -1 off (the default: the bytes
+ * are whatever the last user left, as in the product library), 0 .. 255 every byte takes that value, 256 "small": 32-bit word i
+ * is mix(i + seed) % 5 -- in range as an index, a count or a flag of every table, so that a stale read is a wrong answer and no
+ * wild address --, 257 "random": word i is mix(i + seed).  While it is on, the fill is applied, and waited for, before the first
+ * use of: the bytes asked of the pool for every pooled device block (the derived-array and query routes, the build of the
+ * host-pointer path on its full and its reduced-memory route, the pinned spill of the latter included); the pinned blocks the
+ * small-text and small-batch kernels read and write zero-copy; every allocation an index or a token index owns, the slack
+ * behind its text included.  The contract it tests: no result and no statistic depends on those bytes. */
+int32_t sa_amd_debug_fill_blocks(int32_t pattern);
 int32_t sa_amd_debug_sort_variant_count(void);
 const char *sa_amd_debug_sort_variant_name(int32_t index);
 /* stable LSD radix sort of (u64 key, u32 value) pairs on bits [begin_bit, end_bit); host buffers */

@@ -35,6 +35,11 @@ SA_EXPORT int32_t sa_amd_debug_doc_tf_bounds(int32_t mode)
     return sa::g_doc_tf_plain_bounds.exchange(mode ? 1 : 0);
 }
 
+SA_EXPORT int32_t sa_amd_debug_fill_blocks(int32_t pattern)
+{
+    return sa::g_fill_pattern.exchange(pattern < 0 || pattern > sa::FILL_RANDOM ? sa::FILL_OFF : pattern);
+}
+
 SA_EXPORT int32_t sa_amd_debug_dsub_plain_atomics(int32_t mode)
 {
     return sa::g_dsub_plain_atomics.exchange(mode ? 1 : 0);

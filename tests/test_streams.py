@@ -576,10 +576,11 @@ def env():
 
 class Buffers:
     """the device buffers of one call: inputs, the sources the real input waits in, outputs with 256 canary bytes on either side,
-    the work block and the source of its fill"""
+    the work block and the source of its fill.  fill(bytes) -> the array the source of the fill holds (default: the word 1)"""
 
-    def __init__(self, env, v):
+    def __init__(self, env, v, fill=None):
         self.env, self.hip, self.v = env, env.hip, v
+        self.fill_source = fill if fill is not None else (lambda size: np.ones(size // 4, dtype=np.uint32))
         self.all = []
         self.sizes = [a.nbytes for a in v.inputs("real")]
         self.ins = [self.take(s + 16) for s in self.sizes]
@@ -601,8 +602,8 @@ class Buffers:
             assert self.hip.hipMemcpy(dst, a.ctypes.data, a.nbytes, H2D) == 0
 
     def load(self, ins_from, srcs_from=None):
-        """synchronously: `ins_from` into the inputs, `srcs_from` into the sources, the canary into the outputs, ones into the
-        fill's source; then the device is idle"""
+        """synchronously: `ins_from` into the inputs, `srcs_from` into the sources, the canary into the outputs, the fill into
+        its source (ones by default); then the device is idle"""
         for p, a in zip(self.ins, self.v.inputs(ins_from)):
             self.upload(p, a)
         if srcs_from:
@@ -611,7 +612,7 @@ class Buffers:
         for p, s in zip(self.outs, self.out_sizes):
             assert self.hip.hipMemset(p, CANARY, s + 512) == 0
         if self.wb:
-            self.upload(self.fill, np.ones(self.wb // 4, dtype=np.uint32))
+            self.upload(self.fill, self.fill_source(self.wb))
         assert self.hip.hipDeviceSynchronize() == 0
 
     def queue_real_input(self, stream):
