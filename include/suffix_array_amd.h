@@ -1157,4 +1157,10 @@ const char *sa_amd_profile_kernel_name(int32_t index);
 #ifdef __cplusplus
 }
 #endif
+
+/* Texts of 32-bit token ids below 2^24 -- sa_amd_saca_u32, sa_amd_tok32_index_* (an extension): the
+ * 16-bit token forms above for tokeniser ids held in uint32_t.  Part of this interface, declared and documented in a file of
+ * its own. */
+#include "suffix_array_amd_tok32.h"
+
 #endif /* SUFFIX_ARRAY_AMD_H */

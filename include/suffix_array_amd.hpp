@@ -479,29 +479,59 @@ private:
     std::size_t n_ = 0, ndocs_ = 0;
 };
 
-// EXTENSION (not in the reference): a text of 16-bit tokens and its suffix array resident on the device (sa_amd_tok_index;
-// suffix_array_amd.h, "Texts over a 16-bit token alphabet").  Tokens compare as unsigned 16-bit values; every length, position
-// and offset is in tokens.
-class TokenIndex {
+// The entry points of one token width (suffix_array_amd.h): what TokenIndex and TokenIndex32 differ in.
+struct TokenAbi16 {
+    using Token = std::uint16_t;
+    using Handle = sa_amd_tok_index;
+    static constexpr std::size_t max_tokens = MAX_LENGTH / 2;
+    static constexpr auto create = sa_amd_tok_index_create;
+    static constexpr auto destroy = sa_amd_tok_index_destroy;
+    static constexpr auto sa = sa_amd_tok_index_sa;
+    static constexpr auto search = sa_amd_tok_index_search;
+    static constexpr auto next_tokens = sa_amd_tok_index_next_tokens;
+    static constexpr auto infgram = sa_amd_tok_index_infgram;
+    static constexpr auto infgram_score = sa_amd_tok_index_infgram_score;
+};
+struct TokenAbi32 {
+    using Token = std::uint32_t;
+    using Handle = sa_amd_tok32_index;
+    static constexpr std::size_t max_tokens = MAX_LENGTH / 3;
+    static constexpr auto create = sa_amd_tok32_index_create;
+    static constexpr auto destroy = sa_amd_tok32_index_destroy;
+    static constexpr auto sa = sa_amd_tok32_index_sa;
+    static constexpr auto search = sa_amd_tok32_index_search;
+    static constexpr auto next_tokens = sa_amd_tok32_index_next_tokens;
+    static constexpr auto infgram = sa_amd_tok32_index_infgram;
+    static constexpr auto infgram_score = sa_amd_tok32_index_infgram_score;
+};
+
+// EXTENSION (not in the reference): a token text and its suffix array resident on the device.  Tokens compare as unsigned
+// values; every length, position and offset is in tokens.
+//   TokenIndex    16-bit tokens (sa_amd_tok_index; suffix_array_amd.h, "Texts over a 16-bit token alphabet")
+//   TokenIndex32  token ids below 2^24 in std::uint32_t (sa_amd_tok32_index; suffix_array_amd_tok32.h): an id of
+//                 2^24 or more in the text, a pattern, a prompt or a query throws std::runtime_error (SA_AMD_ERANGE)
+template <class Abi>
+class BasicTokenIndex {
 public:
-    using Tokens = std::vector<std::uint16_t>;
+    using Token = typename Abi::Token;
+    using Tokens = std::vector<Token>;
     // sa == nullptr: the suffix array is built on the device and never downloaded; a supplied one (n + 1 entries) is range-checked
-    TokenIndex(const std::uint16_t *t, std::size_t n, const std::uint32_t *sa = nullptr)
+    BasicTokenIndex(const Token *t, std::size_t n, const std::uint32_t *sa = nullptr)
     {
-        if (n > static_cast<std::size_t>(MAX_LENGTH / 2)) throw std::logic_error("assertion failed: t.len() <= MAX_LENGTH / 2");
-        check(sa_amd_tok_index_create(t, static_cast<std::int32_t>(n), sa, &ix_));
+        if (n > Abi::max_tokens) throw std::logic_error("assertion failed: t.len() <= the longest token text");
+        check(Abi::create(t, static_cast<std::int32_t>(n), sa, &ix_));
         n_ = n;
     }
-    TokenIndex(const TokenIndex &) = delete;
-    TokenIndex &operator=(const TokenIndex &) = delete;
-    ~TokenIndex() { sa_amd_tok_index_destroy(ix_); }
+    BasicTokenIndex(const BasicTokenIndex &) = delete;
+    BasicTokenIndex &operator=(const BasicTokenIndex &) = delete;
+    ~BasicTokenIndex() { Abi::destroy(ix_); }
 
     std::size_t len() const { return n_; }
     // the token suffix array: n + 1 entries, entry 0 is n
     std::vector<std::uint32_t> sa() const
     {
         std::vector<std::uint32_t> out(n_ + 1);
-        check(sa_amd_tok_index_sa(ix_, out.data()));
+        check(Abi::sa(ix_, out.data()));
         return out;
     }
     // per pattern its match range [lo, hi) in the token suffix array; lo == hi where it does not occur
@@ -509,7 +539,7 @@ public:
     {
         const Batch b(patterns);
         std::vector<std::uint32_t> lo(patterns.size() + 1), hi(patterns.size() + 1);
-        check(sa_amd_tok_index_search(ix_, b.toks.data(), b.off.data(), b.count(), nullptr, lo.data(), hi.data()));
+        check(Abi::search(ix_, b.toks.data(), b.off.data(), b.count(), nullptr, lo.data(), hi.data()));
         std::vector<std::pair<std::uint32_t, std::uint32_t>> out(patterns.size());
         for (std::size_t q = 0; q < out.size(); ++q) out[q] = { lo[q], hi[q] };
         return out;
@@ -534,7 +564,7 @@ public:
     struct NextTokens {
         std::uint32_t lo = 0, hi = 0;
         bool at_end = false;
-        std::vector<std::pair<std::uint16_t, std::uint32_t>> next;
+        std::vector<std::pair<Token, std::uint32_t>> next;
     };
     // the same for the longest suffix of a prompt that occurs at least min_count times: suffix_len is its length in tokens
     struct Infgram : NextTokens {
@@ -568,10 +598,10 @@ public:
         const std::size_t m = query.size();
         Score r;
         r.s.resize(m + 1); r.lo.resize(m + 1); r.hi.resize(m + 1); r.nlo.resize(m + 1); r.nhi.resize(m + 1); r.at_end.resize(m + 1);
-        check(sa_amd_tok_index_infgram_score(ix_, m ? query.data() : nullptr, static_cast<std::int64_t>(m),
-                                             doc_offsets.empty() ? nullptr : doc_offsets.data(),
-                                             doc_offsets.empty() ? 0 : static_cast<std::int64_t>(doc_offsets.size()) - 1, min_count, max_len,
-                                             r.s.data(), r.lo.data(), r.hi.data(), r.at_end.data(), r.nlo.data(), r.nhi.data()));
+        check(Abi::infgram_score(ix_, m ? query.data() : nullptr, static_cast<std::int64_t>(m),
+                                 doc_offsets.empty() ? nullptr : doc_offsets.data(),
+                                 doc_offsets.empty() ? 0 : static_cast<std::int64_t>(doc_offsets.size()) - 1, min_count, max_len,
+                                 r.s.data(), r.lo.data(), r.hi.data(), r.at_end.data(), r.nlo.data(), r.nhi.data()));
         r.s.resize(m); r.lo.resize(m); r.hi.resize(m); r.nlo.resize(m); r.nhi.resize(m); r.at_end.resize(m);
         return r;
     }
@@ -604,11 +634,11 @@ private:
         for (;;) {
             const std::int64_t cap = static_cast<std::int64_t>(toks.size());
             if (backoff)
-                check(sa_amd_tok_index_infgram(ix_, b.toks.data(), b.off.data(), b.count(), min_count, max_len, slen, lo.data(), hi.data(), ae.data(),
-                                               loff.data(), toks.data(), counts.data(), cap, &total));
+                check(Abi::infgram(ix_, b.toks.data(), b.off.data(), b.count(), min_count, max_len, slen, lo.data(), hi.data(), ae.data(),
+                                   loff.data(), toks.data(), counts.data(), cap, &total));
             else
-                check(sa_amd_tok_index_next_tokens(ix_, b.toks.data(), b.off.data(), b.count(), lo.data(), hi.data(), ae.data(), loff.data(),
-                                                   toks.data(), counts.data(), cap, &total));
+                check(Abi::next_tokens(ix_, b.toks.data(), b.off.data(), b.count(), lo.data(), hi.data(), ae.data(), loff.data(),
+                                       toks.data(), counts.data(), cap, &total));
             if (total <= cap) break;
             toks.resize(static_cast<std::size_t>(total));
             counts.resize(static_cast<std::size_t>(total));
@@ -624,8 +654,11 @@ private:
         if (rc == SA_AMD_EINVAL) throw std::invalid_argument("suffix_array_amd: invalid argument");
         if (rc != SA_AMD_OK) throw std::runtime_error(std::string("suffix_array_amd: ") + sa_amd_strerror(rc));
     }
-    sa_amd_tok_index *ix_ = nullptr;
+    typename Abi::Handle *ix_ = nullptr;
     std::size_t n_ = 0;
 };
+
+using TokenIndex = BasicTokenIndex<TokenAbi16>;
+using TokenIndex32 = BasicTokenIndex<TokenAbi32>;
 
 }  // namespace suffix_array

@@ -41,12 +41,17 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "NgramStats", "last_ngram_stats", "ngram_set_stream_cap", "NGRAM_STREAM_CAP_DEFAULT",
            "ScoreStats", "ScoreResult", "last_score_stats", "score_set_group_cap", "score_work_bytes", "infgram_score_device_ptr",
            "SCORE_MAX_CONTEXT", "SCORE_GROUP_CAP_DEFAULT", "SCORE_TILE",
-           "saca_u16", "MAX_TOKENS_U16", "TokenIndex", "TokStats", "last_tok_stats", "TokScoreStats", "last_tok_score_stats"]
+           "saca_u16", "MAX_TOKENS_U16", "TokenIndex", "TokStats", "last_tok_stats", "TokScoreStats", "last_tok_score_stats",
+           "saca_u32", "MAX_TOKENS_U32", "TOKEN_LIMIT_U32", "TokenIndex32"]
 
 #: reference src/saca.rs:6
 MAX_LENGTH = 2**31 - 1
 #: the longest 16-bit token text (sa_amd_max_tokens_u16): its byte image has at most MAX_LENGTH bytes
 MAX_TOKENS_U16 = MAX_LENGTH // 2
+#: the ids of a 32-bit token text lie below it (SA_AMD_TOKEN_LIMIT_U32): three bytes a token in the image
+TOKEN_LIMIT_U32 = 1 << 24
+#: the longest 32-bit token text (sa_amd_max_tokens_u32): its 3-byte image has at most MAX_LENGTH bytes
+MAX_TOKENS_U32 = MAX_LENGTH // 3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libsuffix_array_amd.so"
@@ -588,6 +593,11 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_tok_index_infgram_score.restype = ctypes.c_int32
         L.sa_amd_last_tok_score_stats.argtypes = [c_vp]
         L.sa_amd_last_tok_score_stats.restype = None
+        for u16_name, u32_name in (("sa_amd_max_tokens_u16", "sa_amd_max_tokens_u32"), ("sa_amd_saca_u16", "sa_amd_saca_u32")) + tuple(
+                ("sa_amd_tok_index_" + op, "sa_amd_tok32_index_" + op)
+                for op in ("create", "destroy", "sa", "search", "next_tokens", "infgram", "infgram_score")):
+            u16_fn, u32_fn = getattr(L, u16_name), getattr(L, u32_name)       # (the signatures are the u16 ones with uint32_t tokens)
+            u32_fn.argtypes, u32_fn.restype = u16_fn.argtypes, u16_fn.restype
         _lib = L
     return _lib
 
@@ -1660,30 +1670,53 @@ class DeviceIndex:
         return {"contains": c.astype(bool), "lo": lo, "hi": hi, "lcp_start": ls, "lcp_len": ll}
 
 
-def _as_u16(tokens, what: str = "tokens") -> np.ndarray:
-    """a uint16 array as it is, or a sequence of ints in 0 .. 65 535 -> contiguous 1-D uint16; anything else raises before the
-    library is called"""
+def _as_tokens(tokens, what: str, dtype, limit: int, check_array: bool = False) -> np.ndarray:
+    """an array of ``dtype`` as it is, or a sequence of ints in 0 .. limit - 1 -> contiguous 1-D ``dtype``; anything else raises
+    before the library is called.  ``check_array``: the values of an array are checked against ``limit`` too"""
+    kind = f"a 1-D {np.dtype(dtype).name} array or a sequence of ints in 0 .. {limit - 1}"
     if isinstance(tokens, np.ndarray):
-        if tokens.dtype != np.uint16 or tokens.ndim != 1:
-            raise TypeError(f"{what}: a 1-D uint16 array or a sequence of ints in 0 .. 65535")
+        if tokens.dtype != dtype or tokens.ndim != 1:
+            raise TypeError(f"{what}: {kind}")
+        if check_array and tokens.size and int(tokens.max()) >= limit:
+            raise ValueError(f"{what}: token {int(tokens.max())} is outside 0 .. {limit - 1}")
         return np.ascontiguousarray(tokens)
     if isinstance(tokens, (bytes, bytearray, str)):
-        raise TypeError(f"{what}: a 1-D uint16 array or a sequence of ints in 0 .. 65535, not {type(tokens).__name__}")
+        raise TypeError(f"{what}: {kind}, not {type(tokens).__name__}")
     vals = list(tokens)
     for v in vals:
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
             raise TypeError(f"{what}: {v!r} is not an int")
-        if not 0 <= int(v) <= 65535:
-            raise ValueError(f"{what}: token {int(v)} is outside 0 .. 65535")
-    return np.array(vals, dtype=np.uint16).reshape(-1)
+        if not 0 <= int(v) < limit:
+            raise ValueError(f"{what}: token {int(v)} is outside 0 .. {limit - 1}")
+    return np.array(vals, dtype=dtype).reshape(-1)
+
+
+def _as_u16(tokens, what: str = "tokens") -> np.ndarray:
+    """a uint16 array as it is, or a sequence of ints in 0 .. 65 535 -> contiguous 1-D uint16; anything else raises before the
+    library is called"""
+    return _as_tokens(tokens, what, np.uint16, 1 << 16)
+
+
+def _as_u32(tokens, what: str = "tokens", text: bool = False) -> np.ndarray:
+    """a uint32 array as it is, or a sequence of ints in 0 .. 2^24 - 1 -> contiguous 1-D uint32; anything else raises before the
+    library is called.  The ids of an array are checked here unless it is a ``text``, whose ids the device checks (an id of 2^24
+    or more is the library's SA_AMD_ERANGE)"""
+    return _as_tokens(tokens, what, np.uint32, TOKEN_LIMIT_U32, check_array=not text)
+
+
+def _batch_of(pats, dtype):
+    off = np.zeros(len(pats) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([p.size for p in pats])
+    data = np.concatenate(pats) if off[-1] else np.zeros(1, dtype=dtype)
+    return np.ascontiguousarray(data, dtype=dtype), off, len(pats)
 
 
 def _token_batch(patterns):
-    pats = [_as_u16(p, "pattern") for p in patterns]
-    off = np.zeros(len(pats) + 1, dtype=np.int64)
-    off[1:] = np.cumsum([p.size for p in pats])
-    data = np.concatenate(pats) if off[-1] else np.zeros(1, dtype=np.uint16)
-    return np.ascontiguousarray(data, dtype=np.uint16), off, len(pats)
+    return _batch_of([_as_u16(p, "pattern") for p in patterns], np.uint16)
+
+
+def _token_batch32(patterns):
+    return _batch_of([_as_u32(p, "pattern") for p in patterns], np.uint32)
 
 
 def saca_u16(tokens) -> np.ndarray:
@@ -1695,6 +1728,19 @@ def saca_u16(tokens) -> np.ndarray:
         raise ValueError(f"saca_u16: at most {MAX_TOKENS_U16} tokens")
     out = np.empty(t.size + 1, dtype=np.uint32)
     _check(lib().sa_amd_saca_u16(t.ctypes.data if t.size else None, out.ctypes.data, t.size))
+    return out
+
+
+def saca_u32(tokens) -> np.ndarray:
+    """EXTENSION: the suffix array of a text of token ids below 2^24 held in uint32 (``sa_amd_saca_u32``) -> uint32 array of
+    ``n + 1`` entries in token positions, entry 0 is ``n``: ``saca_u16`` for the vocabularies that do not fit 16 bits.  Built on
+    the GPU from the big-endian image at three bytes a token; an id of 2^24 or more in an array is found there
+    (``SuffixArrayError``, SA_AMD_ERANGE), in a sequence of ints here (``ValueError``)."""
+    t = _as_u32(tokens, text=True)
+    if t.size > MAX_TOKENS_U32:
+        raise ValueError(f"saca_u32: at most {MAX_TOKENS_U32} tokens")
+    out = np.empty(t.size + 1, dtype=np.uint32)
+    _check(lib().sa_amd_saca_u32(t.ctypes.data if t.size else None, out.ctypes.data, t.size))
     return out
 
 
@@ -1721,22 +1767,34 @@ class TokenIndex:
     array on the device without downloading it; a supplied array is range-checked.  Patterns are sequences of uint16 arrays
     or of sequences of ints in 0 .. 65 535; every length and offset is in tokens."""
 
+    # what TokenIndex32 replaces: the prefix of the ABI's names, the token type, the longest text, the coercions
+    _abi = "sa_amd_tok_index_"
+    _dtype = np.uint16
+    _max_tokens = MAX_TOKENS_U16
+    _as_text = staticmethod(lambda tokens: _as_u16(tokens))
+    _as_query = staticmethod(lambda tokens: _as_u16(tokens, "query"))
+    _batch = staticmethod(lambda patterns: _token_batch(patterns))
+
+    def _fn(self, op: str, library=None):
+        return getattr(library or lib(), self._abi + op)
+
     def __init__(self, tokens, sa: Optional[np.ndarray] = None):
-        self._t = _as_u16(tokens)
-        if self._t.size > MAX_TOKENS_U16:
-            raise ValueError(f"TokenIndex: at most {MAX_TOKENS_U16} tokens")
+        name = type(self).__name__
+        self._t = self._as_text(tokens)
+        if self._t.size > self._max_tokens:
+            raise ValueError(f"{name}: at most {self._max_tokens} tokens")
         a = None if sa is None else np.ascontiguousarray(sa, dtype=np.uint32)
         if a is not None and a.size != self._t.size + 1:
-            raise ValueError("TokenIndex: sa has len(tokens) + 1 entries")
+            raise ValueError(f"{name}: sa has len(tokens) + 1 entries")
         h = ctypes.c_void_p()
         self._lib = lib()              # (as DeviceIndex: destroyed through the library that made it)
-        _check(self._lib.sa_amd_tok_index_create(self._t.ctypes.data if self._t.size else None, self._t.size,
-                                                 None if a is None else a.ctypes.data, ctypes.byref(h)))
+        _check(self._fn("create", self._lib)(self._t.ctypes.data if self._t.size else None, self._t.size,
+                                             None if a is None else a.ctypes.data, ctypes.byref(h)))
         self._h = h
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.sa_amd_tok_index_destroy(self._h)
+            self._fn("destroy", self._lib)(self._h)
             self._h = None
 
     __del__ = close
@@ -1746,15 +1804,15 @@ class TokenIndex:
 
     def sa(self) -> np.ndarray:
         out = np.empty(self._t.size + 1, dtype=np.uint32)
-        _check(lib().sa_amd_tok_index_sa(self._h, out.ctypes.data))
+        _check(self._fn("sa")(self._h, out.ctypes.data))
         return out
 
     def _search(self, patterns, contains: bool):
-        data, off, cnt = _token_batch(patterns)
+        data, off, cnt = self._batch(patterns)
         lo, hi = np.zeros(cnt, dtype=np.uint32), np.zeros(cnt, dtype=np.uint32)
         has = np.zeros(cnt, dtype=np.uint8)
-        _check(lib().sa_amd_tok_index_search(self._h, data.ctypes.data, off.ctypes.data, cnt, has.ctypes.data if contains else None,
-                                             lo.ctypes.data, hi.ctypes.data))
+        _check(self._fn("search")(self._h, data.ctypes.data, off.ctypes.data, cnt, has.ctypes.data if contains else None,
+                                  lo.ctypes.data, hi.ctypes.data))
         return has, lo, hi
 
     def search(self, patterns):
@@ -1771,8 +1829,8 @@ class TokenIndex:
         return self._search(patterns, True)[0].astype(bool)
 
     def _ngram(self, patterns, backoff: bool, min_count: int, max_len: int):
-        batch = _token_batch(patterns)
-        return _ngram_query(lib().sa_amd_tok_index_next_tokens, lib().sa_amd_tok_index_infgram, self._h, batch, np.uint16,
+        batch = self._batch(patterns)
+        return _ngram_query(self._fn("next_tokens"), self._fn("infgram"), self._h, batch, self._dtype,
                             max(1 << 16, 8 * batch[2]), backoff, min_count, max_len)
 
     def next_tokens(self, patterns):
@@ -1798,17 +1856,32 @@ class TokenIndex:
         it, ``[nlo, nhi)`` is the part of its range that ``query[j]`` follows (empty, at its insertion point, where it never
         does).  ``doc_offsets``: ``ndocs + 1`` non-decreasing values from 0 to ``len(query)``, in tokens; ``None`` is one
         document.  The query (2 bytes a token) is read once on the device; ``score_set_group_cap`` applies, counted in tokens."""
-        q = _as_u16(query, "query")
+        q = self._as_query(query)
         if int(min_count) < 1:
             raise SuffixArrayError(-1, "infgram_score: min_count >= 1")
         off, ndocs = _score_offsets(doc_offsets)
         m = int(q.size)
         s, lo, hi, nlo, nhi = (np.zeros(m, dtype=np.uint32) for _ in range(5))
         ae = np.zeros(m, dtype=np.uint8)
-        _check(lib().sa_amd_tok_index_infgram_score(self._h, q.ctypes.data if m else None, m, off.ctypes.data if off is not None else None, ndocs,
-                                                    min(int(min_count), 2**31 - 1), max(-1, min(int(max_len), 2**31 - 1)), s.ctypes.data,
-                                                    lo.ctypes.data, hi.ctypes.data, ae.ctypes.data, nlo.ctypes.data, nhi.ctypes.data))
+        _check(self._fn("infgram_score")(self._h, q.ctypes.data if m else None, m, off.ctypes.data if off is not None else None, ndocs,
+                                         min(int(min_count), 2**31 - 1), max(-1, min(int(max_len), 2**31 - 1)), s.ctypes.data,
+                                         lo.ctypes.data, hi.ctypes.data, ae.ctypes.data, nlo.ctypes.data, nhi.ctypes.data))
         return ScoreResult(s, lo, hi, ae, nlo, nhi)
+
+
+class TokenIndex32(TokenIndex):
+    """EXTENSION: ``TokenIndex`` for token ids below 2^24 held in uint32 (sa_amd_tok32_index of include/suffix_array_amd_tok32.h): the
+    same methods with the same results, the listings' tokens as uint32, a query at 4 bytes a token.  ``tokens`` is a 1-D uint32
+    array (an id of 2^24 or more is found on the device: ``SuffixArrayError``, SA_AMD_ERANGE) or a sequence of ints in
+    0 .. 2^24 - 1; patterns, prompts and queries likewise, and an id of 2^24 or more in one of them is a ``ValueError`` before
+    the library is called."""
+
+    _abi = "sa_amd_tok32_index_"
+    _dtype = np.uint32
+    _max_tokens = MAX_TOKENS_U32
+    _as_text = staticmethod(lambda tokens: _as_u32(tokens, text=True))
+    _as_query = staticmethod(lambda tokens: _as_u32(tokens, "query"))
+    _batch = staticmethod(lambda patterns: _token_batch32(patterns))
 
 
 def workspace_bytes(n: int) -> int:

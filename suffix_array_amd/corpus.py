@@ -81,16 +81,11 @@ def english_corpus(n: int, seed: int, vocab: int = 50000, dup_fraction: float = 
     return out
 
 
-def token_corpus(n: int, vocab: int = 50000, seed: int = 0) -> np.ndarray:
-    """n tokeniser-like ids (uint16) for the 16-bit token texts: Zipf-distributed ranks (weight 1 / rank) over `vocab` <= 65 536
-    words, the rank -> id map a seeded permutation (frequent words get ids with any high byte), and one block of n / 16 tokens
-    repeated further on (a copied passage: long common prefixes).  numpy only; the same array for the same arguments."""
-    if not 1 <= vocab <= 65536:
-        raise ValueError("token_corpus: 1 <= vocab <= 65536")
-    rng = np.random.default_rng([int(seed), int(vocab), 0x746F6B])
+def _zipf_text(rng, ids: np.ndarray, n: int) -> np.ndarray:
+    """n draws of ids[rank], rank Zipf-distributed (weight 1 / rank), then one block of n / 16 entries repeated further on"""
+    vocab = ids.size
     cdf = np.cumsum(1.0 / np.arange(1, vocab + 1, dtype=np.float64))
-    ids = rng.permutation(vocab).astype(np.uint16)
-    out = np.empty(n, dtype=np.uint16)
+    out = np.empty(n, dtype=ids.dtype)
     step = 1 << 22
     for a in range(0, n, step):                                   # in pieces: the float64 draws of 128 Mi tokens would be 1 GiB
         b = min(n, a + step)
@@ -101,6 +96,28 @@ def token_corpus(n: int, vocab: int = 50000, seed: int = 0) -> np.ndarray:
         dst = int(rng.integers(src + blk, n - blk + 1))
         out[dst:dst + blk] = out[src:src + blk]
     return out
+
+
+def token_corpus(n: int, vocab: int = 50000, seed: int = 0) -> np.ndarray:
+    """n tokeniser-like ids (uint16) for the 16-bit token texts: Zipf-distributed ranks (weight 1 / rank) over `vocab` <= 65 536
+    words, the rank -> id map a seeded permutation (frequent words get ids with any high byte), and one block of n / 16 tokens
+    repeated further on (a copied passage: long common prefixes).  numpy only; the same array for the same arguments."""
+    if not 1 <= vocab <= 65536:
+        raise ValueError("token_corpus: 1 <= vocab <= 65536")
+    rng = np.random.default_rng([int(seed), int(vocab), 0x746F6B])
+    return _zipf_text(rng, rng.permutation(vocab).astype(np.uint16), n)
+
+
+def token_corpus_u32(n: int, vocab: int = 128000, seed: int = 0) -> np.ndarray:
+    """n tokeniser-like ids (uint32, every id below 2^24) for the 32-bit token texts: the Zipf ranks and the copied passage of
+    ``token_corpus`` over `vocab` <= 2^24 words.  The rank -> id map is the seeded bijection rank * a + b modulo 2^24 (a odd), so
+    whatever the vocabulary the ids -- those of the frequent words too -- differ in each of their three bytes."""
+    if not 1 <= vocab <= 1 << 24:
+        raise ValueError("token_corpus_u32: 1 <= vocab <= 2**24")
+    rng = np.random.default_rng([int(seed), int(vocab), 0x746F6B, 32])
+    a, b = (int(x) for x in rng.integers(0, 1 << 24, 2))
+    ids = ((np.arange(vocab, dtype=np.uint64) * np.uint64(a | 1) + np.uint64(b)) & np.uint64(0xFFFFFF)).astype(np.uint32)
+    return _zipf_text(rng, ids, n)
 
 
 #: BASELINE.md section 2 workloads: name -> (generator, n, seed)

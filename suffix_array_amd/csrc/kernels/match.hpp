@@ -66,14 +66,28 @@ __device__ __forceinline__ uint32_t match_lds_word(const uint32_t *s_w, uint32_t
 
 // The compare of two little-endian 32-bit words that hold 4 / sizeof(Sym) symbols each and differ in the bits d != 0: the index
 // of the first differing SYMBOL of the word and *less = the text's symbol there is the smaller VALUE.  With 16-bit tokens the
-// lowest differing byte does not decide: 0x0102 against 0x0201 differs first in a byte that says "greater".
+// lowest differing byte does not decide: 0x0102 against 0x0201 differs first in a byte that says "greater".  A 32-bit symbol is
+// the whole word: index 0, compared by value.
 template <typename Sym>
 __device__ __forceinline__ int match_word_diff(uint32_t d, uint32_t tw, uint32_t qw, bool *less)
 {
-    constexpr uint32_t BITS = 8u * sizeof(Sym), MASK = (1u << BITS) - 1u;
-    const int si = (__ffs(d) - 1) >> (sizeof(Sym) == 1 ? 3 : 4);
-    *less = ((tw >> (BITS * si)) & MASK) < ((qw >> (BITS * si)) & MASK);
-    return si;
+    if constexpr (sizeof(Sym) == 4) {
+        *less = tw < qw;
+        return 0;
+    } else {
+        constexpr uint32_t BITS = 8u * sizeof(Sym), MASK = (1u << BITS) - 1u;
+        const int si = (__ffs(d) - 1) >> (sizeof(Sym) == 1 ? 3 : 4);
+        *less = ((tw >> (BITS * si)) & MASK) < ((qw >> (BITS * si)) & MASK);
+        return si;
+    }
+}
+
+// the bits of a word that hold its first v symbols, 0 < v < 4 / sizeof(Sym) (a word of one symbol has no partial tail)
+template <typename Sym>
+__device__ __forceinline__ uint32_t match_tail_mask(int64_t v)
+{
+    if constexpr (sizeof(Sym) == 4) return 0xffffffffu;
+    else return (1u << (8u * (uint32_t)sizeof(Sym) * (uint32_t)v)) - 1u;
 }
 
 // lcp of T[p ..] and the window at BYTE offset wb of the staged words, both known to agree on [0, from) and compared on
@@ -85,7 +99,7 @@ __device__ __forceinline__ int64_t match_group_lcp(const Sym *__restrict__ T, in
                                                    int64_t from, int64_t limit, int gl, int gshift, unsigned long long *symbols, bool *less)
 {
     constexpr int W = 4 / (int)sizeof(Sym);
-    static_assert(sizeof(Sym) == 1 || sizeof(Sym) == 2, "a word holds whole symbols");
+    static_assert(sizeof(Sym) == 1 || sizeof(Sym) == 2 || sizeof(Sym) == 4, "a word holds whole symbols");
     const uintptr_t beg = (uintptr_t)T, end = (uintptr_t)(T + n);
     for (int64_t off = from; off < limit; off += W * G) {
         const int64_t o = off + W * gl;
@@ -94,7 +108,7 @@ __device__ __forceinline__ int64_t match_group_lcp(const Sym *__restrict__ T, in
             tw = match_word((uintptr_t)(T + p + o), beg, end);
             qw = match_lds_word(s_w, wb + (uint32_t)sizeof(Sym) * (uint32_t)o);
             const int64_t v = limit - o;                           // symbols left: the tail of a word is masked in symbols
-            d = (tw ^ qw) & (v >= W ? 0xffffffffu : ((1u << (8u * (uint32_t)sizeof(Sym) * (uint32_t)v)) - 1u));
+            d = (tw ^ qw) & (v >= W ? 0xffffffffu : match_tail_mask<Sym>(v));
         }
         *symbols += W * G;
         const uint32_t gm = (uint32_t)(__ballot(d != 0) >> gshift) & ((1u << G) - 1u);

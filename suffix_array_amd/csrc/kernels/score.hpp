@@ -3,8 +3,8 @@
 // kernels/ngram.hpp, run backwards from every position), its range, and the sub-range of the context followed by Q[j].
 // Part of the MI355X-native suffix-array engine (gfx950 / CDNA4, wave64).
 //
-// Every kernel is a template over Sym (kernels/sym.hpp): uint8_t bytes for the byte index, uint16_t tokens for the token index
-// (DESIGN.md section 24).  Lengths, offsets, ge, max_len and q_off count symbols; a byte address is sizeof(Sym) times as far.
+// Every kernel is a template over Sym (kernels/sym.hpp): uint8_t bytes for the byte index, uint16_t and uint32_t tokens for the
+// token indexes (DESIGN.md sections 24 and 25).  Lengths, offsets, ge, max_len and q_off count symbols; a byte address is sizeof(Sym) times as far.
 // T has n symbols, SA n + 1 slots; Q has m symbols in documents q_off[0 .. ndocs] (nullptr: one document).  For position j of the
 // document that starts at `start`: cap = min(j - start, max_len), S[j] = the largest s in 0 .. cap whose range has at least
 // min_count slots.  The count never grows with s: the length is found by galloping (s = 1, 2, 4, ... clamped to cap, until a
@@ -39,6 +39,9 @@ enum { SC_W_LONG = 0, SC_W_GROUP_SEARCHES, SC_W_LONG_SEARCHES, SC_W_LOOKUPS, SC_
 // dynamic LDS of k_score_tile: the aligned words that cover ge + SCORE_TILE symbols at any alignment, two more for match_lds_word
 template <typename Sym>
 __host__ __device__ inline int score_stage_words(int ge) { return (3 + (int)sizeof(Sym) * (ge + SCORE_TILE) + 3) / 4 + 2; }
+
+// the bits of a staged word that are the symbol at its start: the whole word for a 4-byte symbol
+template <typename Sym> constexpr uint32_t score_sym_mask() { return sizeof(Sym) == 4 ? 0xffffffffu : (1u << (8 * (sizeof(Sym) & 3))) - 1u; }
 
 // The document of position j < m: *next = the first entry of q_off above j (m where there is none), returns the entry before
 // it, the document's start.  Whatever q_off holds, 0 <= start <= j.
@@ -203,7 +206,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_score_tile(
                 is_long = true;                                                   // ge symbols are good and the document has more
             } else {
                 while (bad - good > 1) probe(good + (bad - good) / 2);
-                const int sym = (int)(match_lds_word(s_w, at) & (uint32_t)(sym_end<Sym>() - 1));
+                const int sym = (int)(match_lds_word(s_w, at) & score_sym_mask<Sym>());
                 uint32_t pr = 0;
                 zero += score_finish(T, SA, n, j, good, lo, hi, sym, gshift, (gl & 1) != 0, out, &pr);
                 if (gl < 2) lookups += pr;

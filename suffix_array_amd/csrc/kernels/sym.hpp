@@ -1,5 +1,5 @@
 // kernels/sym.hpp -- the symbol-generic core of every query over a suffix array (DESIGN.md sections 8f, 11, 21, 23): a text is an
-// array of Sym (uint8_t bytes or uint16_t tokens), and the comparison of a suffix with a pattern, the match range by two lower
+// array of Sym (uint8_t bytes, uint16_t tokens, or token ids below 2^24 in uint32_t), and the comparison of a suffix with a pattern, the match range by two lower
 // bounds and the probe of the symbol behind a context are written once over Sym.  Every function is executed by a whole wave
 // (gfx950, wave64); an SA entry is added to its offset in 64 bits and checked against n before T is read through it.
 #pragma once
@@ -7,11 +7,18 @@
 
 namespace sa {
 
+// the supported symbol types; a uint32_t text holds ids below 2^24 (its owner checks that on the device,
+// and every pattern on the host), so a symbol and the sentinel behind the alphabet fit an int
+template <typename Sym> constexpr bool sym_supported()
+{
+    return std::is_same<Sym, uint8_t>::value || std::is_same<Sym, uint16_t>::value || std::is_same<Sym, uint32_t>::value;
+}
+
 // the "symbol" of a slot whose suffix ends at the context: sorts behind every symbol (NG_END, TK_END)
 template <typename Sym> constexpr int sym_end()
 {
-    static_assert(sizeof(Sym) <= 2, "a 32-bit alphabet needs a sentinel wider than int");
-    return 1 << (8 * sizeof(Sym));
+    static_assert(sym_supported<Sym>(), "bytes, 16-bit tokens, or token ids below 2^24 in 32 bits");
+    return sizeof(Sym) == 4 ? 1 << 24 : 1 << (8 * sizeof(Sym));
 }
 
 struct SuffixCmp { int ord; uint32_t lcp; };   // ord: -1 suffix < pattern, 0 equal, +1 suffix > pattern
@@ -20,7 +27,7 @@ struct NgRange { uint32_t lo, hi; };
 // Rust slice ordering of s[p..] against pat (lexicographic, a proper prefix is smaller) and their lcp, 64 symbols a step: lane l
 // compares symbol c + l of both, a ballot finds the first difference.  From symbol c0 on: the caller knows that they agree on
 // their first c0 symbols.  *symbols grows by the symbols of every chunk loaded.  Reads only T[p + c0 .. min(n, p + plen)) and
-// pat[c0 .. plen).
+// pat[c0 .. plen).  The symbols travel through the shuffle as int: every supported symbol is below 2^24 (sym_end).
 template <typename Sym>
 __device__ __forceinline__ SuffixCmp wave_compare_from(const Sym *__restrict__ T, int64_t n, int64_t p, const Sym *__restrict__ pat,
                                                        int64_t plen, int64_t c0, int64_t *symbols)
@@ -68,7 +75,8 @@ __device__ __forceinline__ NgRange plain_range(const Sym *__restrict__ T, const 
     return r;
 }
 
-// the symbol behind the context of p symbols of slot i < n + 1, sym_end where the suffix ends at or before it
+// the symbol behind the context of p symbols of slot i < n + 1, sym_end where the suffix ends at or before it ((int) keeps the
+// value: ids are below 2^24)
 template <typename Sym>
 __device__ __forceinline__ int next_symbol(const Sym *__restrict__ T, const uint32_t *__restrict__ SA, int64_t n, int64_t p, uint32_t i)
 {

@@ -1,10 +1,12 @@
-// kernels/tokens.hpp -- texts over a 16-bit token alphabet.  Construction: the big-endian byte image B
-// of the token text (k_tok_be_image), the byte builder on B, then an order-preserving compaction that keeps the even entries of
-// B's suffix array, halved (k_tok_compact_count, one scan, k_tok_compact_scatter) -- big-endian bytes compare like the tokens and
-// two even-offset suffixes of B have even lengths, so their byte order is the token order.  Queries over a resident token index:
-// range search (k_tok_search), back-off (k_infgram_suffix<uint16_t>) and the counts of the token that follows a context (k_tok_next),
-// the token forms of kernels/ngram.hpp.  One wave per query, no atomics on the answers.  gfx950, wave64.  Every slot read lies
-// in [0, n + 1) and every SA entry is checked against n before T is read through it, whatever the arrays hold.
+// kernels/tokens.hpp -- texts over a token alphabet: 16-bit tokens and token ids below 2^24 in 32-bit
+// storage (section 25).  Construction: the big-endian byte image B of the token text, STRIDE = 2 or 3 bytes a token
+// (k_tok_be_image, k_tok_be_image3), the byte builder on B, then an order-preserving compaction that keeps the entries of B's
+// suffix array that are divisible by STRIDE, divided by it (k_tok_compact_count, one scan, k_tok_compact_scatter) -- big-endian
+// bytes compare like the tokens and two suffixes of B at offsets divisible by STRIDE have lengths divisible by STRIDE, so their
+// byte order is the token order.  Queries over a resident token index, written once over Sym = uint16_t / uint32_t:
+// range search (k_tok_search), back-off (k_infgram_suffix<uint16_t>, <uint32_t>) and the counts of the token that follows a
+// context (k_tok_next), the token forms of kernels/ngram.hpp.  One wave per query, no atomics on the answers.  gfx950, wave64.
+// Every slot read lies in [0, n + 1) and every SA entry is checked against n before T is read through it, whatever the arrays hold.
 #pragma once
 #include "ngram.hpp"
 
@@ -18,7 +20,15 @@ constexpr int TK_WAVE_ITEMS = TK_LOADS * TK_CHUNK;          // consecutive entri
 constexpr int TK_TILE = TK_WAVES * TK_WAVE_ITEMS;           // 2048 entries of the byte-level array: one count
 constexpr int TK_SPAN = 4;                                  // consecutive tiles a workgroup takes in one trip
 constexpr int TK_IMAGE_ITEMS = 8;                           // tokens per work-item of the image pass: one 16-byte load and store
+constexpr int TK_IMAGE3_ITEMS = 16;                         // tokens per work-item of the 3-byte image pass: four 16-byte loads, three stores
 constexpr int TK_END = 65536;                               // the "token" of a slot whose suffix ends at the context: sym_end<uint16_t>()
+constexpr uint32_t TK_LIMIT_U32 = 1u << 24;                 // SA_AMD_TOKEN_LIMIT_U32: the ids of a 32-bit token text lie below it (= sym_end<uint32_t>())
+
+// the bytes a token of Sym has in the image: the stride of the kept entries of the byte-level array
+template <typename Sym> struct TokStrideOf;
+template <> struct TokStrideOf<uint16_t> { static constexpr int value = 2; };
+template <> struct TokStrideOf<uint32_t> { static constexpr int value = 3; };
+template <int STRIDE> struct TokStride { };                 // a kernel argument: the compaction's stride is deduced from it
 
 // B[2 i] = T[i] >> 8, B[2 i + 1] = T[i] & 255 for i < n: the two bytes of every token swapped.  T and B are 16-byte aligned and
 // their slabs end at or behind the 16-byte group of the last token; the bytes of B behind 2 n are written as zeros.
@@ -40,9 +50,68 @@ __global__ __launch_bounds__(TK_THREADS) void k_tok_be_image(const uint16_t *__r
     }
 }
 
+// The 3-byte image: B[3 i] = T[i] >> 16, B[3 i + 1] = (T[i] >> 8) & 255, B[3 i + 2] = T[i] & 255 for i < n.  A work-item takes 16
+// tokens: four 16-byte loads (one that starts at or behind token n is not made), twelve words, three aligned 16-byte stores (one
+// that starts at or behind byte 3 n is not made); the bytes of B behind 3 n in the last store are zeros.  T and B are 16-byte
+// aligned with 16 bytes of slack behind the tokens / the image.  flags[0] |= 1 where a token is not below 2^24 (its low 24 bits
+// go to the image): one ballot and one atomic per wave, as k_tok_sa_range.
+__global__ __launch_bounds__(TK_THREADS) void k_tok_be_image3(const uint32_t *__restrict__ T, uint8_t *__restrict__ B, int64_t n,
+                                                             uint32_t *__restrict__ flags)
+{
+    const int64_t groups = (n + TK_IMAGE3_ITEMS - 1) / TK_IMAGE3_ITEMS;
+    bool bad = false;
+    for (int64_t g = (int64_t)blockIdx.x * TK_THREADS + threadIdx.x; g < groups; g += (int64_t)gridDim.x * TK_THREADS) {
+        const int64_t first = g * TK_IMAGE3_ITEMS;
+        uint4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            v[k] = first + 4 * k < n ? *reinterpret_cast<const uint4 *>(T + first + 4 * k) : make_uint4(0u, 0u, 0u, 0u);
+        uint32_t w[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            uint32_t t[4] = { v[k].x, v[k].y, v[k].z, v[k].w }, p[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (first + 4 * k + i >= n) t[i] = 0u;                     // (slack behind the text: any bytes)
+                bad |= t[i] >= TK_LIMIT_U32;
+                p[i] = __builtin_bswap32(t[i]) >> 8;                       // the token's three bytes, the top one lowest
+            }
+            w[3 * k] = p[0] | (p[1] << 24);
+            w[3 * k + 1] = (p[1] >> 8) | (p[2] << 16);
+            w[3 * k + 2] = (p[2] >> 16) | (p[3] << 8);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (3 * first + 16 * k < 3 * n)
+                *reinterpret_cast<uint4 *>(B + 3 * first + 16 * k) = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+    }
+    if (__ballot(bad) && lane_id() == 0) atomicOr(flags, 1u);
+}
+
+// flags[0] |= 1 where a token of T[0 .. n) is not below 2^24: the range pass over a 32-bit token text that is not built from
+__global__ __launch_bounds__(TK_THREADS) void k_tok_id_range(const uint32_t *__restrict__ T, int64_t n, uint32_t *__restrict__ flags)
+{
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * TK_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * TK_THREADS)
+        bad |= T[i] >= TK_LIMIT_U32;
+    if (__ballot(bad) && lane_id() == 0) atomicOr(flags, 1u);
+}
+
+// Is the entry e of the byte-level array kept, and *q = e / STRIDE where it is.  STRIDE 2: the even entries, halved.  STRIDE 3:
+// 0xAAAAAAAB is the inverse of 3 modulo 2^32, so e = 3 k gives e * 0xAAAAAAAB = k <= 0x55555555 = (2^32 - 1) / 3, and the
+// products of the other residues lie above: one multiply is the test and the quotient.
+template <int STRIDE>
+__device__ __forceinline__ bool tok_kept(uint32_t e, uint32_t *q)
+{
+    static_assert(STRIDE == 2 || STRIDE == 3, "bytes of a token in the image");
+    if constexpr (STRIDE == 2) { *q = e >> 1; return !(e & 1u); }
+    else { *q = e * 0xAAAAAAABu; return *q <= 0x55555555u; }
+}
+
 // The entries [base, base + 4) of the byte-level array that a lane holds after one 16-byte load, and which of them are kept:
-// bit k of the result is set iff base + k < len and the entry is even.  The slab ends at or behind the 16-byte group of the last
-// entry, so the load is in range wherever base < len.
+// bit k of the result is set iff base + k < len and the entry is divisible by STRIDE; e[k] = the entry divided by STRIDE then.
+// The slab ends at or behind the 16-byte group of the last entry, so the load is in range wherever base < len.
+template <int STRIDE>
 __device__ __forceinline__ uint32_t tok_compact_load(const uint32_t *__restrict__ SA2, int64_t len, int64_t base, uint32_t e[4])
 {
     uint32_t keep = 0;
@@ -50,15 +119,16 @@ __device__ __forceinline__ uint32_t tok_compact_load(const uint32_t *__restrict_
         const uint4 v = *reinterpret_cast<const uint4 *>(SA2 + base);
         e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) if (base + k < len && !(e[k] & 1u)) keep |= 1u << k;
+        for (int k = 0; k < 4; ++k) if (tok_kept<STRIDE>(e[k], &e[k]) && base + k < len) keep |= 1u << k;
     }
     return keep;
 }
 
-// cnt[t] = the number of even entries of tile t of SA2[0 .. len); cnt[tiles] = 0 (the scan leaves the number of all kept
+// cnt[t] = the number of kept entries of tile t of SA2[0 .. len); cnt[tiles] = 0 (the scan leaves the number of all kept
 // entries there).  A workgroup takes TK_SPAN tiles a trip, a wave TK_WAVE_ITEMS consecutive entries of each.
+template <int STRIDE>
 __global__ __launch_bounds__(TK_THREADS) void k_tok_compact_count(const uint32_t *__restrict__ SA2, int64_t len, int64_t tiles,
-                                                                 unsigned long long *__restrict__ cnt)
+                                                                 unsigned long long *__restrict__ cnt, TokStride<STRIDE>)
 {
     __shared__ uint32_t s_w[TK_SPAN][TK_WAVES];
     const int l = lane_id(), w = wave_id();
@@ -73,7 +143,7 @@ __global__ __launch_bounds__(TK_THREADS) void k_tok_compact_count(const uint32_t
             for (int c = 0; c < TK_LOADS; ++c) {
                 uint32_t e[4];
                 const int64_t base = tile * TK_TILE + (int64_t)w * TK_WAVE_ITEMS + c * TK_CHUNK + 4 * l;
-                kept += (uint32_t)__popc(tok_compact_load(SA2, len, base, e));
+                kept += (uint32_t)__popc(tok_compact_load<STRIDE>(SA2, len, base, e));
             }
             kept = wave_incl_sum(kept);
             if (l == WAVE - 1) s_w[t][w] = kept;
@@ -89,12 +159,13 @@ __global__ __launch_bounds__(TK_THREADS) void k_tok_compact_count(const uint32_t
     }
 }
 
-// out[off[t] + r] = SA2[i] / 2 for the r-th even entry i of tile t, off the scanned counts: the kept entries in their order.
+// out[off[t] + r] = SA2[i] / STRIDE for the r-th kept entry i of tile t, off the scanned counts: the kept entries in their order.
 // The rank of an entry inside its wave comes from the ballots of the four components of a load and their popcounts below the
 // lane; the waves of a tile meet in LDS.  Exactly off[tiles] <= out_len entries are written.
+template <int STRIDE>
 __global__ __launch_bounds__(TK_THREADS) void k_tok_compact_scatter(const uint32_t *__restrict__ SA2, int64_t len, int64_t tiles,
                                                                    const unsigned long long *__restrict__ off, uint32_t *__restrict__ out,
-                                                                   int64_t out_len)
+                                                                   int64_t out_len, TokStride<STRIDE>)
 {
     __shared__ uint32_t s_w[TK_WAVES];
     const int l = lane_id(), w = wave_id();
@@ -107,7 +178,7 @@ __global__ __launch_bounds__(TK_THREADS) void k_tok_compact_scatter(const uint32
             uint32_t e[TK_LOADS][4], keep[TK_LOADS], rank[TK_LOADS], total = 0;
 #pragma unroll
             for (int c = 0; c < TK_LOADS; ++c)
-                keep[c] = tok_compact_load(SA2, len, tile * TK_TILE + (int64_t)w * TK_WAVE_ITEMS + c * TK_CHUNK + 4 * l, e[c]);
+                keep[c] = tok_compact_load<STRIDE>(SA2, len, tile * TK_TILE + (int64_t)w * TK_WAVE_ITEMS + c * TK_CHUNK + 4 * l, e[c]);
 #pragma unroll
             for (int c = 0; c < TK_LOADS; ++c) {
                 uint32_t before = 0, all = 0;
@@ -132,7 +203,7 @@ __global__ __launch_bounds__(TK_THREADS) void k_tok_compact_scatter(const uint32
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     if (!((keep[c] >> k) & 1u)) continue;
-                    if ((int64_t)at < out_len) out[at] = e[c][k] >> 1;
+                    if ((int64_t)at < out_len) out[at] = e[c][k];
                     ++at;
                 }
             }
@@ -151,8 +222,9 @@ __global__ __launch_bounds__(TK_THREADS) void k_tok_sa_range(const uint32_t *__r
 
 // Range search of `count` patterns, one wave each (a wave takes every waves-th pattern): plain_range (kernels/sym.hpp) over the
 // n + 1 slots, no bucket table and no LCP table; pat_off in tokens.  Every output may be nullptr.
+template <typename Sym>
 __global__ __launch_bounds__(NG_THREADS) void k_tok_search(
-    const uint16_t *__restrict__ T, const uint32_t *__restrict__ SA, int64_t n, const uint16_t *__restrict__ pat_data,
+    const Sym *__restrict__ T, const uint32_t *__restrict__ SA, int64_t n, const Sym *__restrict__ pat_data,
     const int64_t *__restrict__ pat_off, int32_t count, uint8_t *__restrict__ contains, uint32_t *__restrict__ range_lo,
     uint32_t *__restrict__ range_hi)
 {
@@ -169,9 +241,10 @@ __global__ __launch_bounds__(NG_THREADS) void k_tok_search(
 }
 
 // one entry of a listing: the token and count of the run with rank `r` behind the listing's offset `o`
-__device__ __forceinline__ void tok_emit_token(uint16_t *__restrict__ toks, unsigned long long o, uint32_t r, unsigned long long capacity, int tok)
+template <typename Sym>
+__device__ __forceinline__ void tok_emit_token(Sym *__restrict__ toks, unsigned long long o, uint32_t r, unsigned long long capacity, int tok)
 {
-    if (toks && o + r < capacity) toks[o + r] = (uint16_t)tok;
+    if (toks && o + r < capacity) toks[o + r] = (Sym)tok;
 }
 __device__ __forceinline__ void tok_emit_count(uint32_t *__restrict__ counts, unsigned long long o, uint32_t r, unsigned long long capacity, uint32_t c)
 {
@@ -181,7 +254,7 @@ __device__ __forceinline__ void tok_emit_count(uint32_t *__restrict__ counts, un
 // Continuations of query q over its window (ng_window of kernels/ngram.hpp: s0, cnt, p, at_end).  Inside the range the slots
 // are sorted by the token behind the context, so the listing is the list of the runs of equal tokens: a run STARTS at place i
 // (relative to s0) where the token differs from the one at i - 1, and its count is the next start (or cnt) less its own.  A run
-// of TK_END (only an array that is no suffix array has one behind s0) ends the run before it and is not listed.  There is no
+// of TK_END = sym_end<Sym>() (only an array that is no suffix array has one behind s0) ends the run before it and is not listed.  There is no
 // table per query: a run's rank in the listing is the number of listed starts before it.
 //   cnt <= stream_cap: the range is read once, NG_LOADS * 64 slots a trip; a lane compares its token with its left neighbour's
 //     (a shuffle; the last token of a trip is carried into the next).  The ranks come from the ballot of the listed starts, the
@@ -194,13 +267,14 @@ __device__ __forceinline__ void tok_emit_count(uint32_t *__restrict__ counts, un
 // EMIT = false: nnz[q] = the number of listed runs (nnz[count] is the host's), at_end[q], and the counters -- one atomic per
 // wave each behind all of its queries.  EMIT = true: nnz holds the scanned offsets; the (token, count) pairs go to toks /
 // counts (either may be nullptr) in ascending token order from nnz[q] on, while the offset is below `capacity`.
-template <bool EMIT>
+template <bool EMIT, typename Sym>
 __global__ __launch_bounds__(NG_THREADS) void k_tok_next(
-    const uint16_t *__restrict__ T, const uint32_t *__restrict__ SA, int64_t n, const uint32_t *__restrict__ range_lo,
+    const Sym *__restrict__ T, const uint32_t *__restrict__ SA, int64_t n, const uint32_t *__restrict__ range_lo,
     const uint32_t *__restrict__ range_hi, const uint32_t *__restrict__ depth, const int64_t *__restrict__ pat_off, int32_t count,
-    uint32_t stream_cap, uint8_t *__restrict__ at_end, unsigned long long *__restrict__ nnz, uint16_t *__restrict__ toks,
+    uint32_t stream_cap, uint8_t *__restrict__ at_end, unsigned long long *__restrict__ nnz, Sym *__restrict__ toks,
     uint32_t *__restrict__ counts, unsigned long long capacity, unsigned long long *__restrict__ ctl)
 {
+    constexpr int TK_END = sym_end<Sym>();
     const int l = lane_id();
     const uint64_t below = (1ull << l) - 1ull;
     const int64_t waves = (int64_t)gridDim.x * NG_WAVES;
@@ -285,5 +359,6 @@ __global__ __launch_bounds__(NG_THREADS) void k_tok_next(
 }
 
 static_assert(TK_END == sym_end<uint16_t>(), "TK_END is the token alphabet's sentinel");
+static_assert((int)TK_LIMIT_U32 == sym_end<uint32_t>(), "the ids of a 32-bit token text lie below their sentinel");
 
 }  // namespace sa

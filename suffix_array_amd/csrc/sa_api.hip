@@ -887,6 +887,87 @@ SA_EXPORT void sa_amd_last_tok_score_stats(sa_amd_tok_score_stats *out)
     if (out) *out = sa::g_last_tok_score_stats;
 }
 
+// ---- 32-bit token texts, ids below 2^24: the same routes at Sym = uint32_t.  The statistics are the
+//      calling thread's sa_amd_last_tok_stats / sa_amd_last_tok_score_stats, whichever width its latest token call had ----
+
+SA_EXPORT int32_t sa_amd_max_tokens_u32(void) { return sa::TOK_MAX_TOKENS_U32; }
+
+SA_EXPORT int32_t sa_amd_saca_u32(const uint32_t *T, uint32_t *SA, int32_t n)
+{
+    if (n < 0 || n > sa::TOK_MAX_TOKENS_U32 || !SA || (n > 0 && !T)) return SA_AMD_EINVAL;
+    if (n == 0) { SA[0] = 0; return SA_AMD_OK; }
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
+    SA_ABI_GUARD_BEGIN
+    return sa::tok_saca_host(T, SA, n);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_create(const uint32_t *T, int32_t n, const uint32_t *SA, sa_amd_tok32_index **out)
+{
+    if (!out || n < 0 || n > sa::TOK_MAX_TOKENS_U32 || (n > 0 && !T)) return SA_AMD_EINVAL;
+    *out = nullptr;
+    if (sa::device_count() <= 0) return SA_AMD_ENODEVICE;
+    SA_ABI_GUARD_BEGIN
+    return sa::tok_index_create(T, n, SA, out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_tok32_index_destroy(sa_amd_tok32_index *ix)  // (frees and deletes: nothing that throws, no change of device)
+{
+    delete ix;
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_sa(const sa_amd_tok32_index *ix, uint32_t *SA_out)
+{
+    if (!ix || !SA_out) return SA_AMD_EINVAL;
+    return sa::tok_index_sa(*ix, SA_out);
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_search(const sa_amd_tok32_index *ix, const uint32_t *pat_data, const int64_t *pat_off, int32_t count,
+                                            uint8_t *contains, uint32_t *range_lo, uint32_t *range_hi)
+{
+    SA_ABI_GUARD_BEGIN
+    if (const int32_t rc = sa::tok_query_args(ix, pat_data, pat_off, count)) return rc;
+    return sa::tok_search(*ix, pat_data, pat_off, count, contains, range_lo, range_hi);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_next_tokens(const sa_amd_tok32_index *ix, const uint32_t *pat_data, const int64_t *pat_off, int32_t count,
+                                                 uint32_t *range_lo, uint32_t *range_hi, uint8_t *at_end, int64_t *list_off, uint32_t *tokens,
+                                                 uint32_t *counts, int64_t capacity, int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    if (capacity < 0) return SA_AMD_EINVAL;
+    if (const int32_t rc = sa::tok_query_args(ix, pat_data, pat_off, count)) return rc;
+    return sa::tok_query(*ix, pat_data, pat_off, count, false, 1, 0, nullptr, range_lo, range_hi, at_end, list_off, tokens, counts, capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_infgram(const sa_amd_tok32_index *ix, const uint32_t *pat_data, const int64_t *pat_off, int32_t count,
+                                             int32_t min_count, int32_t max_len, uint32_t *suffix_len, uint32_t *range_lo, uint32_t *range_hi,
+                                             uint8_t *at_end, int64_t *list_off, uint32_t *tokens, uint32_t *counts, int64_t capacity,
+                                             int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    if (capacity < 0 || min_count < 1) return SA_AMD_EINVAL;
+    if (const int32_t rc = sa::tok_query_args(ix, pat_data, pat_off, count)) return rc;
+    return sa::tok_query(*ix, pat_data, pat_off, count, true, min_count, max_len, suffix_len, range_lo, range_hi, at_end, list_off, tokens, counts,
+                         capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_infgram_score(const sa_amd_tok32_index *ix, const uint32_t *Q, int64_t m, const int64_t *q_off, int64_t ndocs,
+                                                   int32_t min_count, int32_t max_len, uint32_t *S, uint32_t *LO, uint32_t *HI, uint8_t *AT_END,
+                                                   uint32_t *NLO, uint32_t *NHI)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::score_args_valid(m, q_off, ndocs, min_count, max_len) || (m > 0 && (!Q || ((uintptr_t)Q & 3u)))) return SA_AMD_EINVAL;
+    if (!sa::tok_ids_valid(Q, m)) return SA_AMD_ERANGE;
+    return sa::score_host(*ix, Q, m, q_off, ndocs, min_count, max_len, S, LO, HI, AT_END, NLO, NHI, sa::g_last_tok_score_stats,
+                          &sa_amd_tok_score_stats::compared_tokens);
+    SA_ABI_GUARD_END(0)
+}
+
 // ---- packed format (reference src/packed_sa.rs); byte layout: u32 magic "SA4x" LE, u32 length, u64 data length
 //      (bincode's Vec<u8> prefix), data ----
 
