@@ -71,7 +71,7 @@ static Workspace carve(void *base, int64_t n, size_t cap = ~(size_t)0, void *bas
     w.tcnt = (uint32_t *)take(rr_tiles * 4);
     w.thead = (uint32_t *)take(rr_tiles * 4);
     w.tnext = (uint32_t *)take(rr_tiles * 4);
-    w.surv_cnt = (uint32_t *)take(rr_tiles * 4);          // (not tcnt: refine_list uses that one for its own compaction)
+    w.surv_cnt = (uint32_t *)take(rr_tiles * 4);          // (not tcnt: a refinement round uses that one for its own compaction)
     w.ft_cnt = (uint32_t *)take(ft_tiles * 4);
     w.ft_head = (uint32_t *)take(ft_tiles * 4);
     w.bk_start = (uint32_t *)take(((size_t)BK_BUCKETS_MAX + 1) * 4);
@@ -202,60 +202,9 @@ static int scatter_binned(const SortScratch &ss, uint32_t *isa, uint32_t *pk, ui
     return SA_AMD_OK;
 }
 
-struct Refined {
-    const uint64_t *keys; const uint32_t *vals; uint32_t *vnext;
-    int64_t m_global;                      // members ordered by the global sort
-    const uint8_t *status = nullptr;       // != nullptr: the round's status bytes (RS_*, kernels/common.hpp) -- the re-rank reads the group starts from them, `keys` holds true keys at RS_KEYED places only
-};
-
-// Read-backs of a refinement round (DeviceBuild::finish_round).  A round used to block twice: once in the middle for the number
-// of members the local pass could not order (they go through the global sort before the re-rank) and once at its end for the
-// number still tied.  From the second round of a kind on nearly every round has NO such members, so the caller may ask
-// refine_list to DEFER the first question: the local pass and its counting kernels are launched, the count stays on the device
-// (w.total[RC_FLAGGED]) and the re-rank kernels behind it are launched GATED on it -- they do nothing when it is not zero.
-// One read-back at the end of the round then answers both; in the rare round that did have such members the caller calls
-// refine_list again with the words it read (resume_tot), which runs the global sort of those members, and launches the
-// re-rank kernels ungated.
-constexpr int RC_FLAGGED = 16, RC_GROUPS = 8, RC_BIG_LISTED = 12, RC_BIG_ORDERED = 13, RC_WORDS = 17;      // words of w.total
-constexpr int RC_BIG_LISTED_SAVED = 14, RC_BIG_ORDERED_SAVED = 15;     // ... where k_rr_scan_round puts the two big-group counters before it zeroes them for the next round
-constexpr int RC_BIG_CLASS = 17;       // ... and [17], [18]: the lengths of the two lists k_big_classify sorts the listed heads into; zeroed with the two counters
-static_assert(RC_BIG_CLASS == RC_BIG_LISTED + RR_CLEAR_CLASS && RC_BIG_CLASS + 2 <= 64, "k_rr_scan_round zeroes them relative to the big-group counters; w.total has 64 words");
-struct RoundCtl {
-    bool defer = false;                    // in: do not read the local pass's counts back, return right behind its launches
-    const uint32_t *resume_tot = nullptr;  // in: the counts (RC_WORDS words of w.total) of a deferred call that did have flagged members
-    bool skip_big = false;                 // in: no group can be larger than GS_CAP any more: k_group_sort_big is not launched
-    bool counters_clear = false;           // in: the previous round's k_rr_scan_round has zeroed w.total[RC_BIG_LISTED .. +1]
-    bool deferred = false;                 // out: the counts were left on the device
-    int64_t m_flagged = -1;                // out: members the local pass left to the global sort (-1: no local pass ran)
-    int64_t big_listed = -1;               // out: groups listed for k_group_sort_big (-1: not looked for)
-    bool missed = false;                   // out (finish_round): the deferred count was not zero, the global sort ran after all
-};
-
-// The tied list: the m suffixes that still share their rank with a neighbour, in slot order.  A refinement round reads
-// (U, G, V), uses the next buffers as scratch, and the re-rank writes the next list into (Un, Gn, rf.vnext).
-struct TiedList {
-    uint32_t *U = nullptr, *G = nullptr, *V = nullptr;       // per member: its slot in SA, the first slot of its group, the suffix
-    uint32_t *Un = nullptr, *Gn = nullptr;
-    uint64_t *rkA = nullptr, *rkB = nullptr;                 // key buffers of the refinement rounds
-    int64_t m = 0;
-    void advance(const Refined &rf) { std::swap(U, Un); std::swap(G, Gn); V = rf.vnext; }
-    uint32_t *valt(const Workspace &w) const { return V == w.valsA ? w.valsB : w.valsA; }
-    // the sorted initial keys stay where they are (rank look-ups): the rounds take the two key buffers beside them
-    void keys_beside(const Workspace &w, const uint64_t *initial) { rkA = initial == w.keysA ? w.keysB : w.keysA; rkB = w.keysC; }
-};
-
-// The arguments of k_rr_apply (kernels/rerank.hpp) by name, each defaulting to "not used"; DeviceBuild::rr_apply launches it.
-struct RrApply {
-    const uint32_t *V = nullptr, *U = nullptr;               // U == nullptr: element i sits in slot i
-    int64_t m = 0;
-    const uint32_t *tile_cnt = nullptr, *tile_head = nullptr, *tile_total = nullptr;     // nullptr: the workspace's tcnt, thead, total
-    uint32_t *SA = nullptr, *ISA = nullptr, *Uo = nullptr, *Go = nullptr, *Vo = nullptr, n_text = 0;
-    uint32_t *has_isa = nullptr, *pair_v = nullptr, *changed_cnt = nullptr;
-    uint64_t *pair_k = nullptr;
-    const uint32_t *tile_next = nullptr, *gate = nullptr;
-    int g_shift = 0, key_shift = 0, parent_tail = 0, sa_final = 0;
-    const uint8_t *status = nullptr;                         // a round behind a local pass that wrote status bytes (Refined::status)
-};
+}  // namespace sa
+#include "refine_round.hpp"      // a refinement round and what it works on (BuildCore); uses Workspace and scatter_binned above
+namespace sa {
 
 // Gram keys: how many of the sigma^g possible g-grams occur?  A word-structured text uses a small part of them, so a key of
 // dense gram ranks holds more symbols than the base-sigma form, often in fewer digits (C3, sigma = 57: 12 symbols in 7
@@ -330,15 +279,7 @@ struct EarlyDownload {
 // One device-resident build, phase by phase.  The members are what the phases hand to each other; every phase returns an
 // SA_AMD_* status.  The blocking 4-byte read-backs that steer the host (how many suffixes are still tied, how many groups,
 // how many ranks changed) are the read_words calls inside the phases: each one names what it reads.
-struct DeviceBuild {
-    // ---- inputs ----
-    const uint8_t *dT;
-    uint32_t *dSA, *SA;                 // SA = dSA + 1: the n sorted suffixes behind the sentinel slot
-    int64_t n;
-    hipStream_t st;
-    Tuning tn;
-    Workspace w;
-    sa_amd_stats local;
+struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the inputs, the tied list L and the re-rank launchers)
     EarlyDownload *early = nullptr;     // host-pointer callers: the array starts travelling before the last rounds are done
     bool trace = false;
     double trace_t = 0;
@@ -353,8 +294,8 @@ struct DeviceBuild {
     }
     // ---- key geometry and route (geometry_and_probes) ----
     KeyParams P, Ptext;
-    int sigma = 0, key_bits = 0, g_bits = 0, top_shift = 0;
-    bool force_dense = false, text_ok = false, local_ok = false, probe_dense = false;
+    int sigma = 0, key_bits = 0, top_shift = 0;
+    bool force_dense = false, text_ok = false, probe_dense = false;
     // ---- initial order (initial_sort) ----
     SortResult<uint64_t> sr;
     const uint32_t *sorted32 = nullptr; // top-32 stage: the sorted 32-bit keys (no 64-bit sorted array exists)
@@ -362,23 +303,14 @@ struct DeviceBuild {
     bool flat_text = false;             // short text whose byte values are equally frequent: narrower initial keys (geometry_and_probes)
     bool bucket_finished = false;       // ... and k_bucket_sort has already ordered the suffixes tied on those 32 bits by their low key bits
     uint64_t *sorted0 = nullptr;        // the initial keys in SA order (kept for the rank look-ups)
-    // Group-start flags (kernels/common.hpp, OS_HF_*): != nullptr: the last pass of the 64-bit initial sort wrote one flag byte per
-    // slot here instead of the sorted keys, and sr.keys holds true keys only at the ends of that pass's digit runs.  The first
-    // re-rank (group_heads, the rank set-up of the dense route) reads the flags; every other reader of the sorted keys gets them
-    // rebuilt first (rebuild_sorted_keys).  The flags live in w.keysC, which nothing else touches between the last sort pass and
-    // the end of the first k_rr_apply.
-    uint8_t *head_flags = nullptr;
-    bool flags_slab_ok = true;          // w.keysC is device memory (reduced-memory route: it may be the pinned host block -- then the key route is taken)
-    // ---- the tied list and its buffers (from first_round_from_sorted_keys on) ----
-    TiedList L;
+    // ---- the tied list L and its buffers (from first_round_from_sorted_keys on) ----
     int64_t tiles = 0, depth = 0;       // tiles: RR_TILE-element tiles of the whole array (the re-rank steps straight from the initial order)
     uint32_t m32 = 0;
     bool lists_ready = false, finished32 = false, fused64 = false, sparse = false;
     bool isa_tail_ranks = false;        // the rank set-up of the dense route wrote tail ranks (k_rr_apply FTAIL)
-    int s_sym = 0, tkb = 0, key2_bits = 0;
+    int s_sym = 0, tkb = 0;
     bool unary_done = false;            // a text of one byte value: the array was written directly (geometry_and_probes), nothing else runs
-    bool prev_clean = true;             // the last refinement round's local pass ordered every member (optimistic for the first one: a miss costs three empty launches)
-    int deferred_misses = 0;            // rounds that deferred their mid-round read-back and did have members for the global sort (RoundCtl)
+    RoundState rs;                      // what one refinement round leaves for the next
 
     // Early download: called wherever (L.U, L.m) is the current tied list and every slot outside it is final
     int early_maybe_start()
@@ -447,36 +379,6 @@ struct DeviceBuild {
 
     bool flat_rule_applies() const { return n >= 2 && n < tn.top32_probe_min_n && n < ((int64_t)1 << 24) && !tn.no_flat_rule; }
 
-    // ---- the re-rank step: k_rr_count, k_rr_scan (a round: k_rr_scan_round, finish_round), k_rr_apply (kernels/rerank.hpp) ----
-    // One launcher each, over the RR_TILE-element tiles of m elements; tile_cnt / tile_head / total == nullptr: the workspace's.
-    // FLAGS: the groups come from head_flags, not from the keys (the first re-rank behind a flags pass of the initial sort)
-    // (a round: its status bytes, `status`)
-    template <bool FIRST, typename KeyT = uint64_t, bool PARENTS = false, bool FLAGS = false>
-    int rr_count(const KeyT *keys, const uint32_t *U, int64_t m, uint32_t *tile_first = nullptr, int g_shift = 0, const uint32_t *gate = nullptr,
-                 uint32_t *tile_cnt = nullptr, uint32_t *tile_head = nullptr, const uint8_t *status = nullptr)
-    {
-        PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_rr_count<FIRST, KeyT, PARENTS, FLAGS>), dim3(rr_count_grid<FLAGS>(m)), dim3(RR_THREADS), 0, st, keys, U, m,
-                                                    tile_cnt ? tile_cnt : w.tcnt, tile_head ? tile_head : w.thead, 0, tile_first, g_shift, gate,
-                                                    FLAGS ? (status ? status : (const uint8_t *)head_flags) : (const uint8_t *)nullptr));
-        return SA_AMD_OK;
-    }
-    int rr_scan(int64_t m, uint32_t *tile_cnt = nullptr, uint32_t *tile_head = nullptr, uint32_t *total = nullptr)
-    {
-        PROF(KC_RR_SCAN, ceil_div(m, RR_TILE), st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, tile_cnt ? tile_cnt : w.tcnt,
-                                                                      tile_head ? tile_head : w.thead, ceil_div(m, RR_TILE), total ? total : w.total));
-        return SA_AMD_OK;
-    }
-    template <bool FIRST, bool WRITE_SA, int ISA_MODE, typename KeyT = uint64_t, bool FTAIL = false, bool FLAGS = false>
-    int rr_apply(const KeyT *keys, const RrApply &a)
-    {
-        PROF(KC_RR_APPLY, a.m, st, hipLaunchKernelGGL((k_rr_apply<FIRST, WRITE_SA, ISA_MODE, KeyT, FTAIL, FLAGS>), dim3((unsigned)ceil_div(a.m, RR_TILE)), dim3(RR_THREADS), 0, st,
-                                                      keys, a.V, a.U, a.m, a.tile_cnt ? a.tile_cnt : (const uint32_t *)w.tcnt,
-                                                      a.tile_head ? a.tile_head : (const uint32_t *)w.thead, a.SA, a.ISA, a.Uo, a.Go, a.Vo, a.n_text, a.has_isa, a.g_shift,
-                                                      a.pair_k, a.pair_v, a.tile_total ? a.tile_total : (const uint32_t *)w.total, a.key_shift, a.tile_next,
-                                                      a.parent_tail, a.changed_cnt, a.gate, a.sa_final,
-                                                      FLAGS ? (a.status ? a.status : (const uint8_t *)head_flags) : (const uint8_t *)nullptr));
-        return SA_AMD_OK;
-    }
     // the rank set-up of the dense route (ISA_MODE 0: direct ISA stores, 2: ranks for the binned scatter): tail or head ranks,
     // groups from the flags or from the sorted keys
     template <int ISA_MODE>
@@ -507,13 +409,6 @@ struct DeviceBuild {
         a.V = SA; a.m = n; a.SA = SA; a.ISA = w.isa; a.Uo = L.U; a.Go = L.G; a.Vo = L.V; a.n_text = n_text; a.has_isa = has_isa;
         return a;
     }
-    // ... and every re-rank of the tied list: the refined order in, the next list out
-    RrApply round_args(const Refined &rf, RrApply a = RrApply()) const
-    {
-        a.V = rf.vals; a.U = L.U; a.m = L.m; a.SA = SA; a.ISA = w.isa; a.Uo = L.Un; a.Go = L.Gn; a.Vo = rf.vnext; a.n_text = (uint32_t)n;
-        return a;
-    }
-
     // ---- launches that several phases share ----
     // Duplicates among the S sampled keys in w.keysA -> w.total[0] (the caller reads it back): counted in a hash table (4 entries
     // per sample, in the other key buffer) instead of sorting the sample.  zero_bytes: the words of w.total the caller will read.
@@ -546,355 +441,10 @@ struct DeviceBuild {
         return SA_AMD_OK;
     }
 
-    // Three-way split of giant groups around their majority key (kernels/refine.hpp, k_split_*): the keys in L.rkA carry the dense
-    // group index above bit kb, w.ft_cnt the exclusive group-start counts per tile.  *taken = false: the count pass found more
-    // than an eighth of the members off their group's pivot key (or the scratch buffers too small) -- nothing has been changed,
-    // the caller sorts the list with the radix sort.  L.Un / L.Gn: the list's next buffers, free until the re-rank.
-    int split_giant_groups(uint32_t groups, int kb, int sort_bits, Refined *out, bool *taken,
-                           bool starts_ready)            // the gather has written the table of group starts (first array in L.Gn)
-    {
-        const int64_t m = L.m;
-        uint32_t *const Valt = L.valt(w);
-        *taken = false;
-        const int64_t tiles = ceil_div(m, RR_TILE);
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        char *sg = (char *)L.Gn;
-        uint32_t *starts = (uint32_t *)sg;            sg += up(((size_t)groups + 1) * 4);     // list index of every group's first member (+ m)
-        uint32_t *mps = (uint32_t *)sg;               sg += up(((size_t)groups + 1) * 4);     // minority members in front of it (+ their total)
-        uint32_t *Lless = (uint32_t *)sg;             sg += up((size_t)groups * 4);           // minority members of the group below its pivot
-        uint64_t *pivot = (uint64_t *)sg;             sg += up((size_t)groups * 8);
-        const size_t cap = (size_t)m / 8 + 1;                                                  // (minority members when the split is taken)
-        uint32_t *mv = (uint32_t *)sg, *mv_alt = mv + ((cap + 63) & ~(size_t)63);
-        uint64_t *mk = (uint64_t *)L.Un, *mk_alt = mk + ((cap + 31) & ~(size_t)31);
-        const size_t need_g = (size_t)(sg - (char *)L.Gn) + 2 * ((cap + 63) & ~(size_t)63) * 4;
-        const size_t need_u = 2 * ((cap + 31) & ~(size_t)31) * 8;
-        if (need_g > (size_t)n * 4 || need_u > (size_t)n * 4) return SA_AMD_OK;
-        if (!starts_ready)
-            PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_group_starts), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st, L.U, L.G, m,
-                                                        (const uint32_t *)w.ft_cnt, groups, starts));
-        PROF(KC_MISC, groups, st, hipLaunchKernelGGL((k_split_pivots), dim3((unsigned)ceil_div((int64_t)groups, 256)), dim3(256), 0, st,
-                                                 (const uint64_t *)L.rkA, (const uint32_t *)starts, groups, kb, pivot));
-        PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_split_count), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st, (const uint64_t *)L.rkA, m, kb,
-                                                    (const uint64_t *)pivot, w.tcnt));
-        PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles, w.total));
-        uint32_t minor = 0;
-        { const int rcw = read_words(&minor, w.total, 4, st); if (rcw) return rcw; }
-        if ((int64_t)minor * 8 > m) return SA_AMD_OK;
-        *taken = true;
-        out->m_global = m;
-        if (minor == 0) {                                  // every member carries its group's pivot key: the order stands
-            out->keys = L.rkA; out->vals = L.V; out->vnext = Valt;
-            return SA_AMD_OK;
-        }
-        PROF(KC_RR_APPLY, m, st, hipLaunchKernelGGL((k_split_pass<false>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
-                                                    (const uint64_t *)L.rkA, (const uint32_t *)L.V, m, kb, (const uint64_t *)pivot,
-                                                    (const uint32_t *)w.tcnt, (const uint32_t *)starts, groups, mps, (const uint32_t *)w.total,
-                                                    mk, mv, (const uint32_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr));
-        SortResult<uint64_t> s2;
-        const int rc = sort_pairs(SortJob<uint64_t>{ mk, mv, mk_alt, mv_alt, minor, 0, sort_bits }, w.ss, st, tn, &s2, &local);
-        if (rc) return rc;
-        PROF(KC_MISC, groups, st, hipLaunchKernelGGL((k_split_less), dim3((unsigned)ceil_div((int64_t)groups, 256)), dim3(256), 0, st,
-                                                 (const uint64_t *)s2.keys, (const uint32_t *)mps, (const uint64_t *)pivot, groups, kb, Lless));
-        PROF(KC_RR_APPLY, m, st, hipLaunchKernelGGL((k_split_pass<true>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
-                                                    (const uint64_t *)L.rkA, (const uint32_t *)L.V, m, kb, (const uint64_t *)pivot,
-                                                    (const uint32_t *)w.tcnt, (const uint32_t *)starts, groups, mps, (const uint32_t *)w.total,
-                                                    (uint64_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)Lless, L.rkB, Valt));
-        PROF(KC_SCATTER, minor, st, hipLaunchKernelGGL((k_split_place_minor), dim3((unsigned)ceil_div((int64_t)minor, 256)), dim3(256), 0, st,
-                                                       (const uint64_t *)s2.keys, (const uint32_t *)s2.vals, (int64_t)minor, kb,
-                                                       (const uint32_t *)starts, (const uint32_t *)mps, (const uint32_t *)Lless, L.rkB, Valt));
-        out->keys = L.rkB; out->vals = Valt; out->vnext = L.V;
-        return SA_AMD_OK;
-    }
-
-    // Where a dense doubling round keeps its status bytes (RS_*, kernels/common.hpp; nullptr: the round takes the key route).
-    // They cannot share L.Gn with the key form's flags: k_rr_apply writes the next list's group heads there while it reads them.
-    // On the route that starts rank doubling straight from the initial order the rounds' key buffers are w.keysA / w.keysB and
-    // w.keysC is dead -- the initial sort's group-start flags in it are consumed by the rank set-up, the early download takes it
-    // only when the rounds are over (early_finish).  Behind text rounds w.keysC is a key buffer of the rounds (keys_beside),
-    // and on the reduced-memory route it may be pinned host memory (flags_slab_ok): keys then.  One byte per member, m <= n.
-    uint8_t *round_status_slab(const KeySrc &K) const
-    {
-        if (tn.round_flags == 0 || (K.mode != KS_RANK && K.mode != KS_CHASE)) return nullptr;
-        if (!flags_slab_ok || L.rkA == w.keysC || L.rkB == w.keysC) return nullptr;
-        return (uint8_t *)w.keysC;
-    }
-
-    // One refinement round of the tied list with a secondary key taken from the text (KeySrc): afterwards every
-    // group is ordered by (group head << kb) | key2.  Small groups: gather fused with the in-LDS group sort
-    // (k_group_sort); groups no tile owns, or everything when *use_local is off: plain gather + global radix sort.
-    // L.Un / L.Gn: the list's next buffers, free until the re-rank.
-    int refine_list(const KeyParams &Pk, const KeySrc &K_in, bool *use_local, Refined *out, bool retry_local = false,
-                    int *split_rest = nullptr,        // rounds the three-way split sits out after its count pass found no majority
-                    RoundCtl *ctl = nullptr)
-    {
-        const int64_t m = L.m;
-        uint32_t *const Valt = L.valt(w);
-        KeySrc K = K_in;
-        K.net_min = tn.network_min;
-        const bool resume = ctl && ctl->resume_tot;
-        const int64_t tiles = ceil_div(m, RR_TILE);
-        const int kb = K.kb;
-        SortResult<uint64_t> sr;
-        int rc;
-        // sparse look-up: its own kernel, one suffix per thread (a chain of ~60 dependent loads each)
-        auto gather_sparse = [&]() -> int {
-            int64_t gblocks = ceil_div(m, GK_THREADS);
-            if (gblocks > 8192) gblocks = 8192;
-            PROF(KC_GATHER, m, st, hipLaunchKernelGGL((k_gather_textkey<KS_SPARSE>), dim3((unsigned)gblocks), dim3(GK_THREADS), 0, st,
-                                                      (const uint32_t *)L.V, L.G, dT, Pk, m, n, K, L.rkA));
-            return SA_AMD_OK;
-        };
-        // The local pass was given up because (nearly) every member sat in a group no tile can own.  Lists large enough for the
-        // dense group index count their groups anyway: when the average group has come down to about what a tile can own
-        // (a Fibonacci word's groups shrink while the list does not), the local pass is tried again -- in this round
-        bool counted = false;
-        uint32_t groups = 0;
-        if (!*use_local && retry_local && !tn.no_local_sort && m < tn.dense_rekey_min) *use_local = true;     // (small lists do not count their groups)
-        if (!*use_local && retry_local && !tn.no_local_sort && m >= tn.dense_rekey_min) {
-            PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_flag_count<false>), dim3(rr_count_grid<false>(m)), dim3(RR_THREADS), 0, st,
-                                                        (const uint8_t *)nullptr, L.U, L.G, m, w.tcnt, w.ft_cnt));
-            PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.ft_cnt, w.thead, tiles, w.total + 8));
-            { const int rcw = read_words(&groups, w.total + 8, 4, st); if (rcw) return rcw; }
-            counted = true;
-            if ((int64_t)groups * 2 * tn.group_cap >= m) *use_local = true;
-        }
-        const bool had_local_pass = *use_local;            // (then the keys are in L.rkA already when the whole list goes through the global sort after all)
-        uint8_t *const status = round_status_slab(K);      // != nullptr: the local pass writes status bytes there and no keys for the members it orders
-        out->status = nullptr;
-        if (*use_local) {
-            uint8_t *flags = status ? status : (uint8_t *)L.Gn;
-            const unsigned gs_blocks = (unsigned)ceil_div(m, GS_TILE);
-            const int cap = tn.group_cap;                    // largest group ordered in LDS (C3: 1024 beats 512 by 1%)
-            // groups of up to GB_CAP (8 192) members whose keys fit 32 bits: one workgroup each, in LDS (k_group_sort_big), on the list of
-            // their first members that k_group_sort writes (L.Un is free until k_flag_gather); the rest goes through the global sort
-            const bool big_local = !tn.no_big_group_sort && kb <= 32 && m > GS_CAP && !(ctl && ctl->skip_big);
-            uint32_t *bheads = big_local ? L.Un : (uint32_t *)nullptr, *bcount = big_local ? w.total + RC_BIG_LISTED : (uint32_t *)nullptr;
-            if (!resume) {
-            if (!(ctl && ctl->counters_clear)) {
-                HIP_TRY(hipMemsetAsync(w.total + RC_BIG_LISTED, 0, 8, st));           // [12] listed first members, [13] members ordered by k_group_sort_big
-                HIP_TRY(hipMemsetAsync(w.total + RC_BIG_CLASS, 0, 8, st));            // [17], [18] listed groups of either k_group_sort_big instance
-            }
-            if (K.mode == KS_SPARSE && (rc = gather_sparse())) return rc;      // (then the sort on those keys: KS_PRE)
-            if (status && tn.round_flags == 2) {
-                // (diag library: what the round does not write must not be read -- a poisoned entry that is read changes the result)
-                HIP_TRY(hipMemsetAsync(L.rkA, 0xEE, (size_t)m * 8, st));
-                HIP_TRY(hipMemsetAsync(status, 0xFF, (((size_t)m + 7) & ~(size_t)7) + 8, st));
-            }
-#define GS_LAUNCH(M, S) PROF(KC_LOCAL, m, st, hipLaunchKernelGGL((k_group_sort<M, S>), dim3(gs_blocks), dim3(GS_THREADS), 0, st, (const uint32_t *)L.V, L.G, L.U, dT, Pk, m, n, K, \
-                                                            L.rkA, L.V, flags, cap, bheads, bcount))
-            switch (K.mode) {
-            case KS_TEXT: GS_LAUNCH(KS_TEXT, false); break;
-            case KS_LOWKEY: GS_LAUNCH(KS_LOWKEY, false); break;
-            case KS_RANK: if (status) GS_LAUNCH(KS_RANK, true); else GS_LAUNCH(KS_RANK, false); break;
-            case KS_CHASE: if (status) GS_LAUNCH(KS_CHASE, true); else GS_LAUNCH(KS_CHASE, false); break;
-            default: GS_LAUNCH(KS_PRE, false); break;      // (KS_SPARSE: the keys have just been gathered)
-            }
-#undef GS_LAUNCH
-            if (gs_blocks > 1)
-                PROF(KC_LOCAL, 0, st, hipLaunchKernelGGL((k_group_sort_straddle), dim3(gs_blocks - 1), dim3(GX_THREADS), 0, st, L.rkA, L.V, L.G,
-                                                         L.U, m, flags, cap, K, n));
-            if (big_local) {
-                const int lo = cap > GS_CAP ? cap : GS_CAP;
-                // The listed heads are classified once (k_big_classify) into one list per instance, behind the heads in L.Un.  A tile
-                // lists at most two heads -- the group that runs on beyond it and one of more than GS_CAP members inside it --, so
-                // the heads end before hcap and neither list can outgrow it (3 * hcap <= m <= n: m > GS_CAP).
-                const uint32_t hcap = (2u * gs_blocks + 63u) & ~63u;
-                uint32_t *const bsmall = bheads + hcap, *const blarge = bheads + 2 * (size_t)hcap, *const bclass = w.total + RC_BIG_CLASS;
-                if (3 * (int64_t)hcap > n) return SA_AMD_EINTERNAL;
-                PROF(KC_LOCAL, 0, st, hipLaunchKernelGGL((k_big_classify), dim3((unsigned)ceil_div((int64_t)hcap, GC_THREADS)), dim3(GC_THREADS), 0, st, (const uint32_t *)L.G, m, lo,
-                                                         (const uint32_t *)bheads, (const uint32_t *)bcount, bsmall, blarge, hcap, bclass));
-                PROF(KC_LOCAL, 0, st, hipLaunchKernelGGL((k_group_sort_big<256>), dim3((unsigned)(8 * cu_count())), dim3(256), 0, st, L.rkA, L.V, L.G, m, kb, lo,
-                                                         (const uint32_t *)bsmall, (const uint32_t *)bclass, hcap, flags, w.total + RC_BIG_ORDERED));
-                PROF(KC_LOCAL, 0, st, hipLaunchKernelGGL((k_group_sort_big<512>), dim3((unsigned)(4 * cu_count())), dim3(512), 0, st, L.rkA, L.V, L.G, m, kb,
-                                                         lo > GB_CAP_SMALL ? lo : GB_CAP_SMALL, (const uint32_t *)blarge, (const uint32_t *)(bclass + 1), hcap, flags,
-                                                         w.total + RC_BIG_ORDERED));
-            }
-            PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((status ? k_flag_count<true> : k_flag_count<false>), dim3(status ? rr_count_grid<true>(m) : rr_count_grid<false>(m)), dim3(RR_THREADS), 0, st,
-                                                        (const uint8_t *)flags, L.U, L.G, m, w.tcnt, w.ft_cnt));
-            // (flagged members -> w.total[RC_FLAGGED], flagged groups -> w.total[RC_GROUPS]; one launch)
-            PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan_pair), dim3(2), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, w.total + RC_FLAGGED,
-                                                           w.ft_cnt, (uint32_t *)nullptr, w.total + RC_GROUPS, tiles));
-            }
-            if (ctl && ctl->defer && !resume) {
-                // the counts stay on the device: the caller launches the re-rank kernels gated on w.total[RC_FLAGGED] and reads everything at once
-                ctl->deferred = true;
-                out->keys = L.rkA; out->vals = L.V; out->vnext = Valt; out->m_global = 0; out->status = status;
-                return SA_AMD_OK;
-            }
-            uint32_t tot9[RC_WORDS] = { 0 };                      // [RC_FLAGGED] flagged members, [RC_GROUPS] flagged groups, [RC_BIG_ORDERED] members k_group_sort_big ordered
-            if (resume) memcpy(tot9, ctl->resume_tot, sizeof(tot9));
-            else {
-                const int rcw = read_words(tot9, w.total, sizeof(tot9), st); if (rcw) return rcw;
-                }
-            const int64_t m_big = tot9[RC_FLAGGED], m_big_local = tot9[RC_BIG_ORDERED];
-            if (ctl) { ctl->m_flagged = m_big; ctl->big_listed = big_local ? (int64_t)tot9[RC_BIG_LISTED] : -1; }
-            // the flagged members are sorted in the first `half` entries of L.rkB / Valt with the second half as the alternate
-            // buffers: half is even (16-byte aligned 8-byte keys) and half + m_big never exceeds the n entries the slabs hold
-            const size_t half = ((size_t)n / 2) & ~(size_t)1;
-            if ((size_t)m_big <= half && half + (size_t)m_big <= (size_t)n) {
-                if (m_big > 0) {
-                    // groups no tile owns: global sort of (index of the group among them, key2), then back to their list positions
-                    // (a text that is one long run has ONE such group: no index bits at all, four passes instead of eight)
-                    const int idx_bits = bit_length((uint64_t)(tot9[RC_GROUPS] > 0 ? tot9[RC_GROUPS] - 1 : 0));
-                    PROF(KC_RR_APPLY, m, st, hipLaunchKernelGGL((status ? k_flag_gather<true> : k_flag_gather<false>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st,
-                                                                (const uint8_t *)flags, (const uint64_t *)L.rkA, (const uint32_t *)L.V, L.U, L.G, m,
-                                                                (const uint32_t *)w.tcnt, (const uint32_t *)w.ft_cnt, kb, L.rkB, Valt, L.Un));
-                    SortJob<uint64_t> big{ L.rkB, Valt, L.rkB + half, Valt + half, m_big, 0, kb + idx_bits };
-                    big.may_skip = true;
-                    rc = sort_pairs(big, w.ss, st, tn, &sr, &local);
-                    if (rc) return rc;
-                    PROF(KC_SCATTER, m_big, st, hipLaunchKernelGGL((k_scatter_back), dim3((unsigned)ceil_div(m_big, 256)), dim3(256), 0, st,
-                                                                   (const uint64_t *)sr.keys, (const uint32_t *)sr.vals,
-                                                                   (const uint32_t *)L.Un, L.G, kb, m_big, L.rkA, L.V));
-                }
-                out->keys = L.rkA; out->vals = L.V; out->vnext = Valt; out->m_global = m_big + m_big_local;      // (neither kind has been chased)
-                out->status = status;
-                local.locally_sorted += m - m_big;
-                if (m_big * 2 > m) *use_local = false;           // mostly large groups: not worth another local pass
-                return SA_AMD_OK;
-            }
-            if (m_big * 10 >= m * 9) *use_local = false;     // (nearly) the whole list sits in groups no tile can own (runs, periodic texts): the next rounds skip the local pass
-            if (status) {
-                // The global sort below wants a key for EVERY member and the places the local pass owned have none: the pass runs again
-                // in its key form for those places alone (k_group_sort REFILL), on the order it left.  It changes nothing in that
-                // order and writes the keys it would have written the first time -- after a chase the places of the final
-                // subgroups, so no subgroups merge and the round's tied count is what the key route's is.  The keys of every
-                // other place are where the first launch, k_group_sort_straddle and k_group_sort_big left them.  A tile without an
-                // owned place -- all of them on a run or a periodic text, which is what comes here -- returns behind 2 KiB of bytes.
-#define GS_REFILL(M) PROF(KC_LOCAL, m, st, hipLaunchKernelGGL((k_group_sort<M, false, true>), dim3(gs_blocks), dim3(GS_THREADS), 0, st, (const uint32_t *)L.V, L.G, L.U, dT, Pk, m, n, K, \
-                                                            L.rkA, L.V, status, cap, (uint32_t *)nullptr, (uint32_t *)nullptr))
-                if (K.mode == KS_CHASE) GS_REFILL(KS_CHASE); else GS_REFILL(KS_RANK);
-#undef GS_REFILL
-            }
-        }
-        // the whole list through the global sort.  Large lists are keyed by (index of the group in the list, key2) instead of
-        // (28-bit slot of the group head, key2) when that saves radix passes: count the group heads first, then gather the keys in
-        // that form (k_gather_keyed) or re-key the ones the local pass left (k_rekey_dense).  The head slots are not put back
-        // after the sort: the re-rank kernels only compare neighbouring keys.
-        int sort_bits = kb + g_bits;
-        bool rekeyed = false;
-        if (m >= tn.dense_rekey_min) {
-            if (!counted || had_local_pass) {              // (the local pass has used the count arrays for its own compaction)
-                PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_flag_count<false>), dim3(rr_count_grid<false>(m)), dim3(RR_THREADS), 0, st,
-                                                            (const uint8_t *)nullptr, L.U, L.G, m, w.tcnt, w.ft_cnt));
-                PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.ft_cnt, w.thead, tiles, w.total + 8));
-                { const int rcw = read_words(&groups, w.total + 8, 4, st); if (rcw) return rcw; }
-                }
-            const int idx_bits = bit_length((uint64_t)(groups > 0 ? groups - 1 : 0));
-            if (ceil_div(kb + idx_bits, RADIX_BITS) < ceil_div(kb + g_bits, RADIX_BITS)) {
-                sort_bits = kb + idx_bits;
-                rekeyed = true;
-            }
-        }
-        const bool split_wanted = rekeyed && !tn.no_split && m >= tn.split_min && groups > 0 && (int64_t)groups * tn.split_group_min <= m &&
-                                  !(split_rest && *split_rest > 0);
-        bool starts_ready = false;
-        if (had_local_pass) {
-            if (rekeyed)
-                PROF(KC_RR_APPLY, m, st, hipLaunchKernelGGL((k_rekey_dense), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st, L.rkA, L.U, L.G, m,
-                                                            (const uint32_t *)w.ft_cnt, kb));
-        } else if (K.mode == KS_SPARSE) {
-            if ((rc = gather_sparse())) return rc;
-            if (rekeyed)
-                PROF(KC_RR_APPLY, m, st, hipLaunchKernelGGL((k_rekey_dense), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st, L.rkA, L.U, L.G, m,
-                                                            (const uint32_t *)w.ft_cnt, kb));
-        } else {
-            const uint32_t *th = rekeyed ? (const uint32_t *)w.ft_cnt : (const uint32_t *)nullptr;
-            // (when the three-way split may follow, the gather also writes its table of group starts: the first array in L.Gn)
-            uint32_t *gs = split_wanted ? L.Gn : (uint32_t *)nullptr;
-            starts_ready = gs != nullptr;
-#define GK_LAUNCH(M) PROF(KC_GATHER, m, st, hipLaunchKernelGGL((k_gather_keyed<M>), dim3((unsigned)tiles), dim3(RR_THREADS), 0, st, (const uint32_t *)L.V, L.U, L.G, dT, Pk, m, n, K, \
-                                                              th, L.rkA, gs, groups))
-            switch (K.mode) {
-            case KS_TEXT: GK_LAUNCH(KS_TEXT); break;
-            case KS_LOWKEY: GK_LAUNCH(KS_LOWKEY); break;
-            default: GK_LAUNCH(KS_RANK); break;
-            }
-#undef GK_LAUNCH
-        }
-        // Giant groups (runs, periodic texts, long repeats): all but a few members of a group carry the same key, so the few
-        // are pulled out and sorted on their own and the rest only shifts (split_giant_groups) -- if its count pass finds that
-        // they are few indeed; otherwise the radix sort below.
-        if (split_rest && *split_rest > 0) --*split_rest;
-        else if (split_wanted) {
-            bool taken = false;
-            rc = split_giant_groups(groups, kb, sort_bits, out, &taken, starts_ready);
-            if (rc || taken) return rc;
-            if (split_rest) *split_rest = 3;              // (a Fibonacci word's groups fall into parts of similar size round after round)
-        }
-        SortJob<uint64_t> whole{ L.rkA, L.V, L.rkB, Valt, m, 0, sort_bits };
-        whole.may_skip = true;
-        rc = sort_pairs(whole, w.ss, st, tn, &sr, &local);
-        if (rc) return rc;
-        out->keys = sr.keys; out->vals = sr.vals; out->m_global = m;
-        out->vnext = (sr.vals == L.V) ? Valt : L.V;
-        return SA_AMD_OK;
-    }
-
-    // The end of a refinement round, text-keyed or doubling (RoundCtl): re-rank the order refine_list left in rf -- gated while the
-    // round's mid-round count is deferred --, read the round's words back (words[0]: members still tied) and, when the deferred
-    // count was not zero (ctl.missed), resume refine_list with the words just read and re-rank ungated.  ISA_MODE / PARENTS: the
-    // k_rr_apply / k_rr_count instantiation (3: text-keyed, 1: sparse, 0: dense, 2: dense with binned ISA stores -- never
-    // deferred, its pairs are scattered behind the read-back); extra: the k_rr_apply arguments beside round_args() and the gate.
-    template <int ISA_MODE, bool PARENTS>
-    int finish_round(const KeyParams &Pk, const KeySrc &K, RoundCtl &ctl, Refined &rf, const RrApply &extra, uint32_t *words, size_t words_bytes,
-                     bool retry_local, int *split_rest)
-    {
-        int rc;
-        const int64_t tiles_m = ceil_div(L.m, RR_TILE);
-        for (int attempt = 0; ; ++attempt) {
-            const uint32_t *gate = ctl.deferred ? (const uint32_t *)(w.total + RC_FLAGGED) : (const uint32_t *)nullptr;
-            // dense rounds: a group's rank is its last slot + 1 and a parent's last subgroup keeps it (k_rr_apply, TAIL); the tiles
-            // then also need the first group start BEHIND them (k_rr_scan_next, second block of k_rr_scan_round)
-            // (rf.status: the local pass wrote status bytes, the group starts are read from them -- dense rounds only)
-            bool by_status = false;
-            if constexpr (PARENTS) by_status = rf.status != nullptr;
-            if constexpr (PARENTS) {
-                if (by_status) rc = rr_count<false, uint64_t, true, true>(rf.keys, L.U, L.m, w.tnext, key2_bits, gate, nullptr, nullptr, rf.status);
-            }
-            if (!by_status) rc = rr_count<false, uint64_t, PARENTS>(rf.keys, L.U, L.m, PARENTS ? w.tnext : (uint32_t *)nullptr, PARENTS ? key2_bits : 0, gate);
-            if (rc) return rc;
-            // (second block: the tiles' next group starts and the changed-rank counters of a dense round, the big-group counters saved and zeroed)
-            PROF(KC_RR_SCAN, tiles_m, st, hipLaunchKernelGGL((k_rr_scan_round), dim3(2), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles_m, w.total,
-                                                             PARENTS ? w.tnext : (uint32_t *)nullptr, PARENTS ? w.chg : (uint32_t *)nullptr, w.total + RC_BIG_LISTED, gate));
-            RrApply a = round_args(rf, extra);
-            a.gate = gate;
-            a.status = rf.status;
-            if constexpr (PARENTS) {
-                if (by_status) rc = rr_apply<false, true, ISA_MODE, uint64_t, false, true>(rf.keys, a);
-            }
-            if (!by_status) rc = rr_apply<false, true, ISA_MODE>(rf.keys, a);
-            if (rc) return rc;
-            // the one read-back of the round: w.total and, where asked for, the changed-rank counters behind it (w.chg)
-            { const int rcw = read_words(words, w.total, words_bytes, st); if (rcw) return rcw; }
-            if constexpr (ISA_MODE == 2) {
-                // (only the ranks that change became pairs; their number is in the counters)
-                int64_t pairs = 0;
-                for (int c = 0; c < RR_CHG_COUNTERS; ++c) pairs += words[64 + c * 32];
-                if (pairs > 0 && (rc = scatter_binned(w.ss, w.isa, (uint32_t *)a.pair_k, a.pair_v, (uint32_t *)rf.keys, (uint32_t *)rf.vals, pairs, n, st, &local, tn))) return rc;
-            }
-            if (!ctl.deferred) return SA_AMD_OK;
-            if (words[RC_FLAGGED] == 0) {
-                // as expected: the local pass ordered everything (what k_group_sort_big ordered was not chased: one look-up)
-                ctl.m_flagged = 0;
-                ctl.big_listed = ctl.skip_big ? -1 : (int64_t)words[RC_BIG_LISTED_SAVED];
-                rf.m_global = words[RC_BIG_ORDERED_SAVED];
-                local.locally_sorted += L.m;
-                return SA_AMD_OK;
-            }
-            if (attempt > 0) return SA_AMD_EINTERNAL;
-            ctl.resume_tot = words; ctl.defer = false; ctl.deferred = false;      // (refine_list copies them before anything is read back again)
-            rc = refine_list(Pk, K, &local_ok, &rf, retry_local, split_rest, &ctl);
-            ctl.resume_tot = nullptr;
-            if (rc) return rc;
-            ctl.missed = true;
-        }
-    }
-
     // 1-2. which byte values occur -> symbol codes and key geometry; entropy probe, repeat probe, gram keys (read-backs: the 256 presence flags, two duplicate counts, the number of grams in use)
     int geometry_and_probes()
     {
-        int rc = SA_AMD_OK; (void)rc;
+        int rc;
         // 1. sigma = 256 histogram -> symbol codes, bits per symbol, symbols per key
         HIP_TRY(hipMemsetAsync(w.hist, 0, 256 * 4, st));
         {
@@ -941,12 +491,12 @@ struct DeviceBuild {
         bucket_top_bits = choose_bucket_bits();
         force_dense = tn.force_dense;
         text_ok = !force_dense && !tn.no_text_rounds;
-        local_ok = !tn.no_local_sort;
+        rs.local_ok = !tn.no_local_sort;
 
         // 2. entropy probe: do the top 32 key bits already separate (almost) all suffixes?  Then the initial
         //    sort only needs those 4 digits and a cheap round on the low bits finishes the few ties.
         top_shift = 0;
-        if (text_ok && local_ok && key_bits > 32 && !tn.no_top32) {
+        if (text_ok && rs.local_ok && key_bits > 32 && !tn.no_top32) {
             bool use = tn.force_top32;
             if (!use && n >= tn.top32_probe_min_n) {
                 // 2^20 samples, fewer for texts below 8 Mi suffixes (a power of two: the duplicate count hashes into 4 S slots)
@@ -1009,7 +559,7 @@ struct DeviceBuild {
         //     2k symbols with another suffix.  Many (copied passages, a corpus): the text-keyed rounds cannot finish, so rank
         //     doubling starts right after the initial sort (measured on C3: 64 ms against 68 ms); few: text-keyed rounds.
         probe_dense = false;
-        if (text_ok && local_ok && !top_shift && !force_dense && !tn.no_repeat_probe && n >= ((int64_t)1 << 24)) {
+        if (text_ok && rs.local_ok && !top_shift && !force_dense && !tn.no_repeat_probe && n >= ((int64_t)1 << 24)) {
             const int64_t S = (int64_t)1 << 20;
             PROF(KC_MISC, S, st, hipLaunchKernelGGL((k_sample_repeat_keys), dim3((unsigned)ceil_div(S, GK_THREADS)), dim3(GK_THREADS), 0, st, dT, P, n, S,
                                                     w.keysA));
@@ -1038,7 +588,7 @@ struct DeviceBuild {
     //     global passes (read-back: the largest bucket)
     int initial_sort_top32(uint32_t *vals0, uint8_t *packed_out, bool iota)
     {
-        int rc = SA_AMD_OK; (void)rc;
+        int rc;
         uint32_t *k32a = (uint32_t *)w.keysA, *k32b = (uint32_t *)w.keysB;
         // Two global passes over the top 16 key bits + one pass that orders every bucket (= value of those bits) in LDS, when an
         // average bucket fits a workgroup well (n = 2^28: 4096 pairs, 2^29: 8192); larger texts take two passes of NINE bits
@@ -1100,7 +650,7 @@ struct DeviceBuild {
                 bool done = false, fused = false;
                 uint32_t largest = 0;
                 // the round on the low key bits of the suffixes tied on all 32 (first_round_from_sorted_keys) in the same launch
-                const bool fuse = local_ok && !tn.no_fused_finish && !tn.no_bucket_finish && !timing_only();
+                const bool fuse = rs.local_ok && !tn.no_fused_finish && !tn.no_bucket_finish && !timing_only();
                 BucketFinish F = BucketFinish();
                 KeySrc K = KeySrc();
                 if (fuse) {
@@ -1138,7 +688,7 @@ struct DeviceBuild {
     // 3-4. packed keys and the initial LSD sort, the last pass writing straight into SA
     int initial_sort()
     {
-        int rc = SA_AMD_OK; (void)rc;
+        int rc;
         // 3. packed keys, 4. initial sort: all key bits as (u64 key, u32 suffix) pairs, or only the top 32 bits as
         //    (u32, u32) pairs in 12 Ki-element tiles -- two thirds of the bytes per pass and half the passes
         sr.keys = w.keysA; sr.vals = w.valsA; sr.passes = 0;
@@ -1212,7 +762,7 @@ struct DeviceBuild {
     // list buffers; the fast finish of the 32-bit first stage / the opt-in fused first text round (read-backs: tied counts)
     int first_round_from_sorted_keys()
     {
-        int rc = SA_AMD_OK; (void)rc;
+        int rc;
         // 4. group heads of the initial order; how many suffixes are still tied with a neighbour
         L.U = w.U0; L.Un = w.U1; L.G = w.G0; L.Gn = w.G1;
         L.V = w.valsA;
@@ -1238,7 +788,7 @@ struct DeviceBuild {
             tkb = s_sym * Ptext.bits;
         }
         finished32 = false; fused64 = false;
-        if (top_shift && local_ok && !tn.no_fused_finish && !timing_only()) {
+        if (top_shift && rs.local_ok && !tn.no_fused_finish && !timing_only()) {
             // fast finish of the 32-bit first stage: one pass orders every small group by its low key bits in place
             // (k_finish_sorted); only if some group is too large for it does the general path below run instead
             const int cap = tn.group_cap;
@@ -1252,23 +802,16 @@ struct DeviceBuild {
             }
             // (k_bucket_sort counts its survivors itself: the scan of the tiles' counts runs only if there are any)
             if (!bucket_finished) PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles, w.total));
-            uint32_t cnt3[3] = { 0, 0, 0 };                       // still tied on 64 bits, members of groups nobody owned, tied on 32 bits
-            {
-                uint32_t words[64 + RR_CHG_COUNTERS * 32];         // (the tied-slot counts are spread over w.chg, directly behind w.total)
-                const int rcw = read_words(words, w.total, sizeof(words), st); if (rcw) return rcw;
-                cnt3[0] = words[0]; cnt3[1] = words[1];
-                for (int c = 0; c < RR_CHG_COUNTERS; ++c) cnt3[2] += words[64 + c * 32];
-                if (bucket_finished) {
-                    cnt3[0] = 0;
-                    for (int c = 0; c < RR_CHG_COUNTERS; ++c) cnt3[0] += words[64 + c * 32 + 1];
-                    if (cnt3[0] != 0 && cnt3[1] == 0)
-                        PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles, w.total));
-                }
-            }
-            if (cnt3[1] == 0) {
+            uint32_t words[ROUND_WORDS];         // (the tied-slot counts are spread over w.chg, directly behind w.total)
+            { const int rcw = read_words(words, w.total, sizeof(words), st); if (rcw) return rcw; }
+            // still tied on 64 bits (k_bucket_sort counts them in w.chg), members of groups nobody owned, tied on 32 bits
+            const uint32_t tied64 = bucket_finished ? (uint32_t)chg_sum(words, 1) : words[0], unowned = words[1], tied32 = (uint32_t)chg_sum(words);
+            if (bucket_finished && tied64 != 0 && unowned == 0)
+                PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles, w.total));
+            if (unowned == 0) {
                 finished32 = true;
-                L.m = cnt3[0];
-                local.locally_sorted += cnt3[2];
+                L.m = tied64;
+                local.locally_sorted += tied32;
                 local.unresolved_after_initial = L.m;
                 if (L.m > 0) {
                     PROF(KC_RR_APPLY, n, st, hipLaunchKernelGGL((k_surv_compact), dim3((unsigned)tiles), dim3(256), 0, st, (const uint32_t *)surv_bits,
@@ -1282,10 +825,10 @@ struct DeviceBuild {
         // (SA_AMD_SPARSE_DIV moves the text-round / doubling boundary for the tests: then the general route decides, as before)
         // Opt-in (SA_AMD_FUSED64=1): measured on C3 the one-pass round costs 8.2 ms against the 4.3 ms of k_group_sort on the tied
         // list -- with 68 % of the slots tied the work list is six entries per thread -- and the whole build 31.0 instead of 28.8 ms.
-        if (!top_shift && text_ok && local_ok && s_sym > 0 && tn.fused64 && !tn.no_fused_finish && !tn.sparse_div_set && !timing_only()) {
+        if (!top_shift && text_ok && rs.local_ok && s_sym > 0 && tn.fused64 && !tn.no_fused_finish && !tn.sparse_div_set && !timing_only()) {
             // the first text-keyed round straight from the sorted keys (k_finish_sorted): groups of up to `cap` members are
             // ordered in place by the next s_sym symbols, their still-tied members recorded by slot; the members of larger
-            // groups are listed (k_todo_compact) and take the general route (refine_list + re-rank), joining the same record;
+            // groups are listed (k_todo_compact) and take the general route (RefineRound::run<NO_RERANK> + re-rank), joining the same record;
             // k_surv_compact then lists everything that is still tied, in slot order, for the second round
             const int cap = tn.group_cap;
             const int64_t ft_tiles = ceil_div(n, FT_TILE);
@@ -1303,16 +846,11 @@ struct DeviceBuild {
                                                      (const uint64_t *)sorted0, SA, dT, Ptext, n, K, cap, w.surv_bits, surv_head, w.surv_cnt, w.total,
                                                      w.todo_bits, w.ft_cnt, w.ft_head));
             PROF(KC_RR_SCAN, ft_tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.ft_cnt, w.ft_head, ft_tiles, w.total + 3));
-            uint32_t cnt4[4] = { 0, 0, 0, 0 };                    // [2] tied after the initial sort, [3] members left to the general route
-            {
-                uint32_t words[64 + RR_CHG_COUNTERS * 32];
-                const int rcw = read_words(words, w.total, sizeof(words), st); if (rcw) return rcw;
-                cnt4[0] = words[0]; cnt4[1] = words[1]; cnt4[3] = words[3];
-                for (int c = 0; c < RR_CHG_COUNTERS; ++c) cnt4[2] += words[64 + c * 32];
-            }
-            local.unresolved_after_initial = cnt4[2];
-            const int64_t m_todo = cnt4[3];
-            local.locally_sorted += (int64_t)cnt4[2] - m_todo;
+            uint32_t words[ROUND_WORDS];
+            { const int rcw = read_words(words, w.total, sizeof(words), st); if (rcw) return rcw; }
+            const int64_t tied0 = (uint32_t)chg_sum(words), m_todo = words[3];      // tied after the initial sort, members left to the general route
+            local.unresolved_after_initial = tied0;
+            local.locally_sorted += tied0 - m_todo;
             L.keys_beside(w, sr.keys);
             if (m_todo > 0) {
                 PROF(KC_RR_APPLY, n, st, hipLaunchKernelGGL((k_todo_compact<uint64_t>), dim3((unsigned)ft_tiles), dim3(FT_THREADS), 0, st,
@@ -1320,9 +858,11 @@ struct DeviceBuild {
                                                             (const uint32_t *)w.ft_cnt, (const uint32_t *)w.ft_head, (const uint32_t *)(w.total + 3),
                                                             L.U, L.G, L.V));
                 L.m = m_todo;
-                Refined rf;
-                bool big_local = true;                             // (large groups: the global sort does the work either way)
-                if ((rc = refine_list(Ptext, K, &big_local, &rf))) return rc;
+                RoundState own;                                    // (a switch of its own: large groups, the global sort does the work either way)
+                own.local_ok = true;
+                RefineRound round(*this, Ptext, K, own);
+                if ((rc = round.run<NO_RERANK>())) return rc;
+                const Refined &rf = round.rf;
                 if ((rc = rr_count<false>(rf.keys, L.U, L.m, nullptr, 0, nullptr, w.ft_cnt, w.ft_head))) return rc;
                 if ((rc = rr_scan(L.m, w.ft_cnt, w.ft_head, w.total + 4))) return rc;
                 RrApply a = round_args(rf);
@@ -1343,7 +883,7 @@ struct DeviceBuild {
             depth += s_sym;
             local.text_rounds++;
             local.rounds++;
-            if (trace) fprintf(stderr, "suffix_array_amd: text round %d depth %lld: tied %lld -> %lld  (%.2f ms)\n", local.text_rounds, (long long)depth, (long long)cnt4[2], (long long)L.m, lap());
+            if (trace) fprintf(stderr, "suffix_array_amd: text round %d depth %lld: tied %lld -> %lld  (%.2f ms)\n", local.text_rounds, (long long)depth, (long long)tied0, (long long)L.m, lap());
         }
         return SA_AMD_OK;
     }
@@ -1351,7 +891,7 @@ struct DeviceBuild {
     // 4. group heads of the initial order: how many suffixes are still tied (read-back: that count)
     int group_heads()
     {
-        int rc = SA_AMD_OK; (void)rc;
+        int rc;
         if (!finished32 && !fused64) {
         // (64-bit keys: also every tile's first group start: the dense route's first ranks are tail ranks, k_rr_apply FTAIL)
         rc = top_shift ? rr_count<true, uint32_t>(sorted32, nullptr, n)
@@ -1370,14 +910,15 @@ struct DeviceBuild {
     // the suffixes tied on the top 32 key bits are ordered by their low key bits (read-back: tied on all 64 bits)
     int finish_top32_ties()
     {
-        int rc = SA_AMD_OK; (void)rc;
+        int rc;
         if (!finished32 && top_shift && L.m > 0) {
             // finish the initial sort: the suffixes tied on the top 32 bits are ordered by their low key bits
             L.keys_beside(w, sr.keys);
             if ((rc = rr_apply<true, false, 1, uint32_t>(sorted32, first_args(0u, w.has_isa)))) return rc;
-            Refined rf;
             KeySrc K = KeySrc(); K.mode = KS_LOWKEY; K.kb = top_shift;
-            if ((rc = refine_list(P, K, &local_ok, &rf))) return rc;
+            RefineRound round(*this, P, K, rs);
+            if ((rc = round.run<NO_RERANK>())) return rc;
+            const Refined &rf = round.rf;
             if ((rc = rr_count<false>(rf.keys, L.U, L.m))) return rc;
             if ((rc = rr_scan(L.m))) return rc;
             if ((rc = rr_apply<false, true, 3>(rf.keys, round_args(rf)))) return rc;
@@ -1393,7 +934,7 @@ struct DeviceBuild {
     // 5. dense route: ranks + ISA; otherwise compaction and the text-keyed rounds (read-back per round: tied count)
     int rank_setup_and_text_rounds()
     {
-        int rc = SA_AMD_OK; (void)rc;
+        int rc;
         // 5. refinement of the tied suffixes.  Three regimes:
         //   text rounds  while more than n / SPARSE_DIV suffixes are tied: secondary key = the next symbols of
         //                the text itself (no rank array needed yet), depth grows by s symbols per round;
@@ -1445,26 +986,16 @@ struct DeviceBuild {
             }
             // ---- text-keyed rounds ----
             bool progressing = true;     // a text round that resolves little (runs, long repeats) is the last one
-
-            bool counters_clear = false;      // (RoundCtl: one read-back per round while the rounds have nothing for the global sort)
             while (text_ok && s_sym > 0 && L.m > sparse_limit && local.text_rounds < tn.max_text_rounds && progressing) {
                 if ((rc = early_maybe_start())) return rc;
                 const int64_t m_before = L.m;
-                Refined rf;
                 KeySrc K = KeySrc(); K.mode = KS_TEXT; K.h = depth; K.s = s_sym; K.kb = tkb;
-                RoundCtl ctl;
-                ctl.defer = prev_clean && local_ok && !tn.no_defer;
-                ctl.counters_clear = counters_clear;
-                if ((rc = refine_list(Ptext, K, &local_ok, &rf, false, nullptr, &ctl))) return rc;
-                uint32_t words[RC_WORDS];
-                if ((rc = finish_round<3, false>(Ptext, K, ctl, rf, RrApply(), words, sizeof(words), false, nullptr))) return rc;
-                prev_clean = ctl.m_flagged == 0;
-                counters_clear = true;
-                L.m = words[0];
-                L.advance(rf);
+                // (deferred: one read-back per round while the rounds have nothing for the global sort)
+                RefineRound round(*this, Ptext, K, rs, rs.prev_clean && rs.local_ok && !tn.no_defer);
+                if ((rc = round.run<3>())) return rc;
+                after_round(round);
                 depth += s_sym;
                 local.text_rounds++;
-                local.rounds++;
                 progressing = L.m * 4 <= m_before * 3;
                 if (trace) fprintf(stderr, "suffix_array_amd: text round %d depth %lld: tied %lld -> %lld  (%.2f ms)\n", local.text_rounds, (long long)depth, (long long)m_before, (long long)L.m, lap());
             }
@@ -1494,94 +1025,68 @@ struct DeviceBuild {
         }
         local.sparse_mode = sparse ? 1 : 0;
         if (trace) fprintf(stderr, "suffix_array_amd: initial sort + text rounds + rank set-up done, %lld tied (%.2f ms since the last line)\n", (long long)L.m, lap());
-
         return SA_AMD_OK;
     }
 
     // prefix doubling on what is still tied, dense (ISA) or sparse (read-backs per round: tied count, ranks written)
     int doubling_rounds()
     {
-        int rc = SA_AMD_OK; (void)rc;
-        // prefix doubling on what is still tied; `depth` symbols are sorted, so the first offset is `depth`
+        int rc;
+        // `depth` symbols are sorted, so the first offset is `depth`
         const int64_t depth_text = depth;
         int64_t h = depth;
-        bool chase_ok = false;
-        int split_rest = 0;                               // rounds the three-way split sits out (refine_list)
-        bool parent_tail = isa_tail_ranks;                // the ranks in the ISA are tail ranks (set by the first dense round, or by the rank set-up of the dense route)
-        int64_t changed_prev = isa_tail_ranks ? L.m : 0;    // ranks the last dense round wrote (none yet: expect every rank to change)
-        int64_t m_local_off = L.m;                          // size of the tied list when the local pass was last in use
-        int rounds_local_off = 0;
-        // read-backs (RoundCtl): a round whose predecessor had nothing for the global sort defers that question and blocks ONCE
-        bool all_small = false;                           // ... and listed no group for k_group_sort_big: no group is larger than GS_CAP any more
-        bool counters_clear = false;                      // the previous round's k_rr_scan_round zeroed the big-group counters
-        // dense rounds write a slot of SA once, in the round its suffix leaves the tied list (k_rr_apply sa_final); the loop runs
-        // until the list is empty, so every slot gets its final value.  Sparse rounds look suffixes up in SA (sparse_key2): every round
-        const int sa_final = (!sparse && !tn.sa_every_round) ? 1 : 0;
+        rs.parent_tail = isa_tail_ranks;
+        rs.changed_prev = isa_tail_ranks ? L.m : 0;
+        rs.m_local_off = L.m;
+        rs.counters_clear = false;      // (the first doubling round zeroes the big-group counters itself, whatever the text rounds left)
         while (L.m > 0) {
             if (local.rounds >= 48) return SA_AMD_EINTERNAL;
             if ((rc = early_maybe_start())) return rc;     // (every slot outside the tied list is final from here on)
-            // the same refinement machinery as the text rounds, keyed by ranks -- small groups (a long repeat gives millions of
-            // pairs) are ordered in LDS, only large groups go through the global sort.  Dense: ranks from the ISA; sparse:
-            // looked up without one (sparse_key2)
+            const int64_t m_before = L.m;
+            // the same refinement machinery as the text rounds, keyed by ranks.  Dense: ranks from the ISA; sparse: looked up without one (sparse_key2)
             KeySrc K = KeySrc();
             K.mode = sparse ? KS_SPARSE : KS_RANK; K.h = h; K.kb = key2_bits; K.isa = w.isa;
+            K.has_isa = w.has_isa; K.sorted_keys = sorted0; K.sorted_top32 = sorted32; K.sa = SA; K.depth = depth_text; K.top_shift = top_shift;
+            // the local pass was given up because (nearly) every member sat in a group no tile can own: it is tried again when the list has
+            // halved, and every third round if the round then finds the average group small enough (RefineRound::decide_local; large lists
+            // count their groups anyway; a Fibonacci word's groups shrink while the list does not, a periodic text's never do)
+            if (!rs.local_ok && !tn.no_local_sort && L.m * 2 < rs.m_local_off) rs.local_ok = true;
+            const bool retry_local = !rs.local_ok && ++rs.rounds_local_off >= 3;
+            if (rs.local_ok) { rs.m_local_off = L.m; rs.rounds_local_off = 0; }
             // dense rounds chase (up to `chase` rank look-ups per member inside one launch) once a round has had no group left
             // for the global sort: from then on every surviving group is known to share (iters + 1) * h symbols
-            // the local pass was given up because (nearly) every member sat in a group no tile can own: it is tried again when the
-            // list has halved, and every third round -- if refine_list then finds the average group small enough for a tile (large
-            // lists count their groups anyway; a Fibonacci word's groups shrink while the list does not, a periodic text's never do)
-            if (!local_ok && !tn.no_local_sort && L.m * 2 < m_local_off) local_ok = true;
-            const bool retry_local = !local_ok && ++rounds_local_off >= 3;
-            K.iters = (!sparse && local_ok && chase_ok) ? (L.m >= tn.chase_big_min ? tn.chase_big : tn.chase) : 1;
+            K.iters = (!sparse && rs.local_ok && rs.chase_ok) ? (L.m >= tn.chase_big_min ? tn.chase_big : tn.chase) : 1;
             if (K.iters > 1) K.mode = KS_CHASE;
-            K.has_isa = w.has_isa; K.sorted_keys = sorted0; K.sorted_top32 = sorted32; K.sa = SA; K.depth = depth_text; K.top_shift = top_shift;
-            Refined rf;
-            if (local_ok) { m_local_off = L.m; rounds_local_off = 0; }
             // binned or direct ISA stores: by the number of ranks this round is expected to write -- all of them when the parents'
             // ranks are not tail ranks yet, otherwise about as many as the round before wrote
-            const int64_t expect = (!parent_tail || L.m < changed_prev) ? L.m : changed_prev;
+            const int64_t expect = (!rs.parent_tail || L.m < rs.changed_prev) ? L.m : rs.changed_prev;
             const bool bin = !sparse && binned(n, expect, tn);
-            RoundCtl ctl;
-            ctl.defer = prev_clean && !bin && local_ok && !tn.no_defer;
-            ctl.skip_big = all_small;
-            ctl.counters_clear = counters_clear;
-            if ((rc = refine_list(P, K, &local_ok, &rf, retry_local, &split_rest, &ctl))) return rc;
-            if (retry_local && rf.m_global < L.m) { m_local_off = L.m; rounds_local_off = 0; }      // (the local pass ran again; such a round is never deferred)
-            // w.total (64 words) and, dense rounds, the changed-rank counters behind it (w.chg) in one read-back
-            uint32_t words[64 + RR_CHG_COUNTERS * 32];
-            RrApply a;
-            a.g_shift = key2_bits;
-            if (sparse) a.has_isa = w.has_isa;
-            else { a.tile_next = w.tnext; a.parent_tail = parent_tail ? 1 : 0; a.changed_cnt = w.chg; a.sa_final = sa_final; }
-            // a binned round: L.G has been consumed by the gather, the other key buffer by nothing -- they take the (suffix, rank) pairs
-            if (bin) { a.pair_k = (rf.keys == L.rkA) ? L.rkB : L.rkA; a.pair_v = L.G; }
-            const size_t wb = sparse ? (size_t)RC_WORDS * 4 : sizeof(words);
-            rc = sparse ? finish_round<1, false>(P, K, ctl, rf, a, words, wb, retry_local, &split_rest)
-                 : bin  ? finish_round<2, true>(P, K, ctl, rf, a, words, wb, retry_local, &split_rest)
-                        : finish_round<0, true>(P, K, ctl, rf, a, words, wb, retry_local, &split_rest);
-            if (rc) return rc;
-            if (ctl.missed) ++deferred_misses;
-            prev_clean = ctl.m_flagged == 0;
-            if (prev_clean && (ctl.big_listed == 0 || L.m <= GS_CAP)) all_small = true;
-            counters_clear = true;                        // (k_rr_scan_round ran ungated in the end)
-            {
-                m32 = words[0];
-                if (!sparse) {
-                    changed_prev = 0;
-                    for (int c = 0; c < RR_CHG_COUNTERS; ++c) changed_prev += words[64 + c * 32];
-                    parent_tail = true;
-                }
-            }
-            if (trace) fprintf(stderr, "suffix_array_amd: doubling round %d h %lld (%s, %d look-ups, %lld through the global sort): tied %lld -> %u, %lld ranks written\n", local.rounds + 1, (long long)h, sparse ? "sparse" : "dense", K.iters, (long long)rf.m_global, (long long)L.m, m32, sparse ? -1ll : (long long)changed_prev), fprintf(stderr, "    (%.2f ms)\n", lap());
+            // read-backs: a round whose predecessor had nothing for the global sort defers that question and blocks ONCE
+            RefineRound round(*this, P, K, rs, rs.prev_clean && !bin && rs.local_ok && !tn.no_defer, true, retry_local);
+            if ((rc = sparse ? round.run<1, false>() : bin ? round.run<2, true>() : round.run<0, true>())) return rc;
+            const Refined &rf = round.rf;
+            if (retry_local && rf.m_global < L.m) { rs.m_local_off = L.m; rs.rounds_local_off = 0; }      // (the local pass ran again; such a round is never deferred)
+            if (round.missed) ++rs.deferred_misses;
+            after_round(round);
+            if (rs.prev_clean && (round.big_listed == 0 || m_before <= GS_CAP)) rs.all_small = true;
+            if (!sparse) { rs.changed_prev = chg_sum(round.words); rs.parent_tail = true; }
+            if (trace) fprintf(stderr, "suffix_array_amd: doubling round %d h %lld (%s, %d look-ups, %lld through the global sort): tied %lld -> %u, %lld ranks written\n", local.rounds, (long long)h, sparse ? "sparse" : "dense", K.iters, (long long)rf.m_global, (long long)m_before, round.words[RC_TIED], sparse ? -1ll : (long long)rs.changed_prev), fprintf(stderr, "    (%.2f ms)\n", lap());
             if (trace && !sparse) fprintf(stderr, "    (group starts read from %s)\n", rf.status ? "status bytes" : "keys");
-            L.m = m32;
-            L.advance(rf);
             // every group that is still tied went through K.iters look-ups -- unless some went through the global sort (one look-up)
             h *= (K.iters > 1 && rf.m_global == 0) ? (int64_t)(K.iters + 1) : 2;
-            chase_ok = rf.m_global == 0;
-            local.rounds++;
+            rs.chase_ok = rf.m_global == 0;
         }
         return SA_AMD_OK;
+    }
+
+    // what a round of either loop leaves behind: the next tied list, and what the next round's switches are made from
+    void after_round(const RefineRound &r)
+    {
+        rs.prev_clean = r.m_flagged == 0;
+        rs.counters_clear = true;                     // (k_rr_scan_round ran ungated in the end)
+        L.m = r.words[RC_TIED];
+        L.advance(r.rf);
+        local.rounds++;
     }
 
 };
@@ -1630,12 +1135,12 @@ static int build_device(const uint8_t *dT, uint32_t *dSA, int32_t n32, void *dWo
     int rc;
     if ((rc = B.geometry_and_probes())) return rc;
     if (!B.unary_done) {
-    if ((rc = B.initial_sort())) return rc;
-    if ((rc = B.first_round_from_sorted_keys())) return rc;
-    if ((rc = B.group_heads())) return rc;
-    if ((rc = B.finish_top32_ties())) return rc;
-    if ((rc = B.rank_setup_and_text_rounds())) return rc;
-    if ((rc = B.doubling_rounds())) return rc;
+        if ((rc = B.initial_sort())) return rc;
+        if ((rc = B.first_round_from_sorted_keys())) return rc;
+        if ((rc = B.group_heads())) return rc;
+        if ((rc = B.finish_top32_ties())) return rc;
+        if ((rc = B.rank_setup_and_text_rounds())) return rc;
+        if ((rc = B.doubling_rounds())) return rc;
     }
     if ((rc = B.early_finish())) return rc;
     hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, st, dSA, (uint32_t)n);   // reference src/saca.rs:13
@@ -1648,7 +1153,7 @@ static int build_device(const uint8_t *dT, uint32_t *dSA, int32_t n32, void *dWo
         if (gave_up[0] || gave_up[3]) return SA_AMD_EINTERNAL;
     }
     local.readbacks = g_readbacks;
-    if (B.trace) fprintf(stderr, "suffix_array_amd: %d blocking read-backs in this build (%d rounds deferred their mid-round count and had to run the global sort after all)\n", g_readbacks, B.deferred_misses);
+    if (B.trace) fprintf(stderr, "suffix_array_amd: %d blocking read-backs in this build (%d rounds deferred their mid-round count and had to run the global sort after all)\n", g_readbacks, B.rs.deferred_misses);
     g_prof.resolve();
     g_last_stats = local;
     if (stats) *stats = local;

@@ -1,4 +1,4 @@
-// host/readback.hpp -- small device -> host read-backs of the device pipeline (host/pipeline.hpp): read_words.
+// host/readback.hpp -- small device -> host read-backs of the device pipeline (host/pipeline.hpp, host/refine_round.hpp): read_words.
 #pragma once
 #include "support.hpp"
 #include "pool.hpp"

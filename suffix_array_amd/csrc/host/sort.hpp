@@ -1,4 +1,4 @@
-// host/sort.hpp -- the radix-sort drivers of the device pipeline (host/pipeline.hpp), the product's: what a sort needs (SortScratch),
+// host/sort.hpp -- the radix-sort drivers of the device pipeline (host/pipeline.hpp, host/refine_round.hpp), the product's: what a sort needs (SortScratch),
 // what it is asked (SortJob) and answers (SortResult), the single-pass tile scatter's host side (sort_pairs, sort_pairs32,
 // sort_first_counts) and the in-LDS bucket sort of the 32-bit first stage (bucket_sort32).  The diagnostic library's second engine
 // and its sample sort are in host/sort_diag.hpp.

@@ -713,7 +713,7 @@ __global__ __launch_bounds__(GB_THREADS) void k_group_sort_big(uint64_t *__restr
 // slot of their subgroup's first member in surv_head, count per re-rank tile -- and k_surv_compact
 // turns that into the (slot, group head, suffix) list the later rounds expect.  A group it cannot
 // own (too large / longer overhang) only bumps counters[1]; the host then runs the general path
-// (k_rr_* + refine_list) over everything: correct on any input, fast on the inputs the probe admits.
+// (k_rr_* + RefineRound) over everything: correct on any input, fast on the inputs the probe admits.
 // Algorithmic traffic per slot: 4 B key + (tied: 4 B SA read, text gather, 4 B SA write).
 // ------------------------------------------------------------------------------------------
 constexpr int FT_THREADS = 256;

@@ -297,7 +297,7 @@ __global__ __launch_bounds__(RR_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
                                                           uint32_t *__restrict__ tile_cnt,
                                                           uint32_t *__restrict__ tile_head, int key_shift,
                                                           uint32_t *__restrict__ tile_first, int g_shift,
-                                                          const uint32_t *__restrict__ gate = nullptr,      // != nullptr: the launch does nothing when *gate != 0 (see RoundCtl, host/pipeline.hpp)
+                                                          const uint32_t *__restrict__ gate = nullptr,      // != nullptr: the launch does nothing when *gate != 0 (see RefineRound::defer, host/refine_round.hpp)
                                                           const uint8_t *__restrict__ head_flags = nullptr)
 {
     static_assert(!FLAGS || (sizeof(KeyT) == 8 && (FIRST || PARENTS)), "group-start flags come from the 64-bit initial sort, status bytes from a dense round");

@@ -5,7 +5,7 @@ through it and compares the tied counts round by round.
 
 State is cls[i], an order-preserving dense class id per suffix, starting at 1 (the library's ranks start at 1 too).  Two
 suffixes carry the same id exactly when the steps so far could not tell them apart; a smaller id means a smaller suffix.
-The steps mirror what the host asks of the kernels (csrc/host/pipeline.hpp), at the level of classes only:
+The steps mirror what the host asks of the kernels (csrc/host/pipeline.hpp, csrc/host/refine_round.hpp), at the level of classes only:
 
   initial(T, k)                  the initial sort: the first k symbol codes, zero codes past the end of the text (k_build_keys)
   text_round(cls, T, depth, s)   a text-keyed round: the s padded symbols from offset depth
