@@ -308,6 +308,7 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
     uint32_t m32 = 0;
     bool lists_ready = false, finished32 = false, fused64 = false, sparse = false;
     bool isa_tail_ranks = false;        // the rank set-up of the dense route wrote tail ranks (k_rr_apply FTAIL)
+    bool tnext_scanned = false;         // group_heads scanned w.tnext with its counts (k_rr_scan_round): the rank set-up launches no k_rr_scan_next
     int s_sym = 0, tkb = 0;
     bool unary_done = false;            // a text of one byte value: the array was written directly (geometry_and_probes), nothing else runs
     RoundState rs;                      // what one refinement round leaves for the next
@@ -787,7 +788,7 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
             if (s_sym > 64) s_sym = 64;
             tkb = s_sym * Ptext.bits;
         }
-        finished32 = false; fused64 = false;
+        finished32 = false; fused64 = false; tnext_scanned = false;
         if (top_shift && rs.local_ok && !tn.no_fused_finish && !timing_only()) {
             // fast finish of the 32-bit first stage: one pass orders every small group by its low key bits in place
             // (k_finish_sorted); only if some group is too large for it does the general path below run instead
@@ -898,7 +899,16 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
            : head_flags ? rr_count<true, uint64_t, true, true>((const uint64_t *)sr.keys, nullptr, n, w.tnext)
                         : rr_count<true, uint64_t, true>((const uint64_t *)sr.keys, nullptr, n, w.tnext);
         if (rc) return rc;
-        if ((rc = rr_scan(n))) return rc;
+        // (64-bit keys on a route that is expected to be dense -- the condition the flags pass is chosen by: the tiles' next group
+        // starts are scanned here, as the second block of the launch, not by a launch of their own in front of the rank set-up.
+        // The read-back below waits for both blocks, so the launch is as long as the longer scan -- at C3 size 51 us for this
+        // block against 32 us for k_rr_scan alone: the dense route saves k_rr_scan's 32 us and a launch.  Any other route keeps
+        // the plain scan; should it turn dense after all, the rank set-up launches k_rr_scan_next itself)
+        tnext_scanned = !top_shift && (force_dense || probe_dense || !text_ok);
+        if (tnext_scanned)
+            PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan_round), dim3(2), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles, w.total, w.tnext,
+                                                           (uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr));
+        else if ((rc = rr_scan(n))) return rc;
         { const int rcw = read_words(&m32, w.total, 4, st); if (rcw) return rcw; }
         L.m = m32;
         local.unresolved_after_initial = L.m;
@@ -950,7 +960,7 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
             // the first ranks are TAIL ranks (a group's last slot + 1), the form the dense rounds keep (k_rr_apply): the first doubling
             // round then writes only the ranks that change (SA_AMD_NO_FIRST_TAIL=1: head ranks, everything rewritten in round 1)
             isa_tail_ranks = !tn.no_first_tail;
-            if (isa_tail_ranks)
+            if (isa_tail_ranks && !tnext_scanned)
                 PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan_next), dim3(1), dim3(SPINE_THREADS), 0, st, w.tnext, tiles, (uint32_t *)nullptr));
             RrApply a = first_args((uint32_t)n);
             a.tile_next = isa_tail_ranks ? w.tnext : (uint32_t *)nullptr;

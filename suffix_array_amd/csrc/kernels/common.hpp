@@ -44,7 +44,7 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
 }
 
 // Group-start flags: one byte per position of the sorted initial order, written by the last pass of the 64-bit initial sort
-// (k_onesweep<..., HEAD_FLAGS>, kernels/onesweep.hpp) and read by the first re-rank (rr_wave_classify_flags, kernels/rerank.hpp)
+// (k_onesweep<..., HEAD_FLAGS>, kernels/onesweep.hpp) and read by the first re-rank (rr_lane_bits_flags, kernels/rerank.hpp)
 // in place of the sorted keys.  A group = a maximal run of equal keys.
 constexpr uint8_t OS_HF_SAME = 0;   // position p continues the group of p - 1
 constexpr uint8_t OS_HF_START = 1;  // p starts a group (always so at p = 0)
@@ -52,7 +52,7 @@ constexpr uint8_t OS_HF_SEAM = 2;   // p is the first element of a tile's digit 
                                     // keys of p and p - 1 in its key buffer -- p starts a group iff they differ
 
 // Status byte of a member of the tied list in a dense doubling round: written by the round's local pass (k_group_sort with STATUS,
-// kernels/refine.hpp) per list PLACE, read by the round's re-rank (rr_wave_classify_status, kernels/rerank.hpp) in place of the
+// kernels/refine.hpp) per list PLACE, read by the round's re-rank (rr_lane_bits_status, kernels/rerank.hpp) in place of the
 // 8-byte keys.  A group starts at place i iff  PHEAD(i) || (KEYED(i) ? keys[i] != keys[i - 1] : HEAD(i)).  A KEYED place that is no
 // parent head has a KEYED place of the same parent group before it (ownership is per parent group), so both keys are true keys;
 // no other entry of the key buffer is read, and the owned places have none.

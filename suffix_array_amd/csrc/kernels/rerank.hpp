@@ -77,15 +77,14 @@ __device__ __forceinline__ WaveGroups rr_wave_classify(const KeyT *__restrict__ 
     return g;
 }
 
-// The same masks from the group-start flags of the initial sort's last pass (OS_HF_*, kernels/common.hpp) -- the FIRST re-rank
-// behind a k_onesweep<..., HEAD_FLAGS> pass: one byte per element instead of its 8-byte key.  `keys` is that pass's key buffer and
-// is read only at OS_HF_SEAM positions (p and p - 1: the two entries the pass guarantees).  phead == head: the first ranks
-// have no parent groups (g_shift == 0).
-// A wave's 512 flag bytes come in ONE load of 8 bytes per lane (lane l: elements 8 l .. 8 l + 7 of the wave; the flag slab is
+// The byte forms: the same groups from the group-start flags of the initial sort's last pass (OS_HF_*, kernels/common.hpp) -- the
+// FIRST re-rank behind a k_onesweep<..., HEAD_FLAGS> pass: one byte per element instead of its 8-byte key -- or from the status
+// bytes of a dense doubling round.  In the flags form `keys` is that pass's key buffer and is read only at OS_HF_SEAM positions
+// (p and p - 1: the two entries the pass guarantees); phead == head: the first ranks have no parent groups (g_shift == 0).
+// A wave's 512 bytes come in ONE load of 8 bytes per lane (lane l: elements 8 l .. 8 l + 7 of the wave; the flag slab is
 // 8-byte aligned and 8 (n + 64) bytes long, so the last wave reads, and masks, a few bytes behind the n flags); every lane turns
-// its bytes into 8 head bits, and the wave's 64 such bytes ARE head[0 .. 7] in order: four lanes' bytes are joined into a word
-// and sixteen v_readlane fetch them.  (Measured on C3, 2^28 slots: byte loads in the wave-striped layout of the keys -- eight
-// 64-byte loads per wave -- left k_rr_count at 427 us, 0.63 TB/s: bound by load instructions, not bytes.)
+// its bytes into 8 head bits (LaneBits below).  (Measured on C3, 2^28 slots: byte loads in the wave-striped layout of the keys --
+// eight 64-byte loads per wave -- left k_rr_count at 427 us, 0.63 TB/s: bound by load instructions, not bytes.)
 // The bytes one wave classifies: lane l holds those of elements 8 l .. 8 l + 7 of the wave, every lane the byte of the element
 // behind the wave (`none` when the list ends there).  Loading is a step of its own so that a workgroup of k_rr_count can issue
 // the loads of all the tiles of its span before it classifies the first.
@@ -102,15 +101,21 @@ __device__ __forceinline__ WaveBytes rr_wave_load_bytes(const uint8_t *__restric
     return b;
 }
 
-template <bool PARENTS = false>
-__device__ __forceinline__ WaveGroups rr_wave_classify_flags(const WaveBytes &raw, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase)
+// What a lane makes of its eight bytes, before anything crosses lanes: bit k of hb / pb / vb = element 8 l + k of the wave starts a
+// group / starts a parent group / exists; after (uniform): the element behind the wave is a group boundary (a start, or the end of
+// the list).  Both readers of the bytes start from here: k_rr_apply transposes the bits into the WaveGroups masks
+// (rr_wave_transpose), k_rr_count counts on them where they are (rr_wave_count_bits).
+struct LaneBits { uint32_t hb, pb, vb; bool after; };
+
+// ... from the group-start flags of the initial sort (pb == hb: the first ranks have no parent groups)
+__device__ __forceinline__ LaneBits rr_lane_bits_flags(const WaveBytes &raw, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase)
 {
-    const int l = lane_id();
-    WaveGroups g;
-    const int64_t i0 = wbase + 8 * l;                           // this lane's eight elements
+    const int64_t i0 = wbase + 8 * lane_id();                   // this lane's eight elements
     const int64_t a = wbase + RR_WAVE_ELEMS;                    // (uniform) the element behind the wave
     const uint32_t fa = raw.fa;
+    LaneBits x;
     uint32_t hb = 0;                                            // bit k: element i0 + k starts a group
+    x.vb = 0;
     if (i0 < m) {
         const uint2 w = raw.w;
         // bit 0 of every byte (OS_HF_START) -> four bits per word
@@ -123,58 +128,29 @@ __device__ __forceinline__ WaveGroups rr_wave_classify_flags(const WaveBytes &ra
             }
         }
         if (i0 == 0) hb |= 1u;
-        if (i0 + 8 > m) hb &= (1u << (int)(m - i0)) - 1u;       // (elements behind the end are no heads)
+        x.vb = i0 + 8 > m ? (1u << (int)(m - i0)) - 1u : 255u;
+        hb &= x.vb;                                             // (elements behind the end are no heads)
     }
-    // lane 4 q: the head bytes of lanes 4 q .. 4 q + 3 as one word (shuffles executed by every lane)
-    const uint32_t h1 = (uint32_t)__shfl_down((int)hb, 1, WAVE), h2 = (uint32_t)__shfl_down((int)hb, 2, WAVE), h3 = (uint32_t)__shfl_down((int)hb, 3, WAVE);
-    const uint32_t quad = hb | (h1 << 8) | (h2 << 16) | (h3 << 24);
-    const int64_t left = m - wbase;                             // (uniform) elements of the wave that exist: all 512, or fewer in the last one
-#pragma unroll
-    for (int r = 0; r < RR_ITEMS; ++r) {
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)quad, 8 * r), hi = (uint32_t)__builtin_amdgcn_readlane((int)quad, 8 * r + 4);
-        const int64_t here = left - 64 * r;
-        g.valid[r] = here >= 64 ? ~0ull : (here <= 0 ? 0ull : ((1ull << here) - 1ull));
-        g.head[r] = (((uint64_t)hi << 32) | lo) & g.valid[r];
-        g.phead[r] = PARENTS ? g.head[r] : 0ull;
-    }
-    const bool boundary_after = fa == OS_HF_START || (fa == OS_HF_SEAM && keys[a] != keys[a - 1]);
-#pragma unroll
-    for (int r = 0; r < RR_ITEMS; ++r) {
-        const uint64_t bnd = g.head[r] | ~g.valid[r];
-        const uint64_t bnd_next0 = (r + 1 < RR_ITEMS) ? ((g.head[(r + 1) % RR_ITEMS] | ~g.valid[(r + 1) % RR_ITEMS]) & 1ull)
-                                                      : (boundary_after ? 1ull : 0ull);
-        const uint64_t next = (bnd >> 1) | (bnd_next0 << 63);
-        g.tied[r] = g.valid[r] & ~(g.head[r] & next);
-    }
-    return g;
+    x.hb = hb; x.pb = hb;
+    x.after = fa == OS_HF_START || (fa == OS_HF_SEAM && keys[a] != keys[a - 1]);
+    return x;
 }
 
-template <bool PARENTS = false>
-__device__ __forceinline__ WaveGroups rr_wave_classify_flags(const uint8_t *__restrict__ flags, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase)
-{
-    return rr_wave_classify_flags<PARENTS>(rr_wave_load_bytes(flags, m, wbase, OS_HF_START), keys, m, wbase);
-}
-
-// The same masks from the status bytes of a dense doubling round (RS_*, kernels/common.hpp): one byte per place of the tied list
-// instead of its 8-byte key, loaded and transposed as above (one 8-byte load per lane, v_readlane).  `keys` is the round's key
-// buffer and holds true keys only at RS_KEYED places -- the members the local pass did not own, which on a text with long repeats
-// are tens of millions in long runs: a lane that has such a place among its eight reads its eight keys as one contiguous 64
-// bytes (and the key before them when its first place needs it) and compares neighbours without a branch per element; the keys
-// of the places that are not KEYED are read with them and masked out.  phead: RS_PHEAD.
+// ... from the status bytes of a dense doubling round (RS_*, kernels/common.hpp): one byte per place of the tied list instead of
+// its 8-byte key.  `keys` is the round's key buffer and holds true keys only at RS_KEYED places -- the members the local pass did
+// not own, which on a text with long repeats are tens of millions in long runs: a lane that has such a place among its eight reads
+// its eight keys as one contiguous 64 bytes (and the key before them when its first place needs it) and compares neighbours
+// without a branch per element; the keys of the places that are not KEYED are read with them and masked out.  pb: RS_PHEAD.
 // (Measured on C3: a wave-striped read of the wave's 512 keys where most lanes need them, neighbours from shuffles, chosen per
 // wave from a ballot -- thresholds of 8, 16, 32 and 48 lanes -- was no faster than this read in k_rr_count or k_rr_apply: CHANGELOG.)
-template <bool PARENTS = false>
-__device__ __forceinline__ WaveGroups rr_wave_classify_status(const WaveBytes &raw, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase_in)
+__device__ __forceinline__ LaneBits rr_lane_bits_status(const WaveBytes &raw, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase)
 {
-    const int l = lane_id();
-    WaveGroups g;
-    // (the wave's base is the same in every lane, which the compiler cannot see from threadIdx.x >> 6: said here, the masks below
-    // are scalar values -- left to itself it keeps all 32 of them in vector register pairs and spills)
-    const int64_t wbase = ((int64_t)__builtin_amdgcn_readfirstlane((int)(wbase_in >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wbase_in);
-    const int64_t i0 = wbase + 8 * l;                           // this lane's eight places
+    const int64_t i0 = wbase + 8 * lane_id();                   // this lane's eight places
     const int64_t a = wbase + RR_WAVE_ELEMS;                    // (uniform) the place behind the wave
     const uint32_t fa = raw.fa;
+    LaneBits x;
     uint32_t hb = 0, pb = 0;                                    // bit k: place i0 + k starts a group / a parent group
+    x.vb = 0;
     if (i0 < m) {
         const uint2 w = raw.w;
         // bit `b` of every byte -> eight bits
@@ -182,6 +158,7 @@ __device__ __forceinline__ WaveGroups rr_wave_classify_status(const WaveBytes &r
             return ((((w.x >> b) & 0x01010101u) * 0x01020408u) >> 24 & 15u) | (((((w.y >> b) & 0x01010101u) * 0x01020408u) >> 24 & 15u) << 4);
         };
         const uint32_t here = i0 + 8 > m ? (1u << (int)(m - i0)) - 1u : 255u;       // (places behind the end are nothing)
+        x.vb = here;
         pb = plane(3) & here;
         const uint32_t kd = plane(1) & here;
         hb = pb | (plane(2) & ~kd & here);
@@ -192,9 +169,9 @@ __device__ __forceinline__ WaveGroups rr_wave_classify_status(const WaveBytes &r
                 const uint4 *src = (const uint4 *)(keys + i0);  // (i0 is a multiple of 8: 64-byte aligned)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const uint4 x = src[q];
-                    k[2 * q] = ((uint64_t)x.y << 32) | x.x;
-                    k[2 * q + 1] = ((uint64_t)x.w << 32) | x.z;
+                    const uint4 x4 = src[q];
+                    k[2 * q] = ((uint64_t)x4.y << 32) | x4.x;
+                    k[2 * q + 1] = ((uint64_t)x4.w << 32) | x4.z;
                 }
             } else {
 #pragma unroll
@@ -207,28 +184,40 @@ __device__ __forceinline__ WaveGroups rr_wave_classify_status(const WaveBytes &r
             hb |= need & ne;
         }
     }
+    x.hb = hb; x.pb = pb;
+    x.after = (fa & RS_PHEAD) != 0 || ((fa & RS_KEYED) ? keys[a] != keys[a - 1] : (fa & RS_HEAD) != 0);
+    return x;
+}
+
+// The WaveGroups masks from the lanes' bits: the wave's 64 hb bytes ARE head[0 .. 7] in order -- four lanes' bytes are joined into
+// a word and sixteen v_readlane fetch them (OWN_P: sixteen more for phead; else phead = head where PARENTS).
+template <bool PARENTS, bool OWN_P>
+__device__ __forceinline__ WaveGroups rr_wave_transpose(const LaneBits &x, int64_t m, int64_t wbase)
+{
+    WaveGroups g;
+    const uint32_t hb = x.hb, pb = x.pb;
     // lane 4 q: the bytes of lanes 4 q .. 4 q + 3 as one word (shuffles executed by every lane)
     const uint32_t h1 = (uint32_t)__shfl_down((int)hb, 1, WAVE), h2 = (uint32_t)__shfl_down((int)hb, 2, WAVE), h3 = (uint32_t)__shfl_down((int)hb, 3, WAVE);
     const uint32_t quad = hb | (h1 << 8) | (h2 << 16) | (h3 << 24);
     uint32_t pquad = 0;
-    if (PARENTS) {
+    if (PARENTS && OWN_P) {
         const uint32_t p1 = (uint32_t)__shfl_down((int)pb, 1, WAVE), p2 = (uint32_t)__shfl_down((int)pb, 2, WAVE), p3 = (uint32_t)__shfl_down((int)pb, 3, WAVE);
         pquad = pb | (p1 << 8) | (p2 << 16) | (p3 << 24);
     }
-    const int64_t left = m - wbase;                             // (uniform) places of the wave that exist
+    const int64_t left = m - wbase;                             // (uniform) elements of the wave that exist: all 512, or fewer in the last one
 #pragma unroll
     for (int r = 0; r < RR_ITEMS; ++r) {
         const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)quad, 8 * r), hi = (uint32_t)__builtin_amdgcn_readlane((int)quad, 8 * r + 4);
         const int64_t here = left - 64 * r;
         g.valid[r] = here >= 64 ? ~0ull : (here <= 0 ? 0ull : ((1ull << here) - 1ull));
         g.head[r] = (((uint64_t)hi << 32) | lo) & g.valid[r];
-        g.phead[r] = 0ull;
-        if (PARENTS) {
+        g.phead[r] = (PARENTS && !OWN_P) ? g.head[r] : 0ull;
+        if (PARENTS && OWN_P) {
             const uint32_t plo = (uint32_t)__builtin_amdgcn_readlane((int)pquad, 8 * r), phi = (uint32_t)__builtin_amdgcn_readlane((int)pquad, 8 * r + 4);
             g.phead[r] = (((uint64_t)phi << 32) | plo) & g.valid[r];
         }
     }
-    const bool boundary_after = (fa & RS_PHEAD) != 0 || ((fa & RS_KEYED) ? keys[a] != keys[a - 1] : (fa & RS_HEAD) != 0);
+    const bool boundary_after = x.after;
 #pragma unroll
     for (int r = 0; r < RR_ITEMS; ++r) {
         const uint64_t bnd = g.head[r] | ~g.valid[r];
@@ -240,10 +229,24 @@ __device__ __forceinline__ WaveGroups rr_wave_classify_status(const WaveBytes &r
     return g;
 }
 
-template <bool PARENTS = false>
-__device__ __forceinline__ WaveGroups rr_wave_classify_status(const uint8_t *__restrict__ status, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase)
+// (the wave's base is the same in every lane, which the compiler cannot see from threadIdx.x >> 6: said here, the masks of the
+// byte forms are scalar values -- left to itself it keeps all 32 of them in vector register pairs and spills)
+__device__ __forceinline__ int64_t rr_uniform(int64_t v)
 {
-    return rr_wave_classify_status<PARENTS>(rr_wave_load_bytes(status, m, wbase, RS_PHEAD), keys, m, wbase);
+    return ((int64_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+
+template <bool PARENTS = false>
+__device__ __forceinline__ WaveGroups rr_wave_classify_flags(const uint8_t *__restrict__ flags, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase)
+{
+    return rr_wave_transpose<PARENTS, false>(rr_lane_bits_flags(rr_wave_load_bytes(flags, m, wbase, OS_HF_START), keys, m, wbase), m, wbase);
+}
+
+template <bool PARENTS = false>
+__device__ __forceinline__ WaveGroups rr_wave_classify_status(const uint8_t *__restrict__ status, const uint64_t *__restrict__ keys, int64_t m, int64_t wbase_in)
+{
+    const int64_t wbase = rr_uniform(wbase_in);
+    return rr_wave_transpose<PARENTS, true>(rr_lane_bits_status(rr_wave_load_bytes(status, m, wbase, RS_PHEAD), keys, m, wbase), m, wbase);
 }
 
 // "head code" of the dense doubling rounds: (list index of a group start << 1) | (it also starts a parent group);
@@ -262,6 +265,35 @@ __device__ __forceinline__ uint32_t rr_first_head_code(const WaveGroups &g, int6
         }
     }
     return code;
+}
+
+// What k_rr_count wants of a wave, from the lanes' bits where they are -- no masks, no transposition: a constant number of wave
+// operations whatever the bytes hold.  cnt: members tied with a neighbour; lasthead: list index of the wave's last group start,
+// + 1 (0: none); first_code: head code of its first group start (RR_NO_HEAD: none).  Every lane gets the same three values.
+//   tied: a member is alone iff it starts a group and the element behind it is a boundary; that element's boundary bit is bit
+//         k + 1 of the lane's own bits, for the lane's last element bit 0 of the next lane's (lane 63: x.after)
+struct WaveCount { uint32_t cnt, lasthead, first_code; };
+__device__ __forceinline__ WaveCount rr_wave_count_bits(const LaneBits &x, int64_t wbase)
+{
+    const uint32_t b = (x.hb | ~x.vb) & 255u;                   // boundaries: group starts and what lies behind the end
+    uint32_t nb = (uint32_t)__shfl_down((int)b, 1, WAVE) & 1u;  // (executed by every lane)
+    if (lane_id() == WAVE - 1) nb = x.after ? 1u : 0u;
+    const uint32_t tied = x.vb & ~(x.hb & ((b >> 1) | (nb << 7)));
+    WaveCount c;
+    c.cnt = 0;
+#pragma unroll
+    for (int k = 0; k < RR_ITEMS; ++k) c.cnt += (uint32_t)__popcll(__ballot((tied >> k) & 1u));      // (scalar: eight compares, eight s_bcnt1)
+    c.lasthead = 0; c.first_code = RR_NO_HEAD;
+    const uint64_t any = __ballot(x.hb != 0);                   // lanes with a group start
+    if (any) {                                                  // (uniform)
+        const int top = 63 - __builtin_clzll(any), low = __builtin_ctzll(any);
+        const uint32_t ht = (uint32_t)__builtin_amdgcn_readlane((int)x.hb, top);
+        const uint32_t hl = (uint32_t)__builtin_amdgcn_readlane((int)x.hb, low), pl = (uint32_t)__builtin_amdgcn_readlane((int)x.pb, low);
+        c.lasthead = (uint32_t)(wbase + 8 * top + (31 - __builtin_clz(ht))) + 1u;
+        const int k = __builtin_ctz(hl);
+        c.first_code = ((uint32_t)(wbase + 8 * low + k) << 1) | ((pl >> k) & 1u);
+    }
+    return c;
 }
 
 // Tiles one workgroup of the counting kernels covers when a member is one byte (k_rr_count<.., FLAGS>, k_flag_count<STATUS>,
@@ -286,8 +318,9 @@ __device__ __forceinline__ void rr_reduce16(uint32_t &a, uint32_t &b, uint32_t &
 
 // PARENTS (dense doubling rounds): also tile_first, the head code of the tile's first group start (g_shift: the parent
 // group is the key above that bit)
-// FLAGS: FIRST: the groups come from head_flags (rr_wave_classify_flags), `keys` is the flag pass's sparsely written key buffer;
-// a round (PARENTS): head_flags = the round's status bytes (rr_wave_classify_status), `keys` holds true keys at RS_KEYED places only
+// FLAGS: FIRST: the groups come from head_flags (rr_lane_bits_flags), `keys` is the flag pass's sparsely written key buffer;
+// a round (PARENTS): head_flags = the round's status bytes (rr_lane_bits_status), `keys` holds true keys at RS_KEYED places only.
+// Both count on the lanes' bits where they are (rr_wave_count_bits): no WaveGroups masks
 // A workgroup covers rr_count_span<FLAGS>() consecutive tiles (grid: rr_count_grid).  Its waves carry the LIST INDEX of their last
 // group start, not its slot: slots grow with the index, so the tile's last group start is the largest index, and U is read once
 // per tile, by the lane that writes tile_head, instead of once per wave in the middle of every wave's chain.
@@ -339,12 +372,20 @@ __global__ __launch_bounds__(RR_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
 #pragma unroll
     for (int s = 0; s < SPAN; ++s) {
     const int64_t wbase = (tile0 + s) * RR_TILE + (int64_t)w * RR_WAVE_ELEMS;
-    uint64_t kk[RR_ITEMS + 1];
-    WaveGroups g;
-    if constexpr (FLAGS && FIRST) g = rr_wave_classify_flags<false>(raw[s], (const uint64_t *)keys, m, wbase);
-    else if constexpr (FLAGS) g = rr_wave_classify_status<true>(raw[s], (const uint64_t *)keys, m, wbase);
-    else g = rr_wave_classify<KeyT, false>(keys, m, wbase, key_shift, 0, PARENTS ? kk : nullptr);
     uint32_t cnt = 0, lasthead = 0;                             // lasthead: list index of the wave's last group start, + 1
+    uint32_t first_code = RR_NO_HEAD;
+    if constexpr (FLAGS) {
+        // the byte forms count on each lane's own eight bits (rr_wave_count_bits)
+        const int64_t wb = rr_uniform(wbase);
+        LaneBits x;
+        if constexpr (FIRST) x = rr_lane_bits_flags(raw[s], (const uint64_t *)keys, m, wb);
+        else x = rr_lane_bits_status(raw[s], (const uint64_t *)keys, m, wb);
+        const WaveCount c = rr_wave_count_bits(x, wb);
+        cnt = c.cnt; lasthead = c.lasthead;
+        if (PARENTS) first_code = c.first_code;
+    } else {
+    uint64_t kk[RR_ITEMS + 1];
+    const WaveGroups g = rr_wave_classify<KeyT, false>(keys, m, wbase, key_shift, 0, PARENTS ? kk : nullptr);
 #pragma unroll
     for (int r = 0; r < RR_ITEMS; ++r) {
         cnt += (uint32_t)__popcll(g.tied[r]);
@@ -352,9 +393,7 @@ __global__ __launch_bounds__(RR_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
     }
     // the wave's first group start, and whether its parent group starts there too: only that one element's key and its left
     // neighbour's are compared (wave-uniform item and lane: two shuffles, not a ballot per item)
-    uint32_t first_code = RR_NO_HEAD;
-    if constexpr (PARENTS && FLAGS && !FIRST) first_code = rr_first_head_code(g, wbase, 0);
-    else if (PARENTS) {
+    if (PARENTS) {
         bool found = false;
 #pragma unroll
         for (int r = 0; r < RR_ITEMS; ++r) {
@@ -362,15 +401,13 @@ __global__ __launch_bounds__(RR_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
                 found = true;
                 const int b = __builtin_ctzll(g.head[r]);
                 const int64_t i = wbase + 64 * r + b;
-                if constexpr (FLAGS) first_code = ((uint32_t)i << 1) | 1u;      // (no parent groups yet: every group start starts its parent too)
-                else {
                 const uint64_t mine = shfl64(kk[r], b);
                 const uint64_t left = b ? shfl64(kk[r], b - 1) : (r ? shfl64(kk[r ? r - 1 : 0], 63) : kk[RR_ITEMS]);
                 const uint32_t ph = (i == 0 || ((mine ^ left) >> g_shift) != 0ull) ? 1u : 0u;
                 first_code = ((uint32_t)i << 1) | ph;
-                }
             }
         }
+    }
     }
     if (lane_id() == 0) { wcnt[s][w] = cnt; whead[s][w] = lasthead; wfirst[s][w] = first_code; }
     }
