@@ -1162,5 +1162,8 @@ const char *sa_amd_profile_kernel_name(int32_t index);
  * 16-bit token forms above for tokeniser ids held in uint32_t.  Part of this interface, declared and documented in a file of
  * its own. */
 #include "suffix_array_amd_tok32.h"
+/* Boolean document queries -- sa_amd_index_doc_match, sa_amd_index_doc_match_list (an extension): AND, OR
+ * and NOT over patterns on the collection of sa_amd_index_set_documents.  Declared and documented in a file of its own. */
+#include "suffix_array_amd_docmatch.h"
 
 #endif /* SUFFIX_ARRAY_AMD_H */

@@ -238,6 +238,12 @@ private:
     std::vector<std::uint32_t> bkt_;
 };
 
+// A clause of DocumentIndex::match / match_list: the documents that hold ANY of the patterns, or with `negate` those that hold none
+struct Clause {
+    std::vector<std::string> any;
+    bool negate = false;
+};
+
 // EXTENSION (not in the reference): text + suffix array resident on the device (sa_amd_index) with a collection of documents
 // over it (suffix_array_amd.h, "Document collections over the index").  offsets: ndocs + 1 non-decreasing values from 0 to n.
 class DocumentIndex {
@@ -292,6 +298,34 @@ public:
         }
         std::vector<std::vector<std::uint32_t>> out(patterns.size());
         for (std::size_t q = 0; q < out.size(); ++q) out[q].assign(docs.begin() + loff[q], docs.begin() + loff[q + 1]);
+        return out;
+    }
+    // Boolean document queries (suffix_array_amd_docmatch.h): a query is the AND of its clauses, a clause the OR of its patterns,
+    // negated where `negate` is set.  -> per query the number of documents it holds in; a query without clauses holds in all.
+    std::vector<std::uint32_t> match(const std::vector<std::vector<Clause>> &queries) const
+    {
+        const Queries q(queries);
+        std::vector<std::uint32_t> df(queries.size() + 1);
+        check(sa_amd_index_doc_match(ix_, q.b.data(), q.b.off.data(), q.b.count(), q.coff.data(), q.flags.data(), q.clauses(), q.qoff.data(), q.count(),
+                                     df.data(), nullptr));
+        df.resize(queries.size());
+        return df;
+    }
+    // per query the documents it holds in, in ascending document id
+    std::vector<std::vector<std::uint32_t>> match_list(const std::vector<std::vector<Clause>> &queries) const
+    {
+        const Queries q(queries);
+        std::vector<std::int64_t> loff(queries.size() + 1);
+        std::vector<std::uint32_t> docs(1 << 16);
+        std::int64_t total = 0;
+        for (;;) {
+            check(sa_amd_index_doc_match_list(ix_, q.b.data(), q.b.off.data(), q.b.count(), q.coff.data(), q.flags.data(), q.clauses(), q.qoff.data(),
+                                              q.count(), loff.data(), docs.data(), static_cast<std::int64_t>(docs.size()), &total));
+            if (total <= static_cast<std::int64_t>(docs.size())) break;
+            docs.resize(static_cast<std::size_t>(total));
+        }
+        std::vector<std::vector<std::uint32_t>> out(queries.size());
+        for (std::size_t i = 0; i < out.size(); ++i) out[i].assign(docs.begin() + loff[i], docs.begin() + loff[i + 1]);
         return out;
     }
     // keeps the slots ordered by document (4 bytes per byte of text) that term_frequencies and top_k need; a no-op when they
@@ -461,6 +495,30 @@ private:
         }
         const std::uint8_t *data() const { return reinterpret_cast<const std::uint8_t *>(bytes.data()); }
         std::int32_t count() const { return static_cast<std::int32_t>(off.size() - 1); }
+    };
+    static std::vector<std::string> all_patterns(const std::vector<std::vector<Clause>> &queries)
+    {
+        std::vector<std::string> out;
+        for (const auto &query : queries) for (const auto &c : query) out.insert(out.end(), c.any.begin(), c.any.end());
+        return out;
+    }
+    struct Queries {                                              // the layout of sa_amd_index_doc_match
+        Batch b;
+        std::vector<std::int32_t> coff, qoff;
+        std::vector<std::uint8_t> flags;
+        explicit Queries(const std::vector<std::vector<Clause>> &queries) : b(all_patterns(queries)), coff(1, 0), qoff(1, 0)
+        {
+            for (const auto &query : queries) {
+                for (const auto &c : query) {
+                    coff.push_back(coff.back() + static_cast<std::int32_t>(c.any.size()));
+                    flags.push_back(c.negate ? 1 : 0);
+                }
+                qoff.push_back(static_cast<std::int32_t>(flags.size()));
+            }
+            flags.push_back(0);                                   // (never an empty buffer)
+        }
+        std::int32_t clauses() const { return static_cast<std::int32_t>(coff.size() - 1); }
+        std::int32_t count() const { return static_cast<std::int32_t>(qoff.size() - 1); }
     };
     static std::vector<std::vector<std::pair<std::uint32_t, std::uint32_t>>> pairs(const std::vector<std::int64_t> &off, const std::vector<std::uint32_t> &docs,
                                                                                     const std::vector<std::uint32_t> &tf)

@@ -36,6 +36,7 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "DocRepeatStats", "last_doc_repeat_stats", "doc_repeats_work_bytes", "DOCREP_ANY", "DOCREP_OTHER",
            "DocsStats", "last_docs_stats", "docs_set_chunk", "docs_work_bytes", "doc_of_device_ptr", "DOC_NONE", "DOC_SAMPLES",
            "DOC_CHUNK_MIN", "DOC_CHUNK_MAX", "DOC_CHUNK_DEFAULT",
+           "Not", "DocMatchStats", "last_doc_match_stats", "doc_match_set_budget", "DOC_MATCH_BUDGET_DEFAULT", "DOC_MATCH_TILE_WORDS",
            "DocTfStats", "last_doc_tf_stats", "docs_set_topk_piece", "DOC_TOPK_MAX", "DOC_TOPK_PIECE_MIN", "DOC_TOPK_PIECE_MAX",
            "DOC_TOPK_PIECE_DEFAULT",
            "NgramStats", "last_ngram_stats", "ngram_set_stream_cap", "NGRAM_STREAM_CAP_DEFAULT",
@@ -189,6 +190,31 @@ class DocsStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class DocMatchStats(ctypes.Structure):
+    """sa_amd_doc_match_stats of include/suffix_array_amd_docmatch.h"""
+    _fields_ = [("patterns", ctypes.c_int64), ("clauses", ctypes.c_int64), ("queries", ctypes.c_int64), ("occ_sum", ctypes.c_int64),
+                ("units", ctypes.c_int64), ("marks", ctypes.c_int64), ("bitmap_words", ctypes.c_int64), ("slabs", ctypes.c_int64),
+                ("df_sum", ctypes.c_int64), ("budget", ctypes.c_int64), ("chunk", ctypes.c_int32), ("readbacks", ctypes.c_int32),
+                ("listed", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+class Not:
+    """A negated clause of ``doc_match`` / ``doc_match_list``: ``Not(b"x")`` holds the documents without ``x``,
+    ``Not([b"x", b"y"])`` those with neither."""
+    __slots__ = ("clause",)
+
+    def __init__(self, clause):
+        if isinstance(clause, Not):
+            raise TypeError("Not(Not(...)): pass the clause itself")
+        self.clause = clause
+
+    def __repr__(self):
+        return f"Not({self.clause!r})"
+
+
 class DocTfStats(ctypes.Structure):
     """sa_amd_doc_tf_stats of include/suffix_array_amd.h"""
     _fields_ = [("patterns", ctypes.c_int64), ("occ_sum", ctypes.c_int64), ("df_sum", ctypes.c_int64), ("tf_sum", ctypes.c_int64),
@@ -314,6 +340,10 @@ DOC_SAMPLES = 8192
 DOC_CHUNK_MIN = 64
 DOC_CHUNK_MAX = 1 << 20
 DOC_CHUNK_DEFAULT = 4096
+#: bytes of clause bitmaps a slab of ``doc_match`` queries may hold by default (host/doc_match.hpp), and the bitmap words one
+#: wave combines (kernels/doc_match.hpp): 32 documents a word
+DOC_MATCH_BUDGET_DEFAULT = 256 << 20
+DOC_MATCH_TILE_WORDS = 256
 #: the largest ``k`` of ``doc_topk`` (SA_AMD_DOC_TOPK_MAX of include/suffix_array_amd.h)
 DOC_TOPK_MAX = 1024
 #: keys of a piece of the top-k reduction: the clamp of ``docs_set_topk_piece`` and the default (kernels/doc_tf.hpp)
@@ -528,6 +558,15 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_index_doc_search.restype = ctypes.c_int32
         L.sa_amd_index_doc_list.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.c_int64, c_vp]
         L.sa_amd_index_doc_list.restype = ctypes.c_int32
+        L.sa_amd_index_doc_match.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.c_int32, c_vp, ctypes.c_int32, c_vp, c_vp]
+        L.sa_amd_index_doc_match.restype = ctypes.c_int32
+        L.sa_amd_index_doc_match_list.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.c_int32, c_vp, ctypes.c_int32, c_vp, c_vp,
+                                                  ctypes.c_int64, c_vp]
+        L.sa_amd_index_doc_match_list.restype = ctypes.c_int32
+        L.sa_amd_last_doc_match_stats.argtypes = [c_vp]
+        L.sa_amd_last_doc_match_stats.restype = None
+        L.sa_amd_doc_match_set_budget.argtypes = [ctypes.c_int64]
+        L.sa_amd_doc_match_set_budget.restype = ctypes.c_int64
         L.sa_amd_doc_repeats_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64]
         L.sa_amd_doc_repeats_work_bytes.restype = ctypes.c_int64
         L.sa_amd_index_doc_repeat_spans.argtypes = [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int64, c_vp, c_vp]
@@ -1346,6 +1385,49 @@ def _pattern_batch(patterns):
     return data, off, len(pats)
 
 
+def _is_pattern(x) -> bool:
+    return isinstance(x, (bytes, bytearray, memoryview, str)) or (isinstance(x, np.ndarray) and x.dtype == np.uint8)
+
+
+def _as_pattern(x) -> bytes:
+    return x.encode() if isinstance(x, str) else bytes(x)
+
+
+def _query_batch(queries):
+    """queries -> (pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries) in the layout of
+    sa_amd_index_doc_match.  A query is a sequence of clauses; a clause is one pattern, a sequence of patterns (any of them), or
+    ``Not(...)`` of either."""
+    pats, clause_off, flags, query_off = [], [0], [], [0]
+    for query in queries:
+        if _is_pattern(query) or isinstance(query, Not):
+            raise TypeError("a query is a sequence of clauses: wrap a single clause in a list")
+        for clause in query:
+            neg = isinstance(clause, Not)
+            body = clause.clause if neg else clause
+            pats += [_as_pattern(body)] if _is_pattern(body) else [_as_pattern(p) for p in body]
+            clause_off.append(len(pats))
+            flags.append(1 if neg else 0)
+        query_off.append(len(flags))
+    data, off, cnt = _pattern_batch(pats)
+    cfl = np.array(flags + [0], dtype=np.uint8)                       # (never a zero-sized buffer)
+    return (data, off, cnt, np.array(clause_off, dtype=np.int32), cfl, len(flags), np.array(query_off, dtype=np.int32), len(query_off) - 1)
+
+
+def last_doc_match_stats() -> dict:
+    """patterns / clauses / queries / occ_sum / units / marks / bitmap_words / slabs / df_sum / budget / chunk / readbacks /
+    listed of this thread's most recent ``doc_match`` / ``doc_match_list`` call"""
+    st = DocMatchStats()
+    lib().sa_amd_last_doc_match_stats(ctypes.byref(st))
+    return st.as_dict()
+
+
+def doc_match_set_budget(nbytes: int) -> int:
+    """Route switch of this thread's later ``doc_match`` / ``doc_match_list`` calls (never changes a result): the bytes of
+    clause bitmaps one slab of queries may hold, 4 KiB .. 2^40; negative restores the default of 256 MiB.  Returns the previous
+    value."""
+    return int(lib().sa_amd_doc_match_set_budget(int(nbytes)))
+
+
 def _ngram_query(next_fn, infgram_fn, handle, batch, sym_dtype, cap: int, backoff: bool, min_count: int, max_len: int):
     """the continuation query of either index (``next_fn`` / ``infgram_fn`` of its ABI) over an uploaded ``batch`` of patterns ->
     ``(suffix_len, lo, hi, at_end, list_off, symbols, counts)``; a listing longer than ``cap`` entries is asked for again with
@@ -1568,6 +1650,34 @@ class DeviceIndex:
                                                ctypes.byref(total)))
             if total.value <= cap:
                 return [docs[loff[q]:loff[q + 1]].copy() for q in range(cnt)]
+            cap = int(total.value)
+
+    def doc_match(self, queries, clause_df: bool = False):
+        """EXTENSION: Boolean document queries.  A query is a sequence of clauses that must all hold (AND); a clause is one
+        pattern, a sequence of patterns of which any may occur (OR), or ``Not(...)`` of either.  -> ``df``, uint32 over the
+        queries: the number of documents each query holds in; with ``clause_df=True`` -> ``(df, clause_df)``, the second over
+        all clauses in the order given: the documents in each clause's own set.  A query without clauses holds in every
+        document, empty ones included."""
+        data, off, npat, coff, cfl, ncl, qoff, nq = _query_batch(queries)
+        df = np.zeros(nq, dtype=np.uint32)
+        cdf = np.zeros(ncl, dtype=np.uint32) if clause_df else None
+        _check(lib().sa_amd_index_doc_match(self._h, data.ctypes.data, off.ctypes.data, npat, coff.ctypes.data, cfl.ctypes.data, ncl,
+                                            qoff.ctypes.data, nq, df.ctypes.data if nq else None,
+                                            cdf.ctypes.data if clause_df and ncl else None))
+        return (df, cdf) if clause_df else df
+
+    def doc_match_list(self, queries) -> list:
+        """EXTENSION: per query of ``doc_match`` the uint32 array of the documents it holds in, in ascending document id"""
+        data, off, npat, coff, cfl, ncl, qoff, nq = _query_batch(queries)
+        loff = np.zeros(nq + 1, dtype=np.int64)
+        total = ctypes.c_int64(0)
+        cap = 1 << 16
+        while True:
+            docs = np.empty(cap, dtype=np.uint32)
+            _check(lib().sa_amd_index_doc_match_list(self._h, data.ctypes.data, off.ctypes.data, npat, coff.ctypes.data, cfl.ctypes.data, ncl,
+                                                     qoff.ctypes.data, nq, loff.ctypes.data, docs.ctypes.data, cap, ctypes.byref(total)))
+            if total.value <= cap:
+                return [docs[loff[q]:loff[q + 1]].copy() for q in range(nq)]
             cap = int(total.value)
 
     def enable_doc_freq(self) -> None:
@@ -2108,6 +2218,14 @@ class SuffixArray:
     def doc_list(self, patterns) -> list:
         """EXTENSION (the reference lacks it): the documents each pattern occurs in (see ``DeviceIndex.doc_list``)"""
         return self._index().doc_list(patterns)
+
+    def doc_match(self, queries, clause_df: bool = False):
+        """EXTENSION (the reference lacks it): documents per Boolean query (see ``DeviceIndex.doc_match``)"""
+        return self._index().doc_match(queries, clause_df)
+
+    def doc_match_list(self, queries) -> list:
+        """EXTENSION (the reference lacks it): the documents each Boolean query holds in (see ``DeviceIndex.doc_match_list``)"""
+        return self._index().doc_match_list(queries)
 
     def enable_doc_freq(self) -> None:
         """EXTENSION (the reference lacks it): keep the table ``doc_tf`` / ``doc_topk`` need (see ``DeviceIndex.enable_doc_freq``)"""

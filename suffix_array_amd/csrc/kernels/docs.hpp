@@ -33,17 +33,48 @@ __device__ __forceinline__ uint32_t doc_lookup(const uint32_t *__restrict__ off,
     return lo - 1;
 }
 
+// The sampled top level of the table: smp[k] = off[k * stride] for k < ns <= DOC_SAMPLES, staged by the whole workgroup
+// (THREADS threads); ends in a barrier.
+template <int THREADS>
+__device__ __forceinline__ void doc_stage_samples(uint32_t *__restrict__ smp, const uint32_t *__restrict__ off, uint32_t M, uint32_t stride,
+                                                  uint32_t ns, uint32_t n)
+{
+    for (uint32_t k = threadIdx.x; k < ns; k += THREADS) {
+        const uint64_t j = (uint64_t)k * stride;
+        smp[k] = j < M ? off[j] : n;
+    }
+    __syncthreads();
+}
+
+// doc(p) through the staged samples: the sample interval in LDS, then between two samples in the global table (at most
+// ceil(log2 stride) loads).  p >= n: DOC_NONE.
+__device__ __forceinline__ uint32_t doc_lookup_sampled(const uint32_t *__restrict__ smp, uint32_t ns, uint32_t stride,
+                                                       const uint32_t *__restrict__ off, uint32_t M, uint32_t n, uint32_t p)
+{
+    if (p >= n) return DOC_NONE;
+    uint32_t lo = 1, hi = ns;                                 // first k in [1, ns) with smp[k] > p, else ns
+    while (lo < hi) {
+        const uint32_t m = lo + (hi - lo) / 2;
+        if (smp[m] <= p) lo = m + 1; else hi = m;
+    }
+    const uint64_t k0 = (uint64_t)(lo - 1) * stride;          // off[k0] <= p; off[k0 + stride] > p where it exists
+    uint64_t e = k0 + stride;
+    if (e > M) e = M;
+    uint32_t a = (uint32_t)k0 + 1, b = (uint32_t)e;           // first j in [k0 + 1, e) with off[j] > p, else e
+    while (a < b) {
+        const uint32_t m = a + (b - a) / 2;
+        if (off[m] <= p) a = m + 1; else b = m;
+    }
+    return a - 1;
+}
+
 // pos[0 .. count) -> doc ids.  The workgroup stages off[0], off[s], off[2 s], ... (ns <= DOC_SAMPLES entries, s = stride) in LDS;
 // a lane finds its sample interval there and finishes between two samples in the global table (at most ceil(log2 s) loads).
 __global__ __launch_bounds__(DOC_THREADS) void k_doc_of(const uint32_t *__restrict__ pos, int64_t count, const uint32_t *__restrict__ off,
                                                        uint32_t M, uint32_t stride, uint32_t ns, uint32_t n, uint32_t *__restrict__ out)
 {
     __shared__ uint32_t smp[DOC_SAMPLES];
-    for (uint32_t k = threadIdx.x; k < ns; k += DOC_THREADS) {
-        const uint64_t j = (uint64_t)k * stride;
-        smp[k] = j < M ? off[j] : n;
-    }
-    __syncthreads();
+    doc_stage_samples<DOC_THREADS>(smp, off, M, stride, ns, n);
     const int64_t span = (int64_t)DOC_THREADS * DOC_ITEMS;
     for (int64_t base = (int64_t)blockIdx.x * span; base < count; base += (int64_t)gridDim.x * span) {
         uint32_t p[DOC_ITEMS];
@@ -56,24 +87,7 @@ __global__ __launch_bounds__(DOC_THREADS) void k_doc_of(const uint32_t *__restri
         for (int t = 0; t < DOC_ITEMS; ++t) {
             const int64_t i = base + (int64_t)t * DOC_THREADS + threadIdx.x;
             if (i >= count) continue;
-            uint32_t d = DOC_NONE;
-            if (p[t] < n) {
-                uint32_t lo = 1, hi = ns;                     // first k in [1, ns) with smp[k] > p, else ns
-                while (lo < hi) {
-                    const uint32_t m = lo + (hi - lo) / 2;
-                    if (smp[m] <= p[t]) lo = m + 1; else hi = m;
-                }
-                const uint64_t k0 = (uint64_t)(lo - 1) * stride;      // off[k0] <= p; off[k0 + stride] > p where it exists
-                uint64_t e = k0 + stride;
-                if (e > M) e = M;
-                uint32_t a = (uint32_t)k0 + 1, b = (uint32_t)e;       // first j in [k0 + 1, e) with off[j] > p, else e
-                while (a < b) {
-                    const uint32_t m = a + (b - a) / 2;
-                    if (off[m] <= p[t]) a = m + 1; else b = m;
-                }
-                d = a - 1;
-            }
-            out[i] = d;
+            out[i] = doc_lookup_sampled(smp, ns, stride, off, M, n, p[t]);
         }
     }
 }

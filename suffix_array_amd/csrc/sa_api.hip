@@ -26,6 +26,7 @@
 #include "host/lz.hpp"
 #include "host/match.hpp"
 #include "host/docs.hpp"
+#include "host/doc_match.hpp"
 #include "host/doc_repeats.hpp"
 #include "host/doc_tf.hpp"
 #include "host/substrings.hpp"
@@ -562,6 +563,44 @@ SA_EXPORT int32_t sa_amd_docs_set_chunk(int32_t slots)
 {
     const int32_t prev = sa::g_docs_chunk < 0 ? sa::DOC_CHUNK_DEFAULT : sa::g_docs_chunk;
     sa::g_docs_chunk = slots < 0 ? -1 : (slots < sa::DOC_CHUNK_MIN ? sa::DOC_CHUNK_MIN : (slots > sa::DOC_CHUNK_MAX ? sa::DOC_CHUNK_MAX : slots));
+    return prev;
+}
+
+// ---- Boolean document queries (host/doc_match.hpp, kernels/doc_match.hpp) ----
+
+SA_EXPORT int32_t sa_amd_index_doc_match(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t npat, const int32_t *clause_off,
+                                         const uint8_t *clause_flags, int32_t nclauses, const int32_t *query_off, int32_t nqueries, uint32_t *df,
+                                         uint32_t *clause_df)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::doc_match_args_valid(pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries)) return SA_AMD_EINVAL;
+    if (!ix->doc_off()) return SA_AMD_EINVAL;
+    return sa::doc_match_query(*ix, pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries, false, df, clause_df, nullptr,
+                               nullptr, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_index_doc_match_list(const sa_amd_index *ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t npat,
+                                              const int32_t *clause_off, const uint8_t *clause_flags, int32_t nclauses, const int32_t *query_off,
+                                              int32_t nqueries, int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    if (!ix || !sa::doc_match_args_valid(pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries)) return SA_AMD_EINVAL;
+    if (capacity < 0 || !list_off || !total_out || (capacity > 0 && !docs) || !ix->doc_off()) return SA_AMD_EINVAL;
+    return sa::doc_match_query(*ix, pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries, true, nullptr, nullptr, list_off,
+                               docs, capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT void sa_amd_last_doc_match_stats(sa_amd_doc_match_stats *out)
+{
+    if (out) *out = sa::g_last_doc_match_stats;
+}
+
+SA_EXPORT int64_t sa_amd_doc_match_set_budget(int64_t bytes)
+{
+    const int64_t prev = sa::g_dm_budget < 0 ? sa::DM_BUDGET_DEFAULT : sa::g_dm_budget;
+    sa::g_dm_budget = bytes < 0 ? -1 : (bytes < sa::DM_BUDGET_MIN ? sa::DM_BUDGET_MIN : (bytes > sa::DM_BUDGET_MAX ? sa::DM_BUDGET_MAX : bytes));
     return prev;
 }
 
