@@ -685,14 +685,48 @@ NO_CASE.update({fn: "no device work" for fn in (
     "sa_amd_release_cache", "sa_amd_device_count", "sa_amd_device_pci_bus_id", "sa_amd_strerror", "sa_amd_version", "sa_amd_profile_begin",
     "sa_amd_profile_begin_classes", "sa_amd_profile_end", "sa_amd_profile_kernel_name")})
 NO_CASE.update({fn: "works in the caller's block: tests/test_dirty_work_blocks.py fills that one" for fn in ts.CASES})
+# the sub-headers' functions: their own test files fill their blocks, with the same switch and the same patterns
+TOK32_ELSEWHERE = "tests/test_tokens32.py::test_routes_on_dirty_blocks"
+DOC_MATCH_ELSEWHERE = "tests/test_doc_match.py::test_recycled_blocks"
+TOK32_FNS = ("sa_amd_saca_u32", "sa_amd_tok32_index_create", "sa_amd_tok32_index_destroy", "sa_amd_tok32_index_sa", "sa_amd_tok32_index_search",
+             "sa_amd_tok32_index_next_tokens", "sa_amd_tok32_index_infgram", "sa_amd_tok32_index_infgram_score")
+NO_CASE.update({fn: "its blocks are filled by " + TOK32_ELSEWHERE for fn in TOK32_FNS})
+NO_CASE.update({fn: "its blocks are filled by " + DOC_MATCH_ELSEWHERE for fn in ("sa_amd_index_doc_match", "sa_amd_index_doc_match_list")})
+NO_CASE["sa_amd_last_doc_match_stats"] = "no route here records it: " + DOC_MATCH_ELSEWHERE + " compares it with the clean run under every pattern"
+NO_CASE["sa_amd_doc_match_set_budget"] = "a setter of a per-thread switch"
+NO_CASE["sa_amd_max_tokens_u32"] = "a size query: arithmetic on the host"
+SUB_HEADER_FNS = {"suffix_array_amd_tok32.h": set(TOK32_FNS) | {"sa_amd_max_tokens_u32"},
+                  "suffix_array_amd_docmatch.h": {"sa_amd_index_doc_match", "sa_amd_index_doc_match_list", "sa_amd_last_doc_match_stats",
+                                                  "sa_amd_doc_match_set_budget"}}
+
+
+def _test_functions_of(path):
+    """the names of the test functions a test file defines at its top level"""
+    with open(os.path.join(ROOT, path)) as f:
+        return set(re.findall(r"^def (test_\w+)\(", f.read(), re.M))
 
 
 def test_every_entry_point_of_the_header_has_a_dirty_block_case_or_a_reason():
-    with open(os.path.join(ROOT, "include", "suffix_array_amd.h")) as f:
-        header = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    declared = set(re.findall(r"\b(sa_amd_\w+)\s*\([^;{}()]*\)\s*;", header))
+    """the header is the whole interface: include/suffix_array_amd.h and every suffix_array_amd_*.h it includes.  A new sub-header
+    shows here as soon as the main header names it (and ts.interface_headers refuses one that it does not name)."""
+    import test_tokens32
+    headers = ts.interface_headers()
+    per_header = {name: set(re.findall(r"\b(sa_amd_\w+)\s*\([^;{}()]*\)\s*;", text)) for name, text in headers.items()}
+    declared = set().union(*per_header.values())
+    assert sum(len(v) for v in per_header.values()) == len(declared)  # (no function is declared twice)
     covered = {fn for r in ROUTES for fn in r.fns}
-    assert len(declared) >= 121 and covered <= declared and set(NO_CASE) <= declared
+    assert {k: v for k, v in per_header.items() if k != "suffix_array_amd.h"} == SUB_HEADER_FNS
+    assert len(SUB_HEADER_FNS["suffix_array_amd_tok32.h"] | SUB_HEADER_FNS["suffix_array_amd_docmatch.h"]) == 13
+    assert len(per_header["suffix_array_amd.h"]) >= 121 and "sa_amd_max_tokens_u16" in per_header["suffix_array_amd.h"]
+    # what the reasons of the sub-headers' functions name exists, and the 32-bit suite's own list is this one
+    for why in {w for w in NO_CASE.values() if "::" in w}:
+        for path, test in re.findall(r"(tests/\w+\.py)::(\w+)", why):
+            assert test in _test_functions_of(path), (path, test)
+    assert set(test_tokens32.DIRTY_FNS) == set(TOK32_FNS) and len(test_tokens32.DIRTY_FNS) == len(TOK32_FNS)
+    assert all(TOK32_ELSEWHERE in NO_CASE[fn] for fn in TOK32_FNS)
+    assert all(DOC_MATCH_ELSEWHERE in NO_CASE[fn] for fn in ("sa_amd_index_doc_match", "sa_amd_index_doc_match_list", "sa_amd_last_doc_match_stats"))
+    assert "last_doc_match_stats" not in GETTERS                      # (else it would be a getter of this file's routes)
+    assert len(declared) >= 134 and covered <= declared and set(NO_CASE) <= declared
     assert not covered & set(NO_CASE), sorted(covered & set(NO_CASE))
     assert declared == covered | set(NO_CASE), sorted(declared - covered - set(NO_CASE))
     assert all(NO_CASE.values()) and len({r.name for r in ROUTES}) == len(ROUTES)

@@ -321,9 +321,10 @@ class TokIndex:
         return sa.last_tok_stats()
 
 
-def token_rows(t, lst, distinct, backoff):
+def token_rows(t, lst, distinct, backoff, end=tokens_abi.END):
     """per distinct token query the row Expected takes, from the definitions and route models of tests/test_tokens_abi.py.  The
-    back-off is the bisection (backoff_model), which tests/test_grid_laps_abi.py pins to the definition that tries every length."""
+    back-off is the bisection (backoff_model), which tests/test_grid_laps_abi.py pins to the definition that tries every length.
+    end: the route models' sentinel, sym_end<Sym>() of the index's token type."""
     rows = []
     for p in distinct:
         p = [int(x) for x in p]
@@ -338,9 +339,9 @@ def token_rows(t, lst, distinct, backoff):
         searched = 0
         if cnt:
             run = [t[lst[i] + s] for i in range(lo + ae, hi)]
-            got, slots = tokens_abi.stream_route_model(run)
+            got, slots = tokens_abi.stream_route_model(run, end)
             assert got == listing and slots == cnt
-            got, searched = tokens_abi.search_route_model(run)
+            got, searched = tokens_abi.search_route_model(run, end)
             assert got == listing
         rows.append((s, lo, hi, ae, [v for v, _ in listing], [c for _, c in listing], cnt, searched, probes))
     return rows

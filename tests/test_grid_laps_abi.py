@@ -55,6 +55,7 @@ TK_THREADS = 256              # kernels/tokens.hpp
 TK_TILE = 2048
 TK_SPAN = 4
 TK_IMAGE_ITEMS = 8
+TK_IMAGE3_ITEMS = 16          # tokens per work-item of the 3-byte image pass (32-bit tokens)
 NGRAM_GRID = 16               # workgroups per CU: ngram_grid
 DOCS_UNIT_GRID = 16           # docs_unit_grid
 DOC_TF_GRID = 16              # the k_doc_tf launch of doc_tf_query
@@ -81,8 +82,14 @@ def tok_image_lap(cu):
     return cu * TOK_STREAM_GRID * TK_THREADS * TK_IMAGE_ITEMS
 
 
+def tok_image3_lap(cu):
+    """tokens one lap of k_tok_be_image3 takes"""
+    return cu * TOK_STREAM_GRID * TK_THREADS * TK_IMAGE3_ITEMS
+
+
 def tok_compact_lap(cu):
-    """entries of the byte-level array one lap of the compaction kernels takes"""
+    """entries of the byte-level array one lap of the compaction kernels takes, whatever the stride: a 16-bit text of n tokens has
+    2 n + 1 entries, a 32-bit one 3 n + 1"""
     return cu * TOK_STREAM_GRID * TK_SPAN * TK_TILE
 
 
@@ -91,9 +98,20 @@ def tok_range_lap(cu):
     return cu * TOK_STREAM_GRID * TK_THREADS
 
 
+def tok_id_range_lap(cu):
+    """tokens one lap of k_tok_id_range takes: the number of tok_range_lap, from a launch site of its own"""
+    return cu * TOK_STREAM_GRID * TK_THREADS
+
+
 def tok_build_size(cu):
     """tokens of the build that is just past one compaction lap (2 n + 1 entries, a partial last span)"""
     return tok_compact_lap(cu) // 2 + 3 * TK_TILE + 5
+
+
+def tok32_build_size(cu):
+    """tokens of the 32-bit build that is just past one lap of the image pass with a partial last group of 16 tokens; its 3 n + 1
+    entries lie between one and two compaction laps with a partial last span and a partial last tile"""
+    return tok_image3_lap(cu) + 1369
 
 
 def test_the_caps_and_the_tiles_are_the_ones_the_gpu_suite_sizes_by():
@@ -101,6 +119,7 @@ def test_the_caps_and_the_tiles_are_the_ones_the_gpu_suite_sizes_by():
     assert (ng["NG_THREADS"], ng["NG_WAVES"]) == (NG_THREADS, NG_THREADS // WAVE)
     assert (docs["DOC_THREADS"], docs["DOC_SCAN_TILE"]) == (DOC_THREADS, DOC_SCAN_TILE)
     assert (tok["TK_THREADS"], tok["TK_TILE"], tok["TK_SPAN"], tok["TK_IMAGE_ITEMS"]) == (TK_THREADS, TK_TILE, TK_SPAN, TK_IMAGE_ITEMS)
+    assert tok["TK_IMAGE3_ITEMS"] == TK_IMAGE3_ITEMS
     assert (TK_TILE, TK_SPAN) == (tokens_abi.TILE, tokens_abi.SPAN)
     assert grid_multiplier("ngram.hpp", "ngram_grid") == NGRAM_GRID
     assert grid_multiplier("docs.hpp", "docs_unit_grid") == DOCS_UNIT_GRID
@@ -110,14 +129,19 @@ def test_the_caps_and_the_tiles_are_the_ones_the_gpu_suite_sizes_by():
     for header, kernel, grid in (("ngram.hpp", "kernel", "ngram_grid(count)"), ("ngram.hpp", "k_infgram_suffix<uint8_t>", "ngram_grid(count)"),
                                  ("tokens.hpp", "k_tok_be_image", "tok_stream_grid(ceil_div(n, TK_IMAGE_ITEMS), TK_THREADS)"),
                                  ("tokens.hpp", "k_tok_sa_range", "tok_stream_grid((int64_t)n + 1, TK_THREADS)"),
+                                 ("tokens.hpp", "k_tok_be_image3", "tok_stream_grid(ceil_div(n, TK_IMAGE3_ITEMS), TK_THREADS)"),
+                                 ("tokens.hpp", "k_tok_id_range", "tok_stream_grid((int64_t)n, TK_THREADS)"),
                                  ("docs.hpp", "k_doc_count<true>", "docs_unit_grid((int64_t)units)"),
                                  ("docs.hpp", "k_doc_count<false>", "docs_unit_grid((int64_t)b.units)"),
                                  ("docs.hpp", "k_doc_emit", "docs_unit_grid((int64_t)units)")):
         assert re.search(r"hipLaunchKernelGGL\(\(?" + re.escape(kernel) + r"\)?, dim3\(" + re.escape(grid) + r"\)", _source("host", header)), kernel
     host_tok = _source("host", "tokens.hpp")
     assert "const unsigned grid = tok_stream_grid(ceil_div(L.tiles, TK_SPAN), 1);" in host_tok and "const unsigned grid = ngram_grid(count);" in host_tok
-    for kernel in ("k_tok_compact_count", "k_tok_compact_scatter", "k_tok_search", "(k_infgram_suffix<uint16_t>)"):
+    for kernel in ("k_tok_compact_count", "k_tok_compact_scatter", "k_tok_search", "(k_infgram_suffix<uint16_t>)", "(k_infgram_suffix<uint32_t>)"):
         assert "hipLaunchKernelGGL(" + kernel + ", dim3(grid)" in host_tok, kernel
+    # each of the 32-bit forms' own kernels is launched from one place: no second site with another grid
+    for kernel in ("k_tok_be_image3", "k_tok_id_range", "(k_infgram_suffix<uint32_t>)"):
+        assert host_tok.count("hipLaunchKernelGGL(" + kernel + ",") == 1, kernel
 
 
 def test_the_sizes_on_256_compute_units():
@@ -137,6 +161,30 @@ def test_the_sizes_on_256_compute_units():
         n = tok_build_size(cu)
         assert tok_compact_lap(cu) < 2 * n + 1 < 2 * tok_compact_lap(cu) and (-(-(2 * n + 1) // TK_TILE)) % TK_SPAN != 0
         assert n > 2 * tok_image_lap(cu) and tok_range_lap(cu) + 5 < n
+
+
+def test_the_sizes_of_the_32_bit_build_on_256_compute_units():
+    """the same for the build of tests/test_grid_laps32.py: 3 n + 1 entries, 16 tokens a work-item of the image pass"""
+    assert tok_image3_lap(256) == 8388608 and tok_id_range_lap(256) == tok_range_lap(256) == 524288
+    n = tok32_build_size(256)
+    length = 3 * n + 1
+    assert (n, length) == (8389977, 25169932)
+    assert tok_compact_lap(256) < length < 2 * tok_compact_lap(256)                   # the second lap of the compaction, ...
+    tiles = -(-length // TK_TILE)
+    assert tiles % TK_SPAN == 3 and length % TK_TILE == 12                              # ... a partial last span and a partial last tile
+    assert n % TK_IMAGE3_ITEMS == 9                                                     # a partial last group of the image pass, ...
+    assert tok_image3_lap(256) < n < tok_image3_lap(256) + TK_THREADS * TK_IMAGE3_ITEMS # ... which is just past its first lap
+    assert -(-(tiles + 1) // DOC_SCAN_TILE) == 7                                        # the count scan has seven tiles
+    assert 3 * n > 4 << 20                                                              # the byte builder is past gram_min_n
+    assert 1369 % TK_IMAGE3_ITEMS == 9
+    for cu in (1, 8, 104, 256, 304):                                                    # whatever the CU count: the same shape
+        assert (cu * 98304) % (TK_SPAN * TK_TILE) == 0 and 3 * tok_image3_lap(cu) == cu * 98304
+        n = tok32_build_size(cu)
+        length = 3 * n + 1
+        assert tok_compact_lap(cu) < length < 2 * tok_compact_lap(cu)
+        assert (-(-length // TK_TILE)) % TK_SPAN == 3 and length % TK_TILE == 12 and n % TK_IMAGE3_ITEMS == 9
+        assert tok_image3_lap(cu) + 5 < n - 1 and (n - 1) // TK_IMAGE3_ITEMS == n // TK_IMAGE3_ITEMS      # the cases of the range passes
+        assert 7 < tok_id_range_lap(cu) + 5 < n - 1 and tok_range_lap(cu) + 5 < n
 
 
 # ---------------------------------------------------------------- the lap batch ----

@@ -432,10 +432,24 @@ def _outs(v):
 
 # ---------------------------------------------------------------- the guard and the decoys (CPU) ----
 
+def interface_headers():
+    """name -> text without its comments of include/suffix_array_amd.h and of every suffix_array_amd_*.h it includes: the whole
+    interface.  A sub-header is seen because the main header names it, not because this function does."""
+    def plain(name):
+        with open(os.path.join(ROOT, "include", name)) as f:
+            return re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
+    main = "suffix_array_amd.h"
+    out = {main: plain(main)}
+    for name in re.findall(r'^#include "(suffix_array_amd_\w+\.h)"$', out[main], re.M):
+        out[name] = plain(name)
+    on_disk = {f for f in os.listdir(os.path.join(ROOT, "include")) if re.fullmatch(r"suffix_array_amd(_\w+)?\.h", f)}
+    assert set(out) == on_disk, sorted(on_disk ^ set(out))            # no C header lies beside them that the main one does not bring in
+    return out
+
+
 def declarations_with_a_stream():
-    """name -> parameter list of every declaration of include/suffix_array_amd.h that takes `void *stream`"""
-    with open(os.path.join(ROOT, "include", "suffix_array_amd.h")) as f:
-        header = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
+    """name -> parameter list of every declaration of the interface (interface_headers) that takes `void *stream`"""
+    header = "\n".join(interface_headers().values())
     found = {}
     for name, params in re.findall(r"\b(sa_amd_\w+)\s*\(([^;{}()]*)\)\s*;", header):
         params = [re.sub(r"\s+", " ", p).strip() for p in params.split(",")]
@@ -452,6 +466,10 @@ def wrapper_name(fn):
 def test_the_table_has_a_case_for_every_entry_point_with_a_stream():
     decl = declarations_with_a_stream()
     assert len(decl) >= 15 and set(decl) == set(CASES)
+    # the scan follows the main header's includes; the sub-headers declare host-pointer forms only, so the count is the main header's
+    headers = interface_headers()
+    assert len(headers) >= 3 and len(decl) == 15
+    assert all("void *stream" not in text for name, text in headers.items() if name != "suffix_array_amd.h")
     assert all(variants for variants in CASES.values())
 
 

@@ -254,21 +254,22 @@ def test_compaction_model_is_the_filter(n1):
 
 # ---------------------------------------------------------------- the continuation routes ----
 
-def stream_route_model(run):
+def stream_route_model(run, end=END):
     """the streaming route of k_tok_next: the range is read once, LOADS * 64 slots a trip; a lane compares its token with its
     left neighbour's; ranks from the ballot of the listed starts, counts from the next set bit of the ballot of all starts, the
-    last start of a ballot waits for the first start of a later one.  -> (listing, slots probed)"""
+    last start of a ballot waits for the first start of a later one.  end: the sentinel sym_end<Sym>(), 65 536 at 16 bits and
+    2^24 at 32.  -> (listing, slots probed)"""
     cnt = len(run)
     toks, counts = {}, {}
     listed, carry, pend = 0, -1, None
     for r in range(0, cnt, LOADS * WAVE):
         for k in range(LOADS):
             first = r + k * WAVE
-            b = [run[first + l] if first + l < cnt else END for l in range(WAVE)]
+            b = [run[first + l] if first + l < cnt else end for l in range(WAVE)]
             left = [carry] + b[:-1]
             carry = b[-1]
             start = [first + l < cnt and b[l] != left[l] for l in range(WAVE)]
-            lst = [start[l] and b[l] < END for l in range(WAVE)]
+            lst = [start[l] and b[l] < end for l in range(WAVE)]
             if not any(start):
                 continue
             starts = [l for l in range(WAVE) if start[l]]
@@ -290,11 +291,11 @@ def stream_route_model(run):
     return [(toks[i], counts[i]) for i in range(listed)], cnt
 
 
-def search_route_model(run):
+def search_route_model(run, end=END):
     """the boundary-search route: lane l probes the sample slot l (cnt - 1) / 63; between two samples with different tokens a
     lane finds every run start by one binary search for the first slot with a token above the last one found.  A lane's ranks
     start at the exclusive sum of the starts of the lanes before it; its last run ends at the first start of a later lane.
-    -> (listing, slots probed)"""
+    end: as in stream_route_model.  -> (listing, slots probed)"""
     cnt = len(run)
     pos = [l * (cnt - 1) // (WAVE - 1) for l in range(WAVE)]
     probes = WAVE
@@ -320,7 +321,7 @@ def search_route_model(run):
         later = [f[0][0] for f in found[l + 1:] if f]
         for j, (at, tok) in enumerate(found[l]):
             nxt = found[l][j + 1][0] if j + 1 < len(found[l]) else (later[0] if later else cnt)
-            if tok < END:
+            if tok < end:
                 listing.append((tok, nxt - at))
     return listing, probes
 
