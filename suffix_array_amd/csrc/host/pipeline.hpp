@@ -9,6 +9,7 @@
 #include "sort.hpp"
 #include "readback.hpp"
 
+#include <algorithm>
 #include <functional>
 
 namespace sa {
@@ -276,41 +277,54 @@ struct EarlyDownload {
     hipEvent_t ev = nullptr;
 };
 
-// One device-resident build, phase by phase.  The members are what the phases hand to each other; every phase returns an
-// SA_AMD_* status.  The blocking 4-byte read-backs that steer the host (how many suffixes are still tied, how many groups,
-// how many ranks changed) are the read_words calls inside the phases: each one names what it reads.
+// What is decided before the first key is built: geometry_and_probes fills it, every later phase reads it (const).  g_bits, the
+// bits of a slot, is part of the geometry too and stays in BuildCore, where the rounds read it.
+struct Route {
+    KeyParams P, Pp;                    // the key geometry, plain or gram form; Pp: the same with the bit-packed text (w.packed, != nullptr: initial_sort
+                                        //   writes it) -- every launch behind the key building takes Pp, the key building itself and the probes P
+    int sigma = 0, key_bits = 0, top_shift = 0;      // top_shift != 0: 32-bit first stage on the key bits from there up
+    int bucket_top_bits = 0;            // ... key bits its two global passes in front of the bucket sort order, first estimate (0: four global passes)
+    bool flat_text = false;             // short text whose byte values are equally frequent: narrower initial keys
+    bool unary = false;                 // a text of one byte value: the array was written directly, nothing else runs
+    bool force_dense = false, text_ok = false, probe_dense = false;
+    bool dense_expected() const { return force_dense || probe_dense || !text_ok; }      // rank doubling right behind the initial sort
+};
+// What initial_sort leaves: SA holds the suffixes in the order of their initial keys
+struct InitialOrder {
+    SortResult<uint64_t> sr;            // sr.keys: the initial keys in SA order (kept for the rank look-ups); 32-bit stage: the 8n-byte buffer of `sorted32`
+    const uint32_t *sorted32 = nullptr; // 32-bit stage: the sorted 32-bit keys (no 64-bit sorted array exists)
+    bool bucket_finished = false;       // ... and k_bucket_sort has already ordered the suffixes tied on those 32 bits by their low key bits
+    // Group-start flags (kernels/common.hpp, OS_HF_*): != nullptr: the last pass of the 64-bit initial sort wrote one flag byte per slot
+    // here instead of the sorted keys, and sr.keys holds true keys only at the ends of that pass's digit runs.  The first re-rank
+    // (group_heads, the rank set-up of the dense route) reads the flags; every other reader of the sorted keys gets them rebuilt first
+    // (rebuild_sorted_keys).  They live in w.keysC, which nothing else touches between the last sort pass and the end of the first k_rr_apply.
+    uint8_t *head_flags = nullptr;
+};
+// What the text-keyed rounds key by (open_lists) and where the tied list stands
+struct ListState {
+    KeyParams Ptext;
+    int s_sym = 0, tkb = 0;             // symbols per text round, bits of their packed key
+    int64_t tiles = 0, depth = 0;       // RR_TILE-element tiles of the whole array; symbols the current order is sorted by (grows with the text rounds)
+    bool ready = false;                 // (L.U, L.G, L.V) already hold the tied suffixes
+};
+enum class FirstRound { NONE, FINISHED32, FUSED64 };      // what ran straight from the sorted keys: fast_finish32, fused_first_text_round
+// What rank_setup_and_text_rounds leaves for the doubling rounds.  sparse: few tied suffixes, ranks looked up without an ISA;
+// isa_tail_ranks: the rank set-up of the dense route wrote tail ranks (k_rr_apply FTAIL)
+struct RankSetup { bool sparse = false, isa_tail_ranks = false; };
+
+// One device-resident build, phase by phase.  A phase takes what earlier phases decided or left (Route, InitialOrder, ListState, ...)
+// and returns an SA_AMD_* status; build_device is the sequence.  The blocking 4-byte read-backs that steer the host (how many suffixes
+// are still tied, how many groups, how many ranks changed) are the read_words calls inside the phases: each one names what it reads.
 struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the inputs, the tied list L and the re-rank launchers)
     EarlyDownload *early = nullptr;     // host-pointer callers: the array starts travelling before the last rounds are done
     bool trace = false;
     double trace_t = 0;
     double lap() { const double t = now_ms(), d = t - trace_t; trace_t = t; return d; }
-    bool timing_only() const            // diag library only: stop after the initial sort (array NOT finished)
-    {
 #ifdef SA_AMD_DIAG
-        return tn.timing_only_initial_sort;
+    bool timing_only() const { return tn.timing_only_initial_sort; }      // diag library only: stop after the initial sort (array NOT finished)
 #else
-        return false;
+    bool timing_only() const { return false; }
 #endif
-    }
-    // ---- key geometry and route (geometry_and_probes) ----
-    KeyParams P, Ptext;
-    int sigma = 0, key_bits = 0, top_shift = 0;
-    bool force_dense = false, text_ok = false, probe_dense = false;
-    // ---- initial order (initial_sort) ----
-    SortResult<uint64_t> sr;
-    const uint32_t *sorted32 = nullptr; // top-32 stage: the sorted 32-bit keys (no 64-bit sorted array exists)
-    int bucket_top_bits = 0;            // key bits the two global passes in front of the bucket sort order (0: four global passes)
-    bool flat_text = false;             // short text whose byte values are equally frequent: narrower initial keys (geometry_and_probes)
-    bool bucket_finished = false;       // ... and k_bucket_sort has already ordered the suffixes tied on those 32 bits by their low key bits
-    uint64_t *sorted0 = nullptr;        // the initial keys in SA order (kept for the rank look-ups)
-    // ---- the tied list L and its buffers (from first_round_from_sorted_keys on) ----
-    int64_t tiles = 0, depth = 0;       // tiles: RR_TILE-element tiles of the whole array (the re-rank steps straight from the initial order)
-    uint32_t m32 = 0;
-    bool lists_ready = false, finished32 = false, fused64 = false, sparse = false;
-    bool isa_tail_ranks = false;        // the rank set-up of the dense route wrote tail ranks (k_rr_apply FTAIL)
-    bool tnext_scanned = false;         // group_heads scanned w.tnext with its counts (k_rr_scan_round): the rank set-up launches no k_rr_scan_next
-    int s_sym = 0, tkb = 0;
-    bool unary_done = false;            // a text of one byte value: the array was written directly (geometry_and_probes), nothing else runs
     RoundState rs;                      // what one refinement round leaves for the next
 
     // Early download: called wherever (L.U, L.m) is the current tied list and every slot outside it is final
@@ -321,10 +335,8 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
         hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, st, dSA, (uint32_t)n);   // reference src/saca.rs:13 (the first chunk carries it)
         LAUNCH_CHECK(st);
         HIP_TRY(hipMemsetAsync(w.early_bits, 0, (((size_t)n + 1 + 31) / 32 + EARLY_THREADS) * 4, st));
-        int64_t blocks = ceil_div(L.m, 256 * 8);
-        if (blocks > 65536) blocks = 65536;
         if ((((uintptr_t)L.U) & 15) != 0) return SA_AMD_OK;       // (the list slabs are 256-byte aligned: cannot happen)
-        PROF(KC_MISC, L.m, st, hipLaunchKernelGGL((k_early_mark), dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t *)L.U, L.m, (uint32_t)early->off, w.early_bits));
+        PROF(KC_MISC, L.m, st, hipLaunchKernelGGL((k_early_mark), dim3(capped_grid(L.m, 256 * 8, 65536)), dim3(256), 0, st, (const uint32_t *)L.U, L.m, (uint32_t)early->off, w.early_bits));
         HIP_TRY(hipEventRecord(early->ev, st));
         early->started = true;
         early->m_snap = L.m;
@@ -361,45 +373,69 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
     // Bucket sort of the 32-bit first stage: which key bits do the global passes order?  16 (two passes of 8 bits) when an average
     // bucket fits the 10-pairs-per-thread shapes (n = 2^28: 4096 pairs; 2^29: 8192), 18 (two passes of NINE bits) for larger texts
     // (2^30: 2^18 buckets of 4096), 0 = four global passes.
-    int choose_bucket_bits() const
+    int choose_bucket_bits(const Route &R) const
     {
         if (tn.no_bucket_sort || n < tn.bucket_min_n || n <= 1) return 0;
-        const bool wide_ok = onesweep_on(w.ss, tn) && tn.onesweep32_shape == 0;      // (nine-bit digits: single-pass engine, default tile)
-        if (tn.bucket_bits == 18 && wide_ok) return 18;
+        if (tn.bucket_bits == 18 && wide_ok()) return 18;
         if (tn.bucket_bits == 16) return 16;
-        // (measured, random bytes and DNA: with the two key bits that travel in the values (initial_sort_top32) 18 bits win from about
-        // 4.9e8 suffixes on -- 2^29: 9.09 against 9.36 ms --, without them only where 16 bits no longer fit)
-        const bool value_bits = wide_ok && !tn.no_value_bits && !tn.no_text_keys && g_bits <= 30 &&
-                                ((sigma == 256 && P.bits == 8) || (sigma == 4 && P.bits == 2 && !tn.no_packed_text));
-        if (value_bits && (n >> 16) > 7500 && (n >> 18) * 10 <= bucket_cap_max() * 9) return 18;
+        // (measured, random bytes and DNA: with the two key bits that travel in the values (key_source32) 18 bits win from about
+        // 4.9e8 suffixes on -- 2^29: 9.09 against 9.36 ms --, without them only where 16 bits no longer fit).  Asked before the probe
+        // has set top_shift, so for the 32 that whole keys give: under SA_AMD_KEY_BITS < 64 the stage shifts by less and builds a
+        // key array, and the 18 bits chosen here for value bits get none -- that case is kept as it was.  (== 2: 30-bit indices; n >= 64 here.)
+        const bool value_bits = (n >> 16) > 7500 && key_source32(R, 18, 32).val_extra == 2;
+        if (value_bits && (n >> 18) * 10 <= bucket_cap_max() * 9) return 18;
         if ((n >> 16) * 10 <= bucket_cap(2) * 9) return 16;
-        if (wide_ok && (n >> 18) * 10 <= bucket_cap_max() * 9) return 18;
+        if (wide_ok() && (n >> 18) * 10 <= bucket_cap_max() * 9) return 18;
         if ((n >> 16) * 10 <= bucket_cap_max() * 9) return 16;
         return 0;
     }
-
+    bool wide_ok() const { return onesweep_on(w.ss, tn) && tn.onesweep32_shape == 0; }      // nine-bit digits, keys read from the text: single-pass engine, default tile
+    // Where the 32-bit stage's first global pass over `top_bits` (0: four passes) takes its keys, the stage shifting by top_shift.
+    // A text of all 256 byte values (code = byte, 8 symbols per key): the top 32 key bits are four text bytes -- the pass reads
+    // them from the text (a quarter of the bytes) and no key array is built in front of it; with four symbols (DNA) the bit-packed
+    // text is the stream of keys: it is packed first (n / 4 bytes instead of a key array of 4n), counted and read as it stands.
+    // Key bits for free: an index below 2^g_bits leaves 32 - g_bits bits of the value word unused, and the bucket sort stages
+    // 16 bits per pair of which 32 - top_bits are low key bits.  When both have room (texts of 0.6 - 1 GiB: 18 top bits, 30-bit
+    // indices) the first pass puts the two key bits BEHIND the 32 there and the bucket sort orders 34 bits: a quarter of the ties
+    // on all 32 bits are left for its round on the low key bits (1 GiB of DNA: 22 % of the suffixes -> 6 %).
+    struct KeySource32 { bool text_keys = false, packed_keys = false; int val_extra = 0; };      // (neither: a key array; val_extra: low key bits that travel in the values)
+    KeySource32 key_source32(const Route &R, int top_bits, int top_shift) const
+    {
+        KeySource32 s;
+        // (iota: the values are the indices and the first pass is counted)
+        const bool text_route = top_bits != 0 && iota(R) && top_shift == 32 && wide_ok() && !tn.no_text_keys;
+        s.text_keys = text_route && R.sigma == 256 && R.P.bits == 8;      // (eight bits a symbol: never packed)
+        s.packed_keys = text_route && R.sigma == 4 && R.P.bits == 2 && packs_text(R.P);
+        if ((s.text_keys || s.packed_keys) && !tn.no_value_bits) {
+            s.val_extra = std::max(0, std::min(std::min(32 - g_bits, BK_MAX_LBITS - (32 - top_bits)), 2));
+        }
+        return s;
+    }
+    // alphabets of 2, 4 or 16 symbols: k_build_keys also writes the text as bit-packed codes, which every later random
+    // read of the text uses instead (a key becomes a bit field of two words; DNA shrinks to a quarter: cache-resident)
+    bool packs_text(const KeyParams &P) const { return (P.bits == 1 || P.bits == 2 || P.bits == 4) && n >= 64 && !tn.no_packed_text; }
+    uint8_t *packed_out(const Route &R) const { return R.Pp.packed ? w.packed : (uint8_t *)nullptr; }      // where the key building writes it
     bool flat_rule_applies() const { return n >= 2 && n < tn.top32_probe_min_n && n < ((int64_t)1 << 24) && !tn.no_flat_rule; }
 
     // the rank set-up of the dense route (ISA_MODE 0: direct ISA stores, 2: ranks for the binned scatter): tail or head ranks,
     // groups from the flags or from the sorted keys
     template <int ISA_MODE>
-    int rr_apply_setup(const RrApply &a)
+    int rr_apply_setup(const InitialOrder &O, bool tail, RrApply a)
     {
-        const uint64_t *k = sr.keys;
-        if (head_flags)
-            return isa_tail_ranks ? rr_apply<true, false, ISA_MODE, uint64_t, true, true>(k, a) : rr_apply<true, false, ISA_MODE, uint64_t, false, true>(k, a);
-        return isa_tail_ranks ? rr_apply<true, false, ISA_MODE, uint64_t, true>(k, a) : rr_apply<true, false, ISA_MODE>(k, a);
+        const uint64_t *k = O.sr.keys;
+        a.status = O.head_flags;
+        if (O.head_flags)
+            return tail ? rr_apply<true, false, ISA_MODE, uint64_t, true, true>(k, a) : rr_apply<true, false, ISA_MODE, uint64_t, false, true>(k, a);
+        return tail ? rr_apply<true, false, ISA_MODE, uint64_t, true>(k, a) : rr_apply<true, false, ISA_MODE>(k, a);
     }
     // Flags were emitted but the route that follows reads the sorted keys (compaction for the text rounds, rank look-ups of the
     // sparse rounds): sr.keys[i] = the initial key of suffix SA[i], by the device function those look-ups compare with.  Rare in
     // real use (the flags are asked for only when the dense route is expected) and dear: about 50 ms at 256 MiB with gram keys.
-    int rebuild_sorted_keys()
+    int rebuild_sorted_keys(const Route &R, InitialOrder &O)
     {
-        if (!head_flags) return SA_AMD_OK;
-        int64_t blocks = ceil_div(n, GK_THREADS);
-        if (blocks > 65536) blocks = 65536;
-        PROF(KC_GATHER, n, st, hipLaunchKernelGGL((k_keys_of_suffixes), dim3((unsigned)blocks), dim3(GK_THREADS), 0, st, dT, P, n, (const uint32_t *)SA, sr.keys));
-        head_flags = nullptr;
+        if (!O.head_flags) return SA_AMD_OK;
+        PROF(KC_GATHER, n, st, hipLaunchKernelGGL((k_keys_of_suffixes), dim3(capped_grid(n, GK_THREADS, 65536)), dim3(GK_THREADS), 0, st, dT, R.Pp, n, (const uint32_t *)SA, O.sr.keys));
+        O.head_flags = nullptr;
         if (trace) fprintf(stderr, "suffix_array_amd: sorted keys rebuilt from the suffix array (the route taken reads them)\n");
         return SA_AMD_OK;
     }
@@ -418,17 +454,18 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
         const uint32_t H = (uint32_t)S * 4u;
         HIP_TRY(hipMemsetAsync(w.keysB, 0xff, (size_t)H * 8, st));
         HIP_TRY(hipMemsetAsync(w.total, 0, zero_bytes, st));
-        PROF(KC_MISC, S, st, hipLaunchKernelGGL((k_count_sample_dups), dim3((unsigned)(ceil_div(S, 256) < 4096 ? ceil_div(S, 256) : 4096)), dim3(256), 0, st, (const uint64_t *)w.keysA, S,
+        PROF(KC_MISC, S, st, hipLaunchKernelGGL((k_count_sample_dups), dim3(capped_grid(S, 256, 4096)), dim3(256), 0, st, (const uint64_t *)w.keysA, S,
                                                 (unsigned long long *)w.keysB, H - 1u, w.total));
         return SA_AMD_OK;
     }
     // the 64-bit initial keys (plain or gram form) into w.keysA, with the first sort pass's digit counts when the sort wants them
-    int build_keys64(uint32_t *vals0, uint8_t *packed_out, const FirstCounts &fc, bool counted)
+    int build_keys64(const Route &R, const FirstCounts &fc, bool counted)
     {
-        const int nb0 = key_bits < RADIX_BITS ? key_bits : RADIX_BITS;
-        const unsigned grid = (unsigned)ceil_div(ceil_div(n, KB_TILE), KB_TPW);
-        PROF(KC_BUILD_KEYS, n, st, hipLaunchKernelGGL((P.gram > 0 ? k_build_keys<false, true> : k_build_keys<false>), dim3(grid), dim3(KB_THREADS), 0, st, dT, n, P, w.keysA, vals0,
-                                                      (uint32_t *)nullptr, 0, packed_out, counted ? fc.counts : (uint32_t *)nullptr, fc.chunk_elems, fc.G, (1u << nb0) - 1u, 0));
+        const int nb0 = R.key_bits < RADIX_BITS ? R.key_bits : RADIX_BITS;
+        uint32_t *vals0 = iota(R) ? (uint32_t *)nullptr : w.valsA;
+        PROF(KC_BUILD_KEYS, n, st, hipLaunchKernelGGL((R.P.gram > 0 ? k_build_keys<false, true> : k_build_keys<false>), dim3((unsigned)ceil_div(ceil_div(n, KB_TILE), KB_TPW)),
+                                                      dim3(KB_THREADS), 0, st, dT, n, R.P, w.keysA, vals0,
+                                                      (uint32_t *)nullptr, 0, packed_out(R), counted ? fc.counts : (uint32_t *)nullptr, fc.chunk_elems, fc.G, (1u << nb0) - 1u, 0));
         return SA_AMD_OK;
     }
     // the records of the fast finish of the 32-bit first stage (k_finish_sorted, or k_bucket_sort on its behalf) start from zero
@@ -443,20 +480,14 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
     }
 
     // 1-2. which byte values occur -> symbol codes and key geometry; entropy probe, repeat probe, gram keys (read-backs: the 256 presence flags, two duplicate counts, the number of grams in use)
-    int geometry_and_probes()
+    int geometry_and_probes(Route &R)
     {
         int rc;
         // 1. sigma = 256 histogram -> symbol codes, bits per symbol, symbols per key
         HIP_TRY(hipMemsetAsync(w.hist, 0, 256 * 4, st));
-        {
-            int64_t blocks = ceil_div(ceil_div(n, 16), BH_THREADS);
-            if (blocks > 2048) blocks = 2048;
-            if (blocks < 1) blocks = 1;
-            // (texts below the entropy probe's size: with counts, for the flat-histogram rule below)
-            const bool counts = flat_rule_applies();
-            if (counts) PROF(KC_BYTE_HIST, n, st, hipLaunchKernelGGL((k_byte_hist_counts), dim3((unsigned)(blocks > 256 ? 256 : blocks)), dim3(BH_THREADS), 0, st, dT, n, w.hist));
-            else PROF(KC_BYTE_HIST, n, st, hipLaunchKernelGGL((k_byte_hist), dim3((unsigned)blocks), dim3(BH_THREADS), 0, st, dT, n, w.hist));
-        }
+        // (texts below the entropy probe's size: with counts, for the flat-histogram rule below)
+        if (flat_rule_applies()) PROF(KC_BYTE_HIST, n, st, hipLaunchKernelGGL((k_byte_hist_counts), dim3(capped_grid(ceil_div(n, 16), BH_THREADS, 256)), dim3(BH_THREADS), 0, st, dT, n, w.hist));
+        else PROF(KC_BYTE_HIST, n, st, hipLaunchKernelGGL((k_byte_hist), dim3(capped_grid(ceil_div(n, 16), BH_THREADS, 2048)), dim3(BH_THREADS), 0, st, dT, n, w.hist));
         uint32_t hist[256];
         { const int rcw = read_words(hist, w.hist, sizeof(hist), st); if (rcw) return rcw; }
         // Texts too short for the entropy probe (a sampling pass and a read-back of its own): byte values that are all equally
@@ -473,31 +504,30 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
                 int kb = (bit_length((uint64_t)(n - 1)) + 20 + 7) / 8 * 8;
                 if (kb < 32) kb = 32;
                 if (kb < kb_max) kb_max = kb;
-                flat_text = true;
+                R.flat_text = true;
             }
         }
-        key_bits = make_key_params(hist, &P, &sigma, kb_max);      // (gram keys, step 2c, may shorten it)
-        local.sigma = sigma; local.bits_per_symbol = P.bits; local.symbols_per_key = P.k;
-        if (sigma == 1 && !tn.no_unary_shortcut) {
+        KeyParams &P = R.P;
+        int &key_bits = R.key_bits, &top_shift = R.top_shift;
+        key_bits = make_key_params(hist, &P, &R.sigma, kb_max);      // (gram keys, step 2c, may shorten it)
+        local.sigma = R.sigma; local.bits_per_symbol = P.bits; local.symbols_per_key = P.k;
+        if (R.sigma == 1 && !tn.no_unary_shortcut) {
             // one byte value repeated: every suffix is a proper prefix of every longer one, the order is by length.  (The general
             // path gets there too -- 23 doubling rounds over one group of n members, 214 ms at 256 MiB -- and stays tested.)
-            int64_t blocks = ceil_div(n, 256 * 16);
-            if (blocks > 16384) blocks = 16384;
-            PROF(KC_MISC, n, st, hipLaunchKernelGGL((k_fill_descending), dim3((unsigned)blocks), dim3(256), 0, st, SA, n));
-            unary_done = true;
+            PROF(KC_MISC, n, st, hipLaunchKernelGGL((k_fill_descending), dim3(capped_grid(n, 256 * 16, 16384)), dim3(256), 0, st, SA, n));
+            R.unary = true;
             return SA_AMD_OK;
         }
 
         g_bits = bit_length((uint64_t)(n - 1 > 0 ? n - 1 : 1));
-        bucket_top_bits = choose_bucket_bits();
-        force_dense = tn.force_dense;
-        text_ok = !force_dense && !tn.no_text_rounds;
+        R.bucket_top_bits = choose_bucket_bits(R);
+        R.force_dense = tn.force_dense;
+        R.text_ok = !R.force_dense && !tn.no_text_rounds;
         rs.local_ok = !tn.no_local_sort;
 
         // 2. entropy probe: do the top 32 key bits already separate (almost) all suffixes?  Then the initial
         //    sort only needs those 4 digits and a cheap round on the low bits finishes the few ties.
-        top_shift = 0;
-        if (text_ok && rs.local_ok && key_bits > 32 && !tn.no_top32) {
+        if (R.text_ok && rs.local_ok && key_bits > 32 && !tn.no_top32) {
             bool use = tn.force_top32;
             if (!use && n >= tn.top32_probe_min_n) {
                 // 2^20 samples, fewer for texts below 8 Mi suffixes (a power of two: the duplicate count hashes into 4 S slots)
@@ -507,7 +537,7 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
                                                         key_bits - 32, w.keysA));
                 if ((rc = count_sample_dups(S, 8))) return rc;
                 // the same samples, counted per bucket of the bucket sort: an estimate of its largest bucket (word 1 of the read-back)
-                const int tb = choose_bucket_bits();
+                const int tb = R.bucket_top_bits;
                 if (tb) {
                     HIP_TRY(hipMemsetAsync(w.keysC, 0, ((size_t)1 << tb) * 4, st));
                     // (a quarter of the samples is enough to tell a bucket with a tenth of the text from a flat one, and a quarter of the atomics)
@@ -524,7 +554,7 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
                     // (a flat text of 2^28 bytes: 4 samples per bucket on average, the fullest holds about 14 -> 14 336 estimated, 4400 true)
                     const double est = (double)two[1] * (double)n / (double)(S / 4);
                     if (tb && est > 3.0 * (double)bucket_cap_max()) {
-                        bucket_top_bits = 0;
+                        R.bucket_top_bits = 0;
                         if (trace) fprintf(stderr, "suffix_array_amd: bucket sort of the 32-bit first stage: largest bucket estimated at %.0f suffixes -> four global passes\n", est);
                     }
                 }
@@ -559,8 +589,7 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
         // 2b. repeat probe (texts the first probe did not send to the 32-bit route): the fraction of suffixes that share
         //     2k symbols with another suffix.  Many (copied passages, a corpus): the text-keyed rounds cannot finish, so rank
         //     doubling starts right after the initial sort (measured on C3: 64 ms against 68 ms); few: text-keyed rounds.
-        probe_dense = false;
-        if (text_ok && rs.local_ok && !top_shift && !force_dense && !tn.no_repeat_probe && n >= ((int64_t)1 << 24)) {
+        if (R.text_ok && rs.local_ok && !top_shift && !tn.no_repeat_probe && n >= ((int64_t)1 << 24)) {      // (text_ok: not force_dense)
             const int64_t S = (int64_t)1 << 20;
             PROF(KC_MISC, S, st, hipLaunchKernelGGL((k_sample_repeat_keys), dim3((unsigned)ceil_div(S, GK_THREADS)), dim3(GK_THREADS), 0, st, dT, P, n, S,
                                                     w.keysA));
@@ -569,168 +598,142 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
             { const int rcw = read_words(&dups, w.total, 4, st); if (rcw) return rcw; }
             const double chance = (double)S * (double)S / 8589934592.0;           // 32-bit hash collisions among S samples
             const double frac = ((double)dups - chance) * (double)n / ((double)S * (double)S);
-            probe_dense = frac > 0.04;
+            R.probe_dense = frac > 0.04;
             if (trace) fprintf(stderr, "suffix_array_amd: repeat probe: %u duplicates among %lld samples (repeat index %.3f, threshold 0.04) -> %s\n",
-                               dups, (long long)S, frac, probe_dense ? "rank doubling from the start" : "text-keyed rounds");
+                               dups, (long long)S, frac, R.probe_dense ? "rank doubling from the start" : "text-keyed rounds");
         }
 
         // 2c. gram keys (texts that did not take the 32-bit route): choose_gram_keys measures and decides; the probes above keep
         //     using the plain key
-        if (!top_shift && !tn.no_gram_keys && n >= tn.gram_min_n && n >= 2 && sigma >= 2 && tn.key_bits_max == 64) {
-            const int rcg = choose_gram_keys(dT, n, &P, &key_bits, w, st, tn, trace);
-            if (rcg) return rcg;
+        if (!top_shift && !tn.no_gram_keys && n >= tn.gram_min_n && n >= 2 && R.sigma >= 2 && tn.key_bits_max == 64) {
+            if ((rc = choose_gram_keys(dT, n, &P, &key_bits, w, st, tn, trace))) return rc;
             local.bits_per_symbol = P.bits; local.symbols_per_key = P.k;
         }
-
+        R.Pp = P;
+        if (packs_text(P)) R.Pp.packed = w.packed;
         return SA_AMD_OK;
     }
 
     // 4b. the 32-bit first stage: the top 32 key bits as (u32, u32) pairs -- two global passes + the in-LDS bucket sort, or four
-    //     global passes (read-back: the largest bucket)
-    int initial_sort_top32(uint32_t *vals0, uint8_t *packed_out, bool iota)
+    //     global passes (read-back: the largest bucket).  Its keys for passes over `top_bits` (key_source32) and the sort they go into:
+    bool iota(const Route &R) const { return n >= 2 && R.key_bits > 0; }      // value of pair i = i: not stored by k_build_keys, the first sort pass takes the index (saves 8 B / suffix)
+    int top32_keys(const Route &R, int top_bits, SortJob<uint32_t> *job)
+    {
+        // the first radix pass's digit histogram comes out of k_build_keys (keys in registers there): one read of every key less
+        const FirstCounts fc = sort_first_counts(w.ss, tn, n, true);
+        const bool counted = n > 1;
+        const int rbits = top_bits == 18 ? 9 : RADIX_BITS;
+        const KeySource32 ks = key_source32(R, top_bits, R.top_shift);
+        uint8_t *const packed_out = this->packed_out(R);
+        if (counted) HIP_TRY(hipMemsetAsync(fc.zero_ptr, 0, fc.zero_bytes, st));
+        if (ks.text_keys || ks.packed_keys) {
+            int split = 2048 / fc.G;
+            while (split > 1 && fc.chunk_elems / split < 16384) split /= 2;
+            const int64_t sub = (ceil_div(fc.chunk_elems, split) + 15) & ~(int64_t)15;
+            if (ks.packed_keys) {
+                PROF(KC_BUILD_KEYS, n, st, hipLaunchKernelGGL((k_pack_text2), dim3(capped_grid(ceil_div(n, 16), 256, 16384)), dim3(256), 0, st, dT, n, R.P, packed_out));
+                PROF(KC_BUILD_KEYS, n, st, hipLaunchKernelGGL((k_packed2_upsweep32), dim3((unsigned)(fc.G * split)), dim3(SORT_THREADS), 0, st, (const uint8_t *)packed_out, n,
+                                                              fc.counts, 32 - top_bits, (1u << rbits) - 1u, fc.chunk_elems, fc.G, split, sub));
+            } else
+            PROF(KC_BUILD_KEYS, n, st, hipLaunchKernelGGL((k_text_upsweep32), dim3((unsigned)(fc.G * split)), dim3(SORT_THREADS), 0, st, dT, n, fc.counts,
+                                                          32 - top_bits, (1u << rbits) - 1u, fc.chunk_elems, fc.G, split, sub));
+        } else
+        PROF(KC_BUILD_KEYS, n, st, hipLaunchKernelGGL((k_build_keys<true>), dim3((unsigned)ceil_div(ceil_div(n, KB_TILE), KB_TPW)), dim3(KB_THREADS), 0, st, dT, n, R.P,
+                                                      (uint64_t *)nullptr, iota(R) ? (uint32_t *)nullptr : w.valsA, (uint32_t *)w.keysA, R.top_shift, packed_out,
+                                                      counted ? fc.counts : (uint32_t *)nullptr, fc.chunk_elems, fc.G, (1u << rbits) - 1u, top_bits ? 32 - top_bits : 0));
+        *job = SortJob<uint32_t>{ (uint32_t *)w.keysA, w.valsA, (uint32_t *)w.keysB, w.valsB, n, top_bits ? 32 - top_bits : 0, 32 };
+        job->iota = iota(R); job->first_counted = counted;
+        if (top_bits) {
+            job->rbits = rbits;
+            job->text = ks.text_keys ? dT : (ks.packed_keys ? (const uint8_t *)packed_out : (const uint8_t *)nullptr);
+            job->text_n = n; job->text_bits = ks.packed_keys ? 2 : 8;
+            job->val_extra = ks.val_extra;
+        }
+        return SA_AMD_OK;
+    }
+    // Bucket route: two global passes over the top 16 key bits + one pass that orders every bucket (= value of those bits) in LDS,
+    // when an average bucket fits a workgroup well (n = 2^28: 4096 pairs, 2^29: 8192); larger texts take two passes of NINE bits
+    // (2^30: 2^18 buckets of 4096).  May decline (*done = false, nothing written to SA): a text whose LARGEST bucket fits no
+    // workgroup -- known only once the two passes have run -- builds its keys again and takes the four global passes.
+    int top32_bucket_route(const Route &R, InitialOrder &O, bool *done)
     {
         int rc;
-        uint32_t *k32a = (uint32_t *)w.keysA, *k32b = (uint32_t *)w.keysB;
-        // Two global passes over the top 16 key bits + one pass that orders every bucket (= value of those bits) in LDS, when an
-        // average bucket fits a workgroup well (n = 2^28: 4096 pairs, 2^29: 8192); larger texts take two passes of NINE bits
-        // (2^30: 2^18 buckets of 4096).  A text whose LARGEST bucket fits no workgroup -- known only once the two passes have
-        // run -- builds its keys again and takes the four global passes.
-        int top_bits = bucket_top_bits;      // 0: four global passes (choose_bucket_bits, the probe's estimate of the largest bucket)
-        for (;;) {
-            // the first radix pass's digit histogram comes out of k_build_keys (keys in registers there): one read of every key less
-            const FirstCounts fc = sort_first_counts(w.ss, tn, n, true);
-            const bool counted = n > 1;
-            const int rbits = top_bits == 18 ? 9 : RADIX_BITS;
-            // a text of all 256 byte values (code = byte, 8 symbols per key): the top 32 key bits are four text bytes -- the first
-            // global pass reads them from the text (a quarter of the bytes) and no key array is built in front of it
-            const bool text_route = top_bits != 0 && counted && iota && top_shift == 32 && onesweep_on(w.ss, tn) && tn.onesweep32_shape == 0 && !tn.no_text_keys;
-            const bool text_keys = text_route && sigma == 256 && P.bits == 8 && packed_out == nullptr;
-            // ... and with four symbols (DNA) the bit-packed text is the stream of keys: it is packed first (n / 4 bytes instead of a
-            // key array of 4n), and counted and read by the first pass as it stands
-            const bool packed_keys = text_route && sigma == 4 && P.bits == 2 && packed_out != nullptr;
-            // Key bits for free: an index below 2^g_bits leaves 32 - g_bits bits of the value word unused, and the bucket sort stages
-            // 16 bits per pair of which 32 - top_bits are low key bits.  When both have room (texts of 0.6 - 1 GiB: 18 top bits, 30-bit
-            // indices) the first pass puts the two key bits BEHIND the 32 there and the bucket sort orders 34 bits: a quarter of the ties
-            // on all 32 bits are left for its round on the low key bits (1 GiB of DNA: 22 % of the suffixes -> 6 %).
-            int val_extra = 0;
-            if ((text_keys || packed_keys) && !tn.no_value_bits) {
-                val_extra = 32 - g_bits;
-                if (val_extra > BK_MAX_LBITS - (32 - top_bits)) val_extra = BK_MAX_LBITS - (32 - top_bits);
-                if (val_extra > 2) val_extra = 2;
-                if (val_extra < 0) val_extra = 0;
-            }
-            if (counted) HIP_TRY(hipMemsetAsync(fc.zero_ptr, 0, fc.zero_bytes, st));
-            if (text_keys || packed_keys) {
-                int split = 2048 / fc.G;
-                while (split > 1 && fc.chunk_elems / split < 16384) split /= 2;
-                const int64_t sub = (ceil_div(fc.chunk_elems, split) + 15) & ~(int64_t)15;
-                if (packed_keys) {
-                    int64_t pblocks = ceil_div(ceil_div(n, 16), 256);
-                    if (pblocks > 16384) pblocks = 16384;
-                    PROF(KC_BUILD_KEYS, n, st, hipLaunchKernelGGL((k_pack_text2), dim3((unsigned)pblocks), dim3(256), 0, st, dT, n, P, packed_out));
-                    PROF(KC_BUILD_KEYS, n, st, hipLaunchKernelGGL((k_packed2_upsweep32), dim3((unsigned)(fc.G * split)), dim3(SORT_THREADS), 0, st, (const uint8_t *)packed_out, n,
-                                                                  fc.counts, 32 - top_bits, (1u << rbits) - 1u, fc.chunk_elems, fc.G, split, sub));
-                } else
-                PROF(KC_BUILD_KEYS, n, st, hipLaunchKernelGGL((k_text_upsweep32), dim3((unsigned)(fc.G * split)), dim3(SORT_THREADS), 0, st, dT, n, fc.counts,
-                                                              32 - top_bits, (1u << rbits) - 1u, fc.chunk_elems, fc.G, split, sub));
-            } else
-            PROF(KC_BUILD_KEYS, n, st, hipLaunchKernelGGL((k_build_keys<true>), dim3((unsigned)ceil_div(ceil_div(n, KB_TILE), KB_TPW)), dim3(KB_THREADS), 0, st, dT, n, P,
-                                                          (uint64_t *)nullptr, vals0, k32a, top_shift, packed_out,
-                                                          counted ? fc.counts : (uint32_t *)nullptr, fc.chunk_elems, fc.G, (1u << rbits) - 1u, top_bits ? 32 - top_bits : 0));
-            SortResult<uint32_t> s32;
-            SortJob<uint32_t> job{ k32a, w.valsA, k32b, w.valsB, n, top_bits ? 32 - top_bits : 0, 32 };
-            job.iota = iota; job.first_counted = counted;
-            if (top_bits) {
-                job.rbits = rbits;
-                job.text = text_keys ? dT : (packed_keys ? (const uint8_t *)packed_out : (const uint8_t *)nullptr);
-                job.text_n = n; job.text_bits = packed_keys ? 2 : 8;
-                job.val_extra = val_extra;
-                rc = sort_pairs32(job, w.ss, st, tn, &s32, &local);
-                if (rc) return rc;
-                uint32_t *kout = (s32.keys == k32a) ? k32b : k32a;
-                bool done = false, fused = false;
-                uint32_t largest = 0;
-                // the round on the low key bits of the suffixes tied on all 32 (first_round_from_sorted_keys) in the same launch
-                const bool fuse = rs.local_ok && !tn.no_fused_finish && !tn.no_bucket_finish && !timing_only();
-                BucketFinish F = BucketFinish();
-                KeySrc K = KeySrc();
-                if (fuse) {
-                    if ((rc = zero_finish_records())) return rc;
-                    F.T = dT; F.n = n; F.cap = tn.group_cap; F.surv_bits = w.surv_bits; F.surv_head = w.isa; F.tile_cnt = w.tcnt; F.counters = w.total;
-                    K.mode = KS_LOWKEY; K.kb = top_shift;
-                }
-                KeyParams Pf = P;
-                Pf.packed = packed_out;             // (written by now: the fused round's text look-ups take the bit-packed text, a quarter of the lines)
-                rc = bucket_sort32(s32.keys, s32.vals, kout, SA, n, top_bits, w.bk_start, w.ss.err + 2, st, tn, &done, &largest,
-                                   fuse ? &F : nullptr, &Pf, &K, &fused, val_extra);
-                if (rc) return rc;
-                bucket_finished = done && fused;
-                if (trace) fprintf(stderr, "suffix_array_amd: 32-bit first stage: %d global passes over the top %d key bits, largest bucket %u -> %s\n", s32.passes, top_bits, largest,
-                                   done ? (fused ? "low bits and ties on all 32 ordered bucket by bucket in LDS" : "low bits ordered bucket by bucket in LDS")
-                                        : "too large: keys rebuilt, four global passes");
-                if (!done) { top_bits = 0; continue; }      // (nothing was launched: the finish buffers are zeroed again by whoever uses them)
-                local.sort_passes += 1; local.sorted_elements += n;
-                sorted32 = kout;
-                sr.vals = SA; sr.passes = s32.passes + 1;
-                sr.keys = (kout == k32a) ? w.keysA : w.keysB;
-                break;
-            }
-            job.final_vals = SA;
-            rc = sort_pairs32(job, w.ss, st, tn, &s32, &local);
-            if (rc) return rc;
-            sorted32 = s32.keys;
-            sr.vals = s32.vals; sr.passes = s32.passes;
-            sr.keys = (s32.keys == k32a) ? w.keysA : w.keysB;      // the 8n-byte buffer that now holds the sorted 32-bit keys
-            break;
+        const int top_bits = R.bucket_top_bits;
+        SortJob<uint32_t> job{}; SortResult<uint32_t> s32;
+        if ((rc = top32_keys(R, top_bits, &job)) || (rc = sort_pairs32(job, w.ss, st, tn, &s32, &local))) return rc;
+        uint32_t *kout = (s32.keys == job.keys_in) ? job.keys_alt : job.keys_in;
+        bool fused = false; uint32_t largest = 0;
+        // the round on the low key bits of the suffixes tied on all 32 (fast_finish32) in the same launch
+        const bool fuse = rs.local_ok && !tn.no_fused_finish && !tn.no_bucket_finish && !timing_only();
+        BucketFinish F = BucketFinish(); KeySrc K = KeySrc();
+        if (fuse) {
+            if ((rc = zero_finish_records())) return rc;
+            F.T = dT; F.n = n; F.cap = tn.group_cap; F.surv_bits = w.surv_bits; F.surv_head = w.isa; F.tile_cnt = w.tcnt; F.counters = w.total;
+            K.mode = KS_LOWKEY; K.kb = R.top_shift;
         }
+        // (Pp: the text is packed by now, the fused round's text look-ups take the bit-packed text, a quarter of the lines)
+        if ((rc = bucket_sort32(s32.keys, s32.vals, kout, SA, n, top_bits, w.bk_start, w.ss.err + 2, st, tn, done, &largest,
+                                fuse ? &F : nullptr, &R.Pp, &K, &fused, job.val_extra))) return rc;
+        O.bucket_finished = *done && fused;
+        if (trace) fprintf(stderr, "suffix_array_amd: 32-bit first stage: %d global passes over the top %d key bits, largest bucket %u -> %s\n", s32.passes, top_bits, largest,
+                           *done ? (fused ? "low bits and ties on all 32 ordered bucket by bucket in LDS" : "low bits ordered bucket by bucket in LDS")
+                                 : "too large: keys rebuilt, four global passes");
+        if (!*done) return SA_AMD_OK;      // (nothing was launched: the finish buffers are zeroed again by whoever uses them)
+        local.sort_passes += 1; local.sorted_elements += n;
+        O.sorted32 = kout;
+        O.sr.vals = SA; O.sr.passes = s32.passes + 1;
+        O.sr.keys = (kout == job.keys_in) ? w.keysA : w.keysB;
+        return SA_AMD_OK;
+    }
+    // ... or four global passes over a key array, the last one writing into SA
+    int top32_four_passes(const Route &R, InitialOrder &O)
+    {
+        int rc;
+        SortJob<uint32_t> job{}; SortResult<uint32_t> s32;
+        if ((rc = top32_keys(R, 0, &job))) return rc;
+        job.final_vals = SA;
+        if ((rc = sort_pairs32(job, w.ss, st, tn, &s32, &local))) return rc;
+        O.sorted32 = s32.keys;
+        O.sr.vals = s32.vals; O.sr.passes = s32.passes;
+        O.sr.keys = (s32.keys == job.keys_in) ? w.keysA : w.keysB;      // the 8n-byte buffer that now holds the sorted 32-bit keys
         return SA_AMD_OK;
     }
 
     // 3-4. packed keys and the initial LSD sort, the last pass writing straight into SA
-    int initial_sort()
+    int initial_sort(const Route &R, InitialOrder &O)
     {
         int rc;
         // 3. packed keys, 4. initial sort: all key bits as (u64 key, u32 suffix) pairs, or only the top 32 bits as
         //    (u32, u32) pairs in 12 Ki-element tiles -- two thirds of the bytes per pass and half the passes
+        SortResult<uint64_t> &sr = O.sr;
         sr.keys = w.keysA; sr.vals = w.valsA; sr.passes = 0;
-        head_flags = nullptr;
-        sorted32 = nullptr;               // top-32 stage: the sorted 32-bit keys (no 64-bit sorted array exists)
-        bucket_finished = false;
-        // value of pair i = i: not stored by k_build_keys, the first sort pass takes the index (saves 8 B / suffix)
-        const bool iota = n >= 2 && key_bits > 0;
-        uint32_t *vals0 = iota ? (uint32_t *)nullptr : w.valsA;
-        // alphabets of 2, 4 or 16 symbols: k_build_keys also writes the text as bit-packed codes, which every later random
-        // read of the text uses instead (a key becomes a bit field of two words; DNA shrinks to a quarter: cache-resident)
-        uint8_t *packed_out = nullptr;
-        if ((P.bits == 1 || P.bits == 2 || P.bits == 4) && n >= 64 && !tn.no_packed_text) {
-            packed_out = w.packed;
-            HIP_TRY(hipMemsetAsync(packed_out + (size_t)(n >> 3) * P.bits, 0, 64, st));     // the padding behind the last whole group
-        }
-        if (top_shift) {
-            rc = initial_sort_top32(vals0, packed_out, iota);
-            if (rc) return rc;
+        if (R.Pp.packed) HIP_TRY(hipMemsetAsync(w.packed + (size_t)(n >> 3) * R.P.bits, 0, 64, st));     // the padding behind the last whole group
+        if (R.top_shift) {
+            bool done = false;
+            if (R.bucket_top_bits && (rc = top32_bucket_route(R, O, &done))) return rc;
+            if (!done && (rc = top32_four_passes(R, O))) return rc;
         } else {
             const FirstCounts fc = sort_first_counts(w.ss, tn, n, false);
-            const bool counted = n > 1 && key_bits > 0;
+            const bool counted = n > 1 && R.key_bits > 0;
             if (counted) HIP_TRY(hipMemsetAsync(fc.zero_ptr, 0, fc.zero_bytes, st));
-            if ((rc = build_keys64(vals0, packed_out, fc, counted))) return rc;
+            if ((rc = build_keys64(R, fc, counted))) return rc;
             // (a text of ONE byte value -- a zero-filled file -- has the same key everywhere but at its end: its passes are the identity
             // and are looked for; any other text does not pay the read-backs)
             // diagnostic library, SA_AMD_SAMPLE_SORT=1 (a measured dead end, profiles/r04_sample_sort_64.txt): the sample sort -- two
             // distribution passes over quantile digits + every bucket ordered in LDS -- instead of one LSD pass per digit
             bool ss_done = false;
 #ifdef SA_AMD_DIAG
-            if (iota && counted && tn.sample_sort && n >= tn.sample_sort_min_n && key_bits > 32 && onesweep_on(w.ss, tn) && !timing_only()) {
+            if (iota(R) && counted && tn.sample_sort && n >= tn.sample_sort_min_n && R.key_bits > 32 && onesweep_on(w.ss, tn) && !timing_only()) {
                 const size_t need_big = ((size_t)ceil_div(n, SS_TILE) + SS_WAYS) * SS_IDS2 * 4;
                 if (need_big <= (size_t)n * 4 && (size_t)n * 4 >= ((size_t)4 << 20)) {
-                    rc = sample_sort64(w.keysA, w.keysB, w.keysC, w.valsA, w.valsB, w.U0, w.U1, w.isa, w.G0, w.bk_start, SA, n, key_bits, w.ss, st, &local, tn,
+                    rc = sample_sort64(w.keysA, w.keysB, w.keysC, w.valsA, w.valsB, w.U0, w.U1, w.isa, w.G0, w.bk_start, SA, n, R.key_bits, w.ss, st, &local, tn,
                                        &ss_done, trace);
                     if (rc) return rc;
                     if (ss_done) { sr.keys = w.keysB; sr.vals = SA; sr.passes = 3; sr.skipped = 0; }
                     else {
                         // (cannot sort this text in workgroup-sized buckets: the keys again, then the LSD engine)
                         HIP_TRY(hipMemsetAsync(fc.zero_ptr, 0, fc.zero_bytes, st));
-                        if ((rc = build_keys64(vals0, packed_out, fc, true))) return rc;
+                        if ((rc = build_keys64(R, fc, true))) return rc;
                     }
                 }
             }
@@ -739,212 +742,205 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
             // Group-start flags instead of sorted keys from the last pass (head_flags above): asked for when the dense route is
             // expected -- its first re-rank is the only reader of the sorted keys then.  Tuning::head_flags 0: never, 2: always
             // (the routes that need the keys rebuild them: rebuild_sorted_keys); diagnostic library only.
-            const bool dense_expected = force_dense || probe_dense || !text_ok;
-            const bool want_flags = tn.head_flags != 0 && (tn.head_flags == 2 || dense_expected) && flags_slab_ok && onesweep_on(w.ss, tn) && !timing_only() &&
-                                    !tn.fused64 && n >= 2 && key_bits > 0;
-            SortJob<uint64_t> job{ w.keysA, w.valsA, w.keysB, w.valsB, n, 0, key_bits };
+            const bool want_flags = tn.head_flags != 0 && (tn.head_flags == 2 || R.dense_expected()) && flags_slab_ok && onesweep_on(w.ss, tn) && !timing_only() &&
+                                    !tn.fused64 && n >= 2 && R.key_bits > 0;
+            SortJob<uint64_t> job{ w.keysA, w.valsA, w.keysB, w.valsB, n, 0, R.key_bits };
             job.final_vals = SA;
-            job.iota = iota; job.may_skip = sigma == 1; job.first_counted = counted;
+            job.iota = iota(R); job.may_skip = R.sigma == 1; job.first_counted = counted;
             job.head_flags = want_flags ? (uint8_t *)w.keysC : (uint8_t *)nullptr;
-            rc = sort_pairs(job, w.ss, st, tn, &sr, &local);
-            if (rc) return rc;
-            if (want_flags && sr.passes > 0 && sr.vals == SA) head_flags = (uint8_t *)w.keysC;      // (the last pass always runs: it delivers into SA)
-            if (trace && head_flags) fprintf(stderr, "suffix_array_amd: initial sort: the last pass wrote group-start flags, not the sorted keys\n");
+            if ((rc = sort_pairs(job, w.ss, st, tn, &sr, &local))) return rc;
+            if (want_flags && sr.passes > 0 && sr.vals == SA) O.head_flags = (uint8_t *)w.keysC;      // (the last pass always runs: it delivers into SA)
+            if (trace && O.head_flags) fprintf(stderr, "suffix_array_amd: initial sort: the last pass wrote group-start flags, not the sorted keys\n");
             }
         }
-        P.packed = packed_out;
-        if (sr.vals != SA) {   // n == 1: no pass ran, the values are still in the input buffer
+        if (sr.vals != SA)     // n == 1: no pass ran, the values are still in the input buffer
             PROF(KC_MISC, n, st, hipLaunchKernelGGL((k_copy_u32), dim3(1), dim3(256), 0, st, sr.vals, SA, n));
-        }
-
         return SA_AMD_OK;
     }
 
-    // list buffers; the fast finish of the 32-bit first stage / the opt-in fused first text round (read-backs: tied counts)
-    int first_round_from_sorted_keys()
+    // 4. the tied list's buffers and what the text-keyed rounds key by
+    void open_lists(const Route &R, ListState &T)
     {
-        int rc;
-        // 4. group heads of the initial order; how many suffixes are still tied with a neighbour
+        const KeyParams &P = R.Pp;
         L.U = w.U0; L.Un = w.U1; L.G = w.G0; L.Gn = w.G1;
-        L.V = w.valsA;
-        tiles = ceil_div(n, RR_TILE);
-        m32 = 0;
-        L.m = 0;
+        L.V = w.valsA; L.m = 0;
         L.rkA = w.keysA; L.rkB = w.keysB;          // key buffers of the refinement rounds
-        sorted0 = sr.keys;                      // the initial keys in SA order (kept for the rank look-ups)
-        lists_ready = false;                         // (L.U, L.G, L.V) already hold the tied suffixes
-        depth = P.k;                               // symbols the current order is sorted by
+        T.tiles = ceil_div(n, RR_TILE); T.depth = P.k;
         // Text-keyed rounds pack their symbols as bit fields of ceil(log2 sigma) bits whatever the alphabet: a secondary key only
         // has to preserve the order inside one round, and the base-sigma form costs a 64-bit multiply per symbol in kernels
         // that are instruction-bound (k_group_sort: 26 ps per suffix however small the text).  English-like sigma = 56: six
         // symbols in 36 bits either way.
-        Ptext = P;
-        if (P.bits == 0) Ptext.bits = bit_length(P.sigma - 1);
-        Ptext.gram = 0;                                    // (gram ranks are the initial keys' business only)
-        s_sym = 0; tkb = 0;                            // symbols per round, bits of their packed key
-        {
-            const int room = 64 - g_bits;                   // bits left below the group head
-            s_sym = room / Ptext.bits;
-            if (s_sym > 64) s_sym = 64;
-            tkb = s_sym * Ptext.bits;
-        }
-        finished32 = false; fused64 = false; tnext_scanned = false;
-        if (top_shift && rs.local_ok && !tn.no_fused_finish && !timing_only()) {
-            // fast finish of the 32-bit first stage: one pass orders every small group by its low key bits in place
-            // (k_finish_sorted); only if some group is too large for it does the general path below run instead
-            const int cap = tn.group_cap;
-            uint32_t *surv_bits = w.surv_bits, *surv_head = w.isa;  // (the ISA is not in use before the doubling rounds)
-            if (!bucket_finished) {      // (else k_bucket_sort has done this round while it had the buckets in LDS, into the same records)
+        T.Ptext = P;
+        if (P.bits == 0) T.Ptext.bits = bit_length(P.sigma - 1);
+        T.Ptext.gram = 0;                                    // (gram ranks are the initial keys' business only)
+        T.s_sym = (64 - g_bits) / T.Ptext.bits;              // (64 - g_bits: bits left below the group head)
+        if (T.s_sym > 64) T.s_sym = 64;
+        T.tkb = T.s_sym * T.Ptext.bits;
+    }
+
+    // fast finish of the 32-bit first stage: one pass orders every small group by its low key bits in place (k_finish_sorted);
+    // only if some group is too large for it do group_heads and finish_top32_ties run instead (read-back: tied counts)
+    int fast_finish32(const Route &R, const InitialOrder &O, ListState &T, FirstRound *first)
+    {
+        int rc;
+        if (!(R.top_shift && rs.local_ok && !tn.no_fused_finish && !timing_only())) return SA_AMD_OK;
+        const int64_t tiles = T.tiles;
+        uint32_t *surv_bits = w.surv_bits, *surv_head = w.isa;  // (the ISA is not in use before the doubling rounds)
+        if (!O.bucket_finished) {      // (else k_bucket_sort has done this round while it had the buckets in LDS, into the same records)
             if ((rc = zero_finish_records())) return rc;
-            KeySrc K = KeySrc(); K.mode = KS_LOWKEY; K.kb = top_shift;
+            KeySrc K = KeySrc(); K.mode = KS_LOWKEY; K.kb = R.top_shift;
             PROF(KC_FINISH, n, st, hipLaunchKernelGGL((k_finish_sorted<uint32_t, KS_LOWKEY, false>), dim3((unsigned)ceil_div(n, FT_TILE)), dim3(FT_THREADS),
-                                                     0, st, sorted32, SA, dT, P, n, K, cap, surv_bits, surv_head, w.tcnt, w.total, (uint32_t *)nullptr,
+                                                     0, st, O.sorted32, SA, dT, R.Pp, n, K, tn.group_cap, surv_bits, surv_head, w.tcnt, w.total, (uint32_t *)nullptr,
                                                      (uint32_t *)nullptr, (uint32_t *)nullptr));
-            }
             // (k_bucket_sort counts its survivors itself: the scan of the tiles' counts runs only if there are any)
-            if (!bucket_finished) PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles, w.total));
-            uint32_t words[ROUND_WORDS];         // (the tied-slot counts are spread over w.chg, directly behind w.total)
-            { const int rcw = read_words(words, w.total, sizeof(words), st); if (rcw) return rcw; }
-            // still tied on 64 bits (k_bucket_sort counts them in w.chg), members of groups nobody owned, tied on 32 bits
-            const uint32_t tied64 = bucket_finished ? (uint32_t)chg_sum(words, 1) : words[0], unowned = words[1], tied32 = (uint32_t)chg_sum(words);
-            if (bucket_finished && tied64 != 0 && unowned == 0)
-                PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles, w.total));
-            if (unowned == 0) {
-                finished32 = true;
-                L.m = tied64;
-                local.locally_sorted += tied32;
-                local.unresolved_after_initial = L.m;
-                if (L.m > 0) {
-                    PROF(KC_RR_APPLY, n, st, hipLaunchKernelGGL((k_surv_compact), dim3((unsigned)tiles), dim3(256), 0, st, (const uint32_t *)surv_bits,
-                                                                (const uint32_t *)surv_head, (const uint32_t *)SA, n, (const uint32_t *)w.tcnt,
-                                                                (const uint32_t *)w.total, L.U, L.G, L.V));
-                    L.keys_beside(w, sr.keys);
-                    lists_ready = true;
-                }
-            }
+            PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles, w.total));
         }
-        // (SA_AMD_SPARSE_DIV moves the text-round / doubling boundary for the tests: then the general route decides, as before)
-        // Opt-in (SA_AMD_FUSED64=1): measured on C3 the one-pass round costs 8.2 ms against the 4.3 ms of k_group_sort on the tied
-        // list -- with 68 % of the slots tied the work list is six entries per thread -- and the whole build 31.0 instead of 28.8 ms.
-        if (!top_shift && text_ok && rs.local_ok && s_sym > 0 && tn.fused64 && !tn.no_fused_finish && !tn.sparse_div_set && !timing_only()) {
-            // the first text-keyed round straight from the sorted keys (k_finish_sorted): groups of up to `cap` members are
-            // ordered in place by the next s_sym symbols, their still-tied members recorded by slot; the members of larger
-            // groups are listed (k_todo_compact) and take the general route (RefineRound::run<NO_RERANK> + re-rank), joining the same record;
-            // k_surv_compact then lists everything that is still tied, in slot order, for the second round
-            const int cap = tn.group_cap;
-            const int64_t ft_tiles = ceil_div(n, FT_TILE);
-            uint32_t *surv_head = w.isa;
-            HIP_TRY(hipMemsetAsync(w.surv_bits, 0, ((size_t)n + 31) / 32 * 4, st));
-            HIP_TRY(hipMemsetAsync(w.todo_bits, 0, ((size_t)n + 31) / 32 * 4, st));
-            HIP_TRY(hipMemsetAsync(w.ft_cnt, 0, (size_t)(ft_tiles + 1) * 4, st));
-            HIP_TRY(hipMemsetAsync(w.ft_head, 0, (size_t)(ft_tiles + 1) * 4, st));
-            HIP_TRY(hipMemsetAsync(w.surv_cnt, 0, (size_t)tiles * 4, st));
-            HIP_TRY(hipMemsetAsync(w.thead, 0, (size_t)tiles * 4, st));
-            HIP_TRY(hipMemsetAsync(w.total, 0, 32, st));
-            HIP_TRY(hipMemsetAsync(w.chg, 0, (size_t)RR_CHG_COUNTERS * 32 * 4, st));
-            KeySrc K = KeySrc(); K.mode = KS_TEXT; K.h = depth; K.s = s_sym; K.kb = tkb;
-            PROF(KC_FINISH, n, st, hipLaunchKernelGGL((k_finish_sorted<uint64_t, KS_TEXT, true>), dim3((unsigned)ft_tiles), dim3(FT_THREADS), 0, st,
-                                                     (const uint64_t *)sorted0, SA, dT, Ptext, n, K, cap, w.surv_bits, surv_head, w.surv_cnt, w.total,
-                                                     w.todo_bits, w.ft_cnt, w.ft_head));
-            PROF(KC_RR_SCAN, ft_tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.ft_cnt, w.ft_head, ft_tiles, w.total + 3));
-            uint32_t words[ROUND_WORDS];
-            { const int rcw = read_words(words, w.total, sizeof(words), st); if (rcw) return rcw; }
-            const int64_t tied0 = (uint32_t)chg_sum(words), m_todo = words[3];      // tied after the initial sort, members left to the general route
-            local.unresolved_after_initial = tied0;
-            local.locally_sorted += tied0 - m_todo;
-            L.keys_beside(w, sr.keys);
-            if (m_todo > 0) {
-                PROF(KC_RR_APPLY, n, st, hipLaunchKernelGGL((k_todo_compact<uint64_t>), dim3((unsigned)ft_tiles), dim3(FT_THREADS), 0, st,
-                                                            (const uint64_t *)sorted0, (const uint32_t *)SA, n, (const uint32_t *)w.todo_bits,
-                                                            (const uint32_t *)w.ft_cnt, (const uint32_t *)w.ft_head, (const uint32_t *)(w.total + 3),
-                                                            L.U, L.G, L.V));
-                L.m = m_todo;
-                RoundState own;                                    // (a switch of its own: large groups, the global sort does the work either way)
-                own.local_ok = true;
-                RefineRound round(*this, Ptext, K, own);
-                if ((rc = round.run<NO_RERANK>())) return rc;
-                const Refined &rf = round.rf;
-                if ((rc = rr_count<false>(rf.keys, L.U, L.m, nullptr, 0, nullptr, w.ft_cnt, w.ft_head))) return rc;
-                if ((rc = rr_scan(L.m, w.ft_cnt, w.ft_head, w.total + 4))) return rc;
-                RrApply a = round_args(rf);
-                a.tile_cnt = w.ft_cnt; a.tile_head = w.ft_head; a.tile_total = w.total + 4;
-                a.has_isa = w.surv_bits; a.pair_v = w.surv_cnt;
-                if ((rc = rr_apply<false, true, 4>(rf.keys, a))) return rc;
-            }
-            PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.surv_cnt, w.thead, tiles, w.total));
-            { const int rcw = read_words(&m32, w.total, 4, st); if (rcw) return rcw; }
-            L.m = m32;
-            L.U = w.U0; L.G = w.G0; L.V = w.valsA; L.Un = w.U1; L.Gn = w.G1;
-            if (L.m > 0)
-                PROF(KC_RR_APPLY, n, st, hipLaunchKernelGGL((k_surv_compact), dim3((unsigned)tiles), dim3(256), 0, st, (const uint32_t *)w.surv_bits,
-                                                            (const uint32_t *)surv_head, (const uint32_t *)SA, n, (const uint32_t *)w.surv_cnt,
-                                                            (const uint32_t *)w.total, L.U, L.G, L.V));
-            fused64 = true;
-            lists_ready = true;
-            depth += s_sym;
-            local.text_rounds++;
-            local.rounds++;
-            if (trace) fprintf(stderr, "suffix_array_amd: text round %d depth %lld: tied %lld -> %lld  (%.2f ms)\n", local.text_rounds, (long long)depth, (long long)tied0, (long long)L.m, lap());
+        uint32_t words[ROUND_WORDS];         // (the tied-slot counts are spread over w.chg, directly behind w.total)
+        { const int rcw = read_words(words, w.total, sizeof(words), st); if (rcw) return rcw; }
+        // still tied on 64 bits (k_bucket_sort counts them in w.chg), members of groups nobody owned, tied on 32 bits
+        const uint32_t tied64 = O.bucket_finished ? (uint32_t)chg_sum(words, 1) : words[0], unowned = words[1], tied32 = (uint32_t)chg_sum(words);
+        if (O.bucket_finished && tied64 != 0 && unowned == 0)
+            PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles, w.total));
+        if (unowned != 0) return SA_AMD_OK;
+        *first = FirstRound::FINISHED32;
+        L.m = tied64;
+        local.locally_sorted += tied32; local.unresolved_after_initial = L.m;
+        if (L.m > 0) {
+            PROF(KC_RR_APPLY, n, st, hipLaunchKernelGGL((k_surv_compact), dim3((unsigned)tiles), dim3(256), 0, st, (const uint32_t *)surv_bits,
+                                                        (const uint32_t *)surv_head, (const uint32_t *)SA, n, (const uint32_t *)w.tcnt,
+                                                        (const uint32_t *)w.total, L.U, L.G, L.V));
+            L.keys_beside(w, O.sr.keys);
+            T.ready = true;
         }
         return SA_AMD_OK;
     }
 
-    // 4. group heads of the initial order: how many suffixes are still tied (read-back: that count)
-    int group_heads()
+    // Opt-in (SA_AMD_FUSED64=1): measured on C3 the one-pass round costs 8.2 ms against the 4.3 ms of k_group_sort on the tied
+    // list -- with 68 % of the slots tied the work list is six entries per thread -- and the whole build 31.0 instead of 28.8 ms.
+    // (SA_AMD_SPARSE_DIV moves the text-round / doubling boundary for the tests: then the general route decides, as before)
+    int fused_first_text_round(const Route &R, const InitialOrder &O, ListState &T, FirstRound *first)
     {
         int rc;
-        if (!finished32 && !fused64) {
+        if (R.top_shift || !R.text_ok || !rs.local_ok || T.s_sym <= 0 || !tn.fused64 || tn.no_fused_finish || tn.sparse_div_set || timing_only()) return SA_AMD_OK;
+        const int64_t tiles = T.tiles;
+        // the first text-keyed round straight from the sorted keys (k_finish_sorted): groups of up to `cap` members are
+        // ordered in place by the next s_sym symbols, their still-tied members recorded by slot; the members of larger
+        // groups are listed (k_todo_compact) and take the general route (RefineRound::run<NO_RERANK> + re-rank), joining the same record;
+        // k_surv_compact then lists everything that is still tied, in slot order, for the second round
+        const int cap = tn.group_cap;
+        const int64_t ft_tiles = ceil_div(n, FT_TILE);
+        uint32_t *surv_head = w.isa;
+        HIP_TRY(hipMemsetAsync(w.surv_bits, 0, ((size_t)n + 31) / 32 * 4, st));
+        HIP_TRY(hipMemsetAsync(w.todo_bits, 0, ((size_t)n + 31) / 32 * 4, st));
+        HIP_TRY(hipMemsetAsync(w.ft_cnt, 0, (size_t)(ft_tiles + 1) * 4, st));
+        HIP_TRY(hipMemsetAsync(w.ft_head, 0, (size_t)(ft_tiles + 1) * 4, st));
+        HIP_TRY(hipMemsetAsync(w.surv_cnt, 0, (size_t)tiles * 4, st));
+        HIP_TRY(hipMemsetAsync(w.thead, 0, (size_t)tiles * 4, st));
+        HIP_TRY(hipMemsetAsync(w.total, 0, 32, st));
+        HIP_TRY(hipMemsetAsync(w.chg, 0, (size_t)RR_CHG_COUNTERS * 32 * 4, st));
+        KeySrc K = KeySrc(); K.mode = KS_TEXT; K.h = T.depth; K.s = T.s_sym; K.kb = T.tkb;
+        PROF(KC_FINISH, n, st, hipLaunchKernelGGL((k_finish_sorted<uint64_t, KS_TEXT, true>), dim3((unsigned)ft_tiles), dim3(FT_THREADS), 0, st,
+                                                 (const uint64_t *)O.sr.keys, SA, dT, T.Ptext, n, K, cap, w.surv_bits, surv_head, w.surv_cnt, w.total,
+                                                 w.todo_bits, w.ft_cnt, w.ft_head));
+        PROF(KC_RR_SCAN, ft_tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.ft_cnt, w.ft_head, ft_tiles, w.total + 3));
+        uint32_t words[ROUND_WORDS];
+        { const int rcw = read_words(words, w.total, sizeof(words), st); if (rcw) return rcw; }
+        const int64_t tied0 = (uint32_t)chg_sum(words), m_todo = words[3];      // tied after the initial sort, members left to the general route
+        local.unresolved_after_initial = tied0;
+        local.locally_sorted += tied0 - m_todo;
+        L.keys_beside(w, O.sr.keys);
+        if (m_todo > 0) {
+            PROF(KC_RR_APPLY, n, st, hipLaunchKernelGGL((k_todo_compact<uint64_t>), dim3((unsigned)ft_tiles), dim3(FT_THREADS), 0, st,
+                                                        (const uint64_t *)O.sr.keys, (const uint32_t *)SA, n, (const uint32_t *)w.todo_bits,
+                                                        (const uint32_t *)w.ft_cnt, (const uint32_t *)w.ft_head, (const uint32_t *)(w.total + 3),
+                                                        L.U, L.G, L.V));
+            L.m = m_todo;
+            RoundState own;                                    // (a switch of its own: large groups, the global sort does the work either way)
+            own.local_ok = true;
+            RefineRound round(*this, T.Ptext, K, own);
+            if ((rc = round.run<NO_RERANK>())) return rc;
+            const Refined &rf = round.rf;
+            if ((rc = rr_count<false>(rf.keys, L.U, L.m, nullptr, 0, nullptr, w.ft_cnt, w.ft_head))) return rc;
+            if ((rc = rr_scan(L.m, w.ft_cnt, w.ft_head, w.total + 4))) return rc;
+            RrApply a = round_args(rf);
+            a.tile_cnt = w.ft_cnt; a.tile_head = w.ft_head; a.tile_total = w.total + 4;
+            a.has_isa = w.surv_bits; a.pair_v = w.surv_cnt;
+            if ((rc = rr_apply<false, true, 4>(rf.keys, a))) return rc;
+        }
+        PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan), dim3(1), dim3(SPINE_THREADS), 0, st, w.surv_cnt, w.thead, tiles, w.total));
+        uint32_t m32 = 0;
+        { const int rcw = read_words(&m32, w.total, 4, st); if (rcw) return rcw; }
+        L.m = m32;
+        L.U = w.U0; L.G = w.G0; L.V = w.valsA; L.Un = w.U1; L.Gn = w.G1;
+        if (L.m > 0)
+            PROF(KC_RR_APPLY, n, st, hipLaunchKernelGGL((k_surv_compact), dim3((unsigned)tiles), dim3(256), 0, st, (const uint32_t *)w.surv_bits,
+                                                        (const uint32_t *)surv_head, (const uint32_t *)SA, n, (const uint32_t *)w.surv_cnt,
+                                                        (const uint32_t *)w.total, L.U, L.G, L.V));
+        *first = FirstRound::FUSED64;
+        T.ready = true;
+        T.depth += T.s_sym;
+        local.text_rounds++;
+        local.rounds++;
+        if (trace) fprintf(stderr, "suffix_array_amd: text round %d depth %lld: tied %lld -> %lld  (%.2f ms)\n", local.text_rounds, (long long)T.depth, (long long)tied0, (long long)L.m, lap());
+        return SA_AMD_OK;
+    }
+
+    // 4. group heads of the initial order: how many suffixes are still tied (read-back: that count).  *tnext_scanned: w.tnext was
+    // scanned here with the counts (k_rr_scan_round), the rank set-up launches no k_rr_scan_next
+    int group_heads(const Route &R, const InitialOrder &O, int64_t tiles, bool *tnext_scanned)
+    {
+        int rc;
         // (64-bit keys: also every tile's first group start: the dense route's first ranks are tail ranks, k_rr_apply FTAIL)
-        rc = top_shift ? rr_count<true, uint32_t>(sorted32, nullptr, n)
-           : head_flags ? rr_count<true, uint64_t, true, true>((const uint64_t *)sr.keys, nullptr, n, w.tnext)
-                        : rr_count<true, uint64_t, true>((const uint64_t *)sr.keys, nullptr, n, w.tnext);
+        rc = R.top_shift ? rr_count<true, uint32_t>(O.sorted32, nullptr, n)
+           : O.head_flags ? rr_count<true, uint64_t, true, true>((const uint64_t *)O.sr.keys, nullptr, n, w.tnext, 0, nullptr, nullptr, nullptr, O.head_flags)
+                          : rr_count<true, uint64_t, true>((const uint64_t *)O.sr.keys, nullptr, n, w.tnext);
         if (rc) return rc;
-        // (64-bit keys on a route that is expected to be dense -- the condition the flags pass is chosen by: the tiles' next group
-        // starts are scanned here, as the second block of the launch, not by a launch of their own in front of the rank set-up.
-        // The read-back below waits for both blocks, so the launch is as long as the longer scan -- at C3 size 51 us for this
-        // block against 32 us for k_rr_scan alone: the dense route saves k_rr_scan's 32 us and a launch.  Any other route keeps
-        // the plain scan; should it turn dense after all, the rank set-up launches k_rr_scan_next itself)
-        tnext_scanned = !top_shift && (force_dense || probe_dense || !text_ok);
-        if (tnext_scanned)
+        // (64-bit keys on a route that is expected to be dense -- Route::dense_expected, which the flags pass is chosen by too: the
+        // tiles' next group starts are scanned here, as the second block of the launch, not by a launch of their own in front of the
+        // rank set-up.  The read-back below waits for both blocks, so the launch is as long as the longer scan -- at C3 size 51 us
+        // for this block against 32 us for k_rr_scan alone: the dense route saves k_rr_scan's 32 us and a launch.  Any other route
+        // keeps the plain scan; should it turn dense after all, the rank set-up launches k_rr_scan_next itself)
+        *tnext_scanned = !R.top_shift && R.dense_expected();
+        if (*tnext_scanned)
             PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan_round), dim3(2), dim3(SPINE_THREADS), 0, st, w.tcnt, w.thead, tiles, w.total, w.tnext,
                                                            (uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr));
         else if ((rc = rr_scan(n))) return rc;
+        uint32_t m32 = 0;
         { const int rcw = read_words(&m32, w.total, 4, st); if (rcw) return rcw; }
         L.m = m32;
         local.unresolved_after_initial = L.m;
         if (timing_only()) L.m = 0;   // diag library: ablation kernels produce wrong orders; stop here
-        }
         return SA_AMD_OK;
     }
 
-    // the suffixes tied on the top 32 key bits are ordered by their low key bits (read-back: tied on all 64 bits)
-    int finish_top32_ties()
+    // the suffixes tied on the top 32 key bits are ordered by their low key bits: the initial sort is finished (read-back: tied on all 64 bits)
+    int finish_top32_ties(const Route &R, const InitialOrder &O, ListState &T)
     {
         int rc;
-        if (!finished32 && top_shift && L.m > 0) {
-            // finish the initial sort: the suffixes tied on the top 32 bits are ordered by their low key bits
-            L.keys_beside(w, sr.keys);
-            if ((rc = rr_apply<true, false, 1, uint32_t>(sorted32, first_args(0u, w.has_isa)))) return rc;
-            KeySrc K = KeySrc(); K.mode = KS_LOWKEY; K.kb = top_shift;
-            RefineRound round(*this, P, K, rs);
-            if ((rc = round.run<NO_RERANK>())) return rc;
-            const Refined &rf = round.rf;
-            if ((rc = rr_count<false>(rf.keys, L.U, L.m))) return rc;
-            if ((rc = rr_scan(L.m))) return rc;
-            if ((rc = rr_apply<false, true, 3>(rf.keys, round_args(rf)))) return rc;
-            { const int rcw = read_words(&m32, w.total, 4, st); if (rcw) return rcw; }
-            L.m = m32;
-            L.advance(rf);
-            lists_ready = true;
-            local.unresolved_after_initial = L.m;           // now: tied on the whole 64-bit key, as after a full sort
-        }
+        if (!R.top_shift || L.m <= 0) return SA_AMD_OK;
+        L.keys_beside(w, O.sr.keys);
+        if ((rc = rr_apply<true, false, 1, uint32_t>(O.sorted32, first_args(0u, w.has_isa)))) return rc;
+        KeySrc K = KeySrc(); K.mode = KS_LOWKEY; K.kb = R.top_shift;
+        RefineRound round(*this, R.Pp, K, rs);
+        if ((rc = round.run<NO_RERANK>())) return rc;
+        const Refined &rf = round.rf;
+        if ((rc = rr_count<false>(rf.keys, L.U, L.m))) return rc;
+        if ((rc = rr_scan(L.m))) return rc;
+        if ((rc = rr_apply<false, true, 3>(rf.keys, round_args(rf)))) return rc;
+        uint32_t m32 = 0;
+        { const int rcw = read_words(&m32, w.total, 4, st); if (rcw) return rcw; }
+        L.m = m32;
+        L.advance(rf);
+        T.ready = true;
+        local.unresolved_after_initial = L.m;           // now: tied on the whole 64-bit key, as after a full sort
         return SA_AMD_OK;
     }
 
     // 5. dense route: ranks + ISA; otherwise compaction and the text-keyed rounds (read-back per round: tied count)
-    int rank_setup_and_text_rounds()
+    int rank_setup_and_text_rounds(const Route &R, InitialOrder &O, ListState &T, bool tnext_scanned, RankSetup *setup)
     {
         int rc;
+        const SortResult<uint64_t> &sr = O.sr; const int64_t tiles = T.tiles;
         // 5. refinement of the tied suffixes.  Three regimes:
         //   text rounds  while more than n / SPARSE_DIV suffixes are tied: secondary key = the next symbols of
         //                the text itself (no rank array needed yet), depth grows by s symbols per round;
@@ -953,13 +949,13 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
         key2_bits = bit_length((uint64_t)(2 * n));
         const int64_t sparse_div = tn.sparse_div;      // (SA_AMD_SPARSE_DIV moves the boundary for tests / A-B)
         const int64_t sparse_limit = n / sparse_div;
-        sparse = false;
-        const bool dense_first = L.m > 0 && !lists_ready && (force_dense || (!text_ok && L.m > sparse_limit) || (probe_dense && L.m > sparse_limit));
-        if (L.m > 0 && dense_first) {
+        // (dense_expected without force_dense: only while more suffixes are tied than the sparse rounds take)
+        const bool dense_first = L.m > 0 && !T.ready && (R.force_dense || (R.dense_expected() && L.m > sparse_limit));
+        if (dense_first) {
             // ranks (ISA scatter) + compaction of the tied suffixes; SA already holds the sorted order
             // the first ranks are TAIL ranks (a group's last slot + 1), the form the dense rounds keep (k_rr_apply): the first doubling
             // round then writes only the ranks that change (SA_AMD_NO_FIRST_TAIL=1: head ranks, everything rewritten in round 1)
-            isa_tail_ranks = !tn.no_first_tail;
+            const bool isa_tail_ranks = setup->isa_tail_ranks = !tn.no_first_tail;
             if (isa_tail_ranks && !tnext_scanned)
                 PROF(KC_RR_SCAN, tiles, st, hipLaunchKernelGGL((k_rr_scan_next), dim3(1), dim3(SPINE_THREADS), 0, st, w.tnext, tiles, (uint32_t *)nullptr));
             RrApply a = first_args((uint32_t)n);
@@ -977,7 +973,7 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
                 uint64_t *pk_out = from_sa ? (uint64_t *)nullptr : pk;
                 uint32_t *pv_out = from_sa ? pk32 + H + 1 : w.U1;
                 a.pair_k = pk_out; a.pair_v = pv_out;
-                if ((rc = rr_apply_setup<2>(a))) return rc;
+                if ((rc = rr_apply_setup<2>(O, isa_tail_ranks, a))) return rc;
                 if (from_sa) {
                     hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, st, dSA, (uint32_t)n);
                     LAUNCH_CHECK(st);
@@ -985,34 +981,32 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
                 } else
                     rc = scatter_binned(w.ss, w.isa, (uint32_t *)pk, w.U1, (uint32_t *)sr.keys, w.G1, n, n, st, &local, tn);
                 if (rc) return rc;
-            } else if ((rc = rr_apply_setup<0>(a))) return rc;
+            } else if ((rc = rr_apply_setup<0>(O, isa_tail_ranks, a))) return rc;
         } else if (L.m > 0) {
             // compaction only; the sorted initial keys stay intact for the rank look-ups
-            if ((rc = rebuild_sorted_keys())) return rc;
+            if ((rc = rebuild_sorted_keys(R, O))) return rc;
             HIP_TRY(hipMemsetAsync(w.has_isa, 0, ((size_t)n + 31) / 32 * 4, st));
-            if (!lists_ready) {
+            if (!T.ready) {
                 L.keys_beside(w, sr.keys);
-                if ((rc = rr_apply<true, false, 1>((const uint64_t *)sorted0, first_args(0u, w.has_isa)))) return rc;
+                if ((rc = rr_apply<true, false, 1>((const uint64_t *)sr.keys, first_args(0u, w.has_isa)))) return rc;
             }
             // ---- text-keyed rounds ----
             bool progressing = true;     // a text round that resolves little (runs, long repeats) is the last one
-            while (text_ok && s_sym > 0 && L.m > sparse_limit && local.text_rounds < tn.max_text_rounds && progressing) {
+            while (R.text_ok && T.s_sym > 0 && L.m > sparse_limit && local.text_rounds < tn.max_text_rounds && progressing) {
                 if ((rc = early_maybe_start())) return rc;
                 const int64_t m_before = L.m;
-                KeySrc K = KeySrc(); K.mode = KS_TEXT; K.h = depth; K.s = s_sym; K.kb = tkb;
+                KeySrc K = KeySrc(); K.mode = KS_TEXT; K.h = T.depth; K.s = T.s_sym; K.kb = T.tkb;
                 // (deferred: one read-back per round while the rounds have nothing for the global sort)
-                RefineRound round(*this, Ptext, K, rs, rs.prev_clean && rs.local_ok && !tn.no_defer);
+                RefineRound round(*this, T.Ptext, K, rs, rs.prev_clean && rs.local_ok && !tn.no_defer);
                 if ((rc = round.run<3>())) return rc;
                 after_round(round);
-                depth += s_sym;
+                T.depth += T.s_sym;
                 local.text_rounds++;
                 progressing = L.m * 4 <= m_before * 3;
-                if (trace) fprintf(stderr, "suffix_array_amd: text round %d depth %lld: tied %lld -> %lld  (%.2f ms)\n", local.text_rounds, (long long)depth, (long long)m_before, (long long)L.m, lap());
+                if (trace) fprintf(stderr, "suffix_array_amd: text round %d depth %lld: tied %lld -> %lld  (%.2f ms)\n", local.text_rounds, (long long)T.depth, (long long)m_before, (long long)L.m, lap());
             }
             if (L.m > sparse_limit) {
                 // still many ties (repetitive text): build the ISA of the current order and double densely
-                int64_t blocks = ceil_div(n, 256);
-                if (blocks > 16384) blocks = 16384;
                 if (binned(n, n, tn) && (((uintptr_t)dSA) & 15) == 0) {
                     // inverse permutation without n random 4-byte stores: dSA[0 .. n] itself is the key array (dSA[0] = n, the
                     // sentinel, is skipped by the scatter), the value is the index = rank; one 32-bit radix pass bins the pairs by
@@ -1024,29 +1018,28 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
                                         (uint32_t *)L.rkA, (uint32_t *)L.rkA + H);
                     if (rc) return rc;
                 } else
-                    PROF(KC_SCATTER, n, st, hipLaunchKernelGGL((k_isa_from_sa), dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t *)SA, w.isa, n));
-                blocks = ceil_div(L.m, 256);
-                if (blocks > 16384) blocks = 16384;
-                PROF(KC_SCATTER, L.m, st, hipLaunchKernelGGL((k_isa_tied), dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t *)L.V,
+                    PROF(KC_SCATTER, n, st, hipLaunchKernelGGL((k_isa_from_sa), dim3(capped_grid(n, 256, 16384)), dim3(256), 0, st, (const uint32_t *)SA, w.isa, n));
+                PROF(KC_SCATTER, L.m, st, hipLaunchKernelGGL((k_isa_tied), dim3(capped_grid(L.m, 256, 16384)), dim3(256), 0, st, (const uint32_t *)L.V,
                                                            (const uint32_t *)L.G, w.isa, L.m, n));
             } else {
-                sparse = L.m > 0;
+                setup->sparse = L.m > 0;
             }
         }
-        local.sparse_mode = sparse ? 1 : 0;
+        local.sparse_mode = setup->sparse ? 1 : 0;
         if (trace) fprintf(stderr, "suffix_array_amd: initial sort + text rounds + rank set-up done, %lld tied (%.2f ms since the last line)\n", (long long)L.m, lap());
         return SA_AMD_OK;
     }
 
     // prefix doubling on what is still tied, dense (ISA) or sparse (read-backs per round: tied count, ranks written)
-    int doubling_rounds()
+    int doubling_rounds(const Route &R, const InitialOrder &O, int64_t depth, const RankSetup &setup)
     {
         int rc;
         // `depth` symbols are sorted, so the first offset is `depth`
         const int64_t depth_text = depth;
         int64_t h = depth;
-        rs.parent_tail = isa_tail_ranks;
-        rs.changed_prev = isa_tail_ranks ? L.m : 0;
+        const bool sparse = setup.sparse;
+        rs.parent_tail = setup.isa_tail_ranks;
+        rs.changed_prev = setup.isa_tail_ranks ? L.m : 0;
         rs.m_local_off = L.m;
         rs.counters_clear = false;      // (the first doubling round zeroes the big-group counters itself, whatever the text rounds left)
         while (L.m > 0) {
@@ -1056,7 +1049,7 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
             // the same refinement machinery as the text rounds, keyed by ranks.  Dense: ranks from the ISA; sparse: looked up without one (sparse_key2)
             KeySrc K = KeySrc();
             K.mode = sparse ? KS_SPARSE : KS_RANK; K.h = h; K.kb = key2_bits; K.isa = w.isa;
-            K.has_isa = w.has_isa; K.sorted_keys = sorted0; K.sorted_top32 = sorted32; K.sa = SA; K.depth = depth_text; K.top_shift = top_shift;
+            K.has_isa = w.has_isa; K.sorted_keys = O.sr.keys; K.sorted_top32 = O.sorted32; K.sa = SA; K.depth = depth_text; K.top_shift = R.top_shift;
             // the local pass was given up because (nearly) every member sat in a group no tile can own: it is tried again when the list has
             // halved, and every third round if the round then finds the average group small enough (RefineRound::decide_local; large lists
             // count their groups anyway; a Fibonacci word's groups shrink while the list does not, a periodic text's never do)
@@ -1072,7 +1065,7 @@ struct DeviceBuild : BuildCore {       // (BuildCore, host/refine_round.hpp: the
             const int64_t expect = (!rs.parent_tail || L.m < rs.changed_prev) ? L.m : rs.changed_prev;
             const bool bin = !sparse && binned(n, expect, tn);
             // read-backs: a round whose predecessor had nothing for the global sort defers that question and blocks ONCE
-            RefineRound round(*this, P, K, rs, rs.prev_clean && !bin && rs.local_ok && !tn.no_defer, true, retry_local);
+            RefineRound round(*this, R.Pp, K, rs, rs.prev_clean && !bin && rs.local_ok && !tn.no_defer, true, retry_local);
             if ((rc = sparse ? round.run<1, false>() : bin ? round.run<2, true>() : round.run<0, true>())) return rc;
             const Refined &rf = round.rf;
             if (retry_local && rf.m_global < L.m) { rs.m_local_off = L.m; rs.rounds_local_off = 0; }      // (the local pass ran again; such a round is never deferred)
@@ -1143,14 +1136,21 @@ static int build_device(const uint8_t *dT, uint32_t *dSA, int32_t n32, void *dWo
     }
     HIP_TRY(hipMemsetAsync(w.ss.err, 0, 16, st));          // look-back give-ups of the single-pass scatter: checked at the end
     int rc;
-    if ((rc = B.geometry_and_probes())) return rc;
-    if (!B.unary_done) {
-        if ((rc = B.initial_sort())) return rc;
-        if ((rc = B.first_round_from_sorted_keys())) return rc;
-        if ((rc = B.group_heads())) return rc;
-        if ((rc = B.finish_top32_ties())) return rc;
-        if ((rc = B.rank_setup_and_text_rounds())) return rc;
-        if ((rc = B.doubling_rounds())) return rc;
+    Route R;
+    if ((rc = B.geometry_and_probes(R))) return rc;
+    if (!R.unary) {
+        InitialOrder O; ListState T; RankSetup ranks;
+        FirstRound first = FirstRound::NONE; bool tnext_scanned = false;
+        if ((rc = B.initial_sort(R, O))) return rc;
+        B.open_lists(R, T);
+        if ((rc = B.fast_finish32(R, O, T, &first))) return rc;
+        if ((rc = B.fused_first_text_round(R, O, T, &first))) return rc;
+        if (first == FirstRound::NONE) {      // (else the tied list is counted, and listed unless it is empty)
+            if ((rc = B.group_heads(R, O, T.tiles, &tnext_scanned))) return rc;
+            if ((rc = B.finish_top32_ties(R, O, T))) return rc;
+        }
+        if ((rc = B.rank_setup_and_text_rounds(R, O, T, tnext_scanned, &ranks))) return rc;
+        if ((rc = B.doubling_rounds(R, O, T.depth, ranks))) return rc;
     }
     if ((rc = B.early_finish())) return rc;
     hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, st, dSA, (uint32_t)n);   // reference src/saca.rs:13

@@ -87,24 +87,19 @@ struct BuildCore {
     Workspace w;
     sa_amd_stats local;
     int g_bits = 0, key2_bits = 0;      // bits of a slot, of a doubling round's secondary key
-    // Group-start flags (kernels/common.hpp, OS_HF_*): != nullptr: the last pass of the 64-bit initial sort wrote one flag byte per slot
-    // here instead of the sorted keys, and sr.keys holds true keys only at the ends of that pass's digit runs.  The first re-rank
-    // (group_heads, the rank set-up of the dense route) reads the flags; every other reader of the sorted keys gets them rebuilt first
-    // (rebuild_sorted_keys).  They live in w.keysC, which nothing else touches between the last sort pass and the end of the first k_rr_apply.
-    uint8_t *head_flags = nullptr;
     bool flags_slab_ok = true;          // w.keysC is device memory (reduced-memory route: it may be the pinned host block -- then the key route is taken)
     TiedList L;
 
     // ---- the re-rank step: k_rr_count, k_rr_scan (a round: k_rr_scan_round, RefineRound::rerank), k_rr_apply (kernels/rerank.hpp) ----
     // One launcher each, over the RR_TILE-element tiles of m elements; tile_cnt / tile_head / total == nullptr: the workspace's.
-    // FLAGS: the groups come from head_flags (the first re-rank behind a flags pass of the initial sort; a round: its `status` bytes), not from the keys
+    // FLAGS: the groups come from `status` (the first re-rank behind a flags pass of the initial sort: InitialOrder::head_flags; a round: its status bytes), not from the keys
     template <bool FIRST, typename KeyT = uint64_t, bool PARENTS = false, bool FLAGS = false>
     int rr_count(const KeyT *keys, const uint32_t *U, int64_t m, uint32_t *tile_first = nullptr, int g_shift = 0, const uint32_t *gate = nullptr,
                  uint32_t *tile_cnt = nullptr, uint32_t *tile_head = nullptr, const uint8_t *status = nullptr)
     {
         PROF(KC_RR_COUNT, m, st, hipLaunchKernelGGL((k_rr_count<FIRST, KeyT, PARENTS, FLAGS>), dim3(rr_count_grid<FLAGS>(m)), dim3(RR_THREADS), 0, st, keys, U, m,
                                                     tile_cnt ? tile_cnt : w.tcnt, tile_head ? tile_head : w.thead, 0, tile_first, g_shift, gate,
-                                                    FLAGS ? (status ? status : (const uint8_t *)head_flags) : (const uint8_t *)nullptr));
+                                                    FLAGS ? status : (const uint8_t *)nullptr));
         return SA_AMD_OK;
     }
     int rr_scan(int64_t m, uint32_t *tile_cnt = nullptr, uint32_t *tile_head = nullptr, uint32_t *total = nullptr)
@@ -121,7 +116,7 @@ struct BuildCore {
                                                       a.tile_head ? a.tile_head : (const uint32_t *)w.thead, a.SA, a.ISA, a.Uo, a.Go, a.Vo, a.n_text, a.has_isa, a.g_shift,
                                                       a.pair_k, a.pair_v, a.tile_total ? a.tile_total : (const uint32_t *)w.total, a.key_shift, a.tile_next,
                                                       a.parent_tail, a.changed_cnt, a.gate, a.sa_final,
-                                                      FLAGS ? (a.status ? a.status : (const uint8_t *)head_flags) : (const uint8_t *)nullptr));
+                                                      FLAGS ? a.status : (const uint8_t *)nullptr));
         return SA_AMD_OK;
     }
     // what every re-rank of the tied list shares: the refined order in, the next list out

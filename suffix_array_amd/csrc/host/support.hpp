@@ -178,6 +178,8 @@ struct DeviceGuard {
       catch (...) { return (fallback) == 0 ? SA_AMD_EINTERNAL : (fallback); }
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// the grid of a kernel whose blocks stride over their work: one block per `per_block` items, `cap` blocks at the most
+static inline unsigned capped_grid(int64_t items, int64_t per_block, int64_t cap) { const int64_t b = ceil_div(items, per_block); return (unsigned)(b < cap ? b : cap); }
 static inline int bit_length(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

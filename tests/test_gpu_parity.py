@@ -1043,7 +1043,8 @@ def test_group_sort_caps(oracle, monkeypatch, gen, n, seed, cap):
 def test_first_round_from_sorted_keys(oracle, monkeypatch, gen, n, seed, cap):
     """k_finish_sorted on 64-bit keys (opt-in SA_AMD_FUSED64): the first text-keyed round in one pass over the sorted keys,
     groups too large for a tile listed by k_todo_compact for the general route, survivors of both merged by k_surv_compact;
-    and the same kernel finishing the 32-bit first stage (forced), with its fall-back to the general route"""
+    and the same kernel finishing the 32-bit first stage (forced), with its fall-back to the general route.
+    (host/pipeline.hpp: open_lists, fused_first_text_round and fast_finish32, once one function of this test's name)"""
     if gen == "periodic":
         text = np.resize(np.frombuffer(b"abcabcabd", dtype=np.uint8), n)
     elif gen == "unary":
