@@ -51,6 +51,8 @@ int32_t sa_amd_divsufsort(const uint8_t *T, int32_t *SA, int32_t n);
  * Replaces `pub fn saca(s: &[u8], sa: &mut [u32])` itself (reference src/saca.rs:9-15):
  * SA has n + 1 entries, SA[0] = n (src/saca.rs:13), SA[1..=n] as above.  The two asserts of
  * src/saca.rs:10-11 become the caller's job (lengths are implied by n).
+ * A refused allocation is SA_AMD_ENOMEM (after the reduced-memory route has been tried) with SA untouched, with one exception: the
+ * front of a large array travels while the last rounds run, so a failing call can leave SA (partly) written once the early download has begun.
  */
 int32_t sa_amd_saca_u8(const uint8_t *T, uint32_t *SA, int32_t n);
 
@@ -147,7 +149,8 @@ const char *sa_amd_version(void);
 /* T: n bytes, bkt: 65 793 entries; host buffers.  SA is not read (the reference's enable_buckets never touches the
  * array either) and may be NULL; the parameter stays for callers of the earlier form */
 int32_t sa_amd_bucket_table(const uint8_t *T, int32_t n, const uint32_t *SA, uint32_t *bkt);
-/* SuffixArray::new followed by enable_buckets in one device round trip (the text is uploaded once) */
+/* SuffixArray::new followed by enable_buckets in one device round trip (the text is uploaded once).  A refused allocation is
+ * SA_AMD_ENOMEM with neither SA nor bkt written: outputs are written only after the last step that can fail. */
 int32_t sa_amd_saca_u8_buckets(const uint8_t *T, uint32_t *SA, int32_t n, uint32_t *bkt);
 /* dSA == NULL: from the text alone (bigram counts; dBkt doubles as the scratch); dSA = a valid device-resident suffix
  * array of dT: one binary search per bucket edge instead (what sa_amd_index_buckets uses) */
@@ -180,6 +183,13 @@ int32_t sa_amd_check_integrity_device(const uint8_t *dT, int32_t n, const uint32
  *   contains[q]            1 iff the pattern occurs                            (src/sa.rs:164-170)
  *   range_lo/hi[q]         search_all(pat) == &sa[lo..hi]                      (src/sa.rs:173-204)
  *   lcp_start/len[q]       search_lcp(pat) == start..start+len                 (src/sa.rs:207-253)
+ * A refused allocation is SA_AMD_ENOMEM, here and in every host-pointer and index entry point of this header: outputs are written
+ * only after the last step that can fail (a table-building call leaves the index as it was), and the thread is left with no
+ * pending runtime error.  The creating calls -- this one, sa_amd_tok_index_create, sa_amd_tok32_index_create -- are the exception
+ * that protects the caller: a failing create sets *out to NULL, so that no caller is left with a dangling handle.  Where the refused request has a fallback -- the small integrity
+ * block, the reduced-memory route of a build, the read-backs' pinned block -- the call succeeds with the same answers instead.
+ * The other exceptions are named where they apply (sa_amd_unpack's *length; tf of sa_amd_index_doc_tf / _doc_topk; the array of a
+ * build whose early download had begun, see sa_amd_saca_u8).
  */
 typedef struct sa_amd_index sa_amd_index;
 int32_t sa_amd_index_create(const uint8_t *T, int32_t n, const uint32_t *SA, sa_amd_index **out);
@@ -202,6 +212,8 @@ int32_t sa_amd_index_search(const sa_amd_index *ix, const uint8_t *pat_data, con
  * reference's own test pins the round trip only (src/tests.rs:61-76).
  * sa_amd_pack: SA has `length` entries, out has sa_amd_pack_bound(length) bytes; *out_len = bytes written.
  * sa_amd_unpack: *length receives the stored length; SA (capacity entries) receives the array.
+ * A refused allocation is SA_AMD_ENOMEM; outputs are written only after the last step that can fail, with one exception, so that
+ * a caller can size SA from a call that fails: *length receives the stored length as soon as the header has been read, also where the call then fails.
  */
 int64_t sa_amd_pack_bound(int64_t length);
 int32_t sa_amd_pack(const uint32_t *SA, int64_t length, uint8_t *out, int64_t capacity, int64_t *out_len);

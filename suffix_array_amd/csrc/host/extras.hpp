@@ -142,19 +142,21 @@ static int32_t extras_host(const uint8_t *T, int32_t n, uint32_t *SA, int64_t sa
     if (N) HIP_TRY(hipMemcpy(dT.p, T, N, hipMemcpyHostToDevice));
     if (which == 3) {
         const int64_t wb = (int64_t)carve(nullptr, n).bytes;
+        // every buffer is taken, and both results exist on the device, before either comes down: outputs are written only
+        // after the last step that can fail
         if ((rc = dW.alloc((size_t)wb))) return rc;
-        if ((rc = build_device(dT.as<uint8_t>(), dSA.as<uint32_t>(), n, dW.p, wb, nullptr, nullptr))) return rc;
-        HIP_TRY(hipMemcpy(SA, dSA.p, (N + 1) * 4, hipMemcpyDeviceToHost));
-        // the text is in HBM already: the table from its bigrams, as the reference counts them
         if ((rc = dB.alloc((size_t)BKT_LEN * 4))) return rc;
+        if ((rc = build_device(dT.as<uint8_t>(), dSA.as<uint32_t>(), n, dW.p, wb, nullptr, nullptr))) return rc;
+        // the text is in HBM already: the table from its bigrams, as the reference counts them
         if ((rc = bucket_table_device(dT.as<uint8_t>(), nullptr, n, dB.as<uint32_t>(), nullptr))) return rc;
+        HIP_TRY(hipMemcpy(SA, dSA.p, (N + 1) * 4, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(bkt, dB.p, (size_t)BKT_LEN * 4, hipMemcpyDeviceToHost));
         return SA_AMD_OK;
     }
     HIP_TRY(hipMemcpy(dSA.p, SA, (N + 1) * 4, hipMemcpyHostToDevice));
     int64_t wb = (int64_t)ci_layout(n).bytes;              // the streaming form; the small block if that much is not to be had
     rc = dW.alloc((size_t)wb);
-    if (rc == SA_AMD_ENOMEM) { (void)hipGetLastError(); wb = ((int64_t)n + 1) * 4 + 256; rc = dW.alloc((size_t)wb); }
+    if (rc == SA_AMD_ENOMEM) { wb = ((int64_t)n + 1) * 4 + 256; rc = dW.alloc((size_t)wb); }
     if (rc) return rc;
     return check_integrity_device(dT.as<uint8_t>(), n, dSA.as<uint32_t>(), dW.p, wb, nullptr);
 }

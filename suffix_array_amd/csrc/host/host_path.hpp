@@ -579,7 +579,11 @@ static int acquire_build_block(int32_t n, int node, const HostTuning &ht, BuildB
     const size_t margin = (size_t)256 << 20;
     const size_t floor_ws = carve(nullptr, n, ~(size_t)0, nullptr).bytes - (size_t)n * 32 - 64 * 8;      // everything but one value buffer, isa, the lists and the third key buffer
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b <= margin + b.tb + b.sb + floor_ws) { (void)hipGetLastError(); return rc; }
-    const size_t cap = ((free_b - margin) & ~(((size_t)2 << 20) - 1)) - b.tb - b.sb;
+    size_t cap = ((free_b - margin) & ~(((size_t)2 << 20) - 1)) - b.tb - b.sb;
+    // The runtime has just refused text + array + wb, whatever it reports as free now (fragments, another tenant's block on its
+    // way): the same request again is known to fail.  So the route always asks for less than was refused -- at least the
+    // least-used slab goes to the host.
+    if (cap >= wb) cap = wb - 256;
     const Workspace dry = carve(nullptr, n, cap, nullptr);
     rc = pool().acquire(b.device, b.tb + b.sb + align_up(dry.bytes, 256), &b.blk);
     if (rc == SA_AMD_OK && dry.bytes2 > 0) {

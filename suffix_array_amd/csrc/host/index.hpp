@@ -34,12 +34,7 @@ struct sa_amd_index {
 
 namespace sa {
 
-// the allocation of a table that is to outlive the call; the refused allocation's error is cleared, as everywhere
-static inline int32_t index_table_alloc(DevBuf &b, size_t bytes)
-{
-    if (b.alloc(bytes) == SA_AMD_OK) return SA_AMD_OK;
-    (void)hipGetLastError();
-    return SA_AMD_ENOMEM;
-}
+// the allocation of a table that is to outlive the call (DevBuf::alloc clears a refused allocation's error, for every caller)
+static inline int32_t index_table_alloc(DevBuf &b, size_t bytes) { return b.alloc(bytes); }
 
 }  // namespace sa

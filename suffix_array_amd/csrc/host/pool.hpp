@@ -36,6 +36,15 @@ public:
     // a free block of `device` with at least `need` bytes (the smallest such), else a new allocation
     int acquire(int device, size_t need, DevBlock *out)
     {
+#ifdef SA_AMD_DIAG
+        if (diag_request(REQ_DEVICE)) {      // (sa_amd_debug_refuse_alloc: the runtime's own refusal, left as below; the pool is not touched)
+            void *q = nullptr;
+            const hipError_t r = hipMalloc(&q, DIAG_REFUSED_BYTES);
+            if (r == hipSuccess) { (void)hipFree(q); return SA_AMD_EINTERNAL; }
+            (void)hipGetLastError();
+            return hip_status(r);
+        }
+#endif
         trim_idle();
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -75,6 +84,7 @@ public:
             e = hipMalloc(&p, want);
             if (e != hipSuccess) { (void)hipGetLastError(); return hip_status(e); }
         }
+        SA_DIAG_LIVE(g_live_device, 1);
         out->device = device; out->p = p; out->bytes = want;
         return SA_AMD_OK;
     }
@@ -111,7 +121,7 @@ public:
                 retained_ += b.bytes;
             }
         }
-        for (auto &d : drop) (void)hipFree(d.p);
+        for (auto &d : drop) { (void)hipFree(d.p); SA_DIAG_LIVE(g_live_device, -1); }
     }
     // blocks nobody has asked for in SA_AMD_CACHE_IDLE_MS go back to the device (checked by whoever uses the pool next: there is no
     // background thread -- a process that never calls again keeps its last blocks until sa_amd_release_cache or exit)
@@ -131,7 +141,7 @@ public:
                     blocks_.erase(blocks_.begin() + i);
                 }
         }
-        for (auto &d : drop) (void)hipFree(d.p);
+        for (auto &d : drop) { (void)hipFree(d.p); SA_DIAG_LIVE(g_live_device, -1); }
     }
     // what the pool may keep of a device's memory (mu_ held): twice the largest recent request, at least 256 MiB, at most the cap
     size_t device_limit(int device)
@@ -157,7 +167,7 @@ public:
                     blocks_.erase(blocks_.begin() + i);
                 }
         }
-        for (auto &d : drop) (void)hipFree(d.p);
+        for (auto &d : drop) { (void)hipFree(d.p); SA_DIAG_LIVE(g_live_device, -1); }
     }
     int stream(int device, hipStream_t *out)
     {
@@ -191,6 +201,15 @@ public:
     }
     int pinned(size_t bytes, int node, int device, PinBlock *out)
     {
+#ifdef SA_AMD_DIAG
+        if (diag_request(REQ_PINNED)) {      // (sa_amd_debug_refuse_alloc: on the calling thread, before a helper is asked; the pool is not touched)
+            void *q = nullptr;
+            const hipError_t r = hipHostMalloc(&q, DIAG_REFUSED_BYTES, hipHostMallocPortable | hipHostMallocMapped);
+            if (r == hipSuccess) { (void)hipHostFree(q); return SA_AMD_EINTERNAL; }
+            (void)hipGetLastError();
+            return hip_status(r);
+        }
+#endif
         const size_t want = pinned_size_class(bytes);
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -214,6 +233,7 @@ public:
         };
         if (node >= 0) helper_pool(node).run_on_helper(alloc); else alloc();
         if (e != hipSuccess) { (void)hipGetLastError(); return hip_status(e); }
+        SA_DIAG_LIVE(g_live_pinned, 1);
         out->p = p; out->bytes = want; out->node = node; out->stamp = 0;
         return SA_AMD_OK;
     }
@@ -239,7 +259,7 @@ public:
                 pinned_retained_ += b.bytes;
             }
         }
-        for (auto &d : drop) (void)hipHostFree(d.p);
+        for (auto &d : drop) { (void)hipHostFree(d.p); SA_DIAG_LIVE(g_live_pinned, -1); }
     }
     void clear()
     {
@@ -250,8 +270,8 @@ public:
             retained_ = 0; pinned_retained_ = 0;
             recent_.clear();
         }
-        for (auto &d : drop) (void)hipFree(d.p);
-        for (auto &d : pdrop) (void)hipHostFree(d.p);
+        for (auto &d : drop) { (void)hipFree(d.p); SA_DIAG_LIVE(g_live_device, -1); }
+        for (auto &d : pdrop) { (void)hipHostFree(d.p); SA_DIAG_LIVE(g_live_pinned, -1); }
         for (auto &s : sdrop) (void)hipStreamDestroy(s.second);
     }
 };

@@ -122,6 +122,39 @@ static inline void diag_fill_host(void *p, size_t bytes)
     for (size_t i = 0; i < words; ++i) w[i] = fill_word((uint32_t)i, seed, pattern);
     for (size_t i = words * 4; i < bytes; ++i) ((uint8_t *)p)[i] = (uint8_t)fill_word((uint32_t)words, seed, pattern);
 }
+
+// The refusal switch and the ledger of the diagnostic library only (sa_amd_debug_refuse_alloc, sa_amd_debug_live_allocations,
+// csrc/sa_diag.h; DESIGN.md section 10, "Refused allocations").  All memory the library takes goes through three seams --
+// ResourcePool::acquire, ResourcePool::pinned (pool.hpp) and DevBuf::alloc (below) -- and each of them calls diag_request first,
+// on the thread that called the seam: before the pool looks for a free block and before pinned() hands work to a helper, so
+// that the count depends neither on what the pool holds nor on the thread that ends up calling the runtime.  A request that is
+// to be refused asks the runtime for DIAG_REFUSED_BYTES, more than any device has: the runtime says no on the host, nobody's
+// memory is taken, and the thread is left exactly as a real refusal leaves it (the runtime's per-thread error included).
+enum { REQ_DEVICE = 1, REQ_PINNED = 2, REQ_TABLE = 3 };
+constexpr size_t DIAG_REFUSED_BYTES = SIZE_MAX / 2;
+constexpr int DIAG_KINDS_MAX = 64;
+struct RefuseSwitch {
+    int nth = -1;                 // -1 off (nothing is counted), 0 count only, k >= 1: the k-th request from arming on is refused, once
+    int count = 0;                // requests since the switch was last set
+    bool fired = false;
+    uint8_t kinds[DIAG_KINDS_MAX] = { 0 };      // REQ_* of the first DIAG_KINDS_MAX counted requests
+};
+static thread_local RefuseSwitch g_refuse;
+inline std::atomic<int64_t> g_live_device{0}, g_live_pinned{0};      // allocations made through the seams and not yet freed (process-wide)
+
+// counts a request of `kind` of the calling thread; true: this one is to be refused
+static inline bool diag_request(int kind)
+{
+    RefuseSwitch &r = g_refuse;
+    if (r.nth < 0) return false;
+    if (r.count < DIAG_KINDS_MAX) r.kinds[r.count] = (uint8_t)kind;
+    ++r.count;
+    if (r.nth >= 1 && r.count == r.nth && !r.fired) { r.fired = true; return true; }
+    return false;
+}
+#define SA_DIAG_LIVE(counter, delta) ((void)sa::counter.fetch_add((delta), std::memory_order_relaxed))
+#else
+#define SA_DIAG_LIVE(counter, delta) ((void)0)
 #endif
 
 // device memory that is freed on every exit path (HIP_TRY returns early)
@@ -136,16 +169,25 @@ struct DevBuf {
         return *this;
     }
     ~DevBuf() { reset(); }
+    // A refused allocation is SA_AMD_ENOMEM with nothing held, and the runtime's per-thread error is cleared here, once for every
+    // caller: hipGetLastError keeps it until somebody reads it, and the next launch check of the thread would report it.
     int alloc(size_t bytes)
     {
         reset();
-        int rc = hip_status(hipMalloc(&p, bytes ? bytes : 1));
+        size_t ask = bytes ? bytes : 1;
 #ifdef SA_AMD_DIAG
-        if (rc == SA_AMD_OK) rc = diag_fill_device(p, bytes ? bytes : 1, nullptr);      // (an index's tables, the slack behind its text included)
+        if (diag_request(REQ_TABLE)) ask = DIAG_REFUSED_BYTES;      // (sa_amd_debug_refuse_alloc: the runtime's own refusal, on the path below)
+#endif
+        const hipError_t e = hipMalloc(&p, ask);
+        if (e != hipSuccess) { p = nullptr; (void)hipGetLastError(); return hip_status(e); }
+        SA_DIAG_LIVE(g_live_device, 1);
+        int rc = SA_AMD_OK;
+#ifdef SA_AMD_DIAG
+        rc = diag_fill_device(p, ask, nullptr);      // (an index's tables, the slack behind its text included)
 #endif
         return rc;
     }
-    void reset() { if (p) (void)hipFree(p); p = nullptr; }
+    void reset() { if (p) { (void)hipFree(p); SA_DIAG_LIVE(g_live_device, -1); } p = nullptr; }
     template <typename T> T *as() const { return (T *)p; }
 };
 

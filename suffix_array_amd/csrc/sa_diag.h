@@ -45,6 +45,27 @@ int32_t sa_amd_debug_dsub_plain_atomics(int32_t mode);
  * small-text and small-batch kernels read and write zero-copy; every allocation an index or a token index owns, the slack
  * behind its text included.  The contract it tests: no result and no statistic depends on those bytes. */
 int32_t sa_amd_debug_fill_blocks(int32_t pattern);
+/* Refused allocations.  All memory the library takes goes through three seams: a pooled device block
+ * (ResourcePool::acquire), a pinned host block (ResourcePool::pinned) and a table of an index or a buffer of a host form
+ * (DevBuf::alloc).  Each seam counts a request at its top, on the thread that calls it: before the pool looks for a free block
+ * and before a pinned block's allocation is handed to a helper thread, so the count depends neither on what the pool holds nor
+ * on the thread that ends up calling the runtime.  The switch acts on the CALLING THREAD only: nth >= 1: the nth request this
+ * thread makes from now on is refused, once; 0: count only; -1: off (the default: nothing is counted).  Returns the number of
+ * requests this thread made since the previous call of this function.  A refused request asks the runtime for more bytes than
+ * any device has (SIZE_MAX / 2) and returns what the seam returns for that answer, without touching the pool: the runtime
+ * refuses on the host, nobody's memory is taken, and the thread is left as a real refusal leaves it.  Requests made by helper
+ * and worker threads (the early pullers of a download, the workers of sa_amd_saca_batch) belong to those threads, not to the
+ * thread that armed the switch: they are neither counted nor refused.  Stream and event creation are no memory requests (they
+ * fail with SA_AMD_EHIP) and are out of this switch's reach. */
+int32_t sa_amd_debug_refuse_alloc(int32_t nth);
+/* 1 when the refusal armed by the calling thread's last sa_amd_debug_refuse_alloc(nth >= 1) has happened, else 0 */
+int32_t sa_amd_debug_refuse_fired(void);
+/* the kinds of the requests counted since the calling thread last set the switch, in order: 1 a pooled device block, 2 a pinned
+ * block, 3 a table / buffer (DevBuf); at most `capacity` (and at most 64) are written; returns the number of requests counted */
+int32_t sa_amd_debug_refuse_kinds(uint8_t *kinds, int32_t capacity);
+/* the ledger (process-wide): allocations made through the three seams and not yet given back to the runtime at one of the seven
+ * hipFree / hipHostFree sites (pool.hpp, support.hpp) -- blocks the pool retains are live; sa_amd_release_cache frees them */
+int32_t sa_amd_debug_live_allocations(int64_t *device, int64_t *pinned);
 int32_t sa_amd_debug_sort_variant_count(void);
 const char *sa_amd_debug_sort_variant_name(int32_t index);
 /* stable LSD radix sort of (u64 key, u32 value) pairs on bits [begin_bit, end_bit); host buffers */

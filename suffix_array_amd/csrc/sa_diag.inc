@@ -40,6 +40,34 @@ SA_EXPORT int32_t sa_amd_debug_fill_blocks(int32_t pattern)
     return sa::g_fill_pattern.exchange(pattern < 0 || pattern > sa::FILL_RANDOM ? sa::FILL_OFF : pattern);
 }
 
+SA_EXPORT int32_t sa_amd_debug_refuse_alloc(int32_t nth)
+{
+    sa::RefuseSwitch &r = sa::g_refuse;
+    const int32_t made = r.count;
+    r.nth = nth < -1 ? -1 : nth;
+    r.count = 0;
+    r.fired = false;
+    return made;
+}
+
+SA_EXPORT int32_t sa_amd_debug_refuse_fired(void) { return sa::g_refuse.fired ? 1 : 0; }
+
+SA_EXPORT int32_t sa_amd_debug_refuse_kinds(uint8_t *kinds, int32_t capacity)
+{
+    const sa::RefuseSwitch &r = sa::g_refuse;
+    const int have = r.count < sa::DIAG_KINDS_MAX ? r.count : sa::DIAG_KINDS_MAX;
+    for (int i = 0; kinds && i < have && i < capacity; ++i) kinds[i] = r.kinds[i];
+    return r.count;
+}
+
+SA_EXPORT int32_t sa_amd_debug_live_allocations(int64_t *device, int64_t *pinned)
+{
+    if (!device || !pinned) return SA_AMD_EINVAL;
+    *device = sa::g_live_device.load(std::memory_order_relaxed);
+    *pinned = sa::g_live_pinned.load(std::memory_order_relaxed);
+    return SA_AMD_OK;
+}
+
 SA_EXPORT int32_t sa_amd_debug_dsub_plain_atomics(int32_t mode)
 {
     return sa::g_dsub_plain_atomics.exchange(mode ? 1 : 0);
