@@ -22,6 +22,7 @@
 // Rust panics (assert!, engine failure) are std::logic_error / std::runtime_error here.
 #pragma once
 #include "suffix_array_amd.h"
+#include "sa_amd_tokdocs.h"
 
 #include <cstdint>
 #include <cstring>
@@ -239,10 +240,13 @@ private:
 };
 
 // A clause of DocumentIndex::match / match_list: the documents that hold ANY of the patterns, or with `negate` those that hold none
-struct Clause {
-    std::vector<std::string> any;
+// (written once over the pattern type: byte strings here, token sequences for TokenIndex::match)
+template <class Pattern>
+struct BasicClause {
+    std::vector<Pattern> any;
     bool negate = false;
 };
+using Clause = BasicClause<std::string>;
 
 // EXTENSION (not in the reference): text + suffix array resident on the device (sa_amd_index) with a collection of documents
 // over it (suffix_array_amd.h, "Document collections over the index").  offsets: ndocs + 1 non-decreasing values from 0 to n.
@@ -549,6 +553,14 @@ struct TokenAbi16 {
     static constexpr auto next_tokens = sa_amd_tok_index_next_tokens;
     static constexpr auto infgram = sa_amd_tok_index_infgram;
     static constexpr auto infgram_score = sa_amd_tok_index_infgram_score;
+    static constexpr auto set_documents = sa_amd_tok_index_set_documents;
+    static constexpr auto set_documents_by_separator = sa_amd_tok_index_set_documents_by_separator;
+    static constexpr auto doc_offsets = sa_amd_tok_index_doc_offsets;
+    static constexpr auto doc_of = sa_amd_tok_index_doc_of;
+    static constexpr auto doc_search = sa_amd_tok_index_doc_search;
+    static constexpr auto doc_list = sa_amd_tok_index_doc_list;
+    static constexpr auto doc_match = sa_amd_tok_index_doc_match;
+    static constexpr auto doc_match_list = sa_amd_tok_index_doc_match_list;
 };
 struct TokenAbi32 {
     using Token = std::uint32_t;
@@ -561,6 +573,14 @@ struct TokenAbi32 {
     static constexpr auto next_tokens = sa_amd_tok32_index_next_tokens;
     static constexpr auto infgram = sa_amd_tok32_index_infgram;
     static constexpr auto infgram_score = sa_amd_tok32_index_infgram_score;
+    static constexpr auto set_documents = sa_amd_tok32_index_set_documents;
+    static constexpr auto set_documents_by_separator = sa_amd_tok32_index_set_documents_by_separator;
+    static constexpr auto doc_offsets = sa_amd_tok32_index_doc_offsets;
+    static constexpr auto doc_of = sa_amd_tok32_index_doc_of;
+    static constexpr auto doc_search = sa_amd_tok32_index_doc_search;
+    static constexpr auto doc_list = sa_amd_tok32_index_doc_list;
+    static constexpr auto doc_match = sa_amd_tok32_index_doc_match;
+    static constexpr auto doc_match_list = sa_amd_tok32_index_doc_match_list;
 };
 
 // EXTENSION (not in the reference): a token text and its suffix array resident on the device.  Tokens compare as unsigned
@@ -664,6 +684,89 @@ public:
         return r;
     }
 
+    // ---- document collections (sa_amd_tokdocs.h): the methods of DocumentIndex with tokens for bytes ----
+
+    // offsets: ndocs + 1 non-decreasing values from 0 to len(), in tokens.  Replaces the collection; malformed offsets throw
+    // std::invalid_argument and leave the previous one in place.  -> ndocs
+    std::size_t set_documents(const std::vector<std::uint32_t> &offsets)
+    {
+        if (offsets.size() < 2) throw std::invalid_argument("document offsets: ndocs + 1 values from 0 to n");
+        check(Abi::set_documents(ix_, offsets.data(), static_cast<std::int64_t>(offsets.size()) - 1));
+        return offsets.size() - 1;
+    }
+    // every occurrence of `separator` ends a document and belongs to it; found on the device in the resident text.  -> ndocs
+    std::size_t set_documents_by_separator(Token separator)
+    {
+        std::int64_t nd = 0;
+        check(Abi::set_documents_by_separator(ix_, separator, &nd));
+        return static_cast<std::size_t>(nd);
+    }
+    // documents of the collection in effect, as the library holds it (no copy is kept here); 0 before a collection was set
+    std::size_t ndocs() const
+    {
+        std::int64_t nd = 0;
+        const std::int32_t rc = Abi::doc_offsets(ix_, nullptr, 0, &nd);
+        if (rc == SA_AMD_EINVAL) return 0;
+        check(rc);
+        return static_cast<std::size_t>(nd);
+    }
+    // the collection in effect: ndocs + 1 offsets in tokens
+    std::vector<std::uint32_t> doc_offsets() const
+    {
+        std::int64_t nd = 0;
+        check(Abi::doc_offsets(ix_, nullptr, 0, &nd));
+        std::vector<std::uint32_t> out(static_cast<std::size_t>(nd) + 1);
+        check(Abi::doc_offsets(ix_, out.data(), static_cast<std::int64_t>(out.size()), &nd));
+        if (static_cast<std::size_t>(nd) + 1 > out.size()) throw std::runtime_error("suffix_array_amd: the collection was replaced during doc_offsets");
+        out.resize(static_cast<std::size_t>(nd) + 1);
+        return out;
+    }
+    // the document of every token position; SA_AMD_DOC_NONE for positions >= len()
+    std::vector<std::uint32_t> doc_of(const std::vector<std::uint32_t> &positions) const
+    {
+        std::vector<std::uint32_t> out(positions.size());
+        check(Abi::doc_of(ix_, positions.data(), static_cast<std::int64_t>(positions.size()), out.data()));
+        return out;
+    }
+    // per pattern (occ, df): occurrences, and the number of distinct documents an occurrence starts in
+    std::vector<std::pair<std::uint32_t, std::uint32_t>> doc_search(const std::vector<Tokens> &patterns) const
+    {
+        const Batch b(patterns);
+        std::vector<std::uint32_t> occ(patterns.size() + 1), df(patterns.size() + 1);
+        check(Abi::doc_search(ix_, b.toks.data(), b.off.data(), b.count(), occ.data(), df.data()));
+        std::vector<std::pair<std::uint32_t, std::uint32_t>> out(patterns.size());
+        for (std::size_t q = 0; q < out.size(); ++q) out[q] = { occ[q], df[q] };
+        return out;
+    }
+    // per pattern the distinct documents it occurs in, in slot order
+    std::vector<std::vector<std::uint32_t>> doc_list(const std::vector<Tokens> &patterns) const
+    {
+        const Batch b(patterns);
+        return listing(patterns.size(), [&](std::int64_t *loff, std::uint32_t *docs, std::int64_t cap, std::int64_t *total) {
+            return Abi::doc_list(ix_, b.toks.data(), b.off.data(), b.count(), loff, docs, cap, total);
+        });
+    }
+    // Boolean document queries: a query is the AND of its clauses, a clause the OR of its token patterns, negated where `negate`
+    // is set.  -> per query the number of documents it holds in; match_list: the documents, in ascending document id.
+    using Clause = BasicClause<Tokens>;
+    std::vector<std::uint32_t> match(const std::vector<std::vector<Clause>> &queries) const
+    {
+        const Queries q(queries);
+        std::vector<std::uint32_t> df(queries.size() + 1);
+        check(Abi::doc_match(ix_, q.b.toks.data(), q.b.off.data(), q.b.count(), q.coff.data(), q.flags.data(), q.clauses(), q.qoff.data(), q.count(),
+                             df.data(), nullptr));
+        df.resize(queries.size());
+        return df;
+    }
+    std::vector<std::vector<std::uint32_t>> match_list(const std::vector<std::vector<Clause>> &queries) const
+    {
+        const Queries q(queries);
+        return listing(queries.size(), [&](std::int64_t *loff, std::uint32_t *docs, std::int64_t cap, std::int64_t *total) {
+            return Abi::doc_match_list(ix_, q.b.toks.data(), q.b.off.data(), q.b.count(), q.coff.data(), q.flags.data(), q.clauses(), q.qoff.data(),
+                                       q.count(), loff, docs, cap, total);
+        });
+    }
+
 private:
     struct Batch {
         Tokens toks;
@@ -678,6 +781,46 @@ private:
         }
         std::int32_t count() const { return static_cast<std::int32_t>(off.size() - 1); }
     };
+    static std::vector<Tokens> all_patterns(const std::vector<std::vector<Clause>> &queries)
+    {
+        std::vector<Tokens> out;
+        for (const auto &query : queries) for (const auto &c : query) out.insert(out.end(), c.any.begin(), c.any.end());
+        return out;
+    }
+    struct Queries {                                              // the layout of sa_amd_index_doc_match
+        Batch b;
+        std::vector<std::int32_t> coff, qoff;
+        std::vector<std::uint8_t> flags;
+        explicit Queries(const std::vector<std::vector<Clause>> &queries) : b(all_patterns(queries)), coff(1, 0), qoff(1, 0)
+        {
+            for (const auto &query : queries) {
+                for (const auto &c : query) {
+                    coff.push_back(coff.back() + static_cast<std::int32_t>(c.any.size()));
+                    flags.push_back(c.negate ? 1 : 0);
+                }
+                qoff.push_back(static_cast<std::int32_t>(flags.size()));
+            }
+            flags.push_back(0);                                   // (never an empty buffer)
+        }
+        std::int32_t clauses() const { return static_cast<std::int32_t>(coff.size() - 1); }
+        std::int32_t count() const { return static_cast<std::int32_t>(qoff.size() - 1); }
+    };
+    // a listing of `rows` rows: asked for again with the capacity the first call reported where it did not fit
+    template <class Call>
+    static std::vector<std::vector<std::uint32_t>> listing(std::size_t rows, Call call)
+    {
+        std::vector<std::int64_t> loff(rows + 1);
+        std::vector<std::uint32_t> docs(1 << 16);
+        std::int64_t total = 0;
+        for (;;) {
+            check(call(loff.data(), docs.data(), static_cast<std::int64_t>(docs.size()), &total));
+            if (total <= static_cast<std::int64_t>(docs.size())) break;
+            docs.resize(static_cast<std::size_t>(total));
+        }
+        std::vector<std::vector<std::uint32_t>> out(rows);
+        for (std::size_t q = 0; q < rows; ++q) out[q].assign(docs.begin() + loff[q], docs.begin() + loff[q + 1]);
+        return out;
+    }
     template <class Row>
     void ngram(const std::vector<Tokens> &patterns, bool backoff, std::int32_t min_count, std::int32_t max_len, std::vector<Row> &out,
                std::uint32_t *slen) const

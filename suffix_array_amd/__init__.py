@@ -37,6 +37,7 @@ __all__ = ["MAX_LENGTH", "saca", "SuffixArray", "SuffixArrayError", "lib", "diag
            "DocsStats", "last_docs_stats", "docs_set_chunk", "docs_work_bytes", "doc_of_device_ptr", "DOC_NONE", "DOC_SAMPLES",
            "DOC_CHUNK_MIN", "DOC_CHUNK_MAX", "DOC_CHUNK_DEFAULT",
            "Not", "DocMatchStats", "last_doc_match_stats", "doc_match_set_budget", "DOC_MATCH_BUDGET_DEFAULT", "DOC_MATCH_TILE_WORDS",
+           "TOKEN_DOC_OPS",
            "DocTfStats", "last_doc_tf_stats", "docs_set_topk_piece", "DOC_TOPK_MAX", "DOC_TOPK_PIECE_MIN", "DOC_TOPK_PIECE_MAX",
            "DOC_TOPK_PIECE_DEFAULT",
            "NgramStats", "last_ngram_stats", "ngram_set_stream_cap", "NGRAM_STREAM_CAP_DEFAULT",
@@ -344,6 +345,9 @@ DOC_CHUNK_DEFAULT = 4096
 #: wave combines (kernels/doc_match.hpp): 32 documents a word
 DOC_MATCH_BUDGET_DEFAULT = 256 << 20
 DOC_MATCH_TILE_WORDS = 256
+#: the document calls of include/sa_amd_tokdocs.h, each behind ``sa_amd_tok_index_`` and ``sa_amd_tok32_index_``
+TOKEN_DOC_OPS = ("set_documents", "set_documents_by_separator", "doc_offsets", "doc_of", "doc_search", "doc_list", "doc_match", "doc_match_list")
+
 #: the largest ``k`` of ``doc_topk`` (SA_AMD_DOC_TOPK_MAX of include/suffix_array_amd.h)
 DOC_TOPK_MAX = 1024
 #: keys of a piece of the top-k reduction: the clamp of ``docs_set_topk_piece`` and the default (kernels/doc_tf.hpp)
@@ -632,9 +636,20 @@ def lib() -> ctypes.CDLL:
         L.sa_amd_tok_index_infgram_score.restype = ctypes.c_int32
         L.sa_amd_last_tok_score_stats.argtypes = [c_vp]
         L.sa_amd_last_tok_score_stats.restype = None
+        # include/sa_amd_tokdocs.h: the document calls of the byte index on the token indexes
+        L.sa_amd_tok_index_set_documents.argtypes = [c_vp, c_vp, ctypes.c_int64]
+        L.sa_amd_tok_index_set_documents_by_separator.argtypes = [c_vp, ctypes.c_uint32, c_vp]
+        L.sa_amd_tok_index_doc_offsets.argtypes = [c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_tok_index_doc_of.argtypes = [c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_tok_index_doc_search.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp]
+        L.sa_amd_tok_index_doc_list.argtypes = [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.c_int64, c_vp]
+        L.sa_amd_tok_index_doc_match.argtypes = L.sa_amd_index_doc_match.argtypes
+        L.sa_amd_tok_index_doc_match_list.argtypes = L.sa_amd_index_doc_match_list.argtypes
+        for op in TOKEN_DOC_OPS:
+            getattr(L, "sa_amd_tok_index_" + op).restype = ctypes.c_int32
         for u16_name, u32_name in (("sa_amd_max_tokens_u16", "sa_amd_max_tokens_u32"), ("sa_amd_saca_u16", "sa_amd_saca_u32")) + tuple(
                 ("sa_amd_tok_index_" + op, "sa_amd_tok32_index_" + op)
-                for op in ("create", "destroy", "sa", "search", "next_tokens", "infgram", "infgram_score")):
+                for op in ("create", "destroy", "sa", "search", "next_tokens", "infgram", "infgram_score") + TOKEN_DOC_OPS):
             u16_fn, u32_fn = getattr(L, u16_name), getattr(L, u32_name)       # (the signatures are the u16 ones with uint32_t tokens)
             u32_fn.argtypes, u32_fn.restype = u16_fn.argtypes, u16_fn.restype
         _lib = L
@@ -1393,22 +1408,22 @@ def _as_pattern(x) -> bytes:
     return x.encode() if isinstance(x, str) else bytes(x)
 
 
-def _query_batch(queries):
+def _query_batch(queries, is_pattern=_is_pattern, as_pattern=_as_pattern, batch=_pattern_batch):
     """queries -> (pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries) in the layout of
     sa_amd_index_doc_match.  A query is a sequence of clauses; a clause is one pattern, a sequence of patterns (any of them), or
-    ``Not(...)`` of either."""
+    ``Not(...)`` of either.  The token indexes pass their own idea of a pattern and their own batch."""
     pats, clause_off, flags, query_off = [], [0], [], [0]
     for query in queries:
-        if _is_pattern(query) or isinstance(query, Not):
+        if is_pattern(query) or isinstance(query, Not):
             raise TypeError("a query is a sequence of clauses: wrap a single clause in a list")
         for clause in query:
             neg = isinstance(clause, Not)
             body = clause.clause if neg else clause
-            pats += [_as_pattern(body)] if _is_pattern(body) else [_as_pattern(p) for p in body]
+            pats += [as_pattern(body)] if is_pattern(body) else [as_pattern(p) for p in body]
             clause_off.append(len(pats))
             flags.append(1 if neg else 0)
         query_off.append(len(flags))
-    data, off, cnt = _pattern_batch(pats)
+    data, off, cnt = batch(pats)
     cfl = np.array(flags + [0], dtype=np.uint8)                       # (never a zero-sized buffer)
     return (data, off, cnt, np.array(clause_off, dtype=np.int32), cfl, len(flags), np.array(query_off, dtype=np.int32), len(query_off) - 1)
 
@@ -1821,6 +1836,14 @@ def _batch_of(pats, dtype):
     return np.ascontiguousarray(data, dtype=dtype), off, len(pats)
 
 
+def _is_token_pattern(x) -> bool:
+    """one token pattern: a 1-D array, or a non-empty list or tuple of ints (an empty list is a clause without patterns, as for
+    ``DeviceIndex``; the empty pattern is an empty array)"""
+    if isinstance(x, np.ndarray):
+        return x.ndim == 1
+    return isinstance(x, (list, tuple)) and len(x) > 0 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in x)
+
+
 def _token_batch(patterns):
     return _batch_of([_as_u16(p, "pattern") for p in patterns], np.uint16)
 
@@ -1977,6 +2000,100 @@ class TokenIndex:
                                          min(int(min_count), 2**31 - 1), max(-1, min(int(max_len), 2**31 - 1)), s.ctypes.data,
                                          lo.ctypes.data, hi.ctypes.data, ae.ctypes.data, nlo.ctypes.data, nhi.ctypes.data))
         return ScoreResult(s, lo, hi, ae, nlo, nhi)
+
+    # ---- document collections (include/sa_amd_tokdocs.h): the methods of ``DeviceIndex`` with tokens for bytes ----
+
+    def set_documents(self, offsets=None, *, separator=None) -> int:
+        """EXTENSION: make the text a collection of documents -> ``ndocs``.  Exactly one of the two: ``offsets``, ``ndocs + 1``
+        non-decreasing values from 0 to ``len(self)`` in tokens (document ``d`` is ``tokens[offsets[d]:offsets[d + 1]]``, empty
+        documents are legal), or ``separator``, a token id: every occurrence ends a document and belongs to it, found on the
+        device in the resident text; what follows the last one is a last document.  Replaces an earlier collection; a call that
+        fails leaves it in place."""
+        if (offsets is None) == (separator is None):
+            raise TypeError("set_documents: exactly one of offsets and separator")
+        if separator is not None:
+            if isinstance(separator, bool) or not isinstance(separator, (int, np.integer)) or not 0 <= int(separator) <= 0xFFFFFFFF:
+                raise TypeError("set_documents: separator is a token id")
+            nd = ctypes.c_int64(0)
+            _check(self._fn("set_documents_by_separator")(self._h, int(separator), ctypes.byref(nd)))
+            return int(nd.value)
+        off = np.ascontiguousarray(offsets)
+        if off.ndim != 1 or off.size < 2 or off.dtype.kind not in "iu" or off.min() < 0 or off.max() > 0xFFFFFFFF:
+            raise SuffixArrayError(-1, "document offsets: ndocs + 1 integers in 0 .. len(tokens)")
+        off = off.astype(np.uint32)
+        _check(self._fn("set_documents")(self._h, off.ctypes.data, off.size - 1))
+        return off.size - 1
+
+    @property
+    def ndocs(self) -> int:
+        """documents of the collection in effect, as the library holds it (no copy is kept here); 0 before ``set_documents``"""
+        nd = ctypes.c_int64(0)
+        rc = self._fn("doc_offsets")(self._h, None, 0, ctypes.byref(nd))
+        if rc == -1:                                                  # SA_AMD_EINVAL: no collection yet
+            return 0
+        _check(rc)
+        return int(nd.value)
+
+    def doc_offsets(self) -> np.ndarray:
+        """the collection in effect as ``set_documents`` takes it: ``ndocs + 1`` offsets in tokens (uint32), from the device"""
+        nd = ctypes.c_int64(0)
+        _check(self._fn("doc_offsets")(self._h, None, 0, ctypes.byref(nd)))
+        out = np.empty(int(nd.value) + 1, dtype=np.uint32)
+        _check(self._fn("doc_offsets")(self._h, out.ctypes.data, out.size, ctypes.byref(nd)))
+        return out[:int(nd.value) + 1] if int(nd.value) + 1 <= out.size else self.doc_offsets()      # (replaced in between: again)
+
+    def doc_of(self, positions) -> np.ndarray:
+        """the document each token position lies in (uint32; ``DOC_NONE`` for positions ``>= len(self)``)"""
+        pos = np.ascontiguousarray(positions, dtype=np.uint32).ravel()
+        out = np.empty(pos.size, dtype=np.uint32)
+        _check(self._fn("doc_of")(self._h, pos.ctypes.data, pos.size, out.ctypes.data))
+        return out
+
+    def doc_search(self, patterns):
+        """-> ``(occ, df)``, uint32 arrays over the patterns: occurrences (``hi - lo`` of ``search``), and the number of distinct
+        documents an occurrence starts in"""
+        data, off, cnt = self._batch(patterns)
+        out = np.zeros((2, cnt), dtype=np.uint32)
+        _check(self._fn("doc_search")(self._h, data.ctypes.data, off.ctypes.data, cnt, out[0].ctypes.data, out[1].ctypes.data))
+        return out[0], out[1]
+
+    def _doc_listing(self, fn, args, rows: int) -> list:
+        loff = np.zeros(rows + 1, dtype=np.int64)
+        total = ctypes.c_int64(0)
+        cap = 1 << 16
+        while True:
+            docs = np.empty(cap, dtype=np.uint32)
+            _check(fn(self._h, *args, loff.ctypes.data, docs.ctypes.data, cap, ctypes.byref(total)))
+            if total.value <= cap:
+                return [docs[loff[q]:loff[q + 1]].copy() for q in range(rows)]
+            cap = int(total.value)
+
+    def doc_list(self, patterns) -> list:
+        """-> per pattern the uint32 array of the distinct documents it occurs in, ordered by the document's smallest matching
+        suffix (slot order)"""
+        data, off, cnt = self._batch(patterns)
+        return self._doc_listing(self._fn("doc_list"), (data.ctypes.data, off.ctypes.data, cnt), cnt)
+
+    def _queries(self, queries):
+        return _query_batch(queries, _is_token_pattern, lambda p: p, self._batch)
+
+    def doc_match(self, queries, clause_df: bool = False):
+        """EXTENSION: Boolean document queries, the forms and results of ``DeviceIndex.doc_match``: a query is a sequence of
+        clauses that must all hold; a clause is one token pattern (an array, or a non-empty list of ints), a sequence of
+        patterns of which any may occur, or ``Not(...)`` of either.  -> ``df`` over the queries, with ``clause_df=True``
+        ``(df, clause_df)``."""
+        data, off, npat, coff, cfl, ncl, qoff, nq = self._queries(queries)
+        df = np.zeros(nq, dtype=np.uint32)
+        cdf = np.zeros(ncl, dtype=np.uint32) if clause_df else None
+        _check(self._fn("doc_match")(self._h, data.ctypes.data, off.ctypes.data, npat, coff.ctypes.data, cfl.ctypes.data, ncl,
+                                     qoff.ctypes.data, nq, df.ctypes.data if nq else None, cdf.ctypes.data if clause_df and ncl else None))
+        return (df, cdf) if clause_df else df
+
+    def doc_match_list(self, queries) -> list:
+        """EXTENSION: per query of ``doc_match`` the uint32 array of the documents it holds in, in ascending document id"""
+        data, off, npat, coff, cfl, ncl, qoff, nq = self._queries(queries)
+        return self._doc_listing(self._fn("doc_match_list"),
+                                 (data.ctypes.data, off.ctypes.data, npat, coff.ctypes.data, cfl.ctypes.data, ncl, qoff.ctypes.data, nq), nq)
 
 
 class TokenIndex32(TokenIndex):

@@ -57,7 +57,8 @@ static unsigned dm_item_grid(int64_t items)
 
 // !list: df (nqueries entries) and clause_df (nclauses entries), either may be nullptr.  list: list_off (nqueries + 1 entries), the
 // first `capacity` documents to docs, the number of all of them to *total_out.  Host pointers, arguments checked by the caller.
-static int doc_match_query(const sa_amd_index &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t npat, const int32_t *clause_off,
+template <typename Index>
+static int doc_match_query(const Index &ix, const typename DocsSym<Index>::type *pat_data, const int64_t *pat_off, int32_t npat, const int32_t *clause_off,
                            const uint8_t *clause_flags, int32_t nclauses, const int32_t *query_off, int32_t nqueries, bool list, uint32_t *df_out,
                            uint32_t *cdf_out, int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
 {

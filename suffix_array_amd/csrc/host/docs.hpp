@@ -140,12 +140,33 @@ struct DocsBatch {
     explicit DocsBatch(int device) : sc(device, false) {}
 };
 
-// patterns up, the ranges by the search kernels, the units.  One blocking read-back: the number of units (with the summed occ
-// and the bound of the listing).  count >= 1.
-static int docs_ranges(DocsBatch &b, const sa_amd_index &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, bool list)
+// What an index type supplies to the document routes below, which are written once over it: the symbol
+// of its patterns, DocsSym<Index>::type, and the range step, docs_launch_ranges(ix, dP, dO, count, dLo, dHi, st) -- an
+// overload found through the index type.  Everything else they use is common to the owners: device, n, ndocs, sa(), doc_off(),
+// doc_prev().  The byte index: bytes, and the search kernels with the bucket and LCP tables as sa_amd_index_search runs them.
+template <typename Index> struct DocsSym { using type = typename Index::Sym; };
+template <> struct DocsSym<sa_amd_index> { using type = uint8_t; };
+
+static int docs_launch_ranges(const sa_amd_index &ix, const uint8_t *dP, const int64_t *dO, int32_t count, uint32_t *dLo, uint32_t *dHi, hipStream_t st)
 {
+    g_prof.begin(KC_MISC, count, st);
+    const int rcs = launch_search(ix.text(), ix.sa(), ix.n, ix.bkt(), ix.pair(), dP, dO, count, nullptr, dLo, dHi, nullptr, nullptr, nullptr, st);
+    g_prof.end(st);
+    return rcs;
+}
+
+// the end of docs_set: the tables a replaced collection leaves behind.  The byte index drops the frequency table, which was the
+// old collection's.
+static void docs_replaced(sa_amd_index &ix) { ix.dDocSlots.reset(); }
+
+// patterns up, the ranges by the index's range step, the units.  One blocking read-back: the number of units (with the summed
+// occ and the bound of the listing).  count >= 1; pat_off counts symbols.
+template <typename Index>
+static int docs_ranges(DocsBatch &b, const Index &ix, const typename DocsSym<Index>::type *pat_data, const int64_t *pat_off, int32_t count, bool list)
+{
+    using Sym = typename DocsSym<Index>::type;
     route_tuning();                                             // (the posted read-backs' switch; nothing else of the tuning is used here)
-    const size_t C = (size_t)count, total = (size_t)pat_off[count];
+    const size_t C = (size_t)count, total = sizeof(Sym) * (size_t)pat_off[count];
     const uint32_t N1 = (uint32_t)ix.n + 1u;
     b.chunk = (uint32_t)(g_docs_chunk < 0 ? DOC_CHUNK_DEFAULT : g_docs_chunk);
     const uint32_t chunk = b.chunk;
@@ -155,7 +176,7 @@ static int docs_ranges(DocsBatch &b, const sa_amd_index &ix, const uint8_t *pat_
     const size_t b_ts = align_up(docs_scan_words((int64_t)C + 1) * 8, 256);
     sc.acquire(256 + b_pat + b_off + 4 * b_w + b_off + b_ts + (list ? b_off : 0));
     unsigned long long *ctl = b.ctl = (unsigned long long *)sc.take(256);
-    uint8_t *dP = (uint8_t *)sc.take(b_pat);
+    Sym *dP = (Sym *)sc.take(b_pat);
     int64_t *dO = (int64_t *)sc.take(b_off);
     uint32_t *dLo = b.dLo = (uint32_t *)sc.take(b_w), *dHi = (uint32_t *)sc.take(b_w);
     b.dOcc = (uint32_t *)sc.take(b_w);
@@ -169,11 +190,8 @@ static int docs_ranges(DocsBatch &b, const sa_amd_index &ix, const uint8_t *pat_
     if (total) HIP_TRY(hipMemcpyAsync(dP, pat_data, total, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dO, pat_off, (C + 1) * 8, hipMemcpyHostToDevice, st));
 
-    // ---- the ranges, by the search kernels as sa_amd_index_search runs them ----
-    g_prof.begin(KC_MISC, count, st);
-    const int rcs = launch_search(ix.text(), ix.sa(), ix.n, ix.bkt(), ix.pair(), dP, dO, count, nullptr, dLo, dHi, nullptr, nullptr, nullptr, st);
-    g_prof.end(st);
-    if (rcs) return rcs;
+    // ---- the ranges, as the index's own search runs them ----
+    { const int rcs = docs_launch_ranges(ix, (const Sym *)dP, (const int64_t *)dO, count, dLo, dHi, st); if (rcs) return rcs; }
     // ---- the units: ceil(occ / chunk) per pattern, scanned; the number of all of them comes back ----
     PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_doc_ranges, dim3((unsigned)ceil_div((int64_t)count + 1, DOC_THREADS)), dim3(DOC_THREADS), 0, st, dLo,
                                                 (const uint32_t *)dHi, count, N1, chunk, ix.ndocs, b.dOcc, uoff, ctl));
@@ -196,7 +214,8 @@ struct DocsListing {
 };
 
 // counts per unit, one scan for the units' offsets and the patterns', ordered compaction; waits for the stream
-static int docs_listing(DocsBatch &b, DocsListing &ls, const sa_amd_index &ix, int32_t count, int64_t capacity)
+template <typename Index>
+static int docs_listing(DocsBatch &b, DocsListing &ls, const Index &ix, int32_t count, int64_t capacity)
 {
     const size_t C = (size_t)count;
     const unsigned long long units = b.units, occ_sum = b.occ_sum;
@@ -235,7 +254,8 @@ static int docs_listing(DocsBatch &b, DocsListing &ls, const sa_amd_index &ix, i
 // Document frequency (!list: occ and df, either may be nullptr) or listing (list_off: count + 1 entries, the first `capacity`
 // documents to docs, the number of all of them to *total_out) of a batch of patterns; host pointers, arguments checked by the
 // caller.
-static int docs_query(const sa_amd_index &ix, const uint8_t *pat_data, const int64_t *pat_off, int32_t count, bool list, uint32_t *occ_out,
+template <typename Index>
+static int docs_query(const Index &ix, const typename DocsSym<Index>::type *pat_data, const int64_t *pat_off, int32_t count, bool list, uint32_t *occ_out,
                       uint32_t *df_out, int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
 {
     sa_amd_docs_stats ds;
@@ -288,10 +308,11 @@ static int docs_query(const sa_amd_index &ix, const uint8_t *pat_data, const int
     return SA_AMD_OK;
 }
 
-// sa_amd_index_set_documents: the collection's two tables, built from the caller's offsets (checked by the caller) and handed to
-// the index.  A failure leaves the previous collection and its frequency table; a success drops that table, which was the old
-// collection's: the caller enables it again.
-static int32_t docs_set(sa_amd_index &ix, const uint32_t *doc_off, int64_t ndocs)
+// sa_amd_index_set_documents and the token indexes' _set_documents: the collection's two tables, built from the caller's offsets
+// (checked by the caller) and handed to the index.  A failure leaves the previous collection and (the byte index) its frequency
+// table; a success drops that table, which was the old collection's: the caller enables it again.
+template <typename Index>
+static int32_t docs_set(Index &ix, const uint32_t *doc_off, int64_t ndocs)
 {
     const size_t M = (size_t)ndocs + 1, N1 = (size_t)ix.n + 1;
     PooledScope sc(ix.device, false);
@@ -306,13 +327,14 @@ static int32_t docs_set(sa_amd_index &ix, const uint32_t *doc_off, int64_t ndocs
     if (sc.finish() != SA_AMD_OK) return sc.rc;                  // (a previous collection stays)
     ix.dDocOff = std::move(off);
     ix.dDocPrev = std::move(prev);
-    ix.dDocSlots.reset();
+    docs_replaced(ix);
     ix.ndocs = (uint32_t)ndocs;
     return SA_AMD_OK;
 }
 
-// sa_amd_index_doc_of: host pointers, count >= 1
-static int32_t doc_of_host(const sa_amd_index &ix, const uint32_t *pos, int64_t count, uint32_t *doc_out)
+// sa_amd_index_doc_of and the token indexes' _doc_of: host pointers, count >= 1
+template <typename Index>
+static int32_t doc_of_host(const Index &ix, const uint32_t *pos, int64_t count, uint32_t *doc_out)
 {
     const size_t b = align_up((size_t)count * 4, 256);
     PooledScope sc(ix.device, false);

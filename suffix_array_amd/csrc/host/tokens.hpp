@@ -3,9 +3,13 @@
 // `sa_amd_tok_index *` / `sa_amd_tok32_index *` (the owner of the token text and its suffix array, as host/index.hpp is for the
 // byte index), the token build -- byte image, the byte builder on it, compaction -- behind sa_amd_saca_u16 / _u32 and the two
 // index_create, and the queries: _search, _next_tokens and _infgram.  The two _infgram_score are host/score.hpp's route on these
-// index types.
+// index types.  A token index owns a document collection as the byte index does: the document routes of
+// host/docs.hpp and host/doc_match.hpp run on it through the range step below, and tok_docs_by_separator defines the collection
+// from the resident text.
 #pragma once
 #include "ngram.hpp"
+#include "doc_match.hpp"
+#include "../../../include/sa_amd_tokdocs.h"
 #include "../kernels/tokens.hpp"
 
 namespace sa {
@@ -17,9 +21,14 @@ struct TokIndexOwner {
     using Sym = SymT;
     int device = 0;
     int32_t n = 0;
+    uint32_t ndocs = 0;
     DevBuf dT, dSA;
+    DevBuf dDocOff;        // document offsets in tokens (ndocs + 1 entries) once a _set_documents call has taken a collection
+    DevBuf dDocPrev;       // per slot: the previous slot of the same document + 1 (n + 1 entries)
     const Sym *text() const { return dT.as<const Sym>(); }
     const uint32_t *sa() const { return dSA.as<const uint32_t>(); }
+    const uint32_t *doc_off() const { return dDocOff.as<const uint32_t>(); }
+    const uint32_t *doc_prev() const { return dDocPrev.as<const uint32_t>(); }
     // no bucket table and no LCP table: what the index-generic routes (host/score.hpp) pass to the kernels
     const uint32_t *bkt() const { return nullptr; }
     const uint64_t *pair() const { return nullptr; }
@@ -195,6 +204,69 @@ static int32_t tok_index_create(const typename Index::Sym *T, int32_t n, const u
     return SA_AMD_OK;
 }
 
+// ---- document collections (host/docs.hpp, host/doc_match.hpp): what the token index supplies to the shared routes ----
+
+// the range step: k_tok_search as _search runs it, no bucket table and no LCP table; dO counts tokens
+template <typename Sym>
+static int docs_launch_ranges(const TokIndexOwner<Sym> &ix, const Sym *dP, const int64_t *dO, int32_t count, uint32_t *dLo, uint32_t *dHi, hipStream_t st)
+{
+    PROF(KC_MISC, count, st, hipLaunchKernelGGL(k_tok_search, dim3(ngram_grid(count)), dim3(NG_THREADS), 0, st, ix.text(), ix.sa(), (int64_t)ix.n, dP, dO,
+                                                count, (uint8_t *)nullptr, dLo, dHi));
+    return SA_AMD_OK;
+}
+
+// (a token index keeps no table that belongs to the collection it replaces)
+template <typename Sym>
+static void docs_replaced(TokIndexOwner<Sym> &) { }
+
+// _set_documents_by_separator behind its argument checks: every occurrence of `sep` ends a document and belongs to it.  The
+// separators are counted per tile of the resident text, the counts scanned, and one blocking read-back brings their number k
+// and whether a last document runs to n; the offsets table is then allocated at its exact size, written by k_tok_sep_emit, and
+// the route is docs_build as for a caller's offsets (its read-back is the sort's error word).  The text is read twice; nothing
+// else of its size is touched before docs_build.  A failure leaves the previous collection; *ndocs_out is written last.
+template <typename Index>
+static int32_t tok_docs_by_separator(Index &ix, uint32_t sep, int64_t *ndocs_out)
+{
+    const int64_t n = ix.n, tiles = ceil_div(n, TK_TILE);
+    PooledScope sc(ix.device, false);
+    const size_t wb = docs_layout(ix.n).bytes, b_cnt = align_up((size_t)(tiles + 2) * 8, 256), b_ts = align_up(docs_scan_words(tiles + 1) * 8, 256);
+    sc.acquire(wb + b_cnt + b_ts);
+    void *dW = sc.take(wb);
+    unsigned long long *cnt = (unsigned long long *)sc.take(b_cnt), *tsum = (unsigned long long *)sc.take(b_ts);
+    if (sc.rc) return sc.rc;
+    hipStream_t st = sc.st;
+    const unsigned grid = tok_stream_grid(ceil_div(tiles, TK_SPAN), 1);
+    PROF(KC_MISC, n, st, hipLaunchKernelGGL(k_tok_sep_count, dim3(grid), dim3(TK_THREADS), 0, st, ix.text(), n, tiles, sep, cnt));
+    { const int rcs = docs_scan(cnt, tiles + 1, tsum, nullptr, st); if (rcs) return rcs; }
+    unsigned long long kw[2];
+    { const int rcw = read_words(kw, cnt + tiles, sizeof(kw), st); if (rcw) return rcw; }
+    if (kw[0] > (unsigned long long)n || kw[1] > 1ull) return SA_AMD_EINTERNAL;
+    const int64_t ndocs = (int64_t)(kw[0] + kw[1]);              // (n <= 2^30: far below the byte forms' limit of documents)
+    DevBuf off, prev;
+    if (index_table_alloc(off, ((size_t)ndocs + 1) * 4) != SA_AMD_OK || index_table_alloc(prev, ((size_t)n + 1) * 4) != SA_AMD_OK) return SA_AMD_ENOMEM;
+    PROF(KC_MISC, n, st, hipLaunchKernelGGL(k_tok_sep_emit, dim3(grid), dim3(TK_THREADS), 0, st, ix.text(), n, tiles, sep, (const unsigned long long *)cnt,
+                                            off.as<uint32_t>(), kw[0], (uint32_t)kw[1]));
+    sc.rc = docs_build(ix.sa(), ix.n, off.as<uint32_t>(), (uint32_t)ndocs, prev.as<uint32_t>(), dW, (int64_t)wb, st);
+    if (sc.finish() != SA_AMD_OK) return sc.rc;                  // (a previous collection stays)
+    ix.dDocOff = std::move(off);
+    ix.dDocPrev = std::move(prev);
+    ix.ndocs = (uint32_t)ndocs;
+    if (ndocs_out) *ndocs_out = ndocs;
+    return SA_AMD_OK;
+}
+
+// _doc_offsets: the first min(capacity, ndocs + 1) offsets come down; *ndocs_out behind the copy, which is the step that can fail
+template <typename Index>
+static int32_t tok_doc_offsets(const Index &ix, uint32_t *doc_off_out, int64_t capacity, int64_t *ndocs_out)
+{
+    DeviceGuard guard(ix.device);
+    if (guard.rc != SA_AMD_OK) return guard.rc;
+    const int64_t M = (int64_t)ix.ndocs + 1, wr = capacity < M ? capacity : M;
+    if (wr > 0) HIP_TRY(hipMemcpy(doc_off_out, ix.doc_off(), (size_t)wr * 4, hipMemcpyDeviceToHost));
+    *ndocs_out = (int64_t)ix.ndocs;
+    return SA_AMD_OK;
+}
+
 template <typename Index>
 static int32_t tok_index_sa(const Index &ix, uint32_t *SA_out)
 {
@@ -334,6 +406,65 @@ static int tok_query(const Index &ix, const typename Index::Sym *pat_data, const
     ngram_stats_fill(ts, ts.compared_tokens, count, backoff, cw, cap > 0 ? 2 : 1, g_readbacks - rb0);
     g_last_tok_stats = ts;
     return SA_AMD_OK;
+}
+
+// ---- the entry points of include/sa_amd_tokdocs.h behind the ABI guard: the argument checks of the byte forms and of
+//      tok_query_args, then the shared routes ----
+
+template <typename Index>
+static int32_t tokdocs_set(Index *ix, const uint32_t *doc_off, int64_t ndocs)
+{
+    if (!ix || !docs_valid(doc_off, ndocs) || doc_off[ndocs] != (uint32_t)ix->n) return SA_AMD_EINVAL;
+    return docs_set(*ix, doc_off, ndocs);
+}
+
+template <typename Index>
+static int32_t tokdocs_set_by_separator(Index *ix, uint32_t separator, int64_t *ndocs_out)
+{
+    if (!ix) return SA_AMD_EINVAL;
+    if (separator >= (uint32_t)sym_end<typename Index::Sym>()) return SA_AMD_ERANGE;
+    return tok_docs_by_separator(*ix, separator, ndocs_out);
+}
+
+template <typename Index>
+static int32_t tokdocs_offsets(const Index *ix, uint32_t *doc_off_out, int64_t capacity, int64_t *ndocs_out)
+{
+    if (!ix || capacity < 0 || !ndocs_out || (capacity > 0 && !doc_off_out) || !ix->doc_off()) return SA_AMD_EINVAL;
+    return tok_doc_offsets(*ix, doc_off_out, capacity, ndocs_out);
+}
+
+template <typename Index>
+static int32_t tokdocs_doc_of(const Index *ix, const uint32_t *pos, int64_t count, uint32_t *doc_out)
+{
+    if (!ix || count < 0 || (count > 0 && (!pos || !doc_out)) || !ix->doc_off()) return SA_AMD_EINVAL;
+    if (count == 0) return SA_AMD_OK;
+    return doc_of_host(*ix, pos, count, doc_out);
+}
+
+// list: the arguments of _doc_list, else those of _doc_search
+template <typename Index>
+static int32_t tokdocs_query(const Index *ix, const typename Index::Sym *pat_data, const int64_t *pat_off, int32_t count, bool list, uint32_t *occ,
+                             uint32_t *df, int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
+{
+    if (list && (capacity < 0 || !list_off || !total_out || (capacity > 0 && !docs))) return SA_AMD_EINVAL;
+    if (const int32_t rc = tok_query_args(ix, pat_data, pat_off, count)) return rc;
+    if (!ix->doc_off()) return SA_AMD_EINVAL;
+    return docs_query(*ix, pat_data, pat_off, count, list, occ, df, list_off, docs, capacity, total_out);
+}
+
+// list: the arguments of _doc_match_list, else those of _doc_match
+template <typename Index>
+static int32_t tokdocs_match(const Index *ix, const typename Index::Sym *pat_data, const int64_t *pat_off, int32_t npat, const int32_t *clause_off,
+                             const uint8_t *clause_flags, int32_t nclauses, const int32_t *query_off, int32_t nqueries, bool list, uint32_t *df,
+                             uint32_t *clause_df, int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
+{
+    // (the cast: doc_match_args_valid looks at pat_data for NULL only and at pat_off, which counts symbols of either kind)
+    if (!ix || !doc_match_args_valid((const uint8_t *)pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries)) return SA_AMD_EINVAL;
+    if (list && (capacity < 0 || !list_off || !total_out || (capacity > 0 && !docs))) return SA_AMD_EINVAL;
+    if (!tok_ids_valid(pat_data, npat > 0 ? pat_off[npat] : 0)) return SA_AMD_ERANGE;
+    if (!ix->doc_off()) return SA_AMD_EINVAL;
+    return doc_match_query(*ix, pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries, list, df, clause_df, list_off, docs,
+                           capacity, total_out);
 }
 
 }  // namespace sa

@@ -5,7 +5,9 @@
 // bytes compare like the tokens and two suffixes of B at offsets divisible by STRIDE have lengths divisible by STRIDE, so their
 // byte order is the token order.  Queries over a resident token index, written once over Sym = uint16_t / uint32_t:
 // range search (k_tok_search), back-off (k_infgram_suffix<uint16_t>, <uint32_t>) and the counts of the token that follows a
-// context (k_tok_next), the token forms of kernels/ngram.hpp.  One wave per query, no atomics on the answers.  gfx950, wave64.
+// context (k_tok_next), the token forms of kernels/ngram.hpp.  One wave per query, no atomics on the answers.  Documents from a
+// separator token (section 27): the compaction's shape over the text itself (k_tok_sep_count, one scan, k_tok_sep_emit).
+// gfx950, wave64.
 // Every slot read lies in [0, n + 1) and every SA entry is checked against n before T is read through it, whatever the arrays hold.
 #pragma once
 #include "ngram.hpp"
@@ -218,6 +220,138 @@ __global__ __launch_bounds__(TK_THREADS) void k_tok_sa_range(const uint32_t *__r
     for (int64_t i = (int64_t)blockIdx.x * TK_THREADS + threadIdx.x; i <= n; i += (int64_t)gridDim.x * TK_THREADS)
         bad |= (int64_t)SA[i] > n;
     if (__ballot(bad) && lane_id() == 0) atomicOr(flags, 1u);
+}
+
+// ---- documents from a separator token: the positions of `sep` in T[0 .. n), each plus one, in their
+//      order -- the compaction above with the text for the byte-level array and "equals sep" for "divisible by STRIDE" ----
+
+template <typename Sym> struct TokSepOf {
+    static constexpr int PER = 16 / (int)sizeof(Sym);                   // tokens of one lane's 16-byte load: 8 or 4
+    static constexpr int LOADS = TK_WAVE_ITEMS / (WAVE * PER);          // wave-wide loads that cover a wave's share of a tile: 1 or 2
+    static_assert(LOADS * WAVE * PER == TK_WAVE_ITEMS, "whole loads cover a wave's share of a tile");
+};
+
+// The PER tokens [base, base + PER) that a lane holds after one 16-byte load: bit k of the result is set iff base + k < n and
+// T[base + k] == sep.  T is 16-byte aligned with 16 bytes of slack behind the tokens and base is a multiple of PER, so the load
+// is in range wherever base < n; what it brings from behind n is masked by index.
+template <typename Sym>
+__device__ __forceinline__ uint32_t tok_sep_load(const Sym *__restrict__ T, int64_t n, int64_t base, uint32_t sep)
+{
+    constexpr int PER = TokSepOf<Sym>::PER;
+    uint32_t m = 0;
+    if (base < n) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(T + base);
+        const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            uint32_t t;
+            if constexpr (sizeof(Sym) == 2) t = (w[k >> 1] >> (16 * (k & 1))) & 0xffffu; else t = w[k];
+            if (t == sep && base + k < n) m |= 1u << k;
+        }
+    }
+    return m;
+}
+
+// the flags of component k of a wave-wide load: how many lanes hold one, and how many of those lie below this lane
+__device__ __forceinline__ void tok_sep_ballot(uint32_t m, int k, uint32_t *before, uint32_t *all)
+{
+    const uint64_t b = __ballot((m >> k) & 1u);
+    *before += __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+    *all += (uint32_t)__popcll(b);
+}
+
+// cnt[t] = the number of separators in tile t (TK_TILE tokens) of T[0 .. n); cnt[tiles] = 0 (the scan leaves the number k of all
+// separators there) and cnt[tiles + 1] = 1 iff a last document runs to n behind the last separator (n == 0 or T[n - 1] != sep),
+// which the scan does not touch: the two words come back together.  A workgroup takes TK_SPAN tiles a trip, a wave
+// TK_WAVE_ITEMS consecutive tokens of each; a tile's count is the popcounts of its waves' ballots, summed in LDS.
+template <typename Sym>
+__global__ __launch_bounds__(TK_THREADS) void k_tok_sep_count(const Sym *__restrict__ T, int64_t n, int64_t tiles, uint32_t sep,
+                                                             unsigned long long *__restrict__ cnt)
+{
+    constexpr int PER = TokSepOf<Sym>::PER, LOADS = TokSepOf<Sym>::LOADS;
+    __shared__ uint32_t s_w[TK_SPAN][TK_WAVES];
+    const int l = lane_id(), w = wave_id();
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        cnt[tiles] = 0ull;
+        cnt[tiles + 1] = n == 0 || (uint32_t)T[n - 1] != sep ? 1ull : 0ull;
+    }
+    const int64_t spans = (tiles + TK_SPAN - 1) / TK_SPAN;
+    for (int64_t sp = blockIdx.x; sp < spans; sp += gridDim.x) {
+#pragma unroll
+        for (int t = 0; t < TK_SPAN; ++t) {
+            const int64_t tile = sp * TK_SPAN + t;
+            uint32_t m[LOADS], before = 0, all = 0;
+#pragma unroll
+            for (int c = 0; c < LOADS; ++c)
+                m[c] = tok_sep_load(T, n, tile * TK_TILE + (int64_t)w * TK_WAVE_ITEMS + (int64_t)c * WAVE * PER + PER * l, sep);
+#pragma unroll
+            for (int c = 0; c < LOADS; ++c)
+#pragma unroll
+                for (int k = 0; k < PER; ++k) tok_sep_ballot(m[c], k, &before, &all);
+            if (l == 0) s_w[t][w] = all;
+        }
+        __syncthreads();
+        if (threadIdx.x < TK_SPAN && sp * TK_SPAN + threadIdx.x < tiles) {
+            uint32_t s = 0;
+#pragma unroll
+            for (int i = 0; i < TK_WAVES; ++i) s += s_w[threadIdx.x][i];
+            cnt[sp * TK_SPAN + threadIdx.x] = s;
+        }
+        __syncthreads();
+    }
+}
+
+// doc_off[1 + base[t] + r] = p + 1 for the r-th separator p of tile t, base the scanned counts: the ends of the documents in
+// their order.  The flags are computed again; the rank of a lane's first separator inside its wave is mbcnt over the ballots of
+// the PER components (the lanes below hold the tokens before its own), the waves of a tile meet in LDS.  One work-item writes
+// doc_off[0] = 0 and, `closing`, doc_off[k + 1] = n.  Entries 1 .. k are written and no other, whatever base holds.
+template <typename Sym>
+__global__ __launch_bounds__(TK_THREADS) void k_tok_sep_emit(const Sym *__restrict__ T, int64_t n, int64_t tiles, uint32_t sep,
+                                                            const unsigned long long *__restrict__ base, uint32_t *__restrict__ doc_off,
+                                                            unsigned long long k_all, uint32_t closing)
+{
+    constexpr int PER = TokSepOf<Sym>::PER, LOADS = TokSepOf<Sym>::LOADS;
+    __shared__ uint32_t s_w[TK_WAVES];
+    const int l = lane_id(), w = wave_id();
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        doc_off[0] = 0u;
+        if (closing) doc_off[k_all + 1] = (uint32_t)n;
+    }
+    const int64_t spans = (tiles + TK_SPAN - 1) / TK_SPAN;
+    for (int64_t sp = blockIdx.x; sp < spans; sp += gridDim.x) {
+        for (int t = 0; t < TK_SPAN; ++t) {
+            const int64_t tile = sp * TK_SPAN + t;
+            if (tile >= tiles) break;                                 // (the same for every work-item)
+            const int64_t first = tile * TK_TILE + (int64_t)w * TK_WAVE_ITEMS + PER * l;
+            uint32_t m[LOADS], rank[LOADS], total = 0;
+#pragma unroll
+            for (int c = 0; c < LOADS; ++c) m[c] = tok_sep_load(T, n, first + (int64_t)c * WAVE * PER, sep);
+#pragma unroll
+            for (int c = 0; c < LOADS; ++c) {
+                uint32_t before = 0, all = 0;
+#pragma unroll
+                for (int k = 0; k < PER; ++k) tok_sep_ballot(m[c], k, &before, &all);
+                rank[c] = total + before;
+                total += all;
+            }
+            if (l == 0) s_w[w] = total;
+            __syncthreads();
+            unsigned long long o = base[tile];
+#pragma unroll
+            for (int i = 0; i < TK_WAVES; ++i) if (i < w) o += s_w[i];
+            __syncthreads();
+#pragma unroll
+            for (int c = 0; c < LOADS; ++c) {
+                unsigned long long at = o + rank[c];
+#pragma unroll
+                for (int k = 0; k < PER; ++k) {
+                    if (!((m[c] >> k) & 1u)) continue;
+                    if (at < k_all) doc_off[at + 1] = (uint32_t)(first + (int64_t)c * WAVE * PER + k + 1);
+                    ++at;
+                }
+            }
+        }
+    }
 }
 
 // Range search of `count` patterns, one wave each (a wave takes every waves-th pattern): plain_range (kernels/sym.hpp) over the

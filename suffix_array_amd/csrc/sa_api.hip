@@ -1007,6 +1007,138 @@ SA_EXPORT int32_t sa_amd_tok32_index_infgram_score(const sa_amd_tok32_index *ix,
     SA_ABI_GUARD_END(0)
 }
 
+// ---- document collections over the token indexes (include/sa_amd_tokdocs.h): the checks are
+//      host/tokens.hpp's, the routes host/docs.hpp's and host/doc_match.hpp's on the token index types ----
+
+SA_EXPORT int32_t sa_amd_tok_index_set_documents(sa_amd_tok_index *ix, const uint32_t *doc_off, int64_t ndocs)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_set(ix, doc_off, ndocs);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_set_documents_by_separator(sa_amd_tok_index *ix, uint32_t separator, int64_t *ndocs_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_set_by_separator(ix, separator, ndocs_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_doc_offsets(const sa_amd_tok_index *ix, uint32_t *doc_off_out, int64_t capacity, int64_t *ndocs_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_offsets(ix, doc_off_out, capacity, ndocs_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_doc_of(const sa_amd_tok_index *ix, const uint32_t *pos, int64_t count, uint32_t *doc_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_doc_of(ix, pos, count, doc_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_doc_search(const sa_amd_tok_index *ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t count, uint32_t *occ,
+                                              uint32_t *df)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_query(ix, pat_data, pat_off, count, false, occ, df, nullptr, nullptr, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_doc_list(const sa_amd_tok_index *ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t count,
+                                            int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_query(ix, pat_data, pat_off, count, true, nullptr, nullptr, list_off, docs, capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_doc_match(const sa_amd_tok_index *ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t npat,
+                                             const int32_t *clause_off, const uint8_t *clause_flags, int32_t nclauses, const int32_t *query_off,
+                                             int32_t nqueries, uint32_t *df, uint32_t *clause_df)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_match(ix, pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries, false, df, clause_df, nullptr,
+                             nullptr, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok_index_doc_match_list(const sa_amd_tok_index *ix, const uint16_t *pat_data, const int64_t *pat_off, int32_t npat,
+                                                  const int32_t *clause_off, const uint8_t *clause_flags, int32_t nclauses, const int32_t *query_off,
+                                                  int32_t nqueries, int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_match(ix, pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries, true, nullptr, nullptr, list_off,
+                             docs, capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_set_documents(sa_amd_tok32_index *ix, const uint32_t *doc_off, int64_t ndocs)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_set(ix, doc_off, ndocs);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_set_documents_by_separator(sa_amd_tok32_index *ix, uint32_t separator, int64_t *ndocs_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_set_by_separator(ix, separator, ndocs_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_doc_offsets(const sa_amd_tok32_index *ix, uint32_t *doc_off_out, int64_t capacity, int64_t *ndocs_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_offsets(ix, doc_off_out, capacity, ndocs_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_doc_of(const sa_amd_tok32_index *ix, const uint32_t *pos, int64_t count, uint32_t *doc_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_doc_of(ix, pos, count, doc_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_doc_search(const sa_amd_tok32_index *ix, const uint32_t *pat_data, const int64_t *pat_off, int32_t count,
+                                                uint32_t *occ, uint32_t *df)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_query(ix, pat_data, pat_off, count, false, occ, df, nullptr, nullptr, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_doc_list(const sa_amd_tok32_index *ix, const uint32_t *pat_data, const int64_t *pat_off, int32_t count,
+                                              int64_t *list_off, uint32_t *docs, int64_t capacity, int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_query(ix, pat_data, pat_off, count, true, nullptr, nullptr, list_off, docs, capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_doc_match(const sa_amd_tok32_index *ix, const uint32_t *pat_data, const int64_t *pat_off, int32_t npat,
+                                               const int32_t *clause_off, const uint8_t *clause_flags, int32_t nclauses, const int32_t *query_off,
+                                               int32_t nqueries, uint32_t *df, uint32_t *clause_df)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_match(ix, pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries, false, df, clause_df, nullptr,
+                             nullptr, 0, nullptr);
+    SA_ABI_GUARD_END(0)
+}
+
+SA_EXPORT int32_t sa_amd_tok32_index_doc_match_list(const sa_amd_tok32_index *ix, const uint32_t *pat_data, const int64_t *pat_off, int32_t npat,
+                                                    const int32_t *clause_off, const uint8_t *clause_flags, int32_t nclauses,
+                                                    const int32_t *query_off, int32_t nqueries, int64_t *list_off, uint32_t *docs, int64_t capacity,
+                                                    int64_t *total_out)
+{
+    SA_ABI_GUARD_BEGIN
+    return sa::tokdocs_match(ix, pat_data, pat_off, npat, clause_off, clause_flags, nclauses, query_off, nqueries, true, nullptr, nullptr, list_off,
+                             docs, capacity, total_out);
+    SA_ABI_GUARD_END(0)
+}
+
 // ---- packed format (reference src/packed_sa.rs); byte layout: u32 magic "SA4x" LE, u32 length, u64 data length
 //      (bincode's Vec<u8> prefix), data ----
 
